@@ -18,13 +18,17 @@
   --in-process          configs 2 / 4 with N > 1: ONE process drives the N devices through msm_*_multi_dev (the shape of the reference's
                         callers, crates/bls-snark-sys/src/signatures.rs:343, crates/epoch-snark/src/api/prover.rs:78): one host thread per
                         device inside the library, partial sums folded on the host, no collective
+  --full                everything beyond the headline (the blocks below, the secondary entry points, config 2's pairing / NTT / wire legs,
+                        --all-configs); a plain run sets up, warms up, times the --steps steps and prints the contract fields
+  --dump-outputs DIR    after the timed steps: what the last one computed as DIR/<name>.npy (affine MSM results as 32-bit limbs in float64,
+                        accept vectors in float32); the inputs are seeded, so two builds can be compared output for output
 
 A "step" is one pass of the hot path over one batch of synthetic input that is resident in HBM before the timed region.
 With N > 1 ranks (one process per GPU, launched by torch.distributed.run) an MSM is ONE job sharded by index range
 (SURVEY.md section 8e): each rank computes the partial sum of its slice, the 144 / 288-byte Jacobian partials are exchanged with
 one RCCL all_gather and every rank folds them; batches and pairing products shard with no exchange at all.
 
-The line carries the driver's contract fields plus
+With --full the line carries the driver's contract fields plus
   "roofline":     the dominant kernel - algorithmic bytes per launch / its HIP-event duration vs the HBM peak
   "cpu_baseline": the oracle's C++ restatement of the arkworks CPU path (kind "port"; the Rust reference cannot be built here)
                   timed on this box's host cores on a bounded sample, after the timed GPU result has been compared with it
@@ -204,6 +208,19 @@ def committed_traffic(kernels, shape):
     return total, " + ".join(srcs) + (" - STALE (%s)" % "; ".join(stale) if stale else " (build signature matches the profiled build)")
 
 
+def affine_limbs(jacobian, p, ext=1):
+    """One Jacobian result of an MSM entry point (Montgomery limbs) as --dump-outputs writes it: the affine point, rows x, y (x.c0, x.c1, y.c0,
+    y.c1 over Fq2) of canonical 32-bit little-endian limbs in float64 (exact); every entry -1 for the point at infinity.  Affine, because the
+    Jacobian representative depends on the schedule and two builds need only agree on the point."""
+    from celo_bls_snark_rs_amd import codec
+    words = (p.bit_length() + 31) // 32
+    P = codec.jacobian_to_affine(jacobian, p, ext)
+    if P is None:
+        return np.full((2 * ext, words), -1.0)
+    coords = list(P) if ext == 1 else [*P[0], *P[1]]
+    return np.array([[(v >> (32 * i)) & 0xFFFFFFFF for i in range(words)] for v in coords], dtype=np.float64)
+
+
 # ===================================================================================================== MSM configurations (2 and 4)
 class MsmConfig:
     def __init__(self, cx, group, log_n_total, name):
@@ -298,17 +315,15 @@ class MsmConfig:
     def units_per_step(self):
         return self.n if self.by_windows else self.cx.nshards * self.n
 
-    def report(self, line, result):
+    def outputs(self, result):
+        from celo_bls_snark_rs_amd import codec
+        return {"msm_affine": affine_limbs(result, codec.Q377 if self.group.startswith("bls12_377") else codec.Q761)}
+
+    def report(self, line, result, full):
         from celo_bls_snark_rs_amd import ffi, synthetic as syn
         cx = self.cx
         tm = ffi.msm_timings(self.group)
-        acc = float(np.median(self.acc_ms))
-        alg = syn.ALG_BYTES[self.group]
-        # algorithmic bytes of ONE launch of the dominant kernel: a window shard reads its n points once per window it owns, i.e. its
-        # share windows_here / windows_of_the_job of the job's n * alg bytes
         nw_job = tm["windows"] * (cx.nshards if self.by_windows else 1)
-        achieved = self.n * alg / (cx.nshards if self.by_windows else 1) / (acc * 1e-3) / 1e9
-        traffic, src = committed_traffic(ACC_KERNEL[self.group], self.log_n) if not self.by_windows else (None, "no committed PMC profile of this launch shape")
         line["metric"] = "%s MSM scalar-muls/sec" % {"bls12_377_g1": "BLS12-377 G1", "bw6_761_g1": "BW6-761 G1"}[self.group]
         line["unit"] = "scalar-muls/s"
         line["config"] = {"workload": "%s, 2^%d random bases/scalars per GPU%s, inputs resident in HBM" % (self.name, self.log_n, " (witness-like scalar mix)" if cx.args.witness_like else ""),
@@ -323,6 +338,22 @@ class MsmConfig:
         if self.by_windows:
             line["config"]["workload"] = "%s, ONE job of 2^%d random bases/scalars replicated on every GPU, windows partitioned, inputs resident in HBM" % (self.name, self.log_n)
             line["config"]["windows_of_the_job"] = nw_job
+        if self.fixed is not None:
+            fi = self.fixed.info()
+            line["config"]["entry_point"] = "msm_%s_fixed_dev: per-key tables T[j][i] = 2^(c j) P_i built once by msm_%s_precompute_dev (the prover's queries stay, the assignment changes)" % (self.group, self.group)
+            line["config"]["fixed_base"] = {"window_bits": fi["window_bits"], "digits_per_scalar": fi["windows"], "virtual_windows": tm["windows"],
+                                            "table_bytes": fi["table_bytes"], "table_build_ms": fi["build_ms"],
+                                            "note": "the table build is outside the timed region: once per proving key (crates/epoch-snark/src/api/setup.rs:63-105)"}
+        if cx.args.subgroup_points:
+            line["config"]["entry_point"] = "msm_bls12_377_g1_subgroup_dev: bases vouched to lie in G1 (what Signature::batch hands over), GLV split"
+        if not full:
+            return
+        acc = float(np.median(self.acc_ms))
+        alg = syn.ALG_BYTES[self.group]
+        # algorithmic bytes of ONE launch of the dominant kernel: a window shard reads its n points once per window it owns, i.e. its
+        # share windows_here / windows_of_the_job of the job's n * alg bytes
+        achieved = self.n * alg / (cx.nshards if self.by_windows else 1) / (acc * 1e-3) / 1e9
+        traffic, src = committed_traffic(ACC_KERNEL[self.group], self.log_n) if not self.by_windows else (None, "no committed PMC profile of this launch shape")
         line["roofline"] = {"bound": "hbm", "kernel": ACC_KERNEL[self.group], "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                             "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": src,
                             "note": "integer-VALU bound, not HBM bound (SURVEY.md section 8d); algorithmic bytes = n*%d B per launch; kernel ms (median over the timed "
@@ -345,18 +376,11 @@ class MsmConfig:
             line["valu_roofline"]["frac_executed"] = line["valu_roofline"]["frac"] * ex / madd
             line["valu_roofline"]["note"] += "; %s executes %d per mixed addition (ten pair products): `frac` prices the useful %d of the one-lane formula, `frac_executed` the issued ones" % (ACC_KERNEL[self.group], ex, madd)
         if self.fixed is not None:
-            fi = self.fixed.info()
-            line["config"]["entry_point"] = "msm_%s_fixed_dev: per-key tables T[j][i] = 2^(c j) P_i built once by msm_%s_precompute_dev (the prover's queries stay, the assignment changes)" % (self.group, self.group)
-            line["config"]["fixed_base"] = {"window_bits": fi["window_bits"], "digits_per_scalar": fi["windows"], "virtual_windows": tm["windows"],
-                                            "table_bytes": fi["table_bytes"], "table_build_ms": fi["build_ms"],
-                                            "note": "the table build is outside the timed region: once per proving key (crates/epoch-snark/src/api/setup.rs:63-105)"}
             fq_ops = self.n * fi["windows"] * madd
             line["valu_roofline"]["achieved"] = fq_ops / (acc * 1e-3) / 1e12
             line["valu_roofline"]["frac"] = line["valu_roofline"]["achieved"] / valu_peak
             line["valu_roofline"]["note"] += "; fixed base: n * digits_per_scalar mixed adds"
             line["roofline"]["traffic"], line["roofline"]["traffic_source"] = None, "no committed PMC profile of this launch shape"
-        if cx.args.subgroup_points:
-            line["config"]["entry_point"] = "msm_bls12_377_g1_subgroup_dev: bases vouched to lie in G1 (what Signature::batch hands over), GLV split"
         if cx.world > 1 and not cx.devices and self.fixed is None and not self.by_windows and cx.args.scaling == "weak" and not cx.args.subgroup_points and not cx.args.witness_like and not cx.args.balanced and self.n <= (1 << 21):
             line["strong"] = self.strong_block()
         if cx.world == 1 and not cx.devices and self.fixed is None and not cx.args.subgroup_points:
@@ -824,20 +848,26 @@ class BatchVerifyConfig:
     def units_per_step(self):
         return self.cx.world * self.m
 
-    def report(self, line, result):
+    def outputs(self, result):
+        return {"batch_verdicts": np.asarray(result, dtype=np.float32)}
+
+    def report(self, line, result, full):
         from celo_bls_snark_rs_amd import synthetic as syn
         cx = self.cx
         if result.tolist() != self.w["expect"].tolist():
             raise SystemExit("PARITY FAILURE: accept vector of the timed step differs from the constructed one")
-        d = np.median(np.array(self.dev_ms), axis=0)
         tot = self.m * self.n
-        achieved = tot * syn.ALG_BYTES["bls12_377_g2"] / (d[1] * 1e-3) / 1e9
         line["metric"] = "Batch::verify batches/sec (BLS12-377: G2 MSM + G1 MSM + 2-pair product per batch)"
         line["unit"] = "batches/s"
         line["config"] = {"workload": "batched aggregated-signature verify: %d batches x %d signers per GPU, 136-bit exponents, 1 %% of the batches corrupted, inputs resident in HBM"
                                       % (self.m, self.n), "batches_per_gpu": self.m, "signers_per_batch": self.n,
-                          "signatures_per_s": None, "miller_loops_per_step": 2 * self.m, "final_exps_per_step": self.m,
+                          "signatures_per_s": line["value"] * self.n, "miller_loops_per_step": 2 * self.m, "final_exps_per_step": self.m,
                           "sharding": "batches sharded by rank, no exchange" if cx.world > 1 else "single GPU"}
+        line["parity"] = {"checked": True, "against": "this rank's accept vector of the timed step == the one built into the workload (1 % of the batches corrupted)"}
+        if not full:
+            return
+        d = np.median(np.array(self.dev_ms), axis=0)
+        achieved = tot * syn.ALG_BYTES["bls12_377_g2"] / (d[1] * 1e-3) / 1e9
         traffic, src = committed_traffic("k_accumulate_pair<G2_377, 1>", "cfg3") if (self.m, self.n) == (4096, 256) else (None, "no committed PMC profile of this launch shape")
         line["roofline"] = {"bound": "hbm", "kernel": "k_accumulate_pair<G2_377, 1> (batched path)", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                             "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": src,
@@ -857,8 +887,6 @@ class BatchVerifyConfig:
                                  "note": pk["note"] + "; achieved = expanded terms x windows mixed additions over Fq2 x %d multiply-adds / accumulate ms - an upper count (a zero digit "
                                          "adds nothing: 1/64 of them at 6-bit windows) over a time that also holds part of the overlapping G1 leg's work; the count is curve.h's one-lane "
                                          "formula (6 products, 2 squarings, the fused Y3) - the lane-pair kernel that runs spends 11 480 (ten pair products): its useful share is what is priced" % MADS["madd"]["bls12_377_g2"]}
-        line["config"]["signatures_per_s"] = line["value"] * self.n
-        line["parity"] = {"checked": True, "against": "this rank's accept vector of the timed step == the one built into the workload (1 % of the batches corrupted)"}
         if not cx.args.no_cpu_baseline and cx.rank == 0:
             line["cpu_baseline"] = self.cpu_baseline(result)
             line["parity"]["against"] += "; a sample of batches incl. rejected ones against the CPU port"
@@ -946,25 +974,32 @@ class MixedConfig:
     def units_per_step(self):
         return self.cx.world * 2 * self.n
 
-    def report(self, line, result):
+    def outputs(self, result):
+        from celo_bls_snark_rs_amd import codec
+        return {"g1_msm_affine": affine_limbs(result[0], codec.Q377), "g2_msm_affine": affine_limbs(result[1], codec.Q377, ext=2),
+                "pairing_verdicts": np.asarray(result[2], dtype=np.float32)}
+
+    def report(self, line, result, full):
         from celo_bls_snark_rs_amd import synthetic as syn
         cx = self.cx
         if result[2].tolist() != self.expect:
             raise SystemExit("PARITY FAILURE: pairing accept vector differs from the constructed one")
+        line["metric"] = "BLS12-377 mixed G1+G2 MSM scalar-muls/sec with concurrent Miller loops"
+        line["unit"] = "scalar-muls/s"
+        line["config"] = {"workload": "mixed: G1 MSM 2^%d + G2 MSM 2^%d + %d Miller loops (%d two-pair products) per GPU, issued concurrently from three host threads, "
+                                      "MSM inputs resident in HBM" % ((self.n - 1).bit_length(), (self.n - 1).bit_length(), self.loops, self.mprod),
+                          "terms_per_group_per_gpu": self.n, "miller_loops_per_gpu": self.loops, "miller_loops_per_s": cx.world * self.loops / (line["ms_per_step"] * 1e-3)}
+        if not full:
+            return
         # overlap gain: the same three legs back to back
         t0 = time.perf_counter()
         for _ in range(3):
             seq = self.step(concurrent=False)
         t_seq = (time.perf_counter() - t0) / 3 * 1e3
+        line["config"].update({"sequential_ms_per_step": t_seq, "overlap_gain": t_seq / line["ms_per_step"]})
         d = np.median(np.array(self.ms), axis=0)
         bytes_step = self.n * (syn.ALG_BYTES["bls12_377_g1"] + syn.ALG_BYTES["bls12_377_g2"]) + self.loops * syn.ALG_BYTES_PER_MILLER_LOOP
         achieved = bytes_step / (line["ms_per_step"] * 1e-3) / 1e9
-        line["metric"] = "BLS12-377 mixed G1+G2 MSM scalar-muls/sec with concurrent Miller loops"
-        line["unit"] = "scalar-muls/s"
-        line["config"] = {"workload": "mixed: G1 MSM 2^%d + G2 MSM 2^%d + %d Miller loops (%d two-pair products) per GPU, issued concurrently from three host threads, "
-                                      "MSM inputs resident in HBM" % ((self.n - 1).bit_length(), (self.n - 1).bit_length(), self.loops, self.mprod),
-                          "terms_per_group_per_gpu": self.n, "miller_loops_per_gpu": self.loops, "miller_loops_per_s": cx.world * self.loops / (line["ms_per_step"] * 1e-3),
-                          "sequential_ms_per_step": t_seq, "overlap_gain": t_seq / line["ms_per_step"]}
         traffic, src = committed_traffic(["k_accumulate<G1_377>", "k_accumulate_pair<G2_377, 1>"], (self.n - 1).bit_length())
         line["roofline"] = {"bound": "hbm", "kernel": "whole step (three concurrent legs)", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                             "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": src,
@@ -1217,11 +1252,18 @@ def main():
     ap.add_argument("--fixed-window-bits", type=int, default=0, help="--fixed-base: table window size c (16..22; 0 = automatic)")
     ap.add_argument("--in-process", action="store_true", help="configs 2 / 4, N > 1: one process drives the N devices through msm_*_multi_dev (no ranks, no collective)")
     ap.add_argument("--devices", default="", help="--in-process: comma-separated device ordinals (default 0..N-1; repeats allowed, e.g. 0,0 on a 1-GPU box)")
+    ap.add_argument("--full", action="store_true", help="after the headline: rooflines, secondary entry points and legs, the CPU baseline and its parity check, "
+                                                        "--all-configs (a plain run times the steps and prints the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the last timed step computed to DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
 
     world_env = int(os.environ.get("WORLD_SIZE", "0"))
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.all_configs and not args.full:
+        raise SystemExit("--all-configs: use it with --full")
     if args.fixed_base and (args.config not in (2, 4) or args.in_process or args.subgroup_points or (args.gpus > 1 and args.scaling == "strong" and args.partition != "index")):
         raise SystemExit("--fixed-base: configs 2 and 4, one table per rank over its index-range shard (weak scaling, or strong with --partition index)")
     if args.in_process and args.config not in (2, 4):
@@ -1293,6 +1335,10 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=cx.xdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and cx.rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in job.outputs(result).items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
 
     line = {"metric": None, "value": job.units_per_step() * args.steps / elapsed, "unit": None, "n_gpus": cx.nshards, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": elapsed * 1e3 / args.steps, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
@@ -1303,18 +1349,21 @@ def main():
                        "backend": ("rccl (torch.distributed 'nccl')" if backend == "nccl" else backend) if cx.world > 1 else None,
                        "launcher": os.environ.get("CELO_BENCH_LAUNCHER", "external (torch.distributed.run)" if cx.world > 1 else "none"),
                        "device_of_rank0": local_rank})
-    job.report(line, result)                                  # every rank takes part (gathers for the full-size parity check)
+    job.report(line, result, args.full)                       # every rank takes part (gathers for the full-size parity check)
+    if "parity" not in line and not args.full:
+        line["parity"] = {"checked": False, "against": "not compared with the CPU port in a plain run (bench.py --full)"}
     if "parity" not in line:
         pw = (line.get("cpu_baseline") or {}).get("parity_with_gpu")
         line["parity"] = {"checked": pw is True, "against": "the CPU port (oracle/cpu), see cpu_baseline" if pw is True else str(pw)}
     if line["n_gpus"] != args.gpus:
         raise SystemExit("bench.py: the job ran on %d GPU(s) but --gpus %d was asked for: no line" % (line["n_gpus"], args.gpus))
     if cx.rank == 0:
-        if cx.cfg == 2 and cx.world == 1 and not args.no_pairing:
-            line["pairing"] = pairing_leg(ffi, check_oracle=not args.no_cpu_baseline)
-            line["ntt"] = ntt_leg(ffi, check_oracle=not args.no_cpu_baseline)
-            line["wire"] = wire_leg(ffi, check_oracle=not args.no_cpu_baseline)
-        add_measured_hbm_peak(line)
+        if args.full:
+            if cx.cfg == 2 and cx.world == 1 and not args.no_pairing:
+                line["pairing"] = pairing_leg(ffi, check_oracle=not args.no_cpu_baseline)
+                line["ntt"] = ntt_leg(ffi, check_oracle=not args.no_cpu_baseline)
+                line["wire"] = wire_leg(ffi, check_oracle=not args.no_cpu_baseline)
+            add_measured_hbm_peak(line)
         print(json.dumps(line), flush=True)
     if args.all_configs and cx.world == 1 and not cx.devices:
         # one more line per remaining BASELINE configuration (a single run times them all); each in a process of its own so that
@@ -1325,7 +1374,7 @@ def main():
         for c in (3, 4, 5):
             if c == cx.cfg:
                 continue
-            cmd = [sys.executable, os.path.abspath(__file__), "--config", str(c), "--steps", str(args.steps), "--warmup", str(args.warmup)]
+            cmd = [sys.executable, os.path.abspath(__file__), "--config", str(c), "--steps", str(args.steps), "--warmup", str(args.warmup), "--full"]
             if args.no_cpu_baseline:
                 cmd.append("--no-cpu-baseline")
             r = subprocess.run(cmd, capture_output=True, text=True)

@@ -111,3 +111,28 @@ def test_bench_gpus_flag_is_not_decorative(monkeypatch):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and "refusing" in (r.stderr + r.stdout) and not r.stdout.strip().startswith("{")
+
+
+def test_bench_dump_form_and_full_only_options():
+    """bench.py --dump-outputs writes an MSM result as its affine point: exact 32-bit limbs in float64, -1 everywhere for the point at infinity,
+    the same array for every Jacobian representative of the point.  --all-configs belongs to --full: a plain run refuses it before any work."""
+    import subprocess
+    import sys
+    import bench
+    from oracle.py import ecc
+    from celo_bls_snark_rs_amd import codec
+    q = codec.Q377
+
+    def limbs_to_int(row):
+        return sum(int(v) << (32 * i) for i, v in enumerate(row))
+    x, y = ecc.E1_377.mul(ecc.G1_377, 12345)
+    for z in (1, 7):                                   # (x z^2, y z^3, z) ~ (x, y)
+        a = bench.affine_limbs(codec.to_mont([x * z * z % q, y * z ** 3 % q, z], q).reshape(-1), q)
+        assert a.dtype == np.float64 and a.shape == (2, 12) and [limbs_to_int(r) for r in a] == [x, y]
+    assert (bench.affine_limbs(np.zeros(18, dtype=np.uint64), q) == -1).all()
+    (x0, x1), (y0, y1) = ecc.E2_377.mul(ecc.G2_377, 6789)
+    a = bench.affine_limbs(codec.to_mont([x0 * 49 % q, x1 * 49 % q, y0 * 343 % q, y1 * 343 % q, 7, 0], q).reshape(-1), q, ext=2)
+    assert a.shape == (4, 12) and [limbs_to_int(r) for r in a] == [x0, x1, y0, y1]
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--all-configs"], capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--full" in r.stderr and not r.stdout.strip()

@@ -6,7 +6,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH=${2:-"python $ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline"}
+BENCH=${2:-"python $ROOT/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline"}
 echo "$BENCH" > $OUT/command.txt
 timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/trace -o trace --output-format csv -- $BENCH > $OUT/trace.log 2>&1
 timeout 900 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/pmc_fetch -o pmc --output-format csv -- $BENCH > $OUT/pmc_fetch.log 2>&1

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 timeout 900 python -m pytest tests/test_msm_ba_gpu.py -m gpu -x -q > $O/pytest_ba.txt 2>&1; echo "pytest ba rc=$?"; tail -3 $O/pytest_ba.txt
 run() {
   tag=$1; shift
-  env "$@" timeout 300 python bench.py --config 4 --no-cpu-baseline --steps 5 --warmup 2 > $O/bench_$tag.json 2> $O/bench_$tag.err; rc=$?
+  env "$@" timeout 300 python bench.py --full --config 4 --no-cpu-baseline --steps 5 --warmup 2 > $O/bench_$tag.json 2> $O/bench_$tag.err; rc=$?
   python - <<P
 import json
 try:

@@ -11,7 +11,7 @@ def short(n):
     n = n.replace("void celo::", "").replace("celo::", "")
     return n.split("(")[0]
 
-cmd = "python bench.py --steps 5 --warmup 2 --no-cpu-baseline"
+cmd = "python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline"
 if os.path.exists(os.path.join(src, "command.txt")):
     cmd = open(os.path.join(src, "command.txt")).read().strip().replace(root + "/", "")
 lines = [f"# rocprofv3 summary — {tag}", "", f"Command: `{cmd}`, MI355X gfx950.", "",
