@@ -77,6 +77,10 @@ int witness_map_253_run(uint64_t*, uint64_t*, uint64_t*, unsigned, const uint64_
 int groth16_prove_377_run(const uint64_t*, size_t, const uint64_t*, size_t, const uint64_t*, size_t, const uint64_t*, size_t, const uint64_t*, const uint64_t*,
                           const uint64_t*, size_t, size_t, const uint64_t*, size_t, uint64_t*, uint64_t*, uint64_t*);
 int wire_decompress(int, const uint8_t*, size_t, int, uint64_t*, uint8_t*, int, void*);
+int wire761_decode(int, int, const uint8_t*, size_t, int, uint64_t*, uint8_t*, int, void*);   // unit_wire761.hip
+int wire761_key_layout(const uint8_t*, size_t, int, uint64_t*);
+int wire761_key_load(const uint8_t*, size_t, int, int, ProvingKey**, uint64_t*);
+void wire761_last_timings(float*);
 float wire_last_ms();
 int wire_normalize(int, const uint64_t*, size_t, uint64_t*, uint8_t*);
 int hash_to_g1_direct_run(const uint8_t*, const uint8_t*, const uint64_t*, const uint8_t*, const uint64_t*, size_t, uint64_t*, uint8_t*, int);
@@ -383,6 +387,31 @@ int decompress_bls12_377_g1_dev(const uint8_t* d_in, size_t n, int check_subgrou
 int decompress_bls12_377_g2_dev(const uint8_t* d_in, size_t n, int check_subgroup, uint64_t* d_out_xy, uint8_t* d_status, void* hip_stream) {
   return wire_decompress(1, d_in, n, check_subgroup, d_out_xy, d_status, 1, hip_stream);
 }
+int decompress_bw6_761_g1(const uint8_t* in, size_t n, int check_subgroup, uint64_t* out_xy, uint8_t* status) {
+  return wire761_decode(0, 1, in, n, check_subgroup, out_xy, status, 0, nullptr);
+}
+int decompress_bw6_761_g2(const uint8_t* in, size_t n, int check_subgroup, uint64_t* out_xy, uint8_t* status) {
+  return wire761_decode(1, 1, in, n, check_subgroup, out_xy, status, 0, nullptr);
+}
+int decompress_bw6_761_g1_dev(const uint8_t* d_in, size_t n, int check_subgroup, uint64_t* d_out_xy, uint8_t* d_status, void* hip_stream) {
+  return wire761_decode(0, 1, d_in, n, check_subgroup, d_out_xy, d_status, 1, hip_stream);
+}
+int decompress_bw6_761_g2_dev(const uint8_t* d_in, size_t n, int check_subgroup, uint64_t* d_out_xy, uint8_t* d_status, void* hip_stream) {
+  return wire761_decode(1, 1, d_in, n, check_subgroup, d_out_xy, d_status, 1, hip_stream);
+}
+int decode_uncompressed_bw6_761_g1(const uint8_t* in, size_t n, int check, uint64_t* out_xy, uint8_t* status) {
+  return wire761_decode(0, 0, in, n, check, out_xy, status, 0, nullptr);
+}
+int decode_uncompressed_bw6_761_g2(const uint8_t* in, size_t n, int check, uint64_t* out_xy, uint8_t* status) {
+  return wire761_decode(1, 0, in, n, check, out_xy, status, 0, nullptr);
+}
+int groth16_key_layout_bw6_761(const uint8_t* bytes, size_t len, int form, uint64_t out[16]) { return wire761_key_layout(bytes, len, form, out); }
+int groth16_load_key_bw6_761_serialized(const uint8_t* bytes, size_t len, int form, int window_bits, void** out_key, uint64_t* first_bad_point) {
+  if (!out_key) return 2;
+  *out_key = nullptr;
+  return wire761_key_load(bytes, len, form, window_bits, (ProvingKey**)out_key, first_bad_point);
+}
+int celo_amd_wire761_last_timings(float ms[4]) { if (!ms) return 2; wire761_last_timings(ms); return 0; }
 int hash_to_g1_direct_bls12_377(const uint8_t domain[8], const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off,
                                 size_t n, uint64_t* out_xy, uint8_t* attempts) {
   return hash_to_g1_direct_run(domain, msgs, msg_off, extras, extra_off, n, out_xy, attempts, 0);

@@ -8,6 +8,7 @@
 #include "pairing.h"
 #include "curve_lanes.h"
 #include "wire.h"
+#include "wire761.h"
 #include "hash_direct.h"
 #include "host64.h"
 #include <cstring>
@@ -306,6 +307,16 @@ void ht_wire_decode(int g2, const uint8_t* in, size_t n, int check, uint64_t* ou
       status[i] = wire_decode_g1(in + i * 48, k, check != 0, p);
       if (status[i] == WIRE_OK) { p.x.to_ark(o); p.y.to_ark(o + 6); }
     }
+  }
+}
+// wire761.h under bounds tracking: n BW6-761 points (compressed 96 B / uncompressed 192 B) -> 24 u64 rows + status (k_decode761 runs the same template)
+void ht_wire761_decode(int g2, int compressed, int check, const uint8_t* in, size_t n, uint64_t* out, uint8_t* status) {
+  const size_t ib = compressed ? 96 : 192;
+  for (size_t i = 0; i < n; i++) {
+    const uint8_t* src = in + i * ib;
+    uint64_t* o = out + i * 24;
+    if (g2) status[i] = compressed ? w761_decode_row<4, true>(src, check != 0, o) : w761_decode_row<4, false>(src, check != 0, o);
+    else status[i] = compressed ? w761_decode_row<-1, true>(src, check != 0, o) : w761_decode_row<-1, false>(src, check != 0, o);
   }
 }
 // the two forms of the subgroup test on one affine on-curve point (ark limbs): bit 0 = endomorphism form (what the decoders run),

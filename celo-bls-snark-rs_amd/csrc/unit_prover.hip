@@ -264,6 +264,24 @@ int groth16_key_load(int curve, const uint64_t* a_query, size_t na, const uint64
   *out = k;
   return 0;
 }
+// The same key from DEVICE rows (wire761_key_load, unit_wire761.hip): the four BW6-761 queries as decoded there (24 u64 per row, row 0 of a / b
+// included) with their per-row identity bytes, and the four key elements as host rows.  The tables are built where the rows lie.
+int groth16_key_load_dev_761(const uint64_t* d_a, const uint8_t* d_ainf, size_t na, const uint64_t* d_b, const uint8_t* d_binf, size_t nb,
+                             const uint64_t* d_h, const uint8_t* d_hinf, size_t nh, const uint64_t* d_l, const uint8_t* d_linf, size_t nl,
+                             const uint64_t* a0, const uint64_t* b0, const uint64_t* alpha_g1, const uint64_t* beta_g2, int window_bits, ProvingKey** out) {
+  if (int rc0 = api_enter()) return rc0;
+  if (!d_a || !d_b || !a0 || !b0 || !alpha_g1 || !beta_g2 || !out || na == 0 || nb == 0 || (nh && !d_h) || (nl && !d_l)) return 2;
+  ProvingKey* k = new ProvingKey();
+  k->curve = 0; k->na = na; k->nb = nb; k->nl = nl; k->nh = nh; k->device = api_device();
+  k->a0.assign(a0, a0 + 24); k->b0.assign(b0, b0 + 24); k->alpha.assign(alpha_g1, alpha_g1 + 24); k->beta.assign(beta_g2, beta_g2 + 24);
+  int rc = na > 1 ? msm_fixed_build_761(d_a + 24, d_ainf + 1, na - 1, 1, window_bits, &k->a) : 0;
+  if (!rc && nb > 1) rc = msm_fixed_build_761(d_b + 24, d_binf + 1, nb - 1, 1, window_bits, &k->b);
+  if (!rc && nl) rc = msm_fixed_build_761(d_l, d_linf, nl, 1, window_bits, &k->l);
+  if (!rc && nh) rc = msm_fixed_build_761(d_h, d_hinf, nh, 1, window_bits, &k->h);
+  if (rc) { groth16_key_free(k); return rc; }
+  *out = k;
+  return 0;
+}
 int groth16_prove_keyed(const ProvingKey* k, const uint64_t* assignment, size_t n_assign, size_t n_aux, const uint64_t* h, size_t n_h, uint64_t* out_a, uint64_t* out_b,
                         uint64_t* out_c) {
   if (int rc0 = api_enter()) return rc0;

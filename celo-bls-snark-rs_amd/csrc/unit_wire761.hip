@@ -1,0 +1,212 @@
+// Translation unit: bulk decoding of serialized BW6-761 points (see wire761.h), one point per lane, and the loader of a serialized
+// ark-groth16 0.1 ProvingKey<BW6_761> that decodes its point sections on the device straight into the buffers the fixed-base table build reads.
+#include "wire761.h"
+#include <hip/hip_runtime.h>
+#include <chrono>
+#include <cstdio>
+#include <mutex>
+#include "runtime.h"
+
+// one wave per SIMD: the square root (four odd powers and the running power, 5 x 28 registers) and the ladder (XYZZ accumulator 4 x 28, the
+// point 2 x 28, the addition's temporaries) do not fit 256 VGPRs.  With the AGPR half of the file k_decode761 needs no scratch and
+// k_subgroup761 36 B/lane (build/unit_wire761.remarks.txt; DESIGN.md section 6c')
+#ifndef W761_OCC
+#define W761_OCC __attribute__((amdgpu_waves_per_eu(1, 1)))
+#endif
+namespace celo {
+struct ProvingKey;
+int groth16_key_load_dev_761(const uint64_t*, const uint8_t*, size_t, const uint64_t*, const uint8_t*, size_t, const uint64_t*, const uint8_t*, size_t,
+                             const uint64_t*, const uint8_t*, size_t, const uint64_t*, const uint64_t*, const uint64_t*, const uint64_t*, int, ProvingKey**);
+void groth16_key_free(ProvingKey*);
+
+// calls from several host threads are serialised per process (they are bulk calls: one fills the GPU); each runs on a stream of its own
+// (host-pointer calls) or on the caller's (the _dev forms)
+static std::mutex w761_mu;
+static float g_w761_ms[4] = {0.f, 0.f, 0.f, 0.f};   // kernel ms of the last decode call; the last key load's transfer / decode / table build
+
+// Two passes, one point per lane.  k_decode761: in n x 96 B (compressed) / n x 192 B (uncompressed) -> out n x 24 u64, (x, y) in arkworks
+// Montgomery limbs (the layout of msm_bw6_761_*), zeros unless status == WIRE_OK; everything but the subgroup test.  k_subgroup761: r P == O
+// for the rows still at status 0 (status 3 and a zero row otherwise); one kernel for both groups (the ladder does not depend on b).  Split
+// because the square root's four odd powers and the ladder's XYZZ state are never live together then: the first pass needs no scratch.
+// Control flow is uniform across the wave up to the per-lane status exits: the root's exponent and the ladder's r are compile-time constants.
+template <int B, bool COMPRESSED> __global__ void __launch_bounds__(64) W761_OCC
+k_decode761(const uint8_t* __restrict__ in, uint64_t* __restrict__ out, uint8_t* __restrict__ status, uint32_t n, int check) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Affine<Fw761> p = {Fw761::zero(), Fw761::zero()};
+  const WireStatus st = w761_parse<B, COMPRESSED>(in + (size_t)i * (COMPRESSED ? 96 : 192), check != 0, p);
+  uint64_t* o = out + (size_t)i * 24;
+  if (st == WIRE_OK) { p.x.to_ark(o); p.y.to_ark(o + 12); }
+  else for (int j = 0; j < 24; j++) o[j] = 0;
+  status[i] = st;
+}
+__global__ void __launch_bounds__(64) W761_OCC k_subgroup761(uint64_t* __restrict__ out, uint8_t* __restrict__ status, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || status[i] != WIRE_OK) return;
+  uint64_t* o = out + (size_t)i * 24;
+  const Affine<Fw761> p = {Fw761::norm(Fw761::from_ark(o)), Fw761::norm(Fw761::from_ark(o + 12))};
+  if (w761_in_subgroup(p)) return;
+  for (int j = 0; j < 24; j++) o[j] = 0;
+  status[i] = WIRE_NOT_IN_SUBGROUP;
+}
+// the smallest index of a rejected point (status 2 or 3)
+__global__ void __launch_bounds__(256) k_first_bad761(const uint8_t* __restrict__ status, uint32_t n, unsigned long long* first) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n && status[i] >= WIRE_INVALID) atomicMin(first, (unsigned long long)i);
+}
+
+static void launch_decode761(int g2, int compressed, const uint8_t* d_in, size_t n, int check, uint64_t* d_out, uint8_t* d_st, hipStream_t s) {
+  const dim3 grid(((uint32_t)n + 63) / 64), block(64);
+  if (g2) {
+    if (compressed) hipLaunchKernelGGL((k_decode761<4, true>), grid, block, 0, s, d_in, d_out, d_st, (uint32_t)n, check);
+    else hipLaunchKernelGGL((k_decode761<4, false>), grid, block, 0, s, d_in, d_out, d_st, (uint32_t)n, check);
+  } else {
+    if (compressed) hipLaunchKernelGGL((k_decode761<-1, true>), grid, block, 0, s, d_in, d_out, d_st, (uint32_t)n, check);
+    else hipLaunchKernelGGL((k_decode761<-1, false>), grid, block, 0, s, d_in, d_out, d_st, (uint32_t)n, check);
+  }
+  if (check) hipLaunchKernelGGL(k_subgroup761, grid, block, 0, s, d_out, d_st, (uint32_t)n);
+}
+
+#define W761_TRY(x)                                                                                  \
+  do {                                                                                               \
+    hipError_t e_ = (x);                                                                             \
+    if (e_ != hipSuccess) { fprintf(stderr, "[celo-amd] %s: %s\n", #x, hipGetErrorString(e_)); rc = 10; goto done; } \
+  } while (0)
+
+// g2: 0 = G1 (b = -1), 1 = G2 (b = 4); compressed: 1 = 96 B points, 0 = 192 B; dev: all four pointers are device pointers, run on stream_
+int wire761_decode(int g2, int compressed, const uint8_t* in, size_t n, int check, uint64_t* out, uint8_t* status, int dev, void* stream_) {
+  if (int rc0 = api_enter()) return rc0;
+  std::lock_guard<std::mutex> lk(w761_mu);
+  if (n == 0) return 0;
+  if (!in || !out || !status || n > 0x7fffffffu) return 2;
+  const size_t ib = compressed ? 96 : 192;
+  hipStream_t stream = dev ? (hipStream_t)stream_ : nullptr;
+  uint8_t *d_in = nullptr, *d_st = nullptr;
+  uint64_t* d_out = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  int rc = 0;
+  if (!dev) W761_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+  if (dev) { d_in = (uint8_t*)in; d_out = out; d_st = status; }
+  else {
+    W761_TRY(hipMalloc(&d_in, n * ib));
+    W761_TRY(hipMalloc(&d_out, n * 24 * 8));
+    W761_TRY(hipMalloc(&d_st, n));
+    W761_TRY(hipMemcpyAsync(d_in, in, n * ib, hipMemcpyHostToDevice, stream));
+  }
+  W761_TRY(hipEventCreate(&e0));
+  W761_TRY(hipEventCreate(&e1));
+  W761_TRY(hipEventRecord(e0, stream));
+  launch_decode761(g2, compressed, d_in, n, check, d_out, d_st, stream);
+  W761_TRY(hipGetLastError());
+  W761_TRY(hipEventRecord(e1, stream));
+  if (!dev) {
+    W761_TRY(hipMemcpyAsync(out, d_out, n * 24 * 8, hipMemcpyDeviceToHost, stream));
+    W761_TRY(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, stream));
+  }
+  W761_TRY(hipStreamSynchronize(stream));
+  W761_TRY(hipEventElapsedTime(&g_w761_ms[0], e0, e1));
+done:
+  if (e0) (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
+  if (!dev) {
+    if (stream) (void)hipStreamSynchronize(stream);
+    if (d_in) (void)hipFree(d_in);
+    if (d_out) (void)hipFree(d_out);
+    if (d_st) (void)hipFree(d_st);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+  return rc;
+}
+
+int wire761_key_layout(const uint8_t* bytes, size_t len, int form, uint64_t out[16]) { return w761_key_layout(bytes, len, form, out); }
+
+// ProvingKey::<BW6_761>::deserialize (form 0) / deserialize_uncompressed (1) / deserialize_unchecked (2), then groth16_load_key_bw6_761.
+// The whole byte string crosses to the device once; every point of every section is decoded there (one launch per section, all into one
+// row buffer indexed by the point's position in serialization order), the first rejected index is found by an atomic minimum, and the four
+// queries' rows and statuses are handed to the table build where they lie (a status-1 row - the point at infinity - is that query's identity
+// through the build's `inf` bytes: after the check every status is 0 or 1).  a_query[0], b_g2_query[0], alpha_g1 and beta_g2, which the key
+// keeps on the host, are decoded again on the host from their bytes (unchecked: the device has checked them).
+int wire761_key_load(const uint8_t* bytes, size_t len, int form, int window_bits, ProvingKey** out_key, uint64_t* first_bad) {
+  if (!out_key) return 2;
+  *out_key = nullptr;
+  uint64_t L[16];
+  if (int rcl = w761_key_layout(bytes, len, form, L)) return rcl;
+  if (L[W761_A] == 0 || L[W761_BG2] == 0) return 2;                 // the proof needs a_query[0] and b_g2_query[0]
+  if (L[W761_NPOINTS] > 0x7fffffffu) return 2;
+  if (int rc0 = api_enter()) return rc0;
+  std::lock_guard<std::mutex> lk(w761_mu);
+  const int compressed = form == 0, check = form != 2;
+  const uint64_t P = L[W761_PT], N = L[W761_NPOINTS];
+  struct Sec { uint64_t off, n; int g2; };
+  const Sec secs[9] = {{0, 1, 0},     {P, 3, 1},           {L[W761_ABC + 1], L[W761_ABC], 0}, {L[W761_BETA_G1], 2, 0}, {L[W761_A + 1], L[W761_A], 0},
+                       {L[W761_BG1 + 1], L[W761_BG1], 0}, {L[W761_BG2 + 1], L[W761_BG2], 1}, {L[W761_H + 1], L[W761_H], 0}, {L[W761_L + 1], L[W761_L], 0}};
+  uint64_t base[9];
+  for (uint64_t s = 0, acc = 0; s < 9; s++) { base[s] = acc; acc += secs[s].n; }
+  hipStream_t stream = nullptr;
+  uint8_t *d_bytes = nullptr, *d_st = nullptr;
+  uint64_t* d_xy = nullptr;
+  unsigned long long* d_first = nullptr;
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  unsigned long long first = ~0ull;
+  ProvingKey* key = nullptr;
+  int rc = 0;
+  W761_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+  for (auto& e : ev) W761_TRY(hipEventCreate(&e));
+  W761_TRY(hipMalloc(&d_bytes, len));
+  W761_TRY(hipMalloc(&d_xy, N * 24 * 8));
+  W761_TRY(hipMalloc(&d_st, N));
+  W761_TRY(hipMalloc(&d_first, sizeof(unsigned long long)));
+  W761_TRY(hipEventRecord(ev[0], stream));
+  W761_TRY(hipMemcpyAsync(d_bytes, bytes, len, hipMemcpyHostToDevice, stream));
+  W761_TRY(hipMemcpyAsync(d_first, &first, sizeof first, hipMemcpyHostToDevice, stream));
+  W761_TRY(hipEventRecord(ev[1], stream));
+  for (int s = 0; s < 9; s++) {
+    if (!secs[s].n) continue;
+    launch_decode761(secs[s].g2, compressed, d_bytes + secs[s].off, secs[s].n, check, d_xy + base[s] * 24, d_st + base[s], stream);
+    W761_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_first_bad761, dim3(((uint32_t)N + 255) / 256), dim3(256), 0, stream, d_st, (uint32_t)N, d_first);
+  W761_TRY(hipGetLastError());
+  W761_TRY(hipEventRecord(ev[2], stream));
+  W761_TRY(hipMemcpyAsync(&first, d_first, sizeof first, hipMemcpyDeviceToHost, stream));
+  W761_TRY(hipStreamSynchronize(stream));
+  W761_TRY(hipEventElapsedTime(&g_w761_ms[1], ev[0], ev[1]));
+  W761_TRY(hipEventElapsedTime(&g_w761_ms[2], ev[1], ev[2]));
+  if (first != ~0ull) {
+    if (first_bad) *first_bad = first;
+    rc = W761_ERR_POINT;
+    goto done;
+  }
+  {
+    // the four key elements the composition keeps on the host (ark's identity encoding (0, 1) for the point at infinity)
+    uint64_t host_rows[4][24];
+    const uint64_t where[4] = {secs[4].off, secs[6].off, 0, P};      // a_query[0], b_g2_query[0], alpha_g1, beta_g2
+    const int grp[4] = {0, 1, 0, 1};
+    for (int q = 0; q < 4; q++) {
+      const uint8_t* src = bytes + where[q];
+      WireStatus st;
+      if (grp[q]) st = compressed ? w761_decode_row<4, true>(src, false, host_rows[q]) : w761_decode_row<4, false>(src, false, host_rows[q]);
+      else st = compressed ? w761_decode_row<-1, true>(src, false, host_rows[q]) : w761_decode_row<-1, false>(src, false, host_rows[q]);
+      if (st == WIRE_INFINITY) Fw761::one().to_ark(host_rows[q] + 12);
+      else if (st != WIRE_OK) { rc = 10; goto done; }                 // not reached: the same function accepted these bytes on the device
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    rc = groth16_key_load_dev_761(d_xy + base[4] * 24, d_st + base[4], L[W761_A], d_xy + base[6] * 24, d_st + base[6], L[W761_BG2],
+                                  d_xy + base[7] * 24, d_st + base[7], L[W761_H], d_xy + base[8] * 24, d_st + base[8], L[W761_L],
+                                  host_rows[0], host_rows[1], host_rows[2], host_rows[3], window_bits, &key);
+    g_w761_ms[3] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+done:
+  if (stream) (void)hipStreamSynchronize(stream);
+  for (auto& e : ev) if (e) (void)hipEventDestroy(e);
+  if (d_bytes) (void)hipFree(d_bytes);
+  if (d_xy) (void)hipFree(d_xy);
+  if (d_st) (void)hipFree(d_st);
+  if (d_first) (void)hipFree(d_first);
+  if (stream) (void)hipStreamDestroy(stream);
+  if (rc) { if (key) groth16_key_free(key); return rc; }
+  *out_key = key;
+  return 0;
+}
+void wire761_last_timings(float ms[4]) { for (int i = 0; i < 4; i++) ms[i] = g_w761_ms[i]; }
+}  // namespace celo

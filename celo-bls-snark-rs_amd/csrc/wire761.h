@@ -1,0 +1,246 @@
+// Point decoding for BW6-761 G1 / G2 (arkworks 0.1 CanonicalDeserialize: coordinates little-endian, 96 B each, flags in the two top bits
+// of the last byte) as host+device templates over the 28-limb field Fp<P761> the MSM uses.  What ark-groth16 0.1 runs per point when it
+// reads a ProvingKey<BW6_761> / VerifyingKey / Proof (crates/epoch-snark/src/api/setup.rs:12,17-20 Groth16Parameters; the "serialized
+// byte arrays of compressed elements" of crates/bls-snark-sys/src/snark/mod.rs:13-17): GroupAffine::deserialize (compressed, checked),
+// deserialize_uncompressed (checked) and deserialize_unchecked (uncompressed, range only).  The single-point host twin of the checked
+// compressed form is seam_a.hip bw6_decompress (Seam A verify); the bulk form is k_decode761 (unit_wire761.hip), one point per lane.
+//
+// Curves (both over Fq, q = 3 mod 4):  G1  y^2 = x^3 - 1,   G2 (M-twist)  y^2 = x^3 + 4.   One template, b as its parameter.
+//
+// Status, in this order (the same codes and order as wire.h WireStatus / wire_decode_g1 and oracle/py/ecc.deser_point):
+//   flags = the top two bits of the last byte (0x40 infinity, 0x80 "y is the lexicographically largest root"; uncompressed: y's last byte)
+//   flags 0xC0                                   -> WIRE_INVALID (2)
+//   infinity flag                                -> WIRE_INFINITY (1), before any range check
+//   a coordinate >= q                            -> 2
+//   compressed: rhs has no square root           -> 2
+//   uncompressed, checked: (x, y) not on the curve -> 2
+//   checked: r P != O (r = r_BW6 = q_BLS12-377)  -> WIRE_NOT_IN_SUBGROUP (3)
+//   otherwise                                    -> WIRE_OK (0)
+// The uncompressed checked form tests the curve equation before the subgroup: stricter than ark 0.1's deserialize_uncompressed, which
+// runs only is_in_correct_subgroup_assuming_on_curve - an off-curve (x, y) is rejected here (2) where ark may accept or reject it.
+// The unchecked form (deserialize_unchecked) tests nothing past the canonical range of x and y.
+#pragma once
+#include <cstdint>
+#include "curve.h"
+#include "wire.h"
+
+namespace celo {
+
+typedef Fq761d Fw761;
+
+// (q + 1) / 4, the exponent of the square root (q = 3 mod 4), and its width-3 sliding-window program: FIRST is the leading odd digit,
+// then STEP[i] = "square once, then multiply by a^d" for d in {0, 1, 3, 5, 7}.  Built at compile time from P761::P64, so the program is
+// the same constant in every lane (the branches below are scalar) and a^1, a^3, a^5, a^7 stay in registers - no run-time-indexed table.
+struct W761Chain {
+  int first = 0, len = 0;
+  uint8_t step[768] = {};
+};
+constexpr int w761_exp_bit(const uint64_t* e, int i) { return (int)((e[i >> 6] >> (i & 63)) & 1); }
+constexpr W761Chain w761_sqrt_chain() {
+  uint64_t e[12] = {};
+  for (int i = 0; i < 12; i++) e[i] = P761::P64[i];
+  e[0] += 1;                                        // no carry: the low limb of q ends in 0x8b
+  for (int i = 0; i < 12; i++) e[i] = (e[i] >> 2) | (i + 1 < 12 ? e[i + 1] << 62 : 0);
+  W761Chain c;
+  int i = 767;
+  while (!w761_exp_bit(e, i)) i--;
+  bool first = true;
+  while (i >= 0) {
+    if (!w761_exp_bit(e, i)) { c.step[c.len++] = 0; i--; continue; }
+    int j = i - 2 < 0 ? 0 : i - 2;                  // the window [i .. j] ends on a set bit
+    while (!w761_exp_bit(e, j)) j++;
+    int v = 0;
+    for (int b = i; b >= j; b--) v = 2 * v + w761_exp_bit(e, b);
+    if (first) { c.first = v; first = false; }
+    else {
+      for (int b = i; b > j; b--) c.step[c.len++] = 0;
+      c.step[c.len++] = (uint8_t)v;
+    }
+    i = j - 1;
+  }
+  return c;
+}
+struct W761Sqrt { static constexpr W761Chain C = w761_sqrt_chain(); };
+
+HD bool w761_eq(const Fw761& a, const Fw761& b) { return Fw761::eq_mod_p(Fw761::norm(a), Fw761::norm(b)); }
+HD Fw761 w761_neg(const Fw761& a) { return Fw761::wred(Fw761::norm(Fw761::neg<64, 1>(Fw761::norm(a)))); }
+// 96 canonical little-endian bytes -> field element; false when the integer is not below q (Fp::deserialize's from_repr failure).
+// flags: the last byte carries the two flag bits, which are not part of the integer.  (Read in place: a private copy of the bytes
+// would be indexed memory.)
+HD bool w761_from_bytes(const uint8_t* in, Fw761& out, bool flags) {
+  uint64_t w[12];
+  for (int i = 0; i < 12; i++) {
+    uint64_t v = 0;
+    for (int b = 7; b >= 0; b--) v = (v << 8) | in[8 * i + b];
+    w[i] = v;
+  }
+  if (flags) w[11] &= ~(0xC0ull << 56);
+  if (wire_cmp(w, P761::P64, 12) >= 0) return false;
+  out = Fw761::from_canonical(w);
+  return true;
+}
+HD bool w761_lex_largest(const Fw761& a) {   // canonical(a) > (q - 1) / 2
+  uint64_t w[12];
+  a.to_canonical(w);
+  return wire_cmp(w, P761::PM1_HALF64, 12) > 0;
+}
+// x^3 + b for b = -1 (G1) or 4 (G2); [1, <= 10]
+template <int B> HD Fw761 w761_rhs(const Fw761& x) {
+  static_assert(B == -1 || B == 4, "BW6-761: G1 has b = -1, the M-twist G2 b = 4");
+  const Fw761 x3 = Fw761::mul(Fw761::sqr(x), x);
+  if constexpr (B < 0) return Fw761::norm(Fw761::sub<4, 1>(x3, Fw761::one()));
+  else return Fw761::norm(Fw761::add(x3, Fw761::norm(Fw761::dbl(Fw761::dbl(Fw761::one())))));
+}
+// y = a^((q+1)/4) and the check y^2 == a (false: a is a non-residue).  758 squarings and 176 products after the four of the odd powers,
+// the same program in every lane.
+HD bool w761_sqrt(const Fw761& a_, Fw761& out) {
+  constexpr const W761Chain& C = W761Sqrt::C;
+  const Fw761 t1 = Fw761::norm(a_), a2 = Fw761::sqr(t1);
+  const Fw761 t3 = Fw761::mul(t1, a2), t5 = Fw761::mul(t3, a2), t7 = Fw761::mul(t5, a2);
+  static_assert(C.first == 1 || C.first == 3 || C.first == 5 || C.first == 7, "odd leading window");
+  Fw761 r = C.first == 1 ? t1 : C.first == 3 ? t3 : C.first == 5 ? t5 : t7;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+  for (int i = 0; i < C.len; i++) {
+    r = Fw761::sqr(r);
+    const int d = C.step[i];
+    if (d == 1) r = Fw761::mul(r, t1);
+    else if (d == 3) r = Fw761::mul(r, t3);
+    else if (d == 5) r = Fw761::mul(r, t5);
+    else if (d == 7) r = Fw761::mul(r, t7);
+  }
+  if (!w761_eq(Fw761::sqr(r), t1)) return false;
+  out = r;
+  return true;
+}
+// acc += p (madd-2008-s, curve.h xyzz_madd) - except when acc == p, where it returns false and leaves acc for the caller to double: the
+// ladder below then runs its one doubling site instead of xyzz_madd's inlined xyzz_dbl_affine, whose extra live range is what spilled the
+// ladder kernel to ~1 KB of scratch per lane.
+HD bool w761_madd(Xyzz<Fw761>& a, const Affine<Fw761>& p) {
+  typedef Fw761 F;
+  if (a.is_identity()) { a = Xyzz<F>::from_affine(p); return true; }
+  F U2 = F::mul_nn(p.x, a.ZZ);                        // [1, 2]
+  F S2 = F::mul_nn(p.y, a.ZZZ);
+  F Pd = F::prep(F::template sub<32, 1>(U2, a.X));    // [3, 18]
+  F R = F::prep(F::template sub<16, 1>(S2, a.Y));     // [3, 18]
+  if (Pd.is_zero_mod_p()) {
+    if (R.is_zero_mod_p()) return false;
+    a = Xyzz<F>::identity();
+    return true;
+  }
+  F PP = F::sqr_nn(Pd);
+  F PPP = F::mul_nn(Pd, PP);
+  F Q = F::mul_nn(a.X, PP);
+  F R2 = F::sqr_nn(R);
+  F s = F::add(F::add(PPP, Q), Q);                    // [3, 6]
+  F X3 = F::norm(F::template sub<16, 3>(R2, s));       // [1, 10]
+  F t = F::prep(F::template sub<32, 1>(Q, X3));       // [3, 18]
+  F Y3 = F::template mul_sub_nn_at<2>(R, t, a.Y, PPP);
+  a.ZZ = F::mul_nn(a.ZZ, PP);
+  a.ZZZ = F::mul_nn(a.ZZZ, PPP);
+  a.X = X3;
+  a.Y = Y3;
+  return true;
+}
+// r P == O with r = q_BLS12-377 (377 bits), MSB-first double-and-add over XYZZ: ark-ec 0.1 is_in_correct_subgroup_assuming_on_curve as
+// written, the predicate of seam_a.hip bw6_decompress.  The XYZZ formulas of curve.h do not depend on b, so one ladder serves both groups.
+// One group operation per iteration (stage 0: double for bit i; 1: add p for bit i; 2: acc was p, double instead of adding).
+// (No endomorphism form: that would come with this ladder kept as its twin, as wire.h does for BLS12-377.)
+HD bool w761_in_subgroup(const Affine<Fw761>& p) {
+  Xyzz<Fw761> acc = Xyzz<Fw761>::from_affine(p);     // bit 376, the top bit of r
+  int i = 375, stage = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+  while (i >= 0) {
+    if (stage == 1) {
+      if (w761_madd(acc, p)) { stage = 0; i--; continue; }
+      stage = 2;
+    }
+    acc = xyzz_dbl(acc);
+    if (stage == 2) { stage = 0; i--; }
+    else if (w761_exp_bit(P377::P64, i)) stage = 1;
+    else i--;
+  }
+  return acc.is_identity() || acc.ZZ.is_zero_mod_p();
+}
+
+// one point up to the subgroup test: in = 96 B (compressed: x with the flags) or 192 B (uncompressed: x, then y with the flags); check:
+// the curve equation of the uncompressed form.  p is set when WIRE_OK.
+template <int B, bool COMPRESSED> HD WireStatus w761_parse(const uint8_t* in, bool check, Affine<Fw761>& p) {
+  constexpr int NB = COMPRESSED ? 96 : 192;
+  const uint8_t flags = in[NB - 1] & 0xC0;
+  if (flags == 0xC0) return WIRE_INVALID;          // ark-serialize SWFlags::from_u8: (sign, infinity) both set is no encoding at all
+  if (flags & 0x40) return WIRE_INFINITY;
+  Fw761 x, y;
+  if (!w761_from_bytes(in, x, COMPRESSED)) return WIRE_INVALID;
+  if constexpr (COMPRESSED) {
+    if (!w761_sqrt(w761_rhs<B>(x), y)) return WIRE_INVALID;
+    if (w761_lex_largest(y) != ((flags & 0x80) != 0)) y = w761_neg(y);
+  } else {
+    if (!w761_from_bytes(in + 96, y, true)) return WIRE_INVALID;
+    if (check && !w761_eq(Fw761::sqr(y), w761_rhs<B>(x))) return WIRE_INVALID;
+  }
+  p = {Fw761::norm(x), Fw761::norm(y)};
+  return WIRE_OK;
+}
+// the whole decoding (the kernels run it in two passes, w761_parse and w761_in_subgroup: unit_wire761.hip)
+template <int B, bool COMPRESSED> HD WireStatus w761_decode(const uint8_t* in, bool check, Affine<Fw761>& p) {
+  const WireStatus st = w761_parse<B, COMPRESSED>(in, check, p);
+  if (st == WIRE_OK && check && !w761_in_subgroup(p)) return WIRE_NOT_IN_SUBGROUP;
+  return st;
+}
+// the row form the MSM entry points take: 24 u64, (x, y) as arkworks Montgomery limbs; zeros unless WIRE_OK
+template <int B, bool COMPRESSED> HD WireStatus w761_decode_row(const uint8_t* in, bool check, uint64_t* out) {
+  Affine<Fw761> p = {Fw761::zero(), Fw761::zero()};
+  const WireStatus st = w761_decode<B, COMPRESSED>(in, check, p);
+  if (st == WIRE_OK) { p.x.to_ark(out); p.y.to_ark(out + 12); }
+  else for (int j = 0; j < 24; j++) out[j] = 0;
+  return st;
+}
+
+// ---- host: the layout of a serialized ark-groth16 0.1 ProvingKey<BW6_761> (its derive order; Vec = u64 LE length, then the elements):
+//   vk { alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1: Vec<G1> }, beta_g1, delta_g1,
+//   a_query: Vec<G1>, b_g1_query: Vec<G1>, b_g2_query: Vec<G2>, h_query: Vec<G1>, l_query: Vec<G1>
+// The length fields are input: no count * size is formed before count is known to fit what is left.
+enum W761Layout { W761_PT = 0, W761_LEN = 1, W761_ABC = 2, W761_A = 4, W761_BG1 = 6, W761_BG2 = 8, W761_H = 10, W761_L = 12, W761_BETA_G1 = 14, W761_NPOINTS = 15 };
+constexpr int W761_ERR_TRUNCATED = 30, W761_ERR_TRAILING = 31, W761_ERR_LENGTH = 32, W761_ERR_POINT = 33;
+inline int w761_key_layout(const uint8_t* bytes, size_t len, int form, uint64_t out[16]) {
+  if (!out || (!bytes && len) || form < 0 || form > 2) return 2;
+  for (int i = 0; i < 16; i++) out[i] = 0;
+  const uint64_t P = form == 0 ? 96 : 192;
+  uint64_t pos = 0, points = 0;
+  auto take = [&](uint64_t count) -> int {          // count points at pos
+    if (count > UINT64_MAX / P) return W761_ERR_LENGTH;
+    if (count * P > len - pos) return W761_ERR_TRUNCATED;
+    pos += count * P;
+    points += count;
+    return 0;
+  };
+  auto vec = [&](int slot) -> int {                 // u64 length, then the points
+    if (len - pos < 8) return W761_ERR_TRUNCATED;
+    uint64_t n = 0;
+    for (int b = 7; b >= 0; b--) n = (n << 8) | bytes[pos + b];
+    pos += 8;
+    out[slot] = n;
+    out[slot + 1] = pos;
+    return take(n);
+  };
+  int rc = take(4);                                 // alpha_g1, beta_g2, gamma_g2, delta_g2
+  if (!rc) rc = vec(W761_ABC);
+  if (!rc) { out[W761_BETA_G1] = pos; rc = take(2); }   // beta_g1, delta_g1
+  if (!rc) rc = vec(W761_A);
+  if (!rc) rc = vec(W761_BG1);
+  if (!rc) rc = vec(W761_BG2);
+  if (!rc) rc = vec(W761_H);
+  if (!rc) rc = vec(W761_L);
+  if (rc) return rc;
+  if (pos != len) return W761_ERR_TRAILING;
+  out[W761_PT] = P;
+  out[W761_LEN] = len;
+  out[W761_NPOINTS] = points;
+  return 0;
+}
+
+}  // namespace celo

@@ -42,6 +42,9 @@ EXPORTS = [
     "ntt_bw6_761_fr", "ntt_bw6_761_fr_dev",
     "groth16_witness_map_bw6_761", "groth16_witness_map_bw6_761_dev", "groth16_prove_bw6_761",
     "decompress_bls12_377_g1", "decompress_bls12_377_g2", "decompress_bls12_377_g1_dev", "decompress_bls12_377_g2_dev",
+    "decompress_bw6_761_g1", "decompress_bw6_761_g2", "decompress_bw6_761_g1_dev", "decompress_bw6_761_g2_dev",
+    "decode_uncompressed_bw6_761_g1", "decode_uncompressed_bw6_761_g2", "groth16_key_layout_bw6_761", "groth16_load_key_bw6_761_serialized",
+    "celo_amd_wire761_last_timings",
     "normalize_bls12_377_g1", "normalize_bls12_377_g2",
     "hash_to_g1_direct_bls12_377", "hash_to_g1_composite_bls12_377", "hash_to_g1_cip22_tail_bls12_377", "composite_crh_bls12_377",
 ]
@@ -524,6 +527,28 @@ def groth16_prove(a_query, b_g2_query, h_query, l_query, alpha_g1, beta_g2, assi
     return out
 
 
+# groth16_key_layout_bw6_761 / groth16_load_key_bw6_761_serialized (include/celo_bls_amd.h)
+KEY_ERR_TRUNCATED, KEY_ERR_TRAILING, KEY_ERR_LENGTH, KEY_ERR_POINT = 30, 31, 32, 33
+KEY_LAYOUT_SLOTS = {"point_bytes": 0, "len": 1, "gamma_abc_g1": 2, "a_query": 4, "b_g1_query": 6, "b_g2_query": 8, "h_query": 10, "l_query": 12}
+
+
+class KeyLoadError(RuntimeError):
+    def __init__(self, code, first_bad_point=None):
+        super().__init__("groth16_load_key_bw6_761_serialized failed with code %d%s"
+                         % (code, "" if first_bad_point is None else " (first rejected point: %d)" % first_bad_point))
+        self.code = code
+        self.first_bad_point = first_bad_point
+
+
+def groth16_key_layout(data, form=0):
+    """Host walk of a serialized ProvingKey<BW6_761> (groth16_key_layout_bw6_761): returns (rc, out) with out the 16 u64 of the header
+    ({section: (count, byte offset)} via KEY_LAYOUT_SLOTS; out[14] the offset of beta_g1, out[15] the number of points)."""
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    out = np.zeros(16, dtype=np.uint64)
+    rc = lib().groth16_key_layout_bw6_761(_p(buf), C.c_size_t(buf.size), C.c_int(form), _p(out))
+    return rc, out
+
+
 class ProvingKey:
     """A loaded Groth16 proving key (groth16_load_key_bw6_761 / _bls12_377): the four queries' fixed-base tables, built once; prove() per
     assignment.  curve: "bw6_761" (points (k, 24), scalars (k, 6)) or "bls12_377" (G1 (k, 12), G2 (k, 24), scalars (k, 4))."""
@@ -532,16 +557,31 @@ class ProvingKey:
         g1w = 24 if curve == "bw6_761" else 12
         self.sw = 6 if curve == "bw6_761" else 4
         self.ow = (36, 36, 36) if curve == "bw6_761" else (18, 36, 18)
+        self.h = C.c_void_p()
+        if a_query is None:                 # from_serialized fills the handle
+            return
         q = [np.ascontiguousarray(a_query, dtype=np.uint64).reshape(-1, g1w), np.ascontiguousarray(b_g2_query, dtype=np.uint64).reshape(-1, 24),
              np.ascontiguousarray(h_query, dtype=np.uint64).reshape(-1, g1w), np.ascontiguousarray(l_query, dtype=np.uint64).reshape(-1, g1w)]
         al = np.ascontiguousarray(alpha_g1, dtype=np.uint64).reshape(g1w)
         be = np.ascontiguousarray(beta_g2, dtype=np.uint64).reshape(24)
-        self.h = C.c_void_p()
         fn = lib().groth16_load_key_bw6_761 if curve == "bw6_761" else lib().groth16_load_key_bls12_377
         rc = fn(_p(q[0]), C.c_size_t(q[0].shape[0]), _p(q[1]), C.c_size_t(q[1].shape[0]), _p(q[2]), C.c_size_t(q[2].shape[0]), _p(q[3]), C.c_size_t(q[3].shape[0]),
                 _p(al), _p(be), C.c_int(window_bits), C.byref(self.h))
         if rc != 0:
             raise RuntimeError("groth16_load_key_%s failed with code %d" % (curve, rc))
+
+    @classmethod
+    def from_serialized(cls, data, form=0, window_bits=0):
+        """A BW6-761 key from the bytes of a serialized ark-groth16 0.1 ProvingKey<BW6_761> (groth16_load_key_bw6_761_serialized): form 0 =
+        compressed, checked; 1 = uncompressed, checked; 2 = uncompressed, unchecked.  Raises KeyLoadError (.code, .first_bad_point)."""
+        k = cls("bw6_761", None, None, None, None, None, None)
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        bad = C.c_uint64(0)
+        rc = lib().groth16_load_key_bw6_761_serialized(_p(buf), C.c_size_t(buf.size), C.c_int(form), C.c_int(window_bits), C.byref(k.h), C.byref(bad))
+        if rc != 0:
+            k.h = C.c_void_p()
+            raise KeyLoadError(rc, bad.value if rc == KEY_ERR_POINT else None)
+        return k
 
     def prove(self, assignment, n_aux, h):
         asg = np.ascontiguousarray(assignment, dtype=np.uint64).reshape(-1, self.sw)
@@ -678,10 +718,12 @@ def pairing_gt_bw6(g1_xy, inf1, g2_xy, inf2, offsets, miller_only=False):
 
 
 def decompress(group, data, check_subgroup=True):
-    """Bulk decoding of compressed points (include/celo_bls_amd.h: decompress_bls12_377_g1/_g2).  group: "g1" (48 B each) or
-    "g2" (96 B each); data: bytes of n concatenated encodings.  Returns (xy, status): xy (n, 12 | 24) uint64 affine arkworks
-    Montgomery limbs (zero rows unless status == 0), status (n,) uint8 (0 ok, 1 infinity, 2 invalid, 3 not in subgroup)."""
-    size, words, fn = {"g1": (48, 12, "decompress_bls12_377_g1"), "g2": (96, 24, "decompress_bls12_377_g2")}[group]
+    """Bulk decoding of compressed points (include/celo_bls_amd.h: decompress_bls12_377_g1/_g2, decompress_bw6_761_g1/_g2).  group:
+    "g1" (48 B each), "g2" (96 B each), "bw6_761_g1" / "bw6_761_g2" (96 B each); data: bytes of n concatenated encodings.  Returns
+    (xy, status): xy (n, 12 | 24) uint64 affine arkworks Montgomery limbs (zero rows unless status == 0), status (n,) uint8 (0 ok,
+    1 infinity, 2 invalid, 3 not in subgroup)."""
+    size, words, fn = {"g1": (48, 12, "decompress_bls12_377_g1"), "g2": (96, 24, "decompress_bls12_377_g2"),
+                       "bw6_761_g1": (96, 24, "decompress_bw6_761_g1"), "bw6_761_g2": (96, 24, "decompress_bw6_761_g2")}[group]
     buf = np.frombuffer(bytes(data), dtype=np.uint8)
     assert buf.size % size == 0
     n = buf.size // size
@@ -694,10 +736,34 @@ def decompress(group, data, check_subgroup=True):
 
 
 def decompress_dev(group, d_in, n, d_out, d_status, check_subgroup=True, stream=0):
-    fn = {"g1": "decompress_bls12_377_g1_dev", "g2": "decompress_bls12_377_g2_dev"}[group]
+    fn = {"g1": "decompress_bls12_377_g1_dev", "g2": "decompress_bls12_377_g2_dev",
+          "bw6_761_g1": "decompress_bw6_761_g1_dev", "bw6_761_g2": "decompress_bw6_761_g2_dev"}[group]
     rc = getattr(lib(), fn)(C.c_void_p(d_in), C.c_size_t(n), C.c_int(1 if check_subgroup else 0), C.c_void_p(d_out), C.c_void_p(d_status), C.c_void_p(stream))
     if rc != 0:
         raise RuntimeError("%s failed with code %d" % (fn, rc))
+
+
+def decode_uncompressed(group, data, check=True):
+    """Bulk decoding of uncompressed BW6-761 points (decode_uncompressed_bw6_761_g1/_g2): group "bw6_761_g1" / "bw6_761_g2", 192 B each
+    (x, then y with the flags).  check: on the curve and in the subgroup (deserialize_uncompressed); False: range only
+    (deserialize_unchecked).  Returns (xy (n, 24) uint64, status (n,) uint8) as decompress()."""
+    fn = {"bw6_761_g1": "decode_uncompressed_bw6_761_g1", "bw6_761_g2": "decode_uncompressed_bw6_761_g2"}[group]
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    assert buf.size % 192 == 0
+    n = buf.size // 192
+    xy = np.zeros((n, 24), dtype=np.uint64)
+    st = np.zeros(n, dtype=np.uint8)
+    rc = getattr(lib(), fn)(_p(buf), C.c_size_t(n), C.c_int(1 if check else 0), _p(xy), _p(st))
+    if rc != 0:
+        raise RuntimeError("%s failed with code %d" % (fn, rc))
+    return xy, st
+
+
+def wire761_last_timings():
+    """(kernel ms of the last BW6-761 decode call, the last serialized key load's transfer / decode / table-build ms)"""
+    ms = (C.c_float * 4)()
+    assert lib().celo_amd_wire761_last_timings(ms) == 0
+    return tuple(ms)
 
 
 def decompress_last_ms():

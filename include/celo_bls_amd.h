@@ -337,6 +337,57 @@ int normalize_bls12_377_g2(const uint64_t* jac /* n x 36 */, size_t n, uint64_t*
 /* kernel time (HIP events) of the last decompress / normalize call */
 int celo_amd_decompress_last_ms(float* ms);
 
+/* ---- bulk decoding of serialized BW6-761 points (the curve of every prover MSM): arkworks 0.1
+ * CanonicalDeserialize of G1 (y^2 = x^3 - 1) and G2 (the M-twist y^2 = x^3 + 4, coordinates in Fq) points, 96 B per coordinate,
+ * little-endian, flags in the two top bits of the last byte (0x40 infinity, 0x80 "y is the larger root").  One point per GPU lane
+ * (csrc/wire761.h, csrc/unit_wire761.hip): the square root rhs^((q+1)/4), the sign choice and, when checked, r*P == O with
+ * r = r_BW6 = q_BLS12-377 by a 377-bit ladder - the predicate of ark-ec 0.1 is_in_correct_subgroup_assuming_on_curve.
+ *   decompress_bw6_761_*:          96 B points; check_subgroup != 0 is GroupAffine::deserialize (what ark-groth16 runs per point of a
+ *                                  ProvingKey / VerifyingKey / Proof: crates/epoch-snark/src/api/setup.rs:12,17-20, the "serialized byte
+ *                                  arrays of compressed elements" of crates/bls-snark-sys/src/snark/mod.rs:13-17), 0 skips the subgroup test.
+ *   decode_uncompressed_bw6_761_*: 192 B points (x, then y with the flags on y's last byte); check != 0: on the curve and in the subgroup
+ *                                  (deserialize_uncompressed - stricter than ark 0.1, which may skip the curve equation: an off-curve point
+ *                                  is status 2 here), check == 0: the canonical range only (deserialize_unchecked).
+ * out_xy: n x 24 u64, affine (x, y) in arkworks Montgomery limbs - the layout msm_bw6_761_* take - all zero unless status[i] == 0.
+ * status[i], checks in this order: flags 0xC0 -> 2; infinity flag -> 1 (before any range check); a coordinate >= q -> 2; no square root
+ * (compressed) or off the curve (uncompressed, checked) -> 2; checked and r*P != O -> 3; else 0.  The _dev forms take device pointers
+ * and run on hip_stream (0: the null stream); calls are serialised per process. */
+int decompress_bw6_761_g1(const uint8_t* in /* n x 96 */, size_t n, int check_subgroup, uint64_t* out_xy /* n x 24 */, uint8_t* status /* n */);
+int decompress_bw6_761_g2(const uint8_t* in /* n x 96 */, size_t n, int check_subgroup, uint64_t* out_xy /* n x 24 */, uint8_t* status /* n */);
+int decompress_bw6_761_g1_dev(const uint8_t* d_in, size_t n, int check_subgroup, uint64_t* d_out_xy, uint8_t* d_status, void* hip_stream);
+int decompress_bw6_761_g2_dev(const uint8_t* d_in, size_t n, int check_subgroup, uint64_t* d_out_xy, uint8_t* d_status, void* hip_stream);
+int decode_uncompressed_bw6_761_g1(const uint8_t* in /* n x 192 */, size_t n, int check, uint64_t* out_xy /* n x 24 */, uint8_t* status /* n */);
+int decode_uncompressed_bw6_761_g2(const uint8_t* in /* n x 192 */, size_t n, int check, uint64_t* out_xy /* n x 24 */, uint8_t* status /* n */);
+/* ---- a serialized ark-groth16 0.1 ProvingKey<BW6_761> (the reference's Groth16Parameters, crates/epoch-snark/src/api/setup.rs:12,17-20),
+ * in the derive order of the struct; a Vec is a u64 little-endian length followed by its elements:
+ *   vk { alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1: Vec<G1> }, beta_g1, delta_g1,
+ *   a_query: Vec<G1>, b_g1_query: Vec<G1>, b_g2_query: Vec<G2>, h_query: Vec<G1>, l_query: Vec<G1>
+ * (the VK prefix is the one csrc/seam_a.hip verify parses).  form: 0 = compressed, checked (ProvingKey::deserialize); 1 = uncompressed,
+ * checked (deserialize_uncompressed); 2 = uncompressed, unchecked (deserialize_unchecked).  Points are 96 B (form 0) or 192 B.
+ *
+ * groth16_key_layout_bw6_761: a host walk of that structure (no device call).  out[16]:
+ *   [0] bytes per point        [1] len                      [2] / [3]   gamma_abc_g1: count / byte offset of its first point
+ *   [4] / [5]   a_query        [6] / [7]   b_g1_query       [8] / [9]   b_g2_query      [10] / [11] h_query      [12] / [13] l_query
+ *   [14] byte offset of beta_g1 (delta_g1 follows)          [15] the number of points in the key
+ * (alpha_g1, beta_g2, gamma_g2, delta_g2 are the points at offsets 0, 1, 2, 3 x [0].)  Points are indexed in serialization order:
+ * 0 alpha_g1, 1-3 beta/gamma/delta_g2, then gamma_abc_g1, beta_g1, delta_g1, a_query, b_g1_query, b_g2_query, h_query, l_query.
+ * Returns 0, 2 (bad arguments), 30 (truncated: the input ends inside a length field or a section), 31 (bytes left over after l_query)
+ * or 32 (a length field whose byte size does not fit 64 bits).  Lengths are checked against what is left before any product is formed.
+ *
+ * groth16_load_key_bw6_761_serialized: the layout walk, one copy of the bytes to the device, every point of every section decoded and checked
+ * there (those create_proof_no_zk never reads included: gamma_*, delta_*, beta_g1, b_g1_query - a corrupt one fails the load as ark's
+ * deserialize would), the four queries decoded straight into the buffers their fixed-base tables are built from (no decoded limbs return to
+ * the host), then the key groth16_load_key_bw6_761 would build with alpha_g1 = vk.alpha_g1 and beta_g2 = vk.beta_g2; a point at infinity in
+ * a query is that row's identity.  It proves with groth16_prove_with_key and is released with groth16_free_key.  Returns the layout codes
+ * above, 2 (bad arguments, or an empty a_query / b_g2_query: the proof needs their first rows), 33 (a point was rejected: status 2 or 3
+ * above; *first_bad_point = its index in serialization order), or the codes of groth16_load_key_bw6_761.  On any failure everything is
+ * freed and *out_key stays NULL; first_bad_point (may be NULL) is written only with 33. */
+int groth16_key_layout_bw6_761(const uint8_t* bytes, size_t len, int form, uint64_t out[16]);
+int groth16_load_key_bw6_761_serialized(const uint8_t* bytes, size_t len, int form, int window_bits, void** out_key, uint64_t* first_bad_point);
+/* ms[0]: kernel time of the last decompress_bw6_761_* / decode_uncompressed_bw6_761_* call; ms[1..3]: the last serialized key load's
+ * transfer of the bytes, decoding (all sections and the rejection scan) and fixed-base table build */
+int celo_amd_wire761_last_timings(float ms[4]);
+
 /* ---- batched hash-to-G1, DIRECT hasher: n messages per launch, one per GPU lane.
  * Replaces n calls of TryAndIncrement<DirectHasher, G1>::hash_with_attempt(domain, message, extra_data)
  * (crates/bls-crypto/src/hash_to_curve/try_and_increment.rs:87-139; DirectHasher = Blake2s CRH + Blake2Xs XOF,
