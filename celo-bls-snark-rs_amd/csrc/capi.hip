@@ -83,6 +83,12 @@ int wire761_key_load(const uint8_t*, size_t, int, int, ProvingKey**, uint64_t*);
 void wire761_last_timings(float*);
 float wire_last_ms();
 int wire_normalize(int, const uint64_t*, size_t, uint64_t*, uint8_t*);
+int fixed_base_mul(int, const uint64_t*, const void*, size_t, void*, void*, int, void*);   // unit_setup.hip
+int fixed_base_set_window(int);
+void setup_last_timings(float*);
+int normalize_761(const uint64_t*, size_t, uint64_t*, uint8_t*);
+int groth16_setup(int, const uint64_t*, const uint64_t*, const uint64_t*, size_t, size_t, const uint64_t*, const uint64_t*, size_t, const uint64_t*, const uint64_t*,
+                  const uint64_t*, int, uint64_t*, uint64_t*, ProvingKey**);
 int hash_to_g1_direct_run(const uint8_t*, const uint8_t*, const uint64_t*, const uint8_t*, const uint64_t*, size_t, uint64_t*, uint8_t*, int);
 float hash_last_ms();
 int pedersen_crh_run(const uint8_t*, const uint64_t*, size_t, uint8_t*);
@@ -435,6 +441,37 @@ int composite_crh_bls12_377(const uint8_t* msgs, const uint64_t* msg_off, size_t
 int celo_amd_hash_last_ms(float* ms) { if (!ms) return 2; *ms = hash_last_ms(); return 0; }
 int normalize_bls12_377_g1(const uint64_t* jac, size_t n, uint64_t* out_xy, uint8_t* inf) { return wire_normalize(0, jac, n, out_xy, inf); }
 int normalize_bls12_377_g2(const uint64_t* jac, size_t n, uint64_t* out_xy, uint8_t* inf) { return wire_normalize(1, jac, n, out_xy, inf); }
+// ---- batched fixed-base scalar multiplication and Groth16 setup (unit_setup.hip)
+int fixed_base_mul_bls12_377_g1(const uint64_t gen_xy[12], const uint64_t* scalars, size_t n, uint64_t* out_xy, uint8_t* inf) { return fixed_base_mul(0, gen_xy, scalars, n, out_xy, inf, 0, nullptr); }
+int fixed_base_mul_bls12_377_g2(const uint64_t gen_xy[24], const uint64_t* scalars, size_t n, uint64_t* out_xy, uint8_t* inf) { return fixed_base_mul(1, gen_xy, scalars, n, out_xy, inf, 0, nullptr); }
+int fixed_base_mul_bw6_761_g1(const uint64_t gen_xy[24], const uint64_t* scalars, size_t n, uint64_t* out_xy, uint8_t* inf) { return fixed_base_mul(2, gen_xy, scalars, n, out_xy, inf, 0, nullptr); }
+int fixed_base_mul_bw6_761_g2(const uint64_t gen_xy[24], const uint64_t* scalars, size_t n, uint64_t* out_xy, uint8_t* inf) { return fixed_base_mul(2, gen_xy, scalars, n, out_xy, inf, 0, nullptr); }
+int fixed_base_mul_bls12_377_g1_dev(const uint64_t* gen_xy, const void* d_scalars, size_t n, void* d_out_xy, void* d_inf, void* hip_stream) {
+  return fixed_base_mul(0, gen_xy, d_scalars, n, d_out_xy, d_inf, 1, hip_stream);
+}
+int fixed_base_mul_bls12_377_g2_dev(const uint64_t* gen_xy, const void* d_scalars, size_t n, void* d_out_xy, void* d_inf, void* hip_stream) {
+  return fixed_base_mul(1, gen_xy, d_scalars, n, d_out_xy, d_inf, 1, hip_stream);
+}
+int fixed_base_mul_bw6_761_g1_dev(const uint64_t* gen_xy, const void* d_scalars, size_t n, void* d_out_xy, void* d_inf, void* hip_stream) {
+  return fixed_base_mul(2, gen_xy, d_scalars, n, d_out_xy, d_inf, 1, hip_stream);
+}
+int fixed_base_mul_bw6_761_g2_dev(const uint64_t* gen_xy, const void* d_scalars, size_t n, void* d_out_xy, void* d_inf, void* hip_stream) {
+  return fixed_base_mul(2, gen_xy, d_scalars, n, d_out_xy, d_inf, 1, hip_stream);
+}
+int normalize_bw6_761_g1(const uint64_t* jac, size_t n, uint64_t* out_xy, uint8_t* inf) { return normalize_761(jac, n, out_xy, inf); }
+int normalize_bw6_761_g2(const uint64_t* jac, size_t n, uint64_t* out_xy, uint8_t* inf) { return normalize_761(jac, n, out_xy, inf); }
+int groth16_setup_bw6_761(const uint64_t* qap_a, const uint64_t* qap_b, const uint64_t* qap_c, size_t n_vars, size_t n_inputs, const uint64_t zt[6], const uint64_t tau[6],
+                          size_t n_h, const uint64_t toxic[24], const uint64_t g1_xy[24], const uint64_t g2_xy[24], int window_bits, uint64_t* out_vk,
+                          uint64_t* out_rows, void** out_key) {
+  return groth16_setup(0, qap_a, qap_b, qap_c, n_vars, n_inputs, zt, tau, n_h, toxic, g1_xy, g2_xy, window_bits, out_vk, out_rows, (ProvingKey**)out_key);
+}
+int groth16_setup_bls12_377(const uint64_t* qap_a, const uint64_t* qap_b, const uint64_t* qap_c, size_t n_vars, size_t n_inputs, const uint64_t zt[4],
+                            const uint64_t tau[4], size_t n_h, const uint64_t toxic[16], const uint64_t g1_xy[12], const uint64_t g2_xy[24], int window_bits,
+                            uint64_t* out_vk, uint64_t* out_rows, void** out_key) {
+  return groth16_setup(1, qap_a, qap_b, qap_c, n_vars, n_inputs, zt, tau, n_h, toxic, g1_xy, g2_xy, window_bits, out_vk, out_rows, (ProvingKey**)out_key);
+}
+int celo_amd_fixed_base_set_window(int window_bits) { return fixed_base_set_window(window_bits); }
+int celo_amd_setup_last_timings(float ms[8]) { if (!ms) return 2; setup_last_timings(ms); return 0; }
 int celo_amd_decompress_last_ms(float* ms) { if (!ms) return 2; *ms = wire_last_ms(); return 0; }
 int celo_amd_msm_last_timings(int group, float ms[5], int cfg[3]) {
   switch (group) {

@@ -9,6 +9,7 @@
 #include "curve_lanes.h"
 #include "wire.h"
 #include "wire761.h"
+#include "fixed_base.h"
 #include "hash_direct.h"
 #include "host64.h"
 #include <cstring>
@@ -447,5 +448,74 @@ void ht_add_affine_raw_377(const uint32_t* x1, const uint32_t* y1, const uint32_
   xyzz_madd(b, q);
   xyzz_to_jac(a, out_start);
   xyzz_to_jac(b, out_madd);
+}
+
+// ---- fixed_base.h: the table build, the digit recoding, the table lookup and the accumulation of unit_setup.hip's kernels, run in host loops
+// (the affine form of each row by its own inversion, where the device batches them).  group: 0 BLS12-377 G1, 1 BLS12-377 G2, 2 BW6-761.
+extern "C++" {
+template <class F, int N64> static void fbm_host(const uint64_t* gen, const uint64_t* sc, size_t n, int c, int bits, uint64_t* out, uint8_t* inf) {
+  constexpr int FW = F::WORDS, A = F::ARK64;
+  const int W = fb_windows(bits, c);
+  const uint32_t H = 1u << (c - 1), E = (uint32_t)W * H;
+  std::vector<uint32_t> bases((size_t)W * 2 * FW), table((size_t)E * 2 * FW);
+  std::vector<uint8_t> binf(W), tinf(E);
+  const Affine<F> g = {F::norm(F::from_ark(gen)), F::norm(F::from_ark(gen + A))};
+  for (int w = 0; w < W; w++) {
+    Affine<F> b = {F::zero(), F::zero()};
+    binf[w] = fb_to_affine(fb_window_base(g, w, c), b) ? 0 : 1;
+    fb_store_entry(&bases[(size_t)w * 2 * FW], b);
+  }
+  for (uint32_t e = 0; e < E; e++) {
+    const uint32_t w = e / H, d = e - w * H + 1;
+    Affine<F> r = {F::zero(), F::zero()};
+    bool ok = false;
+    if (!binf[w]) ok = fb_to_affine(fb_table_entry(fb_load_entry<F>(&bases[(size_t)w * 2 * FW]), d), r);
+    fb_store_entry(&table[(size_t)e * 2 * FW], r);
+    tinf[e] = ok ? 0 : 1;
+  }
+  for (size_t i = 0; i < n; i++) {
+    const Xyzz<F> a = fb_scalar_mul<F, N64>(sc + i * N64, table.data(), tinf.data(), c, W);
+    Affine<F> r;
+    uint64_t* o = out + i * 2 * A;
+    if (fb_to_affine(a, r)) { r.x.to_ark(o); r.y.to_ark(o + A); inf[i] = 0; }
+    else { for (int k = 0; k < 2 * A; k++) o[k] = 0; inf[i] = 1; }
+  }
+}
+}  // extern "C++"
+void ht_fixed_base_mul(int group, const uint64_t* gen, const uint64_t* sc, size_t n, int c, uint64_t* out, uint8_t* inf) {
+  if (group == 0) fbm_host<Fp<P377>, 4>(gen, sc, n, c, 253, out, inf);
+  else if (group == 1) fbm_host<Fp2<P377>, 4>(gen, sc, n, c, 253, out, inf);
+  else fbm_host<Fp<P761>, 6>(gen, sc, n, c, 377, out, inf);
+}
+// the setup's scalar lists as unit_setup.hip lays them out: G1 [alpha, beta, delta, gamma_abc, a, b, h, l], G2 [beta, gamma, delta, b]
+extern "C++" {
+template <class FR> static void setup_host(const uint64_t* qa, const uint64_t* qb, const uint64_t* qc, size_t n_vars, size_t n_inputs, const uint64_t* zt,
+                                           const uint64_t* tau, size_t n_h, const uint64_t* toxic, uint64_t* g1s, uint64_t* g2s) {
+  constexpr int N = FR::ARK64;
+  const FR alpha = FR::norm(FR::from_ark(toxic)), beta = FR::norm(FR::from_ark(toxic + N));
+  const FR ginv = FR::norm(FR::inv(FR::norm(FR::from_ark(toxic + 2 * N)))), dinv = FR::norm(FR::inv(FR::norm(FR::from_ark(toxic + 3 * N))));
+  setup_canon<FR>(toxic, g1s); setup_canon<FR>(toxic + N, g1s + N); setup_canon<FR>(toxic + 3 * N, g1s + 2 * N);
+  setup_canon<FR>(toxic + N, g2s); setup_canon<FR>(toxic + 2 * N, g2s + N); setup_canon<FR>(toxic + 3 * N, g2s + 2 * N);
+  const size_t off_abc = 3, off_a = off_abc + n_inputs, off_b = off_a + n_vars, off_h = off_b + n_vars, off_l = off_h + n_h;
+  for (size_t i = 0; i < n_vars; i++) {
+    const bool inst = i < n_inputs;
+    setup_lc<FR>(qa + i * N, qb + i * N, qc + i * N, alpha, beta, inst ? ginv : dinv, g1s + (inst ? off_abc + i : off_l + (i - n_inputs)) * N);
+    setup_canon<FR>(qa + i * N, g1s + (off_a + i) * N);
+    setup_canon<FR>(qb + i * N, g1s + (off_b + i) * N);
+    setup_canon<FR>(qb + i * N, g2s + (3 + i) * N);
+  }
+  if (n_h) {
+    const FR zt_dinv = FR::norm(FR::mul(FR::from_ark(zt), dinv)), t = FR::norm(FR::from_ark(tau));
+    for (size_t i0 = 0; i0 < n_h; i0 += SETUP_H_BLOCK) {
+      const uint32_t cnt = n_h - i0 < SETUP_H_BLOCK ? (uint32_t)(n_h - i0) : SETUP_H_BLOCK;
+      setup_h_block<FR>(zt_dinv, t, i0, cnt, g1s + (off_h + i0) * N);
+    }
+  }
+}
+}  // extern "C++"
+void ht_setup_scalars(int curve, const uint64_t* qa, const uint64_t* qb, const uint64_t* qc, size_t n_vars, size_t n_inputs, const uint64_t* zt,
+                      const uint64_t* tau, size_t n_h, const uint64_t* toxic, uint64_t* g1s, uint64_t* g2s) {
+  if (curve == 0) setup_host<Fp<P377>>(qa, qb, qc, n_vars, n_inputs, zt, tau, n_h, toxic, g1s, g2s);
+  else setup_host<Fp<P253>>(qa, qb, qc, n_vars, n_inputs, zt, tau, n_h, toxic, g1s, g2s);
 }
 }

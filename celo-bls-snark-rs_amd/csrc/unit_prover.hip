@@ -264,23 +264,33 @@ int groth16_key_load(int curve, const uint64_t* a_query, size_t na, const uint64
   *out = k;
   return 0;
 }
-// The same key from DEVICE rows (wire761_key_load, unit_wire761.hip): the four BW6-761 queries as decoded there (24 u64 per row, row 0 of a / b
-// included) with their per-row identity bytes, and the four key elements as host rows.  The tables are built where the rows lie.
-int groth16_key_load_dev_761(const uint64_t* d_a, const uint8_t* d_ainf, size_t na, const uint64_t* d_b, const uint8_t* d_binf, size_t nb,
-                             const uint64_t* d_h, const uint8_t* d_hinf, size_t nh, const uint64_t* d_l, const uint8_t* d_linf, size_t nl,
-                             const uint64_t* a0, const uint64_t* b0, const uint64_t* alpha_g1, const uint64_t* beta_g2, int window_bits, ProvingKey** out) {
+// The same key from DEVICE rows (wire761_key_load, unit_wire761.hip; groth16_setup, unit_setup.hip): the four queries as they lie there (affine
+// arkworks rows, row 0 of a / b included) with their per-row identity bytes, and the four key elements as host rows.  The tables are built
+// where the rows lie.  curve 0 = BW6-761 (all rows 24 u64), 1 = BLS12-377 (G1 rows 12 u64, G2 rows 24).
+int groth16_key_load_dev(int curve, const uint64_t* d_a, const uint8_t* d_ainf, size_t na, const uint64_t* d_b, const uint8_t* d_binf, size_t nb,
+                         const uint64_t* d_h, const uint8_t* d_hinf, size_t nh, const uint64_t* d_l, const uint8_t* d_linf, size_t nl,
+                         const uint64_t* a0, const uint64_t* b0, const uint64_t* alpha_g1, const uint64_t* beta_g2, int window_bits, ProvingKey** out) {
   if (int rc0 = api_enter()) return rc0;
-  if (!d_a || !d_b || !a0 || !b0 || !alpha_g1 || !beta_g2 || !out || na == 0 || nb == 0 || (nh && !d_h) || (nl && !d_l)) return 2;
+  if (!d_a || !d_b || !a0 || !b0 || !alpha_g1 || !beta_g2 || !out || na == 0 || nb == 0 || (nh && !d_h) || (nl && !d_l) || curve < 0 || curve > 1) return 2;
+  const int r1 = curve ? 12 : 24;
   ProvingKey* k = new ProvingKey();
-  k->curve = 0; k->na = na; k->nb = nb; k->nl = nl; k->nh = nh; k->device = api_device();
-  k->a0.assign(a0, a0 + 24); k->b0.assign(b0, b0 + 24); k->alpha.assign(alpha_g1, alpha_g1 + 24); k->beta.assign(beta_g2, beta_g2 + 24);
-  int rc = na > 1 ? msm_fixed_build_761(d_a + 24, d_ainf + 1, na - 1, 1, window_bits, &k->a) : 0;
-  if (!rc && nb > 1) rc = msm_fixed_build_761(d_b + 24, d_binf + 1, nb - 1, 1, window_bits, &k->b);
-  if (!rc && nl) rc = msm_fixed_build_761(d_l, d_linf, nl, 1, window_bits, &k->l);
-  if (!rc && nh) rc = msm_fixed_build_761(d_h, d_hinf, nh, 1, window_bits, &k->h);
+  k->curve = curve; k->na = na; k->nb = nb; k->nl = nl; k->nh = nh; k->device = api_device();
+  k->a0.assign(a0, a0 + r1); k->b0.assign(b0, b0 + 24); k->alpha.assign(alpha_g1, alpha_g1 + r1); k->beta.assign(beta_g2, beta_g2 + 24);
+  auto build1 = [&](const uint64_t* q, const uint8_t* f, size_t n, FixedTable** t) -> int {        // a G1 query
+    return curve ? msm_fixed_build_g1_377(q, f, n, 1, window_bits, t) : msm_fixed_build_761(q, f, n, 1, window_bits, t);
+  };
+  int rc = na > 1 ? build1(d_a + r1, d_ainf + 1, na - 1, &k->a) : 0;
+  if (!rc && nb > 1) rc = curve ? msm_fixed_build_g2_377(d_b + 24, d_binf + 1, nb - 1, 1, window_bits, &k->b) : msm_fixed_build_761(d_b + 24, d_binf + 1, nb - 1, 1, window_bits, &k->b);
+  if (!rc && nl) rc = build1(d_l, d_linf, nl, &k->l);
+  if (!rc && nh) rc = build1(d_h, d_hinf, nh, &k->h);
   if (rc) { groth16_key_free(k); return rc; }
   *out = k;
   return 0;
+}
+int groth16_key_load_dev_761(const uint64_t* d_a, const uint8_t* d_ainf, size_t na, const uint64_t* d_b, const uint8_t* d_binf, size_t nb,
+                             const uint64_t* d_h, const uint8_t* d_hinf, size_t nh, const uint64_t* d_l, const uint8_t* d_linf, size_t nl,
+                             const uint64_t* a0, const uint64_t* b0, const uint64_t* alpha_g1, const uint64_t* beta_g2, int window_bits, ProvingKey** out) {
+  return groth16_key_load_dev(0, d_a, d_ainf, na, d_b, d_binf, nb, d_h, d_hinf, nh, d_l, d_linf, nl, a0, b0, alpha_g1, beta_g2, window_bits, out);
 }
 int groth16_prove_keyed(const ProvingKey* k, const uint64_t* assignment, size_t n_assign, size_t n_aux, const uint64_t* h, size_t n_h, uint64_t* out_a, uint64_t* out_b,
                         uint64_t* out_c) {

@@ -46,6 +46,10 @@ EXPORTS = [
     "decode_uncompressed_bw6_761_g1", "decode_uncompressed_bw6_761_g2", "groth16_key_layout_bw6_761", "groth16_load_key_bw6_761_serialized",
     "celo_amd_wire761_last_timings",
     "normalize_bls12_377_g1", "normalize_bls12_377_g2",
+    "fixed_base_mul_bls12_377_g1", "fixed_base_mul_bls12_377_g2", "fixed_base_mul_bw6_761_g1", "fixed_base_mul_bw6_761_g2",
+    "fixed_base_mul_bls12_377_g1_dev", "fixed_base_mul_bls12_377_g2_dev", "fixed_base_mul_bw6_761_g1_dev", "fixed_base_mul_bw6_761_g2_dev",
+    "normalize_bw6_761_g1", "normalize_bw6_761_g2", "groth16_setup_bw6_761", "groth16_setup_bls12_377",
+    "celo_amd_fixed_base_set_window", "celo_amd_setup_last_timings",
     "hash_to_g1_direct_bls12_377", "hash_to_g1_composite_bls12_377", "hash_to_g1_cip22_tail_bls12_377", "composite_crh_bls12_377",
 ]
 
@@ -828,9 +832,10 @@ def composite_crh(messages):
 
 
 def normalize(group, jac):
-    """Jacobian -> affine for n points in one GPU launch (include/celo_bls_amd.h: normalize_bls12_377_g1/_g2).  jac: (n, 18 | 36)
-    uint64; returns (xy (n, 12 | 24) uint64, inf (n,) uint8)."""
-    words, fn = {"g1": (6, "normalize_bls12_377_g1"), "g2": (12, "normalize_bls12_377_g2")}[group]
+    """Jacobian -> affine for n points in one GPU launch (include/celo_bls_amd.h: normalize_bls12_377_g1/_g2, normalize_bw6_761_g1/_g2).
+    group: "g1" | "g2" (BLS12-377) | "bw6_761_g1" | "bw6_761_g2".  jac: (n, 18 | 36) uint64; returns (xy (n, 12 | 24) uint64, inf (n,) uint8)."""
+    words, fn = {"g1": (6, "normalize_bls12_377_g1"), "g2": (12, "normalize_bls12_377_g2"),
+                 "bw6_761_g1": (12, "normalize_bw6_761_g1"), "bw6_761_g2": (12, "normalize_bw6_761_g2")}[group]
     j = np.ascontiguousarray(jac, dtype=np.uint64).reshape(-1, 3 * words)
     n = j.shape[0]
     xy = np.zeros((n, 2 * words), dtype=np.uint64)
@@ -839,3 +844,86 @@ def normalize(group, jac):
     if rc != 0:
         raise RuntimeError("%s failed with code %d" % (fn, rc))
     return xy, inf
+
+
+# ---- batched fixed-base scalar multiplication and Groth16 setup (include/celo_bls_amd.h: fixed_base_mul_*, groth16_setup_*)
+def fixed_base_mul(group, gen_xy, scalars):
+    """out_i = k_i G: gen_xy the affine generator (12 | 24 uint64 limbs), scalars (n, 4 | 6) canonical uint64 limbs.  Returns (xy (n, 12 | 24)
+    uint64, inf (n,) uint8).  Raises ValueError on code 2 (a scalar >= r, the identity as generator)."""
+    aw, sw, _ = GROUP_SHAPE[group]
+    g = np.ascontiguousarray(gen_xy, dtype=np.uint64).reshape(aw)
+    sc = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, sw)
+    n = sc.shape[0]
+    xy = np.zeros((n, aw), dtype=np.uint64)
+    inf = np.zeros(n, dtype=np.uint8)
+    rc = getattr(lib(), "fixed_base_mul_" + group)(_p(g), _p(sc), C.c_size_t(n), _p(xy), _p(inf))
+    if rc == 2:
+        raise ValueError("fixed_base_mul_%s: bad arguments (code 2)" % group)
+    if rc != 0:
+        raise RuntimeError("fixed_base_mul_%s failed with code %d" % (group, rc))
+    return xy, inf
+
+
+def fixed_base_mul_dev(group, gen_xy, d_scalars, n, d_out, d_inf, stream=0):
+    """The same on device buffers (data pointers); returns the code (0, or 2 for a scalar >= r: nothing written)."""
+    aw = GROUP_SHAPE[group][0]
+    g = np.ascontiguousarray(gen_xy, dtype=np.uint64).reshape(aw)
+    return getattr(lib(), "fixed_base_mul_%s_dev" % group)(_p(g), C.c_void_p(d_scalars), C.c_size_t(n), C.c_void_p(d_out), C.c_void_p(d_inf),
+                                                         C.c_void_p(stream))
+
+
+def set_fixed_base_window(c):
+    """the generator tables' window bits (0 = the default)"""
+    rc = lib().celo_amd_fixed_base_set_window(C.c_int(c))
+    if rc != 0:
+        raise ValueError("celo_amd_fixed_base_set_window(%d) failed with code %d" % (c, rc))
+
+
+def setup_timings():
+    """the last fixed_base_mul_* / groth16_setup_* call: {table, fr_prep, g1_rows, g2_rows, normalize, key_tables, wall} in ms"""
+    ms = (C.c_float * 8)()
+    lib().celo_amd_setup_last_timings(ms)
+    return dict(zip(("table", "fr_prep", "g1_rows", "g2_rows", "normalize", "key_tables", "wall"), list(ms)[:7]))
+
+
+class SetupError(RuntimeError):
+    def __init__(self, curve, code):
+        super().__init__("groth16_setup_%s failed with code %d" % (curve, code))
+        self.code = code
+
+
+def groth16_setup(curve, qap_a, qap_b, qap_c, n_inputs, zt, tau, n_h, toxic, g1_xy, g2_xy, window_bits=0, want_vk=True, want_rows=True, want_key=False):
+    """Groth16 parameters after the QAP evaluation at tau (groth16_setup_bw6_761 / _bls12_377).  curve: "bw6_761" (Fr 6 u64, G1 rows 24) or
+    "bls12_377" (Fr 4 u64, G1 rows 12); qap_*: (n_vars, 6 | 4) Montgomery limbs; zt, tau: one Montgomery element each; toxic: alpha, beta, gamma,
+    delta (4 elements).  Returns {"vk": {alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1}, "rows": {beta_g1, delta_g1, a_query, b_g1_query,
+    b_g2_query, h_query, l_query}, "key": ProvingKey or None}."""
+    N, R1 = (6, 24) if curve == "bw6_761" else (4, 12)
+    qa, qb, qc = (np.ascontiguousarray(q, dtype=np.uint64).reshape(-1, N) for q in (qap_a, qap_b, qap_c))
+    n_vars = qa.shape[0]
+    z = np.ascontiguousarray(zt, dtype=np.uint64).reshape(N)
+    t = np.ascontiguousarray(tau, dtype=np.uint64).reshape(N)
+    tox = np.ascontiguousarray(toxic, dtype=np.uint64).reshape(4 * N)
+    g1 = np.ascontiguousarray(g1_xy, dtype=np.uint64).reshape(R1)
+    g2 = np.ascontiguousarray(g2_xy, dtype=np.uint64).reshape(24)
+    n_l = max(n_vars - n_inputs, 0)
+    vk = np.zeros(R1 + 3 * 24 + n_inputs * R1, dtype=np.uint64) if want_vk else None
+    rows = np.zeros(2 * R1 + 2 * n_vars * R1 + n_vars * 24 + (n_h + n_l) * R1, dtype=np.uint64) if want_rows else None
+    key = ProvingKey(curve, None, None, None, None, None, None) if want_key else None
+    fn = getattr(lib(), "groth16_setup_" + curve)
+    rc = fn(_p(qa), _p(qb), _p(qc), C.c_size_t(n_vars), C.c_size_t(n_inputs), _p(z), _p(t), C.c_size_t(n_h), _p(tox), _p(g1), _p(g2),
+            C.c_int(window_bits), _p(vk), _p(rows), C.byref(key.h) if key is not None else None)
+    if rc != 0:
+        raise SetupError(curve, rc)
+    out = {"vk": None, "rows": None, "key": key}
+    if vk is not None:
+        out["vk"] = {"alpha_g1": vk[:R1].copy(), "beta_g2": vk[R1:R1 + 24].copy(), "gamma_g2": vk[R1 + 24:R1 + 48].copy(),
+                     "delta_g2": vk[R1 + 48:R1 + 72].copy(), "gamma_abc_g1": vk[R1 + 72:].reshape(n_inputs, R1).copy()}
+    if rows is not None:
+        o, d = 0, {}
+        for name, k, w in (("beta_g1", 1, R1), ("delta_g1", 1, R1), ("a_query", n_vars, R1), ("b_g1_query", n_vars, R1), ("b_g2_query", n_vars, 24),
+                           ("h_query", n_h, R1), ("l_query", n_l, R1)):
+            d[name] = rows[o:o + k * w].reshape(k, w).copy()
+            o += k * w
+        d["beta_g1"], d["delta_g1"] = d["beta_g1"][0], d["delta_g1"][0]
+        out["rows"] = d
+    return out

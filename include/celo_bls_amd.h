@@ -469,6 +469,51 @@ int celo_amd_gen_points_bw6_761_dev(void* d_out_xy, size_t n, uint64_t seed, con
 int celo_amd_gen_points_grouped_bls12_377_g1_dev(void* d_out_xy, size_t n, uint64_t seed, const uint64_t* gens_xy, size_t ngens, uint32_t per, void* stream);
 int celo_amd_gen_points_grouped_bls12_377_g2_dev(void* d_out_xy, size_t n, uint64_t seed, const uint64_t* gens_xy, size_t ngens, uint32_t per, void* stream);
 
+/* ---- batched fixed-base scalar multiplication (ark-ec FixedBaseMSM::multi_scalar_mul, the work of ark_groth16::generate_random_parameters at
+ * crates/epoch-snark/src/api/setup.rs:22-46,63-105; csrc/fixed_base.h, csrc/unit_setup.hip): out_i = k_i * G for ONE
+ * generator G and n scalars, n affine rows (not msm_*_fixed, which returns one sum).  The generator's table (d * 2^(c w) * G, signed digits) is
+ * built on the device per call; one lane per scalar, one mixed addition per nonzero digit, a batch normalisation at the end.
+ * scalars: n canonical integers below r (4 u64 BLS12-377, 6 u64 BW6-761), as msm_* take them; a scalar >= r -> 2, nothing written.
+ * gen_xy: affine generator, arkworks Montgomery limbs (must not be the identity: 2).  out_xy: n affine rows; k_i = 0 -> zero row, inf[i] = 1.
+ * Both BW6-761 groups share one coordinate field and group law.  The _dev forms take device scalars / rows / flags and run on hip_stream. */
+int fixed_base_mul_bls12_377_g1(const uint64_t gen_xy[12], const uint64_t* scalars, size_t n, uint64_t* out_xy, uint8_t* inf);
+int fixed_base_mul_bls12_377_g2(const uint64_t gen_xy[24], const uint64_t* scalars, size_t n, uint64_t* out_xy, uint8_t* inf);
+int fixed_base_mul_bw6_761_g1(const uint64_t gen_xy[24], const uint64_t* scalars, size_t n, uint64_t* out_xy, uint8_t* inf);
+int fixed_base_mul_bw6_761_g2(const uint64_t gen_xy[24], const uint64_t* scalars, size_t n, uint64_t* out_xy, uint8_t* inf);
+int fixed_base_mul_bls12_377_g1_dev(const uint64_t* gen_xy, const void* d_scalars, size_t n, void* d_out_xy, void* d_inf, void* hip_stream);
+int fixed_base_mul_bls12_377_g2_dev(const uint64_t* gen_xy, const void* d_scalars, size_t n, void* d_out_xy, void* d_inf, void* hip_stream);
+int fixed_base_mul_bw6_761_g1_dev(const uint64_t* gen_xy, const void* d_scalars, size_t n, void* d_out_xy, void* d_inf, void* hip_stream);
+int fixed_base_mul_bw6_761_g2_dev(const uint64_t* gen_xy, const void* d_scalars, size_t n, void* d_out_xy, void* d_inf, void* hip_stream);
+/* Jacobian -> affine for n BW6-761 points (the twin of normalize_bls12_377_*): jac n x 36 u64, out_xy n x 24, identity -> zero row, inf = 1 */
+int normalize_bw6_761_g1(const uint64_t* jac /* n x 36 */, size_t n, uint64_t* out_xy /* n x 24 */, uint8_t* inf /* n */);
+int normalize_bw6_761_g2(const uint64_t* jac /* n x 36 */, size_t n, uint64_t* out_xy /* n x 24 */, uint8_t* inf /* n */);
+/* ---- Groth16 parameter generation after the QAP evaluation at tau (ark-groth16 0.1 generate_parameters; the caller turns its R1CS into
+ * data, as for the prover).  qap_a / qap_b / qap_c: a_i(tau), b_i(tau), c_i(tau) for n_vars variables (the one variable and the
+ * input-consistency rows included), arkworks Montgomery Fr (6 u64 BW6-761, 4 u64 BLS12-377); n_inputs: instance variables, the one included;
+ * zt = Z(tau); tau and n_h: h_query_i = zt delta^-1 tau^i for i < n_h; toxic: alpha, beta, gamma, delta (Montgomery Fr); g1_xy / g2_xy: the
+ * generators (affine arkworks limbs; ark 0.1 draws them at random).  On the device:
+ *   gamma_abc_i = (beta a_i + alpha b_i + c_i) gamma^-1 (i < n_inputs), l_i = (...) delta^-1 (i >= n_inputs), h_i as above,
+ *   every row of the key one fixed-base multiplication (G1: a_query, b_g1_query, h_query, l_query, gamma_abc_g1, alpha, beta, delta; G2:
+ *   b_g2_query, beta, gamma, delta).
+ * out_vk (NULL allowed): alpha_g1, beta_g2, gamma_g2, delta_g2, then n_inputs rows of gamma_abc_g1.
+ * out_rows (NULL allowed): beta_g1, delta_g1, a_query[n_vars], b_g1_query[n_vars], b_g2_query[n_vars], h_query[n_h], l_query[n_vars - n_inputs]
+ * (ProvingKey field order after the vk).  Rows: G1 24 u64 (BW6-761) / 12 u64 (BLS12-377), G2 24 u64.  Identity rows are arkworks'
+ * GroupAffine::zero() coordinates x = 0, y = 1 (Montgomery): the identity rule of groth16_load_key_*.
+ * out_key (NULL allowed): the handle groth16_load_key_* would build from those rows with the same window_bits, built from the device-resident
+ * rows (no query crosses PCIe); bound to the device, freed with groth16_free_key.
+ * Returns 0; 2: n_inputs == 0, n_inputs > n_vars, gamma or delta zero, a generator that is the identity, all three outputs NULL;
+ * 10: device allocation failure.  On any failure everything is freed and *out_key is not written beyond NULL. */
+int groth16_setup_bw6_761(const uint64_t* qap_a, const uint64_t* qap_b, const uint64_t* qap_c /* n_vars x 6 */, size_t n_vars, size_t n_inputs,
+                          const uint64_t zt[6], const uint64_t tau[6], size_t n_h, const uint64_t toxic[24] /* alpha beta gamma delta */,
+                          const uint64_t g1_xy[24], const uint64_t g2_xy[24], int window_bits, uint64_t* out_vk, uint64_t* out_rows, void** out_key);
+int groth16_setup_bls12_377(const uint64_t* qap_a, const uint64_t* qap_b, const uint64_t* qap_c /* n_vars x 4 */, size_t n_vars, size_t n_inputs,
+                            const uint64_t zt[4], const uint64_t tau[4], size_t n_h, const uint64_t toxic[16], const uint64_t g1_xy[12],
+                            const uint64_t g2_xy[24], int window_bits, uint64_t* out_vk, uint64_t* out_rows, void** out_key);
+/* the generator tables' window bits c (0 = the default of DESIGN.md 6f, else 2 .. 14) and the last fixed_base_mul_* / groth16_setup_* call's
+ * times in ms: [0] table build, [1] Fr preparation, [2] G1 rows, [3] G2 rows, [4] normalisation, [5] key tables, [6] wall, [7] unused */
+int celo_amd_fixed_base_set_window(int window_bits);
+int celo_amd_setup_last_timings(float ms[8]);
+
 #ifdef __cplusplus
 }
 #endif
