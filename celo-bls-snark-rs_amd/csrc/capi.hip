@@ -82,11 +82,10 @@ int wire761_key_layout(const uint8_t*, size_t, int, uint64_t*);
 int wire761_key_load(const uint8_t*, size_t, int, int, ProvingKey**, uint64_t*);
 void wire761_last_timings(float*);
 float wire_last_ms();
-int wire_normalize(int, const uint64_t*, size_t, uint64_t*, uint8_t*);
+int wire_normalize(int, const uint64_t*, size_t, uint64_t*, uint8_t*);   // group 0 / 1: BLS12-377 G1 / G2, 2: BW6-761
 int fixed_base_mul(int, const uint64_t*, const void*, size_t, void*, void*, int, void*);   // unit_setup.hip
 int fixed_base_set_window(int);
 void setup_last_timings(float*);
-int normalize_761(const uint64_t*, size_t, uint64_t*, uint8_t*);
 int groth16_setup(int, const uint64_t*, const uint64_t*, const uint64_t*, size_t, size_t, const uint64_t*, const uint64_t*, size_t, const uint64_t*, const uint64_t*,
                   const uint64_t*, int, uint64_t*, uint64_t*, ProvingKey**);
 int hash_to_g1_direct_run(const uint8_t*, const uint8_t*, const uint64_t*, const uint8_t*, const uint64_t*, size_t, uint64_t*, uint8_t*, int);
@@ -458,8 +457,8 @@ int fixed_base_mul_bw6_761_g1_dev(const uint64_t* gen_xy, const void* d_scalars,
 int fixed_base_mul_bw6_761_g2_dev(const uint64_t* gen_xy, const void* d_scalars, size_t n, void* d_out_xy, void* d_inf, void* hip_stream) {
   return fixed_base_mul(2, gen_xy, d_scalars, n, d_out_xy, d_inf, 1, hip_stream);
 }
-int normalize_bw6_761_g1(const uint64_t* jac, size_t n, uint64_t* out_xy, uint8_t* inf) { return normalize_761(jac, n, out_xy, inf); }
-int normalize_bw6_761_g2(const uint64_t* jac, size_t n, uint64_t* out_xy, uint8_t* inf) { return normalize_761(jac, n, out_xy, inf); }
+int normalize_bw6_761_g1(const uint64_t* jac, size_t n, uint64_t* out_xy, uint8_t* inf) { return wire_normalize(2, jac, n, out_xy, inf); }
+int normalize_bw6_761_g2(const uint64_t* jac, size_t n, uint64_t* out_xy, uint8_t* inf) { return wire_normalize(2, jac, n, out_xy, inf); }
 int groth16_setup_bw6_761(const uint64_t* qap_a, const uint64_t* qap_b, const uint64_t* qap_c, size_t n_vars, size_t n_inputs, const uint64_t zt[6], const uint64_t tau[6],
                           size_t n_h, const uint64_t toxic[24], const uint64_t g1_xy[24], const uint64_t g2_xy[24], int window_bits, uint64_t* out_vk,
                           uint64_t* out_rows, void** out_key) {

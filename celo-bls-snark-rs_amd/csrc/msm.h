@@ -41,15 +41,6 @@
 
 namespace celo {
 
-#define HIP_OK(x)                                                                      \
-  do {                                                                                 \
-    hipError_t e_ = (x);                                                               \
-    if (e_ != hipSuccess) {                                                            \
-      fprintf(stderr, "[celo-amd] HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); \
-      return 1;                                                                        \
-    }                                                                                  \
-  } while (0)
-
 // ---------------------------------------------------------------- group configurations
 struct G1_377 {
   typedef Fp<P377> F;

@@ -188,16 +188,16 @@ template <class G> class MsmEngine {
       if (need > fxs_bytes) {
         if (fxs) (void)hipFree(fxs);
         fxs = nullptr; fxs_bytes = 0;
-        HIP_OK(hipMalloc((void**)&fxs, need + need / 8));
+        HIP_TRY(hipMalloc((void**)&fxs, need + need / 8), 1);
         fxs_bytes = need + need / 8;
       }
       d_fx_v8 = fxs; d_fx_dg = (uint16_t*)(fxs + o_dg); d_fx_cnt = (uint32_t*)(fxs + o_cnt);
-      HIP_OK(hipMemsetAsync(d_fx_cnt, 0, 256 * 4, stream));
+      HIP_TRY(hipMemsetAsync(d_fx_cnt, 0, 256 * 4, stream), 1);
       hipLaunchKernelGGL((k_fixed_digits_c<SW, G::SCALAR_BITS>), dim3((fx->n + 255) / 256), dim3(256), 0, stream, d_scalars, fx->tinf, d_fx_v8, d_fx_dg, d_fx_cnt, fx->n,
                          (uint32_t)n_, fx->cf, fx->W, fx->NV, fx->M);
       uint32_t h_cnt[128];
-      HIP_OK(hipMemcpyAsync(h_cnt, d_fx_cnt, fx->NV * 4, hipMemcpyDeviceToHost, stream));
-      HIP_OK(hipStreamSynchronize(stream));
+      HIP_TRY(hipMemcpyAsync(h_cnt, d_fx_cnt, fx->NV * 4, hipMemcpyDeviceToHost, stream), 1);
+      HIP_TRY(hipStreamSynchronize(stream), 1);
       uint32_t mx = 0;
       for (uint32_t v = 0; v < fx->NV; v++) mx = h_cnt[v] > mx ? h_cnt[v] : mx;
       const uint64_t ep = ((uint64_t)mx + 4095) & ~uint64_t(4095);
@@ -330,7 +330,7 @@ template <class G> class MsmEngine {
 
     uint32_t* d_pbucket = hin ? (uint32_t*)(A + o_pbucket) : nullptr;
     uint32_t* d_carrier = hin ? (uint32_t*)(A + o_carrier) : nullptr;
-    HIP_OK(hipEventRecord(ev[0], stream));
+    HIP_TRY(hipEventRecord(ev[0], stream), 1);
     // mean region ns / NBIN: the smallest workgroup whose tile capacity (TILE_EPT entries per lane) holds it with 20 % to spare
     const uint32_t region = ns / NBIN;
     const uint32_t ts_threads = region <= 2048 ? 256u : region <= 4096 ? 512u : 1024u;
@@ -360,15 +360,15 @@ template <class G> class MsmEngine {
       if (ev_copy.size() < 3 * (size_t)K + 1) {
         const size_t have = ev_copy.size();
         ev_copy.resize(3 * (size_t)K + 1, nullptr);
-        for (size_t i = have; i < ev_copy.size(); i++) HIP_OK(hipEventCreateWithFlags(&ev_copy[i], hipEventDisableTiming));
+        for (size_t i = have; i < ev_copy.size(); i++) HIP_TRY(hipEventCreateWithFlags(&ev_copy[i], hipEventDisableTiming), 1);
       }
       hipEvent_t* ev_sc = ev_copy.data();             // [k]: chunk k's scalars are on the device
       hipEvent_t* ev_bs = ev_copy.data() + K;         // [k]: chunk k's bases are
       hipEvent_t* ev_so = ev_copy.data() + 2 * K;     // [k]: chunk k's runs, pieces and schedule are ready
-      HIP_OK(hipMemsetAsync(d_counts, 0, o_zero_end - o_counts, stream));       // (the per-call fills run under the first transfer)
-      HIP_OK(hipMemsetAsync(d_carrier, 0, (size_t)total * IO::XYZZ_WORDS * 4, stream));
-      HIP_OK(hipEventRecord(ev_copy[3 * K], stream));
-      HIP_OK(hipStreamWaitEvent(ss, ev_copy[3 * K], 0));
+      HIP_TRY(hipMemsetAsync(d_counts, 0, o_zero_end - o_counts, stream), 1);       // (the per-call fills run under the first transfer)
+      HIP_TRY(hipMemsetAsync(d_carrier, 0, (size_t)total * IO::XYZZ_WORDS * 4, stream), 1);
+      HIP_TRY(hipEventRecord(ev_copy[3 * K], stream), 1);
+      HIP_TRY(hipStreamWaitEvent(ss, ev_copy[3 * K], 0), 1);
       constexpr size_t PT_BYTES = 2 * (size_t)IO::ARK64 * 8;
       const uint32_t cslots = (uint32_t)nw * PW;
       ArkCoord<IO::ARK64> ark_one;
@@ -379,16 +379,16 @@ template <class G> class MsmEngine {
         const size_t lo = (size_t)k * cm, cnt = clen[k];      // ... and on the device (virtual index)
         // (the prover's queries - hin->ark_zero: a base row (0, 1) is the identity - need the chunk's bases before its digits: bases first)
         if (hin->ark_zero) {
-          HIP_OK(hipMemcpyAsync((char*)d_ark_bases + lo * PT_BYTES, (const char*)hin->bases + hlo * PT_BYTES, cnt * PT_BYTES, hipMemcpyHostToDevice, cs));
-          HIP_OK(hipEventRecord(ev_bs[k], cs));
+          HIP_TRY(hipMemcpyAsync((char*)d_ark_bases + lo * PT_BYTES, (const char*)hin->bases + hlo * PT_BYTES, cnt * PT_BYTES, hipMemcpyHostToDevice, cs), 1);
+          HIP_TRY(hipEventRecord(ev_bs[k], cs), 1);
         }
         // scalars -> digits, sort, schedule (sort stream)
-        HIP_OK(hipMemcpyAsync((char*)d_scalars + lo * SW * 4, (const char*)hin->scalars + hlo * SW * 4, cnt * SW * 4, hipMemcpyHostToDevice, cs));
-        if (hin->inf) HIP_OK(hipMemcpyAsync((char*)d_inf + lo, hin->inf + hlo, cnt, hipMemcpyHostToDevice, cs));
-        HIP_OK(hipEventRecord(ev_sc[k], cs));
-        HIP_OK(hipStreamWaitEvent(ss, ev_sc[k], 0));
+        HIP_TRY(hipMemcpyAsync((char*)d_scalars + lo * SW * 4, (const char*)hin->scalars + hlo * SW * 4, cnt * SW * 4, hipMemcpyHostToDevice, cs), 1);
+        if (hin->inf) HIP_TRY(hipMemcpyAsync((char*)d_inf + lo, hin->inf + hlo, cnt, hipMemcpyHostToDevice, cs), 1);
+        HIP_TRY(hipEventRecord(ev_sc[k], cs), 1);
+        HIP_TRY(hipStreamWaitEvent(ss, ev_sc[k], 0), 1);
         if (hin->ark_zero) {
-          HIP_OK(hipStreamWaitEvent(ss, ev_bs[k], 0));
+          HIP_TRY(hipStreamWaitEvent(ss, ev_bs[k], 0), 1);
           hipLaunchKernelGGL((k_flag_ark_zero<G>), dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, ss, d_ark_bases + lo * 2 * IO::ARK64,
                              hin->inf ? d_inf + lo : nullptr, d_in_inf + lo, cnt, ark_one);
         }
@@ -398,19 +398,19 @@ template <class G> class MsmEngine {
         hipLaunchKernelGGL((k_size_hist<G>), dim3(cslots / 256 < 512 ? (cslots + 255) / 256 : 512), dim3(256), 0, ss, d_plen + (size_t)k * cslots, bins_k, cslots);
         hipLaunchKernelGGL((k_size_scan<G>), dim3(1), dim3(1024), 0, ss, bins_k, bins_k + SIZE_BINS);
         hipLaunchKernelGGL((k_size_scatter<G>), dim3((cslots + 4095) / 4096), dim3(1024), 0, ss, d_plen + (size_t)k * cslots, bins_k, d_order + (size_t)k * cslots, cslots);
-        HIP_OK(hipEventRecord(ev_so[k], ss));
+        HIP_TRY(hipEventRecord(ev_so[k], ss), 1);
         if (k == 0) {
-          HIP_OK(hipStreamWaitEvent(stream, ev_so[0], 0));
-          HIP_OK(hipEventRecord(ev[1], stream));      // ("convert" = chunk 0's scalars, digits, sort and schedule; "sort" is empty on this path;
-          HIP_OK(hipEventRecord(ev[2], stream));      //  "accumulate" = everything from here to the last chunk's end)
+          HIP_TRY(hipStreamWaitEvent(stream, ev_so[0], 0), 1);
+          HIP_TRY(hipEventRecord(ev[1], stream), 1);      // ("convert" = chunk 0's scalars, digits, sort and schedule; "sort" is empty on this path;
+          HIP_TRY(hipEventRecord(ev[2], stream), 1);      //  "accumulate" = everything from here to the last chunk's end)
         }
         // bases -> conversion, accumulation (the call's stream)
         if (!hin->ark_zero) {
-          HIP_OK(hipMemcpyAsync((char*)d_ark_bases + lo * PT_BYTES, (const char*)hin->bases + hlo * PT_BYTES, cnt * PT_BYTES, hipMemcpyHostToDevice, cs));
-          HIP_OK(hipEventRecord(ev_bs[k], cs));
+          HIP_TRY(hipMemcpyAsync((char*)d_ark_bases + lo * PT_BYTES, (const char*)hin->bases + hlo * PT_BYTES, cnt * PT_BYTES, hipMemcpyHostToDevice, cs), 1);
+          HIP_TRY(hipEventRecord(ev_bs[k], cs), 1);
         }
-        HIP_OK(hipStreamWaitEvent(stream, ev_bs[k], 0));
-        if (k) HIP_OK(hipStreamWaitEvent(stream, ev_so[k], 0));
+        HIP_TRY(hipStreamWaitEvent(stream, ev_bs[k], 0), 1);
+        if (k) HIP_TRY(hipStreamWaitEvent(stream, ev_so[k], 0), 1);
         hipLaunchKernelGGL((k_convert_bases<G>), dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, d_ark_bases + lo * 2 * IO::ARK64, d_bases + lo * IO::AFF_WORDS, cnt);
         hipLaunchKernelGGL((k_accumulate_chunk<G>), dim3((cslots + 255) / 256), dim3(256), 0, stream, d_bases, d_sorted, d_pstart + (size_t)k * cslots, d_plen + (size_t)k * cslots,
                            d_order + (size_t)k * cslots, bins_k + SIZE_BINS, d_partials + (size_t)k * cslots * IO::XYZZ_WORDS, d_pbucket + (size_t)k * cslots, d_carrier, k ? 1u : 0u);
@@ -423,17 +423,17 @@ template <class G> class MsmEngine {
     if (fx) {
       // nothing to convert: the table is in device form
     } else if (side) {
-      HIP_OK(hipEventRecord(ev_side[0], stream));
-      HIP_OK(hipStreamWaitEvent(side_stream_.get(), ev_side[0], 0));
+      HIP_TRY(hipEventRecord(ev_side[0], stream), 1);
+      HIP_TRY(hipStreamWaitEvent(side_stream_.get(), ev_side[0], 0), 1);
       hipLaunchKernelGGL((k_convert_bases<G>), dim3((n + 255) / 256), dim3(256), 0, side_stream_.get(), d_ark_bases, d_bases, (size_t)n);
-      HIP_OK(hipEventRecord(ev_side[1], side_stream_.get()));
+      HIP_TRY(hipEventRecord(ev_side[1], side_stream_.get()), 1);
     } else if (glv) GlvExpand<G>::launch(d_ark_bases, d_inf, d_scalars, (uint32_t)n_, d_bases, (uint32_t*)(A + o_sc2), stream);
     else hipLaunchKernelGGL((k_convert_bases<G>), dim3((n + 255) / 256), dim3(256), 0, stream, d_ark_bases, d_bases, (size_t)n);
-    HIP_OK(hipEventRecord(ev[1], stream));
+    HIP_TRY(hipEventRecord(ev[1], stream), 1);
     // ---- sort
     if (fx && fx_Ep) {
-      HIP_OK(hipMemsetAsync(d_digits_all, 0xFF, (size_t)n * nw_all * 2, stream));             // every slot "no digit" until a record lands in it
-      HIP_OK(hipMemsetAsync(d_fx_cnt + 128, 0, 128 * 4, stream));                               // the rows' cursors
+      HIP_TRY(hipMemsetAsync(d_digits_all, 0xFF, (size_t)n * nw_all * 2, stream), 1);             // every slot "no digit" until a record lands in it
+      HIP_TRY(hipMemsetAsync(d_fx_cnt + 128, 0, 128 * 4, stream), 1);                               // the rows' cursors
       const uint32_t E32 = (uint32_t)fx->E();
       hipLaunchKernelGGL((k_fixed_place<G>), dim3((E32 + 1023) / 1024 < 4096 ? (E32 + 1023) / 1024 : 4096), dim3(1024), 0, stream, d_fx_v8, d_fx_dg, d_fx_cnt + 128, d_digits_all,
                          d_remap, E32, n, fx->NV);
@@ -441,14 +441,14 @@ template <class G> class MsmEngine {
                                fx->cf, fx->W, fx->NV, fx->M);
     else if (glv) { if (launch_digits<4, GlvExpand<G>::BITS>(c, (const uint32_t*)(A + o_sc2), nullptr, d_digits_all, n, stream)) return 3; }
     else if (launch_digits<SW, G::SCALAR_BITS>(c, d_scalars, d_inf, d_digits_all, n, stream)) return 3;
-    HIP_OK(hipMemsetAsync(d_counts, 0, o_zero_end - o_counts, stream));
+    HIP_TRY(hipMemsetAsync(d_counts, 0, o_zero_end - o_counts, stream), 1);
     sort_windows(0, (uint32_t)nw, stream);
     // ---- work items, longest first
     hipLaunchKernelGGL((k_size_hist<G>), dim3(slots / 256 < 512 ? (slots + 255) / 256 : 512), dim3(256), 0, stream, d_plen, d_bins, slots);
     hipLaunchKernelGGL((k_size_scan<G>), dim3(1), dim3(1024), 0, stream, d_bins, d_nwork);
     hipLaunchKernelGGL((k_size_scatter<G>), dim3((slots + 4095) / 4096), dim3(1024), 0, stream, d_plen, d_bins, d_order, slots);
-    if (side) HIP_OK(hipStreamWaitEvent(stream, ev_side[1], 0));
-    HIP_OK(hipEventRecord(ev[2], stream));
+    if (side) HIP_TRY(hipStreamWaitEvent(stream, ev_side[1], 0), 1);
+    HIP_TRY(hipEventRecord(ev[2], stream), 1);
     // ---- accumulate (grid covers every slot; lanes beyond the number of non-empty pieces exit)
     if constexpr (BaCfg<G>::enabled) if (use_ba) {
       uint32_t* d_ba_pts = (uint32_t*)(A + o_ba_pts);
@@ -463,7 +463,7 @@ template <class G> class MsmEngine {
     }
     if (!use_ba) launch_accumulate<G>(slots, stream, d_bases, d_sorted, d_pstart, d_plen, d_order, d_nwork, d_partials);
     }
-    HIP_OK(hipEventRecord(ev[3], stream));
+    HIP_TRY(hipEventRecord(ev[3], stream), 1);
     // ---- bucket reduction
     // (a window shard cuts EVERY bucket in two or three: one group of lanes per bucket of the call, not 21504 groups striding over them)
     const uint32_t mid_blocks = win_cnt ? (total + 20) / 21 < 16384 ? (total + 20) / 21 : 16384 : 1024;
@@ -526,11 +526,11 @@ template <class G> class MsmEngine {
       }
       hipLaunchKernelGGL((k_results_to_ark<G>), dim3((4 * res_pts + 63) / 64), dim3(64), 0, stream, d_work, res_pts);
     }
-    HIP_OK(hipEventRecord(ev[4], stream));
-    HIP_OK(hipMemcpyAsync(h_out, d_work, (size_t)res_pts * IO::XYZZ_WORDS * 4, hipMemcpyDeviceToHost, stream));
-    HIP_OK(hipEventRecord(ev[5], stream));
-    HIP_OK(hipStreamSynchronize(stream));
-    HIP_OK(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev[4], stream), 1);
+    HIP_TRY(hipMemcpyAsync(h_out, d_work, (size_t)res_pts * IO::XYZZ_WORDS * 4, hipMemcpyDeviceToHost, stream), 1);
+    HIP_TRY(hipEventRecord(ev[5], stream), 1);
+    HIP_TRY(hipStreamSynchronize(stream), 1);
+    HIP_TRY(hipGetLastError(), 1);
     (void)hipEventElapsedTime(&tm.convert, ev[0], ev[1]);
     (void)hipEventElapsedTime(&tm.sort, ev[1], ev[2]);
     (void)hipEventElapsedTime(&tm.accumulate, ev[2], ev[3]);
@@ -700,9 +700,9 @@ template <class G> class MsmEngine {
       if (d_in_scalars) (void)hipFree(d_in_scalars);
       if (d_in_inf) (void)hipFree(d_in_inf);
       d_in_bases = nullptr; d_in_scalars = nullptr; d_in_inf = nullptr; cap_in = 0;
-      HIP_OK(hipMalloc(&d_in_bases, n * 2 * IO::ARK64 * 8));
-      HIP_OK(hipMalloc(&d_in_scalars, n * SW * 4));
-      HIP_OK(hipMalloc(&d_in_inf, n));
+      HIP_TRY(hipMalloc(&d_in_bases, n * 2 * IO::ARK64 * 8), 1);
+      HIP_TRY(hipMalloc(&d_in_scalars, n * SW * 4), 1);
+      HIP_TRY(hipMalloc(&d_in_inf, n), 1);
       cap_in = n;
     }
     n = n_real;
@@ -711,9 +711,9 @@ template <class G> class MsmEngine {
       struct GlvOff { bool& f; bool was; GlvOff(bool& x, bool off) : f(x), was(x) { if (off) f = false; } ~GlvOff() { f = was; } } glv_guard(use_glv, glv_plan);
       return run_device_windows(d_in_bases, inf || ark_zero_identity ? d_in_inf : nullptr, (const uint32_t*)d_in_scalars, n, 0, 0, out_jac, out_xyzz, stream, nullptr, &hin);
     }
-    HIP_OK(hipMemcpyAsync(d_in_bases, bases, n * 2 * IO::ARK64 * 8, hipMemcpyHostToDevice, stream));
-    HIP_OK(hipMemcpyAsync(d_in_scalars, scalars, n * SW * 4, hipMemcpyHostToDevice, stream));
-    if (inf) HIP_OK(hipMemcpyAsync(d_in_inf, inf, n, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_in_bases, bases, n * 2 * IO::ARK64 * 8, hipMemcpyHostToDevice, stream), 1);
+    HIP_TRY(hipMemcpyAsync(d_in_scalars, scalars, n * SW * 4, hipMemcpyHostToDevice, stream), 1);
+    if (inf) HIP_TRY(hipMemcpyAsync(d_in_inf, inf, n, hipMemcpyHostToDevice, stream), 1);
     if (ark_zero_identity) {       // the prover's queries: rows (0, 1) are arkworks' encoding of the identity
       ArkCoord<IO::ARK64> one;
       F::one().to_ark(one.v);
@@ -732,10 +732,10 @@ template <class G> class MsmEngine {
       if (n_sc > cap_fx) {
         if (d_fx_scalars) (void)hipFree(d_fx_scalars);
         d_fx_scalars = nullptr; cap_fx = 0;
-        HIP_OK(hipMalloc(&d_fx_scalars, n_sc * SW * 4));
+        HIP_TRY(hipMalloc(&d_fx_scalars, n_sc * SW * 4), 1);
         cap_fx = n_sc;
       }
-      HIP_OK(hipMemcpyAsync(d_fx_scalars, scalars, n_sc * SW * 4, hipMemcpyHostToDevice, stream));
+      HIP_TRY(hipMemcpyAsync(d_fx_scalars, scalars, n_sc * SW * 4, hipMemcpyHostToDevice, stream), 1);
       d_sc = (const uint32_t*)d_fx_scalars;
     }
     return run_device_windows(nullptr, nullptr, d_sc, n_sc, 0, 0, out_jac, nullptr, stream, &T);
@@ -769,20 +769,20 @@ template <class G> class MsmEngine {
     const uint32_t M = cf == 16 ? 32768u : 32767u, NV = ((1u << (cf - 1)) - 1u) / M + 1u;
     const size_t E = (size_t)n * W;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventCreate(&e1));
+    HIP_TRY(hipEventCreate(&e0), 1); HIP_TRY(hipEventCreate(&e1), 1);
     T->n = n; T->W = W; T->NV = NV; T->M = M; T->cf = cf; T->device = api_device();
     T->bytes = E * IO::AFF_WORDS * 4 + E;
-    HIP_OK(hipMalloc(&T->table, E * IO::AFF_WORDS * 4));
-    HIP_OK(hipMalloc(&T->tinf, E));
-    HIP_OK(hipEventRecord(e0, stream));
+    HIP_TRY(hipMalloc(&T->table, E * IO::AFF_WORDS * 4), 1);
+    HIP_TRY(hipMalloc(&T->tinf, E), 1);
+    HIP_TRY(hipEventRecord(e0, stream), 1);
     hipLaunchKernelGGL((k_convert_bases<G>), dim3((n + 255) / 256), dim3(256), 0, stream, d_ark_bases, T->table, (size_t)n);
     hipLaunchKernelGGL((k_fixed_first_flags<G>), dim3((n + 255) / 256), dim3(256), 0, stream, d_inf, T->tinf, n);
     for (uint32_t j = 1; j < W; j++)
       hipLaunchKernelGGL((k_fixed_next<G>), dim3((n + 127) / 128), dim3(128), 0, stream, T->table + (size_t)(j - 1) * n * IO::AFF_WORDS, T->tinf + (size_t)(j - 1) * n,
                          T->table + (size_t)j * n * IO::AFF_WORDS, T->tinf + (size_t)j * n, n, cf);
-    HIP_OK(hipEventRecord(e1, stream));
-    HIP_OK(hipStreamSynchronize(stream));
-    HIP_OK(hipGetLastError());
+    HIP_TRY(hipEventRecord(e1, stream), 1);
+    HIP_TRY(hipStreamSynchronize(stream), 1);
+    HIP_TRY(hipGetLastError(), 1);
     (void)hipEventElapsedTime(&T->build_ms, e0, e1);
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     return 0;
@@ -837,11 +837,11 @@ template <class G> class MsmEngine {
         if (bytes > side_out_bytes) {
           if (d_side_out) (void)hipFree(d_side_out);
           d_side_out = nullptr; side_out_bytes = 0;
-          HIP_OK(hipMalloc(&d_side_out, bytes));
+          HIP_TRY(hipMalloc(&d_side_out, bytes), 1);
           side_out_bytes = bytes;
         }
-        HIP_OK(hipMemcpyAsync(d_side_out, hres.data(), bytes, hipMemcpyHostToDevice, stream));
-        HIP_OK(hipStreamSynchronize(stream));
+        HIP_TRY(hipMemcpyAsync(d_side_out, hres.data(), bytes, hipMemcpyHostToDevice, stream), 1);
+        HIP_TRY(hipStreamSynchronize(stream), 1);
         if (d_out_ret) *d_out_ret = d_side_out;
         side_path = true;
       }
@@ -908,16 +908,16 @@ template <class G> class MsmEngine {
     }
     {
       char* A0 = arena;
-      if (!resident) HIP_OK(hipMemcpyAsync(A0 + o_in_s, scalars, (size_t)total_pts * SW * 4, hipMemcpyHostToDevice, stream));
+      if (!resident) HIP_TRY(hipMemcpyAsync(A0 + o_in_s, scalars, (size_t)total_pts * SW * 4, hipMemcpyHostToDevice, stream), 1);
       int bits = 1;
       if (bits_hint > 0) bits = bits_hint;          // the caller measured these very scalars already (batch verification: the other leg's engine)
       else {
-        HIP_OK(hipMemsetAsync(A0 + o_or, 0, 64 * 4, stream));
+        HIP_TRY(hipMemsetAsync(A0 + o_or, 0, 64 * 4, stream), 1);
         hipLaunchKernelGGL((k_scalar_or<SW>), dim3(2048), dim3(256), 0, stream, resident ? (const uint32_t*)scalars : (const uint32_t*)(A0 + o_in_s),
                            (size_t)total_pts * SW, (uint32_t*)(A0 + o_or));
         uint32_t h_or[SW];
-        HIP_OK(hipMemcpyAsync(h_or, A0 + o_or, SW * 4, hipMemcpyDeviceToHost, stream));
-        HIP_OK(hipStreamSynchronize(stream));
+        HIP_TRY(hipMemcpyAsync(h_or, A0 + o_or, SW * 4, hipMemcpyDeviceToHost, stream), 1);
+        HIP_TRY(hipStreamSynchronize(stream), 1);
         for (int k = SW - 1; k >= 0; k--) if (h_or[k]) { bits = 32 * k + 32 - __builtin_clz(h_or[k]); break; }
       }
       measured_bits = bits;
@@ -943,25 +943,25 @@ template <class G> class MsmEngine {
     uint32_t* d_bins = (uint32_t*)(A + o[5]); uint32_t* d_nwork = d_bins + SIZE_BINS;
     uint32_t* d_partials = (uint32_t*)(A + o[6]); uint32_t* d_wsum = (uint32_t*)(A + o[7]); uint64_t* d_out = (uint64_t*)(A + o[8]);
     if (!resident) {
-      HIP_OK(hipMemcpyAsync(A + o_in_b, bases, (size_t)total_pts * 2 * IO::ARK64 * 8, hipMemcpyHostToDevice, stream));
-      if (inf) HIP_OK(hipMemcpyAsync(A + o_in_i, inf, total_pts, hipMemcpyHostToDevice, stream));
+      HIP_TRY(hipMemcpyAsync(A + o_in_b, bases, (size_t)total_pts * 2 * IO::ARK64 * 8, hipMemcpyHostToDevice, stream), 1);
+      if (inf) HIP_TRY(hipMemcpyAsync(A + o_in_i, inf, total_pts, hipMemcpyHostToDevice, stream), 1);
     }
-    HIP_OK(hipMemcpyAsync(d_off, offsets, (m + 1) * 4, hipMemcpyHostToDevice, stream));
-    HIP_OK(hipEventRecord(ev[0], stream));
-    HIP_OK(hipMemsetAsync(d_bins, 0, (size_t)SIZE_BINS * 4 + 256, stream));
+    HIP_TRY(hipMemcpyAsync(d_off, offsets, (m + 1) * 4, hipMemcpyHostToDevice, stream), 1);
+    HIP_TRY(hipEventRecord(ev[0], stream), 1);
+    HIP_TRY(hipMemsetAsync(d_bins, 0, (size_t)SIZE_BINS * 4 + 256, stream), 1);
     if (nd > 1) {
       uint32_t* d_sc2 = (uint32_t*)(A + o[9]);
       uint8_t* d_inf2 = (uint8_t*)(A + o[10]);
       uint32_t* d_off2 = (uint32_t*)(A + o[11]);
       gls_off.resize(m + 1);
       for (size_t p = 0; p <= m; p++) gls_off[p] = (uint32_t)nd * offsets[p];
-      HIP_OK(hipMemcpyAsync(d_off2, gls_off.data(), (m + 1) * 4, hipMemcpyHostToDevice, stream));
+      HIP_TRY(hipMemcpyAsync(d_off2, gls_off.data(), (m + 1) * 4, hipMemcpyHostToDevice, stream), 1);
       GlsExpand<G>::launch(d_in_b, inf ? d_in_i : nullptr, d_in_s, d_off, (uint32_t)m, max_n, nd, batch_bits, d_bases, d_sc2, inf ? d_inf2 : nullptr, stream);
-      HIP_OK(hipEventRecord(ev[1], stream));
+      HIP_TRY(hipEventRecord(ev[1], stream), 1);
       if (launch_batch_sort<4>(c, eff_max_n, d_sc2, inf ? d_inf2 : nullptr, d_off2, d_sorted, d_pstart, d_plen, (uint32_t)m, nw, stream)) return 3;
     } else {
       hipLaunchKernelGGL((k_convert_bases<G>), dim3((total_pts + 255) / 256), dim3(256), 0, stream, d_in_b, d_bases, (size_t)total_pts);
-      HIP_OK(hipEventRecord(ev[1], stream));
+      HIP_TRY(hipEventRecord(ev[1], stream), 1);
       if (launch_batch_sort<SW>(c, max_n, d_in_s, inf ? d_in_i : nullptr, d_off, d_sorted, d_pstart, d_plen, (uint32_t)m, nw, stream)) return 3;
     }
     last_gls_digits = nd;
@@ -969,20 +969,20 @@ template <class G> class MsmEngine {
     hipLaunchKernelGGL((k_size_hist<G>), dim3(slots / 256 < 2048 ? (slots + 255) / 256 : 2048), dim3(256), 0, stream, d_plen, d_bins, slots);
     hipLaunchKernelGGL((k_size_scan<G>), dim3(1), dim3(1024), 0, stream, d_bins, d_nwork);
     hipLaunchKernelGGL((k_size_scatter<G>), dim3((slots + 4095) / 4096), dim3(1024), 0, stream, d_plen, d_bins, d_order, slots);
-    HIP_OK(hipEventRecord(ev[2], stream));
+    HIP_TRY(hipEventRecord(ev[2], stream), 1);
     launch_accumulate<G>(slots, stream, d_bases, d_sorted, d_pstart, d_plen, d_order, d_nwork, d_partials);
-    HIP_OK(hipEventRecord(ev[3], stream));
+    HIP_TRY(hipEventRecord(ev[3], stream), 1);
     hipLaunchKernelGGL((k_batch_reduce<G>), dim3(((uint32_t)nvw + 127) / 128), dim3(128), 0, stream, d_partials, d_plen, d_wsum, B, (uint32_t)nvw);
     if (lane_horner) BatchHornerLanes<G>::launch(d_wsum, d_out, (uint32_t)nw, (uint32_t)c, (uint32_t)m, stream);
     else hipLaunchKernelGGL((k_batch_horner<G>), dim3(((uint32_t)m + 127) / 128), dim3(128), 0, stream, d_wsum, d_out, (uint32_t)nw, (uint32_t)c, (uint32_t)m);
-    HIP_OK(hipEventRecord(ev[4], stream));
-    if (out) HIP_OK(hipMemcpyAsync(out, d_out, m * 3 * IO::ARK64 * 8, hipMemcpyDeviceToHost, stream));
-    HIP_OK(hipEventRecord(ev[5], stream));
+    HIP_TRY(hipEventRecord(ev[4], stream), 1);
+    if (out) HIP_TRY(hipMemcpyAsync(out, d_out, m * 3 * IO::ARK64 * 8, hipMemcpyDeviceToHost, stream), 1);
+    HIP_TRY(hipEventRecord(ev[5], stream), 1);
     last_c = c; last_nw = nw; last_buckets = (uint32_t)nbuckets;
     if (d_out_ret) *d_out_ret = d_out;
-    if (!out) { HIP_OK(hipGetLastError()); return 0; }     // chained form: the caller synchronises and may call collect_batch_timings()
-    HIP_OK(hipStreamSynchronize(stream));
-    HIP_OK(hipGetLastError());
+    if (!out) { HIP_TRY(hipGetLastError(), 1); return 0; }     // chained form: the caller synchronises and may call collect_batch_timings()
+    HIP_TRY(hipStreamSynchronize(stream), 1);
+    HIP_TRY(hipGetLastError(), 1);
     collect_batch_timings();
     return 0;
   }
@@ -1045,16 +1045,16 @@ template <class G> class MsmEngine {
 
   int ensure(size_t bytes) {
     if (!ev[0]) {
-      for (int i = 0; i < 6; i++) HIP_OK(hipEventCreate(&ev[i]));
-      for (int i = 0; i < 2; i++) HIP_OK(hipEventCreateWithFlags(&ev_side[i], hipEventDisableTiming));
+      for (int i = 0; i < 6; i++) HIP_TRY(hipEventCreate(&ev[i]), 1);
+      for (int i = 0; i < 2; i++) HIP_TRY(hipEventCreateWithFlags(&ev_side[i], hipEventDisableTiming), 1);
     }
     if (!h_out) {
-      HIP_OK(hipHostMalloc(&h_out, H_OUT_POINTS * IO::XYZZ_WORDS * 4));
+      HIP_TRY(hipHostMalloc(&h_out, H_OUT_POINTS * IO::XYZZ_WORDS * 4), 1);
     }
     if (bytes > arena_bytes) {
       if (arena) (void)hipFree(arena);
       arena = nullptr; arena_bytes = 0;
-      HIP_OK(hipMalloc(&arena, bytes));
+      HIP_TRY(hipMalloc(&arena, bytes), 1);
       arena_bytes = bytes;
     }
     return 0;

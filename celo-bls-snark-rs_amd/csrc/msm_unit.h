@@ -49,13 +49,13 @@ template <class F> int gen_points_impl(void* d_out, size_t n, uint64_t seed, con
     Affine<F> g = {F::from_ark(gen_xy + q * 2 * IO::ARK64), F::from_ark(gen_xy + q * 2 * IO::ARK64 + IO::ARK64)};
     IO::store_affine(h.data() + q * IO::AFF_WORDS, g);
   }
-  uint32_t* d_gen = nullptr;
-  HIP_OK(hipMalloc(&d_gen, h.size() * 4));
-  HIP_OK(hipMemcpy(d_gen, h.data(), h.size() * 4, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL((k_gen_points<F>), dim3((unsigned)((n + 127) / 128)), dim3(128), 0, (hipStream_t)stream, (uint64_t*)d_out, n, seed, d_gen, per);
-  HIP_OK(hipStreamSynchronize((hipStream_t)stream));
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipFree(d_gen));
+  CallScope cs((hipStream_t)stream);
+  uint32_t* d_gen;
+  HIP_TRY(cs.alloc(&d_gen, h.size() * 4), 1);
+  HIP_TRY(hipMemcpy(d_gen, h.data(), h.size() * 4, hipMemcpyHostToDevice), 1);
+  hipLaunchKernelGGL((k_gen_points<F>), dim3((unsigned)((n + 127) / 128)), dim3(128), 0, cs.stream(), (uint64_t*)d_out, n, seed, d_gen, per);
+  HIP_TRY(hipStreamSynchronize(cs.stream()), 1);
+  HIP_TRY(hipGetLastError(), 1);
   return 0;
 }
 
@@ -247,61 +247,61 @@ int selftest_accumulate_impl(const uint64_t* gen_xy, uint32_t runs, uint32_t len
   if (!gen_xy || !differ || runs == 0 || len == 0 || len > 1024 || runs > (1u << 20)) return 2;
   const uint32_t npts = 1u << 12, parts = chunked ? 2u : 1u;
   if (check > runs) check = runs;
-  uint64_t* d_ark = nullptr; uint32_t *d_pts = nullptr, *d_sorted = nullptr, *d_tab = nullptr, *d_out = nullptr, *d_part = nullptr;
   std::vector<uint32_t> h_pts((size_t)npts * IO::AFF_WORDS), sorted((size_t)parts * runs * len), tab((size_t)4 * runs + 1), h_out((size_t)runs * IO::XYZZ_WORDS);
-  int rc = 1;
-  hipStream_t st = nullptr;
-  do {
-    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) break;
-    if (hipMalloc(&d_ark, (size_t)npts * 2 * IO::ARK64 * 8) != hipSuccess || hipMalloc(&d_pts, h_pts.size() * 4) != hipSuccess) break;
-    if (hipMalloc(&d_sorted, sorted.size() * 4) != hipSuccess || hipMalloc(&d_tab, tab.size() * 4) != hipSuccess) break;
-    if (hipMalloc(&d_out, h_out.size() * 4) != hipSuccess || hipMalloc(&d_part, h_out.size() * 4) != hipSuccess) break;
-    if (gen_points_impl<F>(d_ark, npts, 0x5E1F7E57ULL + seed, gen_xy, 1, 0, st)) break;
-    hipLaunchKernelGGL((k_convert_bases<G>), dim3(npts / 256), dim3(256), 0, st, d_ark, d_pts, (size_t)npts);
-    if (hipMemcpyAsync(h_pts.data(), d_pts, h_pts.size() * 4, hipMemcpyDeviceToHost, st) != hipSuccess) break;
-    uint32_t h = seed * 0x9E3779B9u + 1u;
-    for (size_t e = 0; e < sorted.size(); e++) { h = h * 1664525u + 1013904223u; sorted[e] = ((h >> 9) % npts) | ((h & 0x100u) ? 0x80000000u : 0u); }
-    // runs 0 / 1 / 2 of every 64 meet the special cases: two equal points first (doubling branch of the affine start / of a mixed addition),
-    // a point and its negative (cancellation, then additions onto the identity)
-    for (uint32_t i = 0; i + 2 < runs; i += 64) {
-      if (len >= 2) { sorted[(size_t)i * len + 1] = sorted[(size_t)i * len]; sorted[(size_t)(i + 1) * len + 1] = sorted[(size_t)(i + 1) * len] ^ 0x80000000u; }
-      if (len >= 3) sorted[(size_t)(i + 2) * len + 2] = sorted[(size_t)(i + 2) * len + 1];
+  CallScope cs(nullptr);
+  HIP_TRY(cs.create_stream(), 1);
+  const hipStream_t st = cs.stream();
+  uint64_t* d_ark;
+  uint32_t *d_pts, *d_sorted, *d_tab, *d_out, *d_part;
+  HIP_TRY(cs.alloc(&d_ark, (size_t)npts * 2 * IO::ARK64 * 8), 1);
+  HIP_TRY(cs.alloc(&d_pts, h_pts.size() * 4), 1);
+  HIP_TRY(cs.alloc(&d_sorted, sorted.size() * 4), 1);
+  HIP_TRY(cs.alloc(&d_tab, tab.size() * 4), 1);
+  HIP_TRY(cs.alloc(&d_out, h_out.size() * 4), 1);
+  HIP_TRY(cs.alloc(&d_part, h_out.size() * 4), 1);
+  if (gen_points_impl<F>(d_ark, npts, 0x5E1F7E57ULL + seed, gen_xy, 1, 0, st)) return 1;
+  hipLaunchKernelGGL((k_convert_bases<G>), dim3(npts / 256), dim3(256), 0, st, d_ark, d_pts, (size_t)npts);
+  HIP_TRY(hipMemcpyAsync(h_pts.data(), d_pts, h_pts.size() * 4, hipMemcpyDeviceToHost, st), 1);
+  uint32_t h = seed * 0x9E3779B9u + 1u;
+  for (size_t e = 0; e < sorted.size(); e++) { h = h * 1664525u + 1013904223u; sorted[e] = ((h >> 9) % npts) | ((h & 0x100u) ? 0x80000000u : 0u); }
+  // runs 0 / 1 / 2 of every 64 meet the special cases: two equal points first (doubling branch of the affine start / of a mixed addition),
+  // a point and its negative (cancellation, then additions onto the identity)
+  for (uint32_t i = 0; i + 2 < runs; i += 64) {
+    if (len >= 2) { sorted[(size_t)i * len + 1] = sorted[(size_t)i * len]; sorted[(size_t)(i + 1) * len + 1] = sorted[(size_t)(i + 1) * len] ^ 0x80000000u; }
+    if (len >= 3) sorted[(size_t)(i + 2) * len + 2] = sorted[(size_t)(i + 2) * len + 1];
+  }
+  uint32_t* pstart = tab.data(); uint32_t* plen = pstart + runs; uint32_t* order = plen + runs; uint32_t* pbucket = order + runs;
+  for (uint32_t i = 0; i < runs; i++) { pstart[i] = i * len; plen[i] = len; order[i] = i; pbucket[i] = i; }
+  tab[(size_t)4 * runs] = runs;
+  HIP_TRY(hipMemcpyAsync(d_sorted, sorted.data(), sorted.size() * 4, hipMemcpyHostToDevice, st), 1);
+  HIP_TRY(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st), 1);
+  const uint32_t *dp = d_tab, *dl = d_tab + runs, *dord = d_tab + 2 * runs, *dpb = d_tab + 3 * runs, *dn = d_tab + 4 * runs;
+  if (!chunked) hipLaunchKernelGGL((k_accumulate<G>), dim3((runs + 255) / 256), dim3(256), 0, st, d_pts, d_sorted, dp, dl, dord, dn, d_out);
+  else for (uint32_t k = 0; k < 2; k++)
+    hipLaunchKernelGGL((k_accumulate_chunk<G>), dim3((runs + 255) / 256), dim3(256), 0, st, d_pts, d_sorted + (size_t)k * runs * len, dp, dl, dord, dn, d_part, dpb, d_out, k);
+  HIP_TRY(hipMemcpyAsync(h_out.data(), d_out, h_out.size() * 4, hipMemcpyDeviceToHost, st), 1);
+  HIP_TRY(hipStreamSynchronize(st), 1);
+  HIP_TRY(hipGetLastError(), 1);
+  uint32_t bad = 0;
+  for (uint32_t i = 0; i < check; i++) {
+    Xyzz<F> acc = Xyzz<F>::identity();
+    for (uint32_t k = 0; k < parts; k++) {
+      const uint32_t* run = &sorted[((size_t)k * runs + i) * len];
+      auto point = [&](uint32_t j) {
+        Affine<F> p = IO::load_affine(&h_pts[(size_t)(run[j] & 0x7fffffffu) * IO::AFF_WORDS]);
+        if (run[j] >> 31) p = affine_neg(p);
+        return p;
+      };
+      uint32_t j0 = 0;
+      if (k == 0 && sizeof(F) <= 14 * sizeof(uint32_t) && len >= 2) { acc = xyzz_add_affine(point(0), point(1)); j0 = 2; }   // the 14-limb kernels' affine start
+      for (uint32_t j = j0; j < len; j++) xyzz_madd(acc, point(j));
     }
-    uint32_t* pstart = tab.data(); uint32_t* plen = pstart + runs; uint32_t* order = plen + runs; uint32_t* pbucket = order + runs;
-    for (uint32_t i = 0; i < runs; i++) { pstart[i] = i * len; plen[i] = len; order[i] = i; pbucket[i] = i; }
-    tab[(size_t)4 * runs] = runs;
-    if (hipMemcpyAsync(d_sorted, sorted.data(), sorted.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess) break;
-    if (hipMemcpyAsync(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess) break;
-    const uint32_t *dp = d_tab, *dl = d_tab + runs, *dord = d_tab + 2 * runs, *dpb = d_tab + 3 * runs, *dn = d_tab + 4 * runs;
-    if (!chunked) hipLaunchKernelGGL((k_accumulate<G>), dim3((runs + 255) / 256), dim3(256), 0, st, d_pts, d_sorted, dp, dl, dord, dn, d_out);
-    else for (uint32_t k = 0; k < 2; k++)
-      hipLaunchKernelGGL((k_accumulate_chunk<G>), dim3((runs + 255) / 256), dim3(256), 0, st, d_pts, d_sorted + (size_t)k * runs * len, dp, dl, dord, dn, d_part, dpb, d_out, k);
-    if (hipMemcpyAsync(h_out.data(), d_out, h_out.size() * 4, hipMemcpyDeviceToHost, st) != hipSuccess) break;
-    if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) break;
-    uint32_t bad = 0;
-    for (uint32_t i = 0; i < check; i++) {
-      Xyzz<F> acc = Xyzz<F>::identity();
-      for (uint32_t k = 0; k < parts; k++) {
-        const uint32_t* run = &sorted[((size_t)k * runs + i) * len];
-        auto point = [&](uint32_t j) {
-          Affine<F> p = IO::load_affine(&h_pts[(size_t)(run[j] & 0x7fffffffu) * IO::AFF_WORDS]);
-          if (run[j] >> 31) p = affine_neg(p);
-          return p;
-        };
-        uint32_t j0 = 0;
-        if (k == 0 && sizeof(F) <= 14 * sizeof(uint32_t) && len >= 2) { acc = xyzz_add_affine(point(0), point(1)); j0 = 2; }   // the 14-limb kernels' affine start
-        for (uint32_t j = j0; j < len; j++) xyzz_madd(acc, point(j));
-      }
-      uint32_t hw[IO::XYZZ_WORDS];
-      IO::store_xyzz(hw, acc);
-      if (memcmp(hw, &h_out[(size_t)i * IO::XYZZ_WORDS], sizeof hw)) bad++;
-    }
-    *differ = bad;
-    rc = 0;
-  } while (0);
-  for (void* p : {(void*)d_ark, (void*)d_pts, (void*)d_sorted, (void*)d_tab, (void*)d_out, (void*)d_part}) if (p) (void)hipFree(p);
-  if (st) (void)hipStreamDestroy(st);
-  return rc;
+    uint32_t hw[IO::XYZZ_WORDS];
+    IO::store_xyzz(hw, acc);
+    if (memcmp(hw, &h_out[(size_t)i * IO::XYZZ_WORDS], sizeof hw)) bad++;
+  }
+  *differ = bad;
+  return 0;
 }
 }  // namespace celo
 

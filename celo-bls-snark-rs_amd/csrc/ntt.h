@@ -235,15 +235,6 @@ __global__ void __launch_bounds__(256) k_ntt_store(const uint32_t* __restrict__ 
   v.to_ark(ark + (size_t)i * FR::ARK64);
 }
 
-#define NTT_HIP_OK(x)                                                                                           \
-  do {                                                                                                          \
-    hipError_t e_ = (x);                                                                                        \
-    if (e_ != hipSuccess) {                                                                                     \
-      fprintf(stderr, "[celo-amd] HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__);         \
-      return 1;                                                                                                 \
-    }                                                                                                           \
-  } while (0)
-
 struct NttTimings { float load = 0, passes = 0, store = 0, total = 0; int npasses = 0; };
 
 template <class FR> class NttEngine {
@@ -281,9 +272,9 @@ template <class FR> class NttEngine {
       while (s > 0) { const int r = s >= max_radix_log2 ? max_radix_log2 : s; kinds[np] = 0; lv[np++] = r; s -= r; }
     }
     const bool fused = fuse_io && np >= 2;      // the first launch reads the caller's array, the last one writes it: they must differ
-    NTT_HIP_OK(hipEventRecord(ev[0], stream));
+    HIP_TRY(hipEventRecord(ev[0], stream), 1);
     if (!fused) hipLaunchKernelGGL((k_ntt_load<FR>), dim3((n + 255) / 256), dim3(256), 0, stream, data_dev, d_work, n, (coset6 && !coset_after) ? glo : nullptr, ghi);
-    NTT_HIP_OK(hipEventRecord(ev[1], stream));
+    HIP_TRY(hipEventRecord(ev[1], stream), 1);
     int s = (int)log_n - 1;
     for (int i = 0; i < np; i++) {
       NttIo io = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -302,12 +293,12 @@ template <class FR> class NttEngine {
       }
       s -= lv[i];
     }
-    NTT_HIP_OK(hipEventRecord(ev[2], stream));
+    HIP_TRY(hipEventRecord(ev[2], stream), 1);
     if (!fused) hipLaunchKernelGGL((k_ntt_store<FR>), dim3((n + 255) / 256), dim3(256), 0, stream, d_work, data_dev, log_n, (coset6 && coset_after) ? glo : nullptr, ghi,
                                    scale6 ? small(4) : nullptr);
-    NTT_HIP_OK(hipEventRecord(ev[3], stream));
-    NTT_HIP_OK(hipStreamSynchronize(stream));
-    NTT_HIP_OK(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev[3], stream), 1);
+    HIP_TRY(hipStreamSynchronize(stream), 1);
+    HIP_TRY(hipGetLastError(), 1);
     (void)hipEventElapsedTime(&tm.load, ev[0], ev[1]);
     (void)hipEventElapsedTime(&tm.passes, ev[1], ev[2]);
     (void)hipEventElapsedTime(&tm.store, ev[2], ev[3]);
@@ -322,12 +313,12 @@ template <class FR> class NttEngine {
     if (bytes > cap_io) {
       if (d_io) (void)hipFree(d_io);
       d_io = nullptr; cap_io = 0;
-      NTT_HIP_OK(hipMalloc(&d_io, bytes));
+      HIP_TRY(hipMalloc(&d_io, bytes), 1);
       cap_io = bytes;
     }
-    NTT_HIP_OK(hipMemcpyAsync(d_io, data, bytes, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_io, data, bytes, hipMemcpyHostToDevice, stream), 1);
     if (int rc = run_device(d_io, log_n, omega6, coset6, coset_after, scale6, stream)) return rc;
-    NTT_HIP_OK(hipMemcpy(data, d_io, bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(data, d_io, bytes, hipMemcpyDeviceToHost), 1);
     return 0;
   }
 
@@ -355,27 +346,27 @@ template <class FR> class NttEngine {
     memset(h[1], 0, sizeof h[1]);
     host_pow1024(b).store(h[1]);
     uint32_t* stage = small(4) + 4 * FR::WORDS;   // scratch slots behind the scale element
-    NTT_HIP_OK(hipMemcpyAsync(stage, h, sizeof h, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(stage, h, sizeof h, hipMemcpyHostToDevice, stream), 1);
     hipLaunchKernelGGL((k_ntt_powers<FR>), dim3(4), dim3(256), 0, stream, stage, small(slot_lo));
     hipLaunchKernelGGL((k_ntt_powers<FR>), dim3(4), dim3(256), 0, stream, stage + FR::WORDS, small(slot_hi));
-    NTT_HIP_OK(hipStreamSynchronize(stream));     // h lives on this stack frame
+    HIP_TRY(hipStreamSynchronize(stream), 1);     // h lives on this stack frame
     return 0;
   }
   int prepare(unsigned log_n, const uint64_t* omega6, const uint64_t* coset6, const uint64_t* scale6, hipStream_t stream) {
-    if (!ev[0]) for (int i = 0; i < 4; i++) NTT_HIP_OK(hipEventCreate(&ev[i]));
+    if (!ev[0]) for (int i = 0; i < 4; i++) HIP_TRY(hipEventCreate(&ev[i]), 1);
     const size_t n = size_t(1) << log_n;
-    if (!d_small) NTT_HIP_OK(hipMalloc(&d_small, (size_t)5 * 1024 * FR::WORDS * 4));
+    if (!d_small) HIP_TRY(hipMalloc(&d_small, (size_t)5 * 1024 * FR::WORDS * 4), 1);
     if (n * FR::WORDS * 4 > cap_work) {
       if (d_work) (void)hipFree(d_work);
       d_work = nullptr; cap_work = 0;
-      NTT_HIP_OK(hipMalloc(&d_work, n * FR::WORDS * 4));
+      HIP_TRY(hipMalloc(&d_work, n * FR::WORDS * 4), 1);
       cap_work = n * FR::WORDS * 4;
     }
     const size_t tw_count = n > 1 ? n / 2 : 1;
     if (tw_count * FR::WORDS * 4 > cap_tw) {
       if (d_tw) (void)hipFree(d_tw);
       d_tw = nullptr; cap_tw = 0; tw_log_n = 0;
-      NTT_HIP_OK(hipMalloc(&d_tw, tw_count * FR::WORDS * 4));
+      HIP_TRY(hipMalloc(&d_tw, tw_count * FR::WORDS * 4), 1);
       cap_tw = tw_count * FR::WORDS * 4;
     }
     if (tw_log_n != log_n || memcmp(tw_omega, omega6, sizeof tw_omega) != 0) {
@@ -388,8 +379,8 @@ template <class FR> class NttEngine {
     if (scale6) {
       uint32_t h[FR::WORDS];
       to_dev_words(scale6, h);
-      NTT_HIP_OK(hipMemcpyAsync(small(4), h, sizeof h, hipMemcpyHostToDevice, stream));
-      NTT_HIP_OK(hipStreamSynchronize(stream));
+      HIP_TRY(hipMemcpyAsync(small(4), h, sizeof h, hipMemcpyHostToDevice, stream), 1);
+      HIP_TRY(hipStreamSynchronize(stream), 1);
     }
     return 0;
   }

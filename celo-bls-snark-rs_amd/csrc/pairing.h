@@ -314,15 +314,6 @@ struct PP761 {
 CELO_DECLARE_LANE_LAUNCH(LaneLaunch377)
 CELO_DECLARE_LANE_LAUNCH(LaneLaunch761)
 
-#define PAIR_HIP_OK(x)                                                                                          \
-  do {                                                                                                          \
-    hipError_t e_ = (x);                                                                                        \
-    if (e_ != hipSuccess) {                                                                                     \
-      fprintf(stderr, "[celo-amd] HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__);         \
-      return 1;                                                                                                 \
-    }                                                                                                           \
-  } while (0)
-
 struct PairingTimings { float miller = 0, product = 0, final_exp = 0, total = 0; };
 // single-product latency path (unit_pairing761_wide.hip): the loops and exponentiations of ONE product side by side in several waves
 int wide_product_761(const uint64_t* d_g1, const uint8_t* d_i1, const uint64_t* d_g2, const uint8_t* d_i2, uint32_t k, uint32_t* d_f, uint32_t* d_lines, uint8_t* d_one,
@@ -374,10 +365,10 @@ template <class PP> class PairingEngine {
     Staged st;
     if (stage(k, m, &st)) return 1;
     if (k) {
-      PAIR_HIP_OK(hipMemcpyAsync(st.d_g1, g1, (size_t)k * PP::G1_ARK64 * 8, hipMemcpyHostToDevice, stream));
-      PAIR_HIP_OK(hipMemcpyAsync(st.d_g2, g2, (size_t)k * PP::G2_ARK64 * 8, hipMemcpyHostToDevice, stream));
-      if (inf1) PAIR_HIP_OK(hipMemcpyAsync(st.d_i1, inf1, k, hipMemcpyHostToDevice, stream));
-      if (inf2) PAIR_HIP_OK(hipMemcpyAsync(st.d_i2, inf2, k, hipMemcpyHostToDevice, stream));
+      HIP_TRY(hipMemcpyAsync(st.d_g1, g1, (size_t)k * PP::G1_ARK64 * 8, hipMemcpyHostToDevice, stream), 1);
+      HIP_TRY(hipMemcpyAsync(st.d_g2, g2, (size_t)k * PP::G2_ARK64 * 8, hipMemcpyHostToDevice, stream), 1);
+      if (inf1) HIP_TRY(hipMemcpyAsync(st.d_i1, inf1, k, hipMemcpyHostToDevice, stream), 1);
+      if (inf2) HIP_TRY(hipMemcpyAsync(st.d_i2, inf2, k, hipMemcpyHostToDevice, stream), 1);
     }
     return run_staged(offsets, m, inf1 != nullptr, inf2 != nullptr, out_is_one, out_gt, mode, stream);
   }
@@ -411,18 +402,18 @@ template <class PP> class PairingEngine {
     uint8_t* d_i1 = (uint8_t*)(A + lay.o_i1); uint8_t* d_i2 = (uint8_t*)(A + lay.o_i2);
     uint32_t* d_off = (uint32_t*)(A + lay.o_off); uint32_t* d_f = (uint32_t*)(A + lay.o_f); uint32_t* d_f2 = (uint32_t*)(A + lay.o_f2);
     uint32_t* d_prod = (uint32_t*)(A + lay.o_prod); uint8_t* d_one = (uint8_t*)(A + lay.o_one); uint64_t* d_gt = (uint64_t*)(A + lay.o_gt);
-    PAIR_HIP_OK(hipMemcpyAsync(d_off, offsets, (m + 1) * 4, hipMemcpyHostToDevice, stream));
-    PAIR_HIP_OK(hipEventRecord(ev[0], stream));
+    HIP_TRY(hipMemcpyAsync(d_off, offsets, (m + 1) * 4, hipMemcpyHostToDevice, stream), 1);
+    HIP_TRY(hipEventRecord(ev[0], stream), 1);
     bool wide = WideProduct<PP>::available && m <= WideProduct<PP>::MAX_PRODUCTS && k >= 1;
     for (size_t p = 0; p < m && wide; p++) wide = offsets[p + 1] - offsets[p] <= WideProduct<PP>::MAX_PAIRS;
     if (wide) {   // few products of few pairs: the latency path (the pieces of a product side by side in several lane groups and waves)
       if (WideProduct<PP>::run(d_g1, has_inf1 ? d_i1 : nullptr, d_g2, has_inf2 ? d_i2 : nullptr, d_off, (uint32_t)m, k, d_f, (uint32_t*)(A + lay.o_wide),
                                out_is_one ? d_one : nullptr, out_gt ? d_gt : nullptr, mode == 0 ? 1 : 0, stream)) return 1;
-      PAIR_HIP_OK(hipEventRecord(ev[3], stream));
-      if (out_is_one) PAIR_HIP_OK(hipMemcpyAsync(out_is_one, d_one, m, hipMemcpyDeviceToHost, stream));
-      if (out_gt) PAIR_HIP_OK(hipMemcpyAsync(out_gt, d_gt, (size_t)m * 72 * 8, hipMemcpyDeviceToHost, stream));
-      PAIR_HIP_OK(hipStreamSynchronize(stream));
-      PAIR_HIP_OK(hipGetLastError());
+      HIP_TRY(hipEventRecord(ev[3], stream), 1);
+      if (out_is_one) HIP_TRY(hipMemcpyAsync(out_is_one, d_one, m, hipMemcpyDeviceToHost, stream), 1);
+      if (out_gt) HIP_TRY(hipMemcpyAsync(out_gt, d_gt, (size_t)m * 72 * 8, hipMemcpyDeviceToHost, stream), 1);
+      HIP_TRY(hipStreamSynchronize(stream), 1);
+      HIP_TRY(hipGetLastError(), 1);
       tm = PairingTimings();
       (void)hipEventElapsedTime(&tm.total, ev[0], ev[3]);
       return 0;
@@ -443,12 +434,12 @@ template <class PP> class PairingEngine {
       uint32_t* d_flag = (uint32_t*)(A + lay.o_flag);
       uint32_t* d_lines = (uint32_t*)(A + lay.o_lines);
       uint32_t h_flag = 1;
-      PAIR_HIP_OK(hipMemcpyAsync(d_flag, &h_flag, 4, hipMemcpyHostToDevice, stream));
+      HIP_TRY(hipMemcpyAsync(d_flag, &h_flag, 4, hipMemcpyHostToDevice, stream), 1);
       LL::first_q_same(d_g2, d_off, (uint32_t)m, d_flag, stream);
-      PAIR_HIP_OK(hipMemcpyAsync(&h_flag, d_flag, 4, hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipMemcpyAsync(&h_flag, d_flag, 4, hipMemcpyDeviceToHost, stream), 1);
       uint64_t h_q0[PP::G2_ARK64];
-      PAIR_HIP_OK(hipMemcpyAsync(h_q0, d_g2 + (size_t)offsets[0] * PP::G2_ARK64, sizeof h_q0, hipMemcpyDeviceToHost, stream));
-      PAIR_HIP_OK(hipStreamSynchronize(stream));
+      HIP_TRY(hipMemcpyAsync(h_q0, d_g2 + (size_t)offsets[0] * PP::G2_ARK64, sizeof h_q0, hipMemcpyDeviceToHost, stream), 1);
+      HIP_TRY(hipStreamSynchronize(stream), 1);
       if (h_flag) {
         // the shared point is -g2 in every verify / Batch::verify of the reference: its 69 line triples are kept between calls (what
         // ark-ec's G2Prepared is for a caller that holds one) and k_prepare_lines - 0.7 ms on one wave - runs when the point changes
@@ -472,7 +463,7 @@ template <class PP> class PairingEngine {
     } else if (shared && most <= 2) LL::miller_product2(d_g1, has_inf1 ? d_i1 : nullptr, d_g2, has_inf2 ? d_i2 : nullptr, d_off, d_prod, (uint32_t)m, stream);
     else if (shared) LL::miller_product(d_g1, has_inf1 ? d_i1 : nullptr, d_g2, has_inf2 ? d_i2 : nullptr, d_off, d_prod, (uint32_t)m, stream);
     else if (k) LL::miller(d_g1, has_inf1 ? d_i1 : nullptr, d_g2, has_inf2 ? d_i2 : nullptr, d_f, k, stream);
-    PAIR_HIP_OK(hipEventRecord(ev[1], stream));
+    HIP_TRY(hipEventRecord(ev[1], stream), 1);
     if (shared) {
       // products already formed by the Miller kernel
     } else if (m == 1 && k > 8) {  // one large product: pairwise tree, log2(k) levels
@@ -483,17 +474,17 @@ template <class PP> class PairingEngine {
         n_in = (n_in + 1) / 2;
         uint32_t* t = src; src = dst; dst = t;
       }
-      PAIR_HIP_OK(hipMemcpyAsync(d_prod, src, W * 4, hipMemcpyDeviceToDevice, stream));
+      HIP_TRY(hipMemcpyAsync(d_prod, src, W * 4, hipMemcpyDeviceToDevice, stream), 1);
     } else {
       LL::gt_product(d_f, d_off, d_prod, (uint32_t)m, stream);
     }
-    PAIR_HIP_OK(hipEventRecord(ev[2], stream));
+    HIP_TRY(hipEventRecord(ev[2], stream), 1);
     LL::final_exp(d_prod, out_is_one ? d_one : nullptr, out_gt ? d_gt : nullptr, (uint32_t)m, mode == 0 ? 1 : 0, stream);
-    PAIR_HIP_OK(hipEventRecord(ev[3], stream));
-    if (out_is_one) PAIR_HIP_OK(hipMemcpyAsync(out_is_one, d_one, m, hipMemcpyDeviceToHost, stream));
-    if (out_gt) PAIR_HIP_OK(hipMemcpyAsync(out_gt, d_gt, (size_t)m * 72 * 8, hipMemcpyDeviceToHost, stream));
-    PAIR_HIP_OK(hipStreamSynchronize(stream));
-    PAIR_HIP_OK(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev[3], stream), 1);
+    if (out_is_one) HIP_TRY(hipMemcpyAsync(out_is_one, d_one, m, hipMemcpyDeviceToHost, stream), 1);
+    if (out_gt) HIP_TRY(hipMemcpyAsync(out_gt, d_gt, (size_t)m * 72 * 8, hipMemcpyDeviceToHost, stream), 1);
+    HIP_TRY(hipStreamSynchronize(stream), 1);
+    HIP_TRY(hipGetLastError(), 1);
     (void)hipEventElapsedTime(&tm.miller, ev[0], ev[1]);
     (void)hipEventElapsedTime(&tm.product, ev[1], ev[2]);
     (void)hipEventElapsedTime(&tm.final_exp, ev[2], ev[3]);
@@ -515,12 +506,12 @@ template <class PP> class PairingEngine {
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   int ensure(size_t bytes) {
     if (!ev[0])
-      for (int i = 0; i < 4; i++) PAIR_HIP_OK(hipEventCreate(&ev[i]));
+      for (int i = 0; i < 4; i++) HIP_TRY(hipEventCreate(&ev[i]), 1);
     if (bytes > arena_bytes) {
       if (arena) (void)hipFree(arena);
       arena = nullptr; arena_bytes = 0;
       lines_valid = false;
-      PAIR_HIP_OK(hipMalloc(&arena, bytes));
+      HIP_TRY(hipMalloc(&arena, bytes), 1);
       arena_bytes = bytes;
     }
     return 0;

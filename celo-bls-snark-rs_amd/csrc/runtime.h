@@ -14,9 +14,20 @@
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <condition_variable>
+#include <cstdio>
 #include <memory>
 #include <mutex>
 #include <vector>
+
+// a failed HIP call: logged (the expression, HIP's message, where), then the calling function returns rc
+#define HIP_TRY(x, rc)                                                                                            \
+  do {                                                                                                            \
+    const hipError_t e_ = (x);                                                                                    \
+    if (e_ != hipSuccess) {                                                                                       \
+      fprintf(stderr, "[celo-amd] %s: %s at %s:%d\n", #x, hipGetErrorString(e_), __FILE__, __LINE__);             \
+      return rc;                                                                                                  \
+    }                                                                                                             \
+  } while (0)
 
 namespace celo {
 
@@ -114,6 +125,48 @@ struct OwnedStream {
     if (!s && hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) s = nullptr;
     return s;
   }
+};
+
+// The device resources of ONE call: its allocations, its events and, when create_stream() made one, its stream.  The call runs on
+// stream() - the caller's, the null stream, or its own.  Released on every exit, in this order: the stream is synchronised, the
+// allocations freed, the events destroyed, then an owned stream destroyed.
+class CallScope {
+ public:
+  explicit CallScope(hipStream_t s) : s_(s) {}
+  CallScope(const CallScope&) = delete;
+  CallScope& operator=(const CallScope&) = delete;
+  ~CallScope() {
+    (void)hipStreamSynchronize(s_);
+    for (void* p : mem_) (void)hipFree(p);
+    for (hipEvent_t e : ev_) (void)hipEventDestroy(e);
+    if (owned_) (void)hipStreamDestroy(s_);
+  }
+  hipStream_t stream() const { return s_; }
+  hipError_t create_stream() {        // a non-blocking stream of the call's own, in place of the one given
+    hipStream_t s = nullptr;
+    const hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+    if (e == hipSuccess) { s_ = s; owned_ = true; }
+    return e;
+  }
+  template <class T> hipError_t alloc(T** p, size_t bytes) {
+    void* q = nullptr;
+    const hipError_t e = hipMalloc(&q, bytes);
+    if (e == hipSuccess) mem_.push_back(q);
+    *p = (T*)q;
+    return e;
+  }
+  hipError_t event(hipEvent_t* out) {
+    hipEvent_t e = nullptr;
+    const hipError_t rc = hipEventCreate(&e);
+    if (rc == hipSuccess) ev_.push_back(e);
+    *out = e;
+    return rc;
+  }
+ private:
+  hipStream_t s_ = nullptr;
+  bool owned_ = false;
+  std::vector<void*> mem_;
+  std::vector<hipEvent_t> ev_;
 };
 
 

@@ -161,14 +161,15 @@ int draw_exponents_run(const uint32_t key[8], const uint32_t* offsets, size_t m,
   if (!key || !offsets || !out || m == 0 || m > 0x7fffffffu) return 2;
   const size_t tot = offsets[m];
   if (tot == 0) return 0;
-  uint32_t* d_off = nullptr; uint64_t* d_out = nullptr;
-  int rc = 1;
-  if (hipMalloc((void**)&d_off, (m + 1) * 4) == hipSuccess && hipMalloc((void**)&d_out, tot * 32) == hipSuccess &&
-      hipMemcpy(d_off, offsets, (m + 1) * 4, hipMemcpyHostToDevice) == hipSuccess && (rc = bv_draw_exponents(key, d_off, m, tot, d_out, nullptr)) == 0)
-    rc = hipMemcpy(out, d_out, tot * 32, hipMemcpyDeviceToHost) == hipSuccess ? 0 : 1;
-  if (d_off) (void)hipFree(d_off);
-  if (d_out) (void)hipFree(d_out);
-  return rc;
+  CallScope cs(nullptr);
+  uint32_t* d_off;
+  uint64_t* d_out;
+  HIP_TRY(cs.alloc(&d_off, (m + 1) * 4), 1);
+  HIP_TRY(cs.alloc(&d_out, tot * 32), 1);
+  HIP_TRY(hipMemcpy(d_off, offsets, (m + 1) * 4, hipMemcpyHostToDevice), 1);
+  if (int rc = bv_draw_exponents(key, d_off, m, tot, d_out, nullptr)) return rc;
+  HIP_TRY(hipMemcpy(out, d_out, tot * 32, hipMemcpyDeviceToHost), 1);
+  return 0;
 }
 
 // The chain in three steps, so that a caller whose inputs arrive in stages (Seam A gathers 10^6 key handles, then 10^6 signature

@@ -108,12 +108,6 @@ static int hash_scratch(size_t need, HashScratch** out) {
 static float g_hash_ms = 0.f;
 static int g_hash_rounds = 0;
 
-#define HASH_TRY(x)                                                                                  \
-  do {                                                                                               \
-    hipError_t e_ = (x);                                                                             \
-    if (e_ != hipSuccess) { fprintf(stderr, "[celo-amd] %s: %s\n", #x, hipGetErrorString(e_)); rc = 10; goto done; } \
-  } while (0)
-
 int hash_to_g1_direct_run(const uint8_t* domain, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off,
                           size_t n, uint64_t* out_xy, uint8_t* attempts, int mode) {
   size_t ngens = 0;
@@ -138,72 +132,64 @@ int hash_to_g1_direct_run(const uint8_t* domain, const uint8_t* msgs, const uint
   if (int rck = wire_consts_device(k)) return rck;
   HashDom dom;
   memcpy(dom.b, domain, 8);
-  uint8_t *d_bytes = nullptr, *d_att = nullptr, *d_redo = nullptr;
-  uint64_t *d_off = nullptr, *d_out = nullptr, *d_cand = nullptr;
-  uint32_t *d_list = nullptr, *d_cnt = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
   std::vector<uint8_t> redo(n);
-  int rc = 0;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~size_t(255); return o; };
+  const size_t o_off = take((n + 1) * 2 * 8), o_out = take(n * 12 * 8), o_cand = take(n * 12 * 8), o_list = take(2 * n * 4), o_cnt = take(256 * 4),
+               o_att = take(n), o_redo = take(n), o_bytes = take(mb + eb + 8);
   HashScratch* hs = nullptr;
-  hipStream_t st = nullptr;
-  {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~size_t(255); return o; };
-    const size_t o_off = take((n + 1) * 2 * 8), o_out = take(n * 12 * 8), o_cand = take(n * 12 * 8), o_list = take(2 * n * 4), o_cnt = take(256 * 4),
-                 o_att = take(n), o_redo = take(n), o_bytes = take(mb + eb + 8);
-    if (hash_scratch(off, &hs)) { rc = 10; goto done; }
-    st = hs->stream;
-    d_off = (uint64_t*)(hs->buf + o_off); d_out = (uint64_t*)(hs->buf + o_out); d_cand = (uint64_t*)(hs->buf + o_cand);
-    d_list = (uint32_t*)(hs->buf + o_list); d_cnt = (uint32_t*)(hs->buf + o_cnt); d_att = hs->buf + o_att; d_redo = hs->buf + o_redo; d_bytes = hs->buf + o_bytes;
-    if (mb) HASH_TRY(hipMemcpyAsync(d_bytes, msgs, mb, hipMemcpyHostToDevice, st));
-    if (eb) HASH_TRY(hipMemcpyAsync(d_bytes + mb, extras, eb, hipMemcpyHostToDevice, st));
-    HASH_TRY(hipMemcpyAsync(d_off, msg_off, (n + 1) * 8, hipMemcpyHostToDevice, st));
-    if (extra_off) HASH_TRY(hipMemcpyAsync(d_off + n + 1, extra_off, (n + 1) * 8, hipMemcpyHostToDevice, st));
-    HASH_TRY(hipMemsetAsync(d_cnt, 0, 256 * 4, st));
-    HASH_TRY(hipEventCreate(&e0));
-    HASH_TRY(hipEventCreate(&e1));
-    HASH_TRY(hipEventRecord(e0, st));
-    const HashIn in = {d_bytes, d_off, d_bytes + mb, extra_off ? d_off + n + 1 : nullptr};
-    uint32_t count = (uint32_t)n, base = 0;
-    int round = 0;
-    while (count && base < 255) {
-      uint32_t cand_log = 0;
-      while (cand_log < 4 && ((size_t)count << (cand_log + 1)) <= (1u << 17)) cand_log++;     // fill ~2^17 lanes, at most 16 counters
-      const uint32_t* list = round ? d_list + (size_t)(round & 1) * n : nullptr;
-      uint32_t* next = d_list + (size_t)((round + 1) & 1) * n;
-      const size_t lanes = (size_t)count << cand_log;
-      hipLaunchKernelGGL(k_hash_candidates, dim3((uint32_t)((lanes + 63) / 64)), dim3(64), 0, st, dom, in, list, count, cand_log, base, mode, d_gens, d_cand, d_att,
-                         next, d_cnt + round, k);
-      HASH_TRY(hipGetLastError());
-      HASH_TRY(hipMemcpyAsync(&count, d_cnt + round, 4, hipMemcpyDeviceToHost, st));
-      HASH_TRY(hipStreamSynchronize(st));
-      base += 1u << cand_log;
-      round++;
-    }
-    g_hash_rounds = round;
-    hipLaunchKernelGGL(k_hash_finish, dim3(((uint32_t)n + 63) / 64), dim3(64), 0, st, d_cand, d_att, d_out, d_redo, (uint32_t)n);
-    HASH_TRY(hipGetLastError());
-    HASH_TRY(hipEventRecord(e1, st));
-    HASH_TRY(hipMemcpyAsync(out_xy, d_out, n * 12 * 8, hipMemcpyDeviceToHost, st));
-    HASH_TRY(hipMemcpyAsync(attempts, d_att, n, hipMemcpyDeviceToHost, st));
-    HASH_TRY(hipMemcpyAsync(redo.data(), d_redo, n, hipMemcpyDeviceToHost, st));
-    HASH_TRY(hipStreamSynchronize(st));
-    HASH_TRY(hipEventElapsedTime(&g_hash_ms, e0, e1));
-    // the counter whose cofactor multiple was the identity is skipped like the reference's loop does: continue serially after it
-    for (size_t i = 0; i < n; i++) {
-      if (!redo[i]) continue;
-      Affine<Fq> p = {Fq::zero(), Fq::zero()};
-      int c = 255;
-      uint64_t* o = out_xy + i * 12;
-      if (hash_to_g1_direct_tai(domain, msgs + msg_off[i], msg_off[i + 1] - msg_off[i], extra_off ? extras + extra_off[i] : nullptr,
-                                extra_off ? extra_off[i + 1] - extra_off[i] : 0, kh, p, c, attempts[i] + 1, mode, h_gens)) { p.x.to_ark(o); p.y.to_ark(o + 6); attempts[i] = (uint8_t)c; }
-      else { attempts[i] = 255; memset(o, 0, 96); }
-    }
+  if (hash_scratch(off, &hs)) return 10;
+  CallScope cs(hs->stream);               // the scratch and its stream stay with the device; the call owns its events
+  const hipStream_t st = cs.stream();
+  uint64_t *d_off = (uint64_t*)(hs->buf + o_off), *d_out = (uint64_t*)(hs->buf + o_out), *d_cand = (uint64_t*)(hs->buf + o_cand);
+  uint32_t *d_list = (uint32_t*)(hs->buf + o_list), *d_cnt = (uint32_t*)(hs->buf + o_cnt);
+  uint8_t *d_att = hs->buf + o_att, *d_redo = hs->buf + o_redo, *d_bytes = hs->buf + o_bytes;
+  if (mb) HIP_TRY(hipMemcpyAsync(d_bytes, msgs, mb, hipMemcpyHostToDevice, st), 10);
+  if (eb) HIP_TRY(hipMemcpyAsync(d_bytes + mb, extras, eb, hipMemcpyHostToDevice, st), 10);
+  HIP_TRY(hipMemcpyAsync(d_off, msg_off, (n + 1) * 8, hipMemcpyHostToDevice, st), 10);
+  if (extra_off) HIP_TRY(hipMemcpyAsync(d_off + n + 1, extra_off, (n + 1) * 8, hipMemcpyHostToDevice, st), 10);
+  HIP_TRY(hipMemsetAsync(d_cnt, 0, 256 * 4, st), 10);
+  hipEvent_t e0, e1;
+  HIP_TRY(cs.event(&e0), 10);
+  HIP_TRY(cs.event(&e1), 10);
+  HIP_TRY(hipEventRecord(e0, st), 10);
+  const HashIn in = {d_bytes, d_off, d_bytes + mb, extra_off ? d_off + n + 1 : nullptr};
+  uint32_t count = (uint32_t)n, base = 0;
+  int round = 0;
+  while (count && base < 255) {
+    uint32_t cand_log = 0;
+    while (cand_log < 4 && ((size_t)count << (cand_log + 1)) <= (1u << 17)) cand_log++;     // fill ~2^17 lanes, at most 16 counters
+    const uint32_t* list = round ? d_list + (size_t)(round & 1) * n : nullptr;
+    uint32_t* next = d_list + (size_t)((round + 1) & 1) * n;
+    const size_t lanes = (size_t)count << cand_log;
+    hipLaunchKernelGGL(k_hash_candidates, dim3((uint32_t)((lanes + 63) / 64)), dim3(64), 0, st, dom, in, list, count, cand_log, base, mode, d_gens, d_cand, d_att,
+                       next, d_cnt + round, k);
+    HIP_TRY(hipGetLastError(), 10);
+    HIP_TRY(hipMemcpyAsync(&count, d_cnt + round, 4, hipMemcpyDeviceToHost, st), 10);
+    HIP_TRY(hipStreamSynchronize(st), 10);
+    base += 1u << cand_log;
+    round++;
   }
-done:
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  return rc;
+  g_hash_rounds = round;
+  hipLaunchKernelGGL(k_hash_finish, dim3(((uint32_t)n + 63) / 64), dim3(64), 0, st, d_cand, d_att, d_out, d_redo, (uint32_t)n);
+  HIP_TRY(hipGetLastError(), 10);
+  HIP_TRY(hipEventRecord(e1, st), 10);
+  HIP_TRY(hipMemcpyAsync(out_xy, d_out, n * 12 * 8, hipMemcpyDeviceToHost, st), 10);
+  HIP_TRY(hipMemcpyAsync(attempts, d_att, n, hipMemcpyDeviceToHost, st), 10);
+  HIP_TRY(hipMemcpyAsync(redo.data(), d_redo, n, hipMemcpyDeviceToHost, st), 10);
+  HIP_TRY(hipStreamSynchronize(st), 10);
+  HIP_TRY(hipEventElapsedTime(&g_hash_ms, e0, e1), 10);
+  // the counter whose cofactor multiple was the identity is skipped like the reference's loop does: continue serially after it
+  for (size_t i = 0; i < n; i++) {
+    if (!redo[i]) continue;
+    Affine<Fq> p = {Fq::zero(), Fq::zero()};
+    int c = 255;
+    uint64_t* o = out_xy + i * 12;
+    if (hash_to_g1_direct_tai(domain, msgs + msg_off[i], msg_off[i + 1] - msg_off[i], extra_off ? extras + extra_off[i] : nullptr,
+                              extra_off ? extra_off[i + 1] - extra_off[i] : 0, kh, p, c, attempts[i] + 1, mode, h_gens)) { p.x.to_ark(o); p.y.to_ark(o + 6); attempts[i] = (uint8_t)c; }
+    else { attempts[i] = 255; memset(o, 0, 96); }
+  }
+  return 0;
 }
 // ---- bulk Pedersen CRH (pedersen.h): one message per lane; the 52080-generator table (11.7 MB) is uploaded on first use
 __global__ void __launch_bounds__(64) FROW_OCC
@@ -227,35 +213,28 @@ int pedersen_crh_run(const uint8_t* msgs, const uint64_t* msg_off, size_t n, uin
   }
   const size_t mb = msg_off[n];
   if (mb && !msgs) return 2;
-  uint8_t *d_bytes = nullptr, *d_out = nullptr;
-  uint64_t* d_off = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  int rc = 0;
   if (int rcg = ensure_device_gens(gens, ngens)) return rcg;
   EdPoint* d_gens = g_d_gens;
+  const size_t o_off = 0, o_out = ((n + 1) * 8 + 255) & ~size_t(255), o_bytes = o_out + ((n * 48 + 255) & ~size_t(255));
   HashScratch* hs = nullptr;
-  hipStream_t st = nullptr;
-  {
-    const size_t o_off = 0, o_out = ((n + 1) * 8 + 255) & ~size_t(255), o_bytes = o_out + ((n * 48 + 255) & ~size_t(255));
-    if (hash_scratch(o_bytes + mb + 8, &hs)) { rc = 10; goto done; }
-    st = hs->stream;
-    d_off = (uint64_t*)(hs->buf + o_off); d_out = hs->buf + o_out; d_bytes = hs->buf + o_bytes;
-  }
-  if (mb) HASH_TRY(hipMemcpyAsync(d_bytes, msgs, mb, hipMemcpyHostToDevice, st));
-  HASH_TRY(hipMemcpyAsync(d_off, msg_off, (n + 1) * 8, hipMemcpyHostToDevice, st));
-  HASH_TRY(hipEventCreate(&e0));
-  HASH_TRY(hipEventCreate(&e1));
-  HASH_TRY(hipEventRecord(e0, st));
+  if (hash_scratch(o_bytes + mb + 8, &hs)) return 10;
+  CallScope cs(hs->stream);
+  const hipStream_t st = cs.stream();
+  uint64_t* d_off = (uint64_t*)(hs->buf + o_off);
+  uint8_t *d_out = hs->buf + o_out, *d_bytes = hs->buf + o_bytes;
+  if (mb) HIP_TRY(hipMemcpyAsync(d_bytes, msgs, mb, hipMemcpyHostToDevice, st), 10);
+  HIP_TRY(hipMemcpyAsync(d_off, msg_off, (n + 1) * 8, hipMemcpyHostToDevice, st), 10);
+  hipEvent_t e0, e1;
+  HIP_TRY(cs.event(&e0), 10);
+  HIP_TRY(cs.event(&e1), 10);
+  HIP_TRY(hipEventRecord(e0, st), 10);
   hipLaunchKernelGGL(k_pedersen_crh, dim3(((uint32_t)n + 63) / 64), dim3(64), 0, st, d_gens, d_bytes, d_off, d_out, (uint32_t)n);
-  HASH_TRY(hipGetLastError());
-  HASH_TRY(hipEventRecord(e1, st));
-  HASH_TRY(hipMemcpyAsync(out48, d_out, n * 48, hipMemcpyDeviceToHost, st));
-  HASH_TRY(hipStreamSynchronize(st));
-  HASH_TRY(hipEventElapsedTime(&g_hash_ms, e0, e1));
-done:
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  return rc;
+  HIP_TRY(hipGetLastError(), 10);
+  HIP_TRY(hipEventRecord(e1, st), 10);
+  HIP_TRY(hipMemcpyAsync(out48, d_out, n * 48, hipMemcpyDeviceToHost, st), 10);
+  HIP_TRY(hipStreamSynchronize(st), 10);
+  HIP_TRY(hipEventElapsedTime(&g_hash_ms, e0, e1), 10);
+  return 0;
 }
 float hash_last_ms() { return g_hash_ms; }
 int hash_last_rounds() { return g_hash_rounds; }

@@ -61,12 +61,6 @@ __global__ void __launch_bounds__(256) k_to_canonical(uint64_t* __restrict__ a, 
   FR::from_ark(a + (size_t)i * FR::ARK64).to_canonical(a + (size_t)i * FR::ARK64);
 }
 
-#define PRV_OK(x)                                                                                                  \
-  do {                                                                                                             \
-    hipError_t e_ = (x);                                                                                           \
-    if (e_ != hipSuccess) { fprintf(stderr, "[celo-amd] %s: %s\n", #x, hipGetErrorString(e_)); rc = 10; goto done; } \
-  } while (0)
-
 // dev = 1: a, b, c are DEVICE pointers (a is overwritten with h; b and c are overwritten with intermediate values).
 template <class FR>
 static int witness_map_t(uint64_t* a, uint64_t* b, uint64_t* c, unsigned log_n, const uint64_t* omega, const uint64_t* omega_inv, const uint64_t* coset,
@@ -74,10 +68,9 @@ static int witness_map_t(uint64_t* a, uint64_t* b, uint64_t* c, unsigned log_n, 
   if (int rc0 = api_enter()) return rc0;
   if (!a || !b || !c || !omega || !omega_inv || !coset || !coset_inv || !n_inv || !z_inv || log_n > 28) return 2;
   const size_t n = size_t(1) << log_n, bytes = n * FR::ARK64 * 8;
-  hipStream_t stream = (hipStream_t)stream_;
+  CallScope cs((hipStream_t)stream_);
+  const hipStream_t stream = cs.stream();
   uint64_t *da = a, *db = b, *dc = c;
-  uint32_t* d_z = nullptr;
-  int rc = 0;
   uint32_t zw[FR::WORDS];
   {
     FR v = FR::wred(FR::from_ark(z_inv));
@@ -85,28 +78,25 @@ static int witness_map_t(uint64_t* a, uint64_t* b, uint64_t* c, unsigned log_n, 
     v.store(zw);
   }
   if (!dev) {
-    da = db = dc = nullptr;
-    PRV_OK(hipMalloc(&da, bytes)); PRV_OK(hipMalloc(&db, bytes)); PRV_OK(hipMalloc(&dc, bytes));
-    PRV_OK(hipMemcpyAsync(da, a, bytes, hipMemcpyHostToDevice, stream));
-    PRV_OK(hipMemcpyAsync(db, b, bytes, hipMemcpyHostToDevice, stream));
-    PRV_OK(hipMemcpyAsync(dc, c, bytes, hipMemcpyHostToDevice, stream));
+    HIP_TRY(cs.alloc(&da, bytes), 10); HIP_TRY(cs.alloc(&db, bytes), 10); HIP_TRY(cs.alloc(&dc, bytes), 10);
+    HIP_TRY(hipMemcpyAsync(da, a, bytes, hipMemcpyHostToDevice, stream), 10);
+    HIP_TRY(hipMemcpyAsync(db, b, bytes, hipMemcpyHostToDevice, stream), 10);
+    HIP_TRY(hipMemcpyAsync(dc, c, bytes, hipMemcpyHostToDevice, stream), 10);
   }
-  PRV_OK(hipMalloc(&d_z, sizeof zw));
-  PRV_OK(hipMemcpyAsync(d_z, zw, sizeof zw, hipMemcpyHostToDevice, stream));
+  uint32_t* d_z;
+  HIP_TRY(cs.alloc(&d_z, sizeof zw), 10);
+  HIP_TRY(hipMemcpyAsync(d_z, zw, sizeof zw, hipMemcpyHostToDevice, stream), 10);
   // an NTT engine keeps the twiddle table of its last (omega, n) and the pool hands the same engine back to a serial caller: the
   // table is rebuilt three times per witness map (inverse, forward, inverse: ~20 us each at 2^20), not seven
-  for (uint64_t* p : {da, db, dc}) if ((rc = NttOf<FR>::run(p, log_n, omega_inv, nullptr, 0, n_inv, stream))) goto done;        // ifft
-  for (uint64_t* p : {da, db, dc}) if ((rc = NttOf<FR>::run(p, log_n, omega, coset, 0, nullptr, stream))) goto done;             // coset_fft
+  for (uint64_t* p : {da, db, dc}) if (int rc = NttOf<FR>::run(p, log_n, omega_inv, nullptr, 0, n_inv, stream)) return rc;        // ifft
+  for (uint64_t* p : {da, db, dc}) if (int rc = NttOf<FR>::run(p, log_n, omega, coset, 0, nullptr, stream)) return rc;             // coset_fft
   hipLaunchKernelGGL((k_qap_combine<FR>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, da, db, dc, (uint32_t)n, d_z);
-  if ((rc = NttOf<FR>::run(da, log_n, omega_inv, coset_inv, 1, n_inv, stream))) goto done;                                          // coset_ifft
+  if (int rc = NttOf<FR>::run(da, log_n, omega_inv, coset_inv, 1, n_inv, stream)) return rc;                                          // coset_ifft
   if (out_canonical) hipLaunchKernelGGL((k_to_canonical<FR>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, da, (uint32_t)n);
-  PRV_OK(hipGetLastError());
-  if (!dev) PRV_OK(hipMemcpyAsync(a, da, bytes, hipMemcpyDeviceToHost, stream));
-  PRV_OK(hipStreamSynchronize(stream));
-done:
-  if (!dev) { if (da) (void)hipFree(da); if (db) (void)hipFree(db); if (dc) (void)hipFree(dc); }
-  if (d_z) (void)hipFree(d_z);
-  return rc;
+  HIP_TRY(hipGetLastError(), 10);
+  if (!dev) HIP_TRY(hipMemcpyAsync(a, da, bytes, hipMemcpyDeviceToHost, stream), 10);
+  HIP_TRY(hipStreamSynchronize(stream), 10);
+  return 0;
 }
 
 int witness_map_run(uint64_t* a, uint64_t* b, uint64_t* c, unsigned log_n, const uint64_t* omega, const uint64_t* omega_inv, const uint64_t* coset,

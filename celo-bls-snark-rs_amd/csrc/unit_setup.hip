@@ -1,13 +1,12 @@
-// Translation unit: batched fixed-base scalar multiplication (fixed_base.h) for the four groups, the BW6-761 batch normalisation, and
-// Groth16 parameter generation after the QAP evaluation at tau (ark-groth16 0.1 generate_parameters, reached through
-// crates/epoch-snark/src/api/setup.rs:22-46,63-105).  DESIGN.md section 6f.
+// Translation unit: batched fixed-base scalar multiplication (fixed_base.h) for the four groups, and Groth16 parameter generation after
+// the QAP evaluation at tau (ark-groth16 0.1 generate_parameters, reached through crates/epoch-snark/src/api/setup.rs:22-46,63-105).
+// DESIGN.md section 6f.
 #include "fixed_base.h"
+#include "normalize.h"
 #include <hip/hip_runtime.h>
 #include <chrono>
-#include <cstdio>
 #include <cstring>
 #include <mutex>
-#include <type_traits>
 #include <vector>
 #include "runtime.h"
 
@@ -15,7 +14,6 @@ namespace celo {
 struct ProvingKey;
 int groth16_key_load_dev(int, const uint64_t*, const uint8_t*, size_t, const uint64_t*, const uint8_t*, size_t, const uint64_t*, const uint8_t*, size_t,
                          const uint64_t*, const uint8_t*, size_t, const uint64_t*, const uint64_t*, const uint64_t*, const uint64_t*, int, ProvingKey**);
-void groth16_key_free(ProvingKey*);
 
 typedef Fp<P377> FrBw6;          // the scalar field of BW6-761 (the base field of BLS12-377)
 typedef Fp<P253> FrBls;          // the scalar field of BLS12-377
@@ -80,73 +78,6 @@ __global__ void __launch_bounds__(256) k_fbm_rows(const uint64_t* __restrict__ s
   a.X.store(o); a.Y.store(o + F::WORDS); a.ZZ.store(o + 2 * F::WORDS); a.ZZZ.store(o + 3 * F::WORDS);
 }
 
-// ---- batch normalisation, Montgomery's trick over K consecutive points of a lane (unit_wire.hip k_normalize's scheme: the prefix products
-// in registers, the denominators read again on the way back).  JAC = false: XYZZ rows in device form, the denominator ZZ ZZZ
-// (x = X ZZZ / (ZZ ZZZ), y = Y ZZ / (ZZ ZZZ)); JAC = true: Jacobian rows in arkworks limbs (x = X / Z^2, y = Y / Z^3).  The identity row is
-// written as zeros, or as arkworks' GroupAffine::zero() coordinates (0, 1) with ark_zero_y; inf[i] = 1 either way.
-template <int N, bool REVERSE, class Fn> __device__ __forceinline__ void fbm_static_for(Fn&& f) {
-  if constexpr (N > 0) {
-    if constexpr (REVERSE) { f(std::integral_constant<int, N - 1>{}); fbm_static_for<N - 1, true>(f); }
-    else { fbm_static_for<N - 1, false>(f); f(std::integral_constant<int, N - 1>{}); }
-  }
-}
-template <class F, int K, bool JAC>
-__global__ void __launch_bounds__(64) k_fbm_normalize(const void* __restrict__ in_, uint64_t* __restrict__ out, uint8_t* __restrict__ inf, uint32_t n, int ark_zero_y) {
-  constexpr int A = F::ARK64, FW = F::WORDS;
-  const uint32_t lo = (blockIdx.x * blockDim.x + threadIdx.x) * K;
-  if (lo >= n) return;
-  const uint32_t cnt = n - lo < (uint32_t)K ? n - lo : (uint32_t)K;
-  const uint64_t* jac = (const uint64_t*)in_;
-  const uint32_t* xyzz = (const uint32_t*)in_;
-  auto den = [&](int j) -> F {
-    if constexpr (JAC) return F::norm(F::from_ark(jac + ((size_t)lo + j) * 3 * A + 2 * A));
-    else {
-      const uint32_t* p = xyzz + ((size_t)lo + j) * 4 * FW;
-      const F zz = F::load(p + 2 * FW);
-      if (zz.limbs_all_zero()) return F::zero();
-      return F::norm(F::mul(zz, F::load(p + 3 * FW)));
-    }
-  };
-  F pre[K];
-  uint32_t idmask = 0;
-  F acc = F::one();
-  fbm_static_for<K, false>([&](auto jc) {
-    constexpr int j = decltype(jc)::value;
-    pre[j] = acc;
-    if ((uint32_t)j < cnt) {
-      const F dj = den(j);
-      if (dj.is_zero_mod_p()) idmask |= 1u << j;
-      else acc = F::norm(F::mul(acc, dj));
-    }
-  });
-  F iv = F::norm(F::inv(acc));
-  fbm_static_for<K, true>([&](auto jc) {
-    constexpr int j = decltype(jc)::value;
-    if ((uint32_t)j < cnt) {
-      uint64_t* o = out + ((size_t)lo + j) * 2 * A;
-      const bool id = (idmask >> j) & 1u;
-      inf[lo + j] = id ? 1 : 0;
-      if (id) {
-        for (int q = 0; q < 2 * A; q++) o[q] = 0;
-        if (ark_zero_y) F::one().to_ark(o + A);
-      } else {
-        const F di = F::norm(F::mul(iv, pre[j]));
-        iv = F::norm(F::mul(iv, den(j)));
-        if constexpr (JAC) {
-          const uint64_t* src = jac + ((size_t)lo + j) * 3 * A;
-          const F di2 = F::norm(F::sqr(di));
-          F::mul(F::from_ark(src), di2).to_ark(o);
-          F::mul(F::from_ark(src + A), F::norm(F::mul(di2, di))).to_ark(o + A);
-        } else {
-          const uint32_t* p = xyzz + ((size_t)lo + j) * 4 * FW;
-          F::mul(F::load(p), F::norm(F::mul(di, F::load(p + 3 * FW)))).to_ark(o);
-          F::mul(F::load(p + FW), F::norm(F::mul(di, F::load(p + 2 * FW)))).to_ark(o + A);
-        }
-      }
-    }
-  });
-}
-
 // ---- the Groth16 setup's scalars (fixed_base.h setup_*), written where the fixed-base kernels read them: the G1 scalar list is
 // [alpha, beta, delta, gamma_abc (n_inputs), a (n_vars), b (n_vars), h (n_h), l (n_vars - n_inputs)], the G2 list [beta, gamma, delta, b (n_vars)]
 // (the first three of each come from the host); one lane per variable.
@@ -175,12 +106,6 @@ __global__ void __launch_bounds__(256) k_setup_h(FR zt_dinv, FR tau, uint32_t n_
   setup_h_block<FR>(zt_dinv, tau, i0, cnt, out + i0 * FR::ARK64);
 }
 
-#define SETUP_TRY(x)                                                                                 \
-  do {                                                                                               \
-    hipError_t e_ = (x);                                                                             \
-    if (e_ != hipSuccess) { fprintf(stderr, "[celo-amd] %s: %s\n", #x, hipGetErrorString(e_)); rc = 10; goto done; } \
-  } while (0)
-
 // kernel-time accounting by event pairs per category (read after the call's final synchronisation)
 struct EvLog {
   struct Rec { int cat; hipEvent_t a, b; };
@@ -206,56 +131,50 @@ template <class F, int N64, int BITS> struct Fbm {
   ~Fbm() { if (table) (void)hipFree(table); if (tinf) (void)hipFree(tinf); }
   // the generator's table (gen: affine arkworks limbs, not the identity)
   int build(const uint64_t* gen, hipStream_t s, EvLog* log) {
-    int rc = 0;
-    uint32_t* bases = nullptr;
-    uint8_t* binf = nullptr;
+    CallScope cs(s);
+    uint32_t* bases;
+    uint8_t* binf;
     ArkWords<2 * A> g;
-    hipEvent_t e0 = nullptr;
     c = g_fb_c ? g_fb_c : FB_DEFAULT_C;
     W = fb_windows(BITS, c);
     H = 1u << (c - 1);
     const uint32_t E = (uint32_t)W * H;
     memcpy(g.v, gen, sizeof g.v);
-    SETUP_TRY(hipMalloc(&bases, (size_t)W * 2 * F::WORDS * 4));
-    SETUP_TRY(hipMalloc(&binf, W));
-    SETUP_TRY(hipMalloc(&table, (size_t)E * 2 * F::WORDS * 4));
-    SETUP_TRY(hipMalloc(&tinf, E));
-    e0 = log->open();
+    HIP_TRY(cs.alloc(&bases, (size_t)W * 2 * F::WORDS * 4), 10);
+    HIP_TRY(cs.alloc(&binf, W), 10);
+    HIP_TRY(hipMalloc(&table, (size_t)E * 2 * F::WORDS * 4), 10);
+    HIP_TRY(hipMalloc(&tinf, E), 10);
+    hipEvent_t e0 = log->open();
     hipLaunchKernelGGL((k_fbm_bases<F>), dim3((W + 63) / 64), dim3(64), 0, s, g, bases, binf, W, c);
     hipLaunchKernelGGL((k_fbm_table<F>), dim3((E + 63) / 64), dim3(64), 0, s, bases, binf, table, tinf, H, E);
     log->close(0, e0);
-    SETUP_TRY(hipGetLastError());
-    SETUP_TRY(hipStreamSynchronize(s));
-  done:
-    if (bases) (void)hipFree(bases);
-    if (binf) (void)hipFree(binf);
-    return rc;
+    HIP_TRY(hipGetLastError(), 10);
+    HIP_TRY(hipStreamSynchronize(s), 10);
+    return 0;
   }
   // n rows from n canonical device scalars into device rows (2 A u64 each) and flags, in chunks that bound the XYZZ scratch buffer.
   // cat: the timing slot of the scalar kernel (2 = G1, 3 = G2); the normalisation goes to slot 4.
   int rows(const uint64_t* d_sc, size_t n, uint64_t* d_out, uint8_t* d_inf, int ark_zero_y, hipStream_t s, EvLog* log, int cat) {
     constexpr size_t CHUNK = size_t(1) << 20;
     constexpr int K = sizeof(F) <= 64 ? 8 : 4;
-    int rc = 0;
-    uint32_t* tmp = nullptr;
     if (n == 0) return 0;
+    CallScope cs(s);
+    uint32_t* tmp;
     const size_t m = n < CHUNK ? n : CHUNK;
-    SETUP_TRY(hipMalloc(&tmp, m * 4 * F::WORDS * 4));
+    HIP_TRY(cs.alloc(&tmp, m * 4 * F::WORDS * 4), 10);
     for (size_t lo = 0; lo < n; lo += CHUNK) {
       const uint32_t k = (uint32_t)(n - lo < CHUNK ? n - lo : CHUNK);
       hipEvent_t e0 = log->open();
       hipLaunchKernelGGL((k_fbm_rows<F, N64>), dim3((k + 255) / 256), dim3(256), 0, s, d_sc + lo * N64, k, table, tinf, c, W, tmp);
       log->close(cat, e0);
       e0 = log->open();
-      hipLaunchKernelGGL((k_fbm_normalize<F, K, false>), dim3(((k + K - 1) / K + 63) / 64), dim3(64), 0, s, (const void*)tmp, d_out + lo * 2 * A, d_inf + lo, k,
+      hipLaunchKernelGGL((k_normalize<F, K, false, 0, true>), dim3(((k + K - 1) / K + 63) / 64), dim3(64), 0, s, (const void*)tmp, d_out + lo * 2 * A, d_inf + lo, k,
                          ark_zero_y);
       log->close(4, e0);
-      SETUP_TRY(hipGetLastError());
+      HIP_TRY(hipGetLastError(), 10);
     }
-    SETUP_TRY(hipStreamSynchronize(s));
-  done:
-    if (tmp) (void)hipFree(tmp);
-    return rc;
+    HIP_TRY(hipStreamSynchronize(s), 10);
+    return 0;
   }
 };
 typedef Fbm<Fp<P377>, 4, 253> FbmG1_377;
@@ -288,51 +207,42 @@ static int fbm_mul(const uint64_t* gen, const void* scalars, size_t n, void* out
     for (size_t i = 0; i < n; i++) if (!fb_below<N64>(sc + i * N64, FrParams<FR>::type::P64)) return 2;
   }
   const auto t0 = std::chrono::steady_clock::now();
-  hipStream_t s = dev ? (hipStream_t)stream_ : nullptr;
-  uint64_t *d_sc = nullptr, *d_out = nullptr;
-  uint8_t* d_inf = nullptr;
-  uint32_t* d_flag = nullptr;
-  int rc = 0;
-  {
-    if (!dev) SETUP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  const int rc = [&]() -> int {     // the device work: its resources are released before the wall time is taken
+    CallScope cs(dev ? (hipStream_t)stream_ : nullptr);
+    if (!dev) HIP_TRY(cs.create_stream(), 10);
+    const hipStream_t s = cs.stream();
     EvLog log(s);
     FB fb;
+    uint64_t *d_sc = (uint64_t*)scalars, *d_out = (uint64_t*)out_xy;
+    uint8_t* d_inf = (uint8_t*)inf;
     if (dev) {
-      d_sc = (uint64_t*)scalars; d_out = (uint64_t*)out_xy; d_inf = (uint8_t*)inf;
       ArkWords<N64> r;
       for (int k = 0; k < N64; k++) r.v[k] = FrParams<FR>::type::P64[k];
       uint32_t flag = 0;
-      SETUP_TRY(hipMalloc(&d_flag, 4));
-      SETUP_TRY(hipMemsetAsync(d_flag, 0, 4, s));
+      uint32_t* d_flag;
+      HIP_TRY(cs.alloc(&d_flag, 4), 10);
+      HIP_TRY(hipMemsetAsync(d_flag, 0, 4, s), 10);
       hipLaunchKernelGGL((k_fbm_range<N64>), dim3(((uint32_t)n + 255) / 256), dim3(256), 0, s, d_sc, (uint32_t)n, r, d_flag);
-      SETUP_TRY(hipGetLastError());
-      SETUP_TRY(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, s));
-      SETUP_TRY(hipStreamSynchronize(s));
-      if (flag) { rc = 2; goto done; }
+      HIP_TRY(hipGetLastError(), 10);
+      HIP_TRY(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, s), 10);
+      HIP_TRY(hipStreamSynchronize(s), 10);
+      if (flag) return 2;
     } else {
-      SETUP_TRY(hipMalloc(&d_sc, n * N64 * 8));
-      SETUP_TRY(hipMalloc(&d_out, n * RW * 8));
-      SETUP_TRY(hipMalloc(&d_inf, n));
-      SETUP_TRY(hipMemcpyAsync(d_sc, scalars, n * N64 * 8, hipMemcpyHostToDevice, s));
+      HIP_TRY(cs.alloc(&d_sc, n * N64 * 8), 10);
+      HIP_TRY(cs.alloc(&d_out, n * RW * 8), 10);
+      HIP_TRY(cs.alloc(&d_inf, n), 10);
+      HIP_TRY(hipMemcpyAsync(d_sc, scalars, n * N64 * 8, hipMemcpyHostToDevice, s), 10);
     }
-    if ((rc = fb.build(gen, s, &log))) goto done;
-    if ((rc = fb.rows(d_sc, n, d_out, d_inf, 0, s, &log, 2))) goto done;
+    if (int rcb = fb.build(gen, s, &log)) return rcb;
+    if (int rcr = fb.rows(d_sc, n, d_out, d_inf, 0, s, &log, 2)) return rcr;
     if (!dev) {
-      SETUP_TRY(hipMemcpyAsync(out_xy, d_out, n * RW * 8, hipMemcpyDeviceToHost, s));
-      SETUP_TRY(hipMemcpyAsync(inf, d_inf, n, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(out_xy, d_out, n * RW * 8, hipMemcpyDeviceToHost, s), 10);
+      HIP_TRY(hipMemcpyAsync(inf, d_inf, n, hipMemcpyDeviceToHost, s), 10);
     }
-    SETUP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipStreamSynchronize(s), 10);
     log.sum(g_setup_ms);
-  }
-done:
-  if (s) (void)hipStreamSynchronize(s);
-  if (d_flag) (void)hipFree(d_flag);
-  if (!dev) {
-    if (d_sc) (void)hipFree(d_sc);
-    if (d_out) (void)hipFree(d_out);
-    if (d_inf) (void)hipFree(d_inf);
-    if (s) (void)hipStreamDestroy(s);
-  }
+    return 0;
+  }();
   g_setup_ms[6] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return rc;
 }
@@ -352,31 +262,6 @@ int fixed_base_set_window(int c) {
   return 0;
 }
 void setup_last_timings(float ms[8]) { for (int i = 0; i < 8; i++) ms[i] = g_setup_ms[i]; }
-
-// Jacobian -> affine for n BW6-761 points (both groups: one coordinate field), arkworks limbs, identity -> zero row and inf = 1
-int normalize_761(const uint64_t* jac, size_t n, uint64_t* out_xy, uint8_t* inf) {
-  if (int rc0 = api_enter()) return rc0;
-  std::lock_guard<std::mutex> lk(setup_mu);
-  if (n == 0) return 0;
-  if (!jac || !out_xy || !inf || n > 0x7fffffffu) return 2;
-  uint64_t *d_in = nullptr, *d_out = nullptr;
-  uint8_t* d_inf = nullptr;
-  int rc = 0;
-  SETUP_TRY(hipMalloc(&d_in, n * 36 * 8));
-  SETUP_TRY(hipMalloc(&d_out, n * 24 * 8));
-  SETUP_TRY(hipMalloc(&d_inf, n));
-  SETUP_TRY(hipMemcpy(d_in, jac, n * 36 * 8, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL((k_fbm_normalize<Fp<P761>, 4, true>), dim3(((uint32_t)((n + 3) / 4) + 63) / 64), dim3(64), 0, 0, (const void*)d_in, d_out, d_inf,
-                     (uint32_t)n, 0);
-  SETUP_TRY(hipGetLastError());
-  SETUP_TRY(hipMemcpy(out_xy, d_out, n * 24 * 8, hipMemcpyDeviceToHost));
-  SETUP_TRY(hipMemcpy(inf, d_inf, n, hipMemcpyDeviceToHost));
-done:
-  if (d_in) (void)hipFree(d_in);
-  if (d_out) (void)hipFree(d_out);
-  if (d_inf) (void)hipFree(d_inf);
-  return rc;
-}
 
 // ---- Groth16 parameter generation (include/celo_bls_amd.h groth16_setup_*).  curve 0 = BW6-761 (FB1 = FB2 = Fbm761), 1 = BLS12-377.
 template <class FB1, class FB2, class FR>
@@ -402,87 +287,78 @@ static int setup_run(int curve, const uint64_t* qa, const uint64_t* qb, const ui
   std::lock_guard<std::mutex> lk(setup_mu);
   for (float& t : g_setup_ms) t = 0.f;
   const auto t0 = std::chrono::steady_clock::now();
-  hipStream_t s = nullptr;
-  uint64_t *d_q = nullptr, *d_s1 = nullptr, *d_s2 = nullptr, *d_r1 = nullptr, *d_r2 = nullptr;
-  uint8_t *d_i1 = nullptr, *d_i2 = nullptr;
-  ProvingKey* key = nullptr;
-  int rc = 0;
-  {
-    SETUP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  const int rc = [&]() -> int {     // the device work: its resources are released before the wall time is taken
+    CallScope cs(nullptr);
+    HIP_TRY(cs.create_stream(), 10);
+    const hipStream_t s = cs.stream();
     EvLog log(s);
     const size_t qb_bytes = n_vars * N * 8;
-    SETUP_TRY(hipMalloc(&d_q, 3 * qb_bytes));
-    SETUP_TRY(hipMalloc(&d_s1, n1 * N * 8));
-    SETUP_TRY(hipMalloc(&d_s2, n2 * N * 8));
-    SETUP_TRY(hipMalloc(&d_r1, n1 * R1 * 8));
-    SETUP_TRY(hipMalloc(&d_r2, n2 * R2 * 8));
-    SETUP_TRY(hipMalloc(&d_i1, n1));
-    SETUP_TRY(hipMalloc(&d_i2, n2));
-    SETUP_TRY(hipMemcpyAsync(d_q, qa, qb_bytes, hipMemcpyHostToDevice, s));
-    SETUP_TRY(hipMemcpyAsync(d_q + n_vars * N, qb, qb_bytes, hipMemcpyHostToDevice, s));
-    SETUP_TRY(hipMemcpyAsync(d_q + 2 * n_vars * N, qc, qb_bytes, hipMemcpyHostToDevice, s));
-    SETUP_TRY(hipMemcpyAsync(d_s1, head1, sizeof head1, hipMemcpyHostToDevice, s));
-    SETUP_TRY(hipMemcpyAsync(d_s2, head2, sizeof head2, hipMemcpyHostToDevice, s));
-    {
-      hipEvent_t e0 = log.open();
-      hipLaunchKernelGGL((k_setup_fr<FR>), dim3((unsigned)((n_vars + 255) / 256)), dim3(256), 0, s, d_q, d_q + n_vars * N, d_q + 2 * n_vars * N,
-                         (uint32_t)n_vars, (uint32_t)n_inputs, alpha, beta, ginv, dinv, d_s1, d_s2, (uint32_t)n_h);
-      if (n_h) {
-        const size_t blocks = (n_h + SETUP_H_BLOCK - 1) / SETUP_H_BLOCK;
-        hipLaunchKernelGGL((k_setup_h<FR>), dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, s, zt_dinv, tau_d, (uint32_t)n_h,
-                           d_s1 + (3 + n_inputs + 2 * n_vars) * N);
-      }
-      log.close(1, e0);
-      SETUP_TRY(hipGetLastError());
+    uint64_t *d_q, *d_s1, *d_s2, *d_r1, *d_r2;
+    uint8_t *d_i1, *d_i2;
+    HIP_TRY(cs.alloc(&d_q, 3 * qb_bytes), 10);
+    HIP_TRY(cs.alloc(&d_s1, n1 * N * 8), 10);
+    HIP_TRY(cs.alloc(&d_s2, n2 * N * 8), 10);
+    HIP_TRY(cs.alloc(&d_r1, n1 * R1 * 8), 10);
+    HIP_TRY(cs.alloc(&d_r2, n2 * R2 * 8), 10);
+    HIP_TRY(cs.alloc(&d_i1, n1), 10);
+    HIP_TRY(cs.alloc(&d_i2, n2), 10);
+    HIP_TRY(hipMemcpyAsync(d_q, qa, qb_bytes, hipMemcpyHostToDevice, s), 10);
+    HIP_TRY(hipMemcpyAsync(d_q + n_vars * N, qb, qb_bytes, hipMemcpyHostToDevice, s), 10);
+    HIP_TRY(hipMemcpyAsync(d_q + 2 * n_vars * N, qc, qb_bytes, hipMemcpyHostToDevice, s), 10);
+    HIP_TRY(hipMemcpyAsync(d_s1, head1, sizeof head1, hipMemcpyHostToDevice, s), 10);
+    HIP_TRY(hipMemcpyAsync(d_s2, head2, sizeof head2, hipMemcpyHostToDevice, s), 10);
+    hipEvent_t e0 = log.open();
+    hipLaunchKernelGGL((k_setup_fr<FR>), dim3((unsigned)((n_vars + 255) / 256)), dim3(256), 0, s, d_q, d_q + n_vars * N, d_q + 2 * n_vars * N,
+                       (uint32_t)n_vars, (uint32_t)n_inputs, alpha, beta, ginv, dinv, d_s1, d_s2, (uint32_t)n_h);
+    if (n_h) {
+      const size_t blocks = (n_h + SETUP_H_BLOCK - 1) / SETUP_H_BLOCK;
+      hipLaunchKernelGGL((k_setup_h<FR>), dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, s, zt_dinv, tau_d, (uint32_t)n_h,
+                         d_s1 + (3 + n_inputs + 2 * n_vars) * N);
     }
+    log.close(1, e0);
+    HIP_TRY(hipGetLastError(), 10);
     {
       FB1 t1;
-      if ((rc = t1.build(g1_xy, s, &log))) goto done;
-      if ((rc = t1.rows(d_s1, n1, d_r1, d_i1, 1, s, &log, 2))) goto done;
+      if (int rcb = t1.build(g1_xy, s, &log)) return rcb;
+      if (int rcr = t1.rows(d_s1, n1, d_r1, d_i1, 1, s, &log, 2)) return rcr;
     }
     {
       FB2 t2;
-      if ((rc = t2.build(g2_xy, s, &log))) goto done;
-      if ((rc = t2.rows(d_s2, n2, d_r2, d_i2, 1, s, &log, 3))) goto done;
+      if (int rcb = t2.build(g2_xy, s, &log)) return rcb;
+      if (int rcr = t2.rows(d_s2, n2, d_r2, d_i2, 1, s, &log, 3)) return rcr;
     }
     const size_t r_abc = 3, r_a = r_abc + n_inputs, r_h = r_a + 2 * n_vars, r_l = r_h + n_h;
     if (out_vk) {
       uint64_t* o = out_vk;
-      SETUP_TRY(hipMemcpyAsync(o, d_r1, R1 * 8, hipMemcpyDeviceToHost, s)); o += R1;
-      SETUP_TRY(hipMemcpyAsync(o, d_r2, 3 * R2 * 8, hipMemcpyDeviceToHost, s)); o += 3 * R2;
-      SETUP_TRY(hipMemcpyAsync(o, d_r1 + r_abc * R1, n_inputs * R1 * 8, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(o, d_r1, R1 * 8, hipMemcpyDeviceToHost, s), 10); o += R1;
+      HIP_TRY(hipMemcpyAsync(o, d_r2, 3 * R2 * 8, hipMemcpyDeviceToHost, s), 10); o += 3 * R2;
+      HIP_TRY(hipMemcpyAsync(o, d_r1 + r_abc * R1, n_inputs * R1 * 8, hipMemcpyDeviceToHost, s), 10);
     }
     if (out_rows) {
       uint64_t* o = out_rows;
-      SETUP_TRY(hipMemcpyAsync(o, d_r1 + R1, 2 * R1 * 8, hipMemcpyDeviceToHost, s)); o += 2 * R1;
-      SETUP_TRY(hipMemcpyAsync(o, d_r1 + r_a * R1, 2 * n_vars * R1 * 8, hipMemcpyDeviceToHost, s)); o += 2 * n_vars * R1;
-      SETUP_TRY(hipMemcpyAsync(o, d_r2 + 3 * R2, n_vars * R2 * 8, hipMemcpyDeviceToHost, s)); o += n_vars * R2;
-      SETUP_TRY(hipMemcpyAsync(o, d_r1 + r_h * R1, (n_h + n_vars - n_inputs) * R1 * 8, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(o, d_r1 + R1, 2 * R1 * 8, hipMemcpyDeviceToHost, s), 10); o += 2 * R1;
+      HIP_TRY(hipMemcpyAsync(o, d_r1 + r_a * R1, 2 * n_vars * R1 * 8, hipMemcpyDeviceToHost, s), 10); o += 2 * n_vars * R1;
+      HIP_TRY(hipMemcpyAsync(o, d_r2 + 3 * R2, n_vars * R2 * 8, hipMemcpyDeviceToHost, s), 10); o += n_vars * R2;
+      HIP_TRY(hipMemcpyAsync(o, d_r1 + r_h * R1, (n_h + n_vars - n_inputs) * R1 * 8, hipMemcpyDeviceToHost, s), 10);
     }
-    SETUP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipStreamSynchronize(s), 10);
     log.sum(g_setup_ms);
-    if (out_key) {
-      // the four key elements the composition keeps on the host (query[0] of a and b_g2, alpha_g1, beta_g2): four rows, not a query
-      uint64_t a0[R1], b0[R2], al[R1], be[R2];
-      SETUP_TRY(hipMemcpy(a0, d_r1 + r_a * R1, sizeof a0, hipMemcpyDeviceToHost));
-      SETUP_TRY(hipMemcpy(b0, d_r2 + 3 * R2, sizeof b0, hipMemcpyDeviceToHost));
-      SETUP_TRY(hipMemcpy(al, d_r1, sizeof al, hipMemcpyDeviceToHost));
-      SETUP_TRY(hipMemcpy(be, d_r2, sizeof be, hipMemcpyDeviceToHost));
-      const auto k0 = std::chrono::steady_clock::now();
-      rc = groth16_key_load_dev(curve, d_r1 + r_a * R1, d_i1 + r_a, n_vars, d_r2 + 3 * R2, d_i2 + 3, n_vars, d_r1 + r_h * R1, d_i1 + r_h, n_h,
-                                d_r1 + r_l * R1, d_i1 + r_l, n_vars - n_inputs, a0, b0, al, be, window_bits, &key);
-      g_setup_ms[5] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - k0).count();
-    }
-  }
-done:
-  if (s) (void)hipStreamSynchronize(s);
-  for (uint64_t* p : {d_q, d_s1, d_s2, d_r1, d_r2}) if (p) (void)hipFree(p);
-  for (uint8_t* p : {d_i1, d_i2}) if (p) (void)hipFree(p);
-  if (s) (void)hipStreamDestroy(s);
+    if (!out_key) return 0;
+    // the four key elements the composition keeps on the host (query[0] of a and b_g2, alpha_g1, beta_g2): four rows, not a query
+    uint64_t a0[R1], b0[R2], al[R1], be[R2];
+    HIP_TRY(hipMemcpy(a0, d_r1 + r_a * R1, sizeof a0, hipMemcpyDeviceToHost), 10);
+    HIP_TRY(hipMemcpy(b0, d_r2 + 3 * R2, sizeof b0, hipMemcpyDeviceToHost), 10);
+    HIP_TRY(hipMemcpy(al, d_r1, sizeof al, hipMemcpyDeviceToHost), 10);
+    HIP_TRY(hipMemcpy(be, d_r2, sizeof be, hipMemcpyDeviceToHost), 10);
+    const auto k0 = std::chrono::steady_clock::now();
+    // (sets *out_key only on success; the key is the call's last step, so nothing after it can fail)
+    const int rck = groth16_key_load_dev(curve, d_r1 + r_a * R1, d_i1 + r_a, n_vars, d_r2 + 3 * R2, d_i2 + 3, n_vars, d_r1 + r_h * R1, d_i1 + r_h, n_h,
+                                         d_r1 + r_l * R1, d_i1 + r_l, n_vars - n_inputs, a0, b0, al, be, window_bits, out_key);
+    g_setup_ms[5] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - k0).count();
+    return rck;
+  }();
   g_setup_ms[6] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  if (rc) { if (key) groth16_key_free(key); return rc; }
-  if (out_key) *out_key = key;
-  return 0;
+  return rc;
 }
 
 int groth16_setup(int curve, const uint64_t* qa, const uint64_t* qb, const uint64_t* qc, size_t n_vars, size_t n_inputs, const uint64_t* zt, const uint64_t* tau,

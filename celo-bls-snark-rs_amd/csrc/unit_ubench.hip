@@ -70,26 +70,21 @@ int ubench_fp_run(float out[9]) {
   hipDeviceProp_t p;
   if (hipGetDeviceProperties(&p, api_device()) != hipSuccess) return 100;
   const int blocks = p.multiProcessorCount * 8;       // 8 workgroups of 4 waves per CU: eight waves per SIMD requested (the 14-limb loops fit; the 28-limb ones get what fits)
-  uint32_t* d_out = nullptr; uint64_t* d_ticks = nullptr;
-  hipStream_t st = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr;
-  int rc = 1;
   std::vector<uint64_t> h_ticks((size_t)blocks * 4 * 2);
-  do {
-    if (hipMalloc(&d_out, (size_t)blocks * 256 * 4) != hipSuccess) break;
-    if (hipMalloc(&d_ticks, h_ticks.size() * 8) != hipSuccess) break;
-    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) break;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) break;
-    if (ubench_one<Fp<P377>, 0>(d_out, d_ticks, h_ticks, blocks, 400, &out[0], &out[5], &out[4], st, e0, e1)) break;
-    if (ubench_one<Fp<P377>, 1>(d_out, d_ticks, h_ticks, blocks, 400, &out[1], &out[6], nullptr, st, e0, e1)) break;
-    if (ubench_one<Fp<P761>, 0>(d_out, d_ticks, h_ticks, blocks, 100, &out[2], &out[7], nullptr, st, e0, e1)) break;
-    if (ubench_one<Fp<P761>, 1>(d_out, d_ticks, h_ticks, blocks, 100, &out[3], &out[8], nullptr, st, e0, e1)) break;
-    rc = 0;
-  } while (0);
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  if (st) (void)hipStreamDestroy(st);
-  if (d_out) (void)hipFree(d_out);
-  if (d_ticks) (void)hipFree(d_ticks);
-  return rc;
+  CallScope cs(nullptr);
+  uint32_t* d_out;
+  uint64_t* d_ticks;
+  hipEvent_t e0, e1;
+  HIP_TRY(cs.alloc(&d_out, (size_t)blocks * 256 * 4), 1);
+  HIP_TRY(cs.alloc(&d_ticks, h_ticks.size() * 8), 1);
+  HIP_TRY(cs.create_stream(), 1);
+  HIP_TRY(cs.event(&e0), 1);
+  HIP_TRY(cs.event(&e1), 1);
+  const hipStream_t st = cs.stream();
+  if (ubench_one<Fp<P377>, 0>(d_out, d_ticks, h_ticks, blocks, 400, &out[0], &out[5], &out[4], st, e0, e1)) return 1;
+  if (ubench_one<Fp<P377>, 1>(d_out, d_ticks, h_ticks, blocks, 400, &out[1], &out[6], nullptr, st, e0, e1)) return 1;
+  if (ubench_one<Fp<P761>, 0>(d_out, d_ticks, h_ticks, blocks, 100, &out[2], &out[7], nullptr, st, e0, e1)) return 1;
+  if (ubench_one<Fp<P761>, 1>(d_out, d_ticks, h_ticks, blocks, 100, &out[3], &out[8], nullptr, st, e0, e1)) return 1;
+  return 0;
 }
 }  // namespace celo

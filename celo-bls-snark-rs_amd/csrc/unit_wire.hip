@@ -1,6 +1,7 @@
-// Translation unit: bulk decoding of compressed BLS12-377 points (see wire.h), one point per lane.
-#include <type_traits>
+// Translation unit: bulk decoding of compressed BLS12-377 points (see wire.h), one point per lane, and the batch normalisation of
+// Jacobian points of both curves (normalize.h).
 #include "wire.h"
+#include "normalize.h"
 #include <hip/hip_runtime.h>
 #include <mutex>
 #include "runtime.h"
@@ -38,62 +39,6 @@ template <bool G2> __global__ void __launch_bounds__(64) FROW_OCC k_decompress(c
   }
 }
 
-// Jacobian -> affine for n points (ProjectiveCurve::batch_normalization_into_affine, called at crates/bls-crypto/src/bls/
-// signature.rs:82 and public.rs:58 before every MSM): Montgomery's trick inside a lane over K consecutive points - one field
-// inversion per K points, 3 products per point for the prefix / suffix products, then x = X z^-2, y = Y z^-3.  in: n x 3
-// coordinates (arkworks Montgomery limbs, identity = Z == 0); out: n x (x, y), zero rows + inf[i] = 1 for the identity.
-// Points that are already affine (Z == 1: everything that came off the wire) take part with z = 1; their x, y come out unchanged.
-template <int N, bool REVERSE, class Fn> __device__ __forceinline__ void norm_static_for(Fn&& f) {   // f(integral_constant<j>) for j = 0 .. N-1 (or N-1 .. 0)
-  if constexpr (N > 0) {
-    if constexpr (REVERSE) { f(std::integral_constant<int, N - 1>{}); norm_static_for<N - 1, true>(f); }
-    else { norm_static_for<N - 1, false>(f); f(std::integral_constant<int, N - 1>{}); }
-  }
-}
-template <class F, int K> __global__ void __launch_bounds__(64) FROW_OCC
-k_normalize(const uint64_t* __restrict__ jac, uint64_t* __restrict__ out, uint8_t* __restrict__ inf, uint32_t n) {
-  constexpr int A = F::ARK64;
-  const uint32_t lo = (blockIdx.x * blockDim.x + threadIdx.x) * K;
-  if (lo >= n) return;
-  const uint32_t cnt = n - lo < (uint32_t)K ? n - lo : (uint32_t)K;
-  // Only the prefix products stay in registers (K x 14 / 28 words); z_j is read again on the way back (one conversion product) instead
-  // of being kept: with both arrays alive the G1 instance (K = 8) held 224 words of state, the loops were not unrolled and the arrays
-  // went to private memory through run-time indices (912 B/lane).
-  F pre[K];
-  uint32_t idmask = 0;
-  F acc = F::one();
-  auto load_z = [&](int j) { return F::norm(F::from_ark(jac + ((size_t)lo + j) * 3 * A + 2 * A)); };
-  // (unrolled by template recursion: `#pragma unroll` over bodies of this size is refused by the optimizer, and a rolled loop
-  // indexes pre[] at run time, i.e. in private memory)
-  norm_static_for<K, false>([&](auto jc) {
-    constexpr int j = decltype(jc)::value;
-    pre[j] = acc;
-    if ((uint32_t)j < cnt) {
-      const F zj = load_z(j);
-      if (zj.is_zero_mod_p()) idmask |= 1u << j;
-      else acc = F::norm(F::mul(acc, zj));
-    }
-  });
-  F inv = F::norm(F::inv(acc));
-  norm_static_for<K, true>([&](auto jc) {
-    constexpr int j = decltype(jc)::value;
-    if ((uint32_t)j < cnt) {
-      uint64_t* o = out + ((size_t)lo + j) * 2 * A;
-      const bool id = (idmask >> j) & 1u;
-      inf[lo + j] = id ? 1 : 0;
-      if (id) {
-        for (int q = 0; q < 2 * A; q++) o[q] = 0;
-      } else {
-        const F zi = F::norm(F::mul(inv, pre[j]));
-        inv = F::norm(F::mul(inv, load_z(j)));
-        const uint64_t* src = jac + ((size_t)lo + j) * 3 * A;
-        const F zi2 = F::norm(F::sqr(zi));
-        F::mul(F::from_ark(src), zi2).to_ark(o);
-        F::mul(F::from_ark(src + A), F::norm(F::mul(zi2, zi))).to_ark(o + A);
-      }
-    }
-  });
-}
-
 // the constants with the discrete-log tables in device memory: one copy per device, uploaded on first use there
 int wire_consts_device(WireConsts& out) {
   static std::mutex mu;
@@ -110,12 +55,6 @@ int wire_consts_device(WireConsts& out) {
 }
 static float g_wire_ms = 0.f;
 
-#define WIRE_TRY(x)                                                                                  \
-  do {                                                                                               \
-    hipError_t e_ = (x);                                                                             \
-    if (e_ != hipSuccess) { fprintf(stderr, "[celo-amd] %s: %s\n", #x, hipGetErrorString(e_)); rc = 10; goto done; } \
-  } while (0)
-
 int wire_decompress(int g2, const uint8_t* in, size_t n, int check, uint64_t* out, uint8_t* status, int dev, void* stream_) {
   if (int rc0 = api_enter()) return rc0;
   std::lock_guard<std::mutex> lk(wire_mu);
@@ -124,69 +63,62 @@ int wire_decompress(int g2, const uint8_t* in, size_t n, int check, uint64_t* ou
   WireConsts k;
   if (int rck = wire_consts_device(k)) return rck;
   const size_t ib = g2 ? 96 : 48, ow = g2 ? 24 : 12;
-  hipStream_t stream = (hipStream_t)stream_;
-  uint8_t *d_in = nullptr, *d_st = nullptr;
-  uint64_t* d_out = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  int rc = 0;
-  if (dev) { d_in = (uint8_t*)in; d_out = out; d_st = status; }
-  else {
-    WIRE_TRY(hipMalloc(&d_in, n * ib));
-    WIRE_TRY(hipMalloc(&d_out, n * ow * 8));
-    WIRE_TRY(hipMalloc(&d_st, n));
-    WIRE_TRY(hipMemcpyAsync(d_in, in, n * ib, hipMemcpyHostToDevice, stream));
+  CallScope cs((hipStream_t)stream_);
+  const hipStream_t stream = cs.stream();
+  uint8_t *d_in = (uint8_t*)in, *d_st = status;
+  uint64_t* d_out = out;
+  if (!dev) {
+    HIP_TRY(cs.alloc(&d_in, n * ib), 10);
+    HIP_TRY(cs.alloc(&d_out, n * ow * 8), 10);
+    HIP_TRY(cs.alloc(&d_st, n), 10);
+    HIP_TRY(hipMemcpyAsync(d_in, in, n * ib, hipMemcpyHostToDevice, stream), 10);
   }
-  WIRE_TRY(hipEventCreate(&e0));
-  WIRE_TRY(hipEventCreate(&e1));
-  WIRE_TRY(hipEventRecord(e0, stream));
+  hipEvent_t e0, e1;
+  HIP_TRY(cs.event(&e0), 10);
+  HIP_TRY(cs.event(&e1), 10);
+  HIP_TRY(hipEventRecord(e0, stream), 10);
   if (g2) hipLaunchKernelGGL((k_decompress<true>), dim3(((uint32_t)n + 63) / 64), dim3(64), 0, stream, d_in, d_out, d_st, (uint32_t)n, check, k);
   else hipLaunchKernelGGL((k_decompress<false>), dim3(((uint32_t)n + 63) / 64), dim3(64), 0, stream, d_in, d_out, d_st, (uint32_t)n, check, k);
-  WIRE_TRY(hipGetLastError());
-  WIRE_TRY(hipEventRecord(e1, stream));
+  HIP_TRY(hipGetLastError(), 10);
+  HIP_TRY(hipEventRecord(e1, stream), 10);
   if (!dev) {
-    WIRE_TRY(hipMemcpyAsync(out, d_out, n * ow * 8, hipMemcpyDeviceToHost, stream));
-    WIRE_TRY(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(out, d_out, n * ow * 8, hipMemcpyDeviceToHost, stream), 10);
+    HIP_TRY(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, stream), 10);
   }
-  WIRE_TRY(hipStreamSynchronize(stream));
-  WIRE_TRY(hipEventElapsedTime(&g_wire_ms, e0, e1));
-done:
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  if (!dev) { if (d_in) (void)hipFree(d_in); if (d_out) (void)hipFree(d_out); if (d_st) (void)hipFree(d_st); }
-  return rc;
+  HIP_TRY(hipStreamSynchronize(stream), 10);
+  HIP_TRY(hipEventElapsedTime(&g_wire_ms, e0, e1), 10);
+  return 0;
 }
-int wire_normalize(int g2, const uint64_t* jac, size_t n, uint64_t* out_xy, uint8_t* inf) {
+// Jacobian -> affine for n points (normalize.h): jac n x 3 coordinates, out_xy n x (x, y), zero rows + inf[i] = 1 for the identity.
+// group 0: BLS12-377 G1, 1: BLS12-377 G2 (both at two waves per SIMD), 2: BW6-761 (G1 and G2: one coordinate field)
+int wire_normalize(int group, const uint64_t* jac, size_t n, uint64_t* out_xy, uint8_t* inf) {
   if (int rc0 = api_enter()) return rc0;
   std::lock_guard<std::mutex> lk(wire_mu);
   if (n == 0) return 0;
   if (!jac || !out_xy || !inf || n > 0x7fffffffu) return 2;
-  const size_t cw = g2 ? 12 : 6;
-  uint64_t *d_in = nullptr, *d_out = nullptr;
-  uint8_t* d_inf = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  int rc = 0;
-  WIRE_TRY(hipMalloc(&d_in, n * 3 * cw * 8));
-  WIRE_TRY(hipMalloc(&d_out, n * 2 * cw * 8));
-  WIRE_TRY(hipMalloc(&d_inf, n));
-  WIRE_TRY(hipMemcpyAsync(d_in, jac, n * 3 * cw * 8, hipMemcpyHostToDevice, 0));
-  WIRE_TRY(hipEventCreate(&e0));
-  WIRE_TRY(hipEventCreate(&e1));
-  WIRE_TRY(hipEventRecord(e0, 0));
-  if (g2) hipLaunchKernelGGL((k_normalize<Fq2, 4>), dim3(((uint32_t)((n + 3) / 4) + 63) / 64), dim3(64), 0, 0, d_in, d_out, d_inf, (uint32_t)n);
-  else hipLaunchKernelGGL((k_normalize<Fq, 8>), dim3(((uint32_t)((n + 7) / 8) + 63) / 64), dim3(64), 0, 0, d_in, d_out, d_inf, (uint32_t)n);
-  WIRE_TRY(hipGetLastError());
-  WIRE_TRY(hipEventRecord(e1, 0));
-  WIRE_TRY(hipMemcpyAsync(out_xy, d_out, n * 2 * cw * 8, hipMemcpyDeviceToHost, 0));
-  WIRE_TRY(hipMemcpyAsync(inf, d_inf, n, hipMemcpyDeviceToHost, 0));
-  WIRE_TRY(hipStreamSynchronize(0));
-  WIRE_TRY(hipEventElapsedTime(&g_wire_ms, e0, e1));
-done:
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  if (d_in) (void)hipFree(d_in);
-  if (d_out) (void)hipFree(d_out);
-  if (d_inf) (void)hipFree(d_inf);
-  return rc;
+  const size_t cw = group ? 12 : 6;
+  CallScope cs(nullptr);
+  uint64_t *d_in, *d_out;
+  uint8_t* d_inf;
+  HIP_TRY(cs.alloc(&d_in, n * 3 * cw * 8), 10);
+  HIP_TRY(cs.alloc(&d_out, n * 2 * cw * 8), 10);
+  HIP_TRY(cs.alloc(&d_inf, n), 10);
+  HIP_TRY(hipMemcpyAsync(d_in, jac, n * 3 * cw * 8, hipMemcpyHostToDevice, 0), 10);
+  hipEvent_t e0, e1;
+  HIP_TRY(cs.event(&e0), 10);
+  HIP_TRY(cs.event(&e1), 10);
+  HIP_TRY(hipEventRecord(e0, 0), 10);
+  const dim3 grid4(((uint32_t)((n + 3) / 4) + 63) / 64), grid8(((uint32_t)((n + 7) / 8) + 63) / 64);
+  if (group == 2) hipLaunchKernelGGL((k_normalize<Fp<P761>, 4, true, 0, true>), grid4, dim3(64), 0, 0, d_in, d_out, d_inf, (uint32_t)n, 0);
+  else if (group == 1) hipLaunchKernelGGL((k_normalize<Fq2, 4, true, 2, false>), grid4, dim3(64), 0, 0, d_in, d_out, d_inf, (uint32_t)n, 0);
+  else hipLaunchKernelGGL((k_normalize<Fq, 8, true, 2, false>), grid8, dim3(64), 0, 0, d_in, d_out, d_inf, (uint32_t)n, 0);
+  HIP_TRY(hipGetLastError(), 10);
+  HIP_TRY(hipEventRecord(e1, 0), 10);
+  HIP_TRY(hipMemcpyAsync(out_xy, d_out, n * 2 * cw * 8, hipMemcpyDeviceToHost, 0), 10);
+  HIP_TRY(hipMemcpyAsync(inf, d_inf, n, hipMemcpyDeviceToHost, 0), 10);
+  HIP_TRY(hipStreamSynchronize(0), 10);
+  HIP_TRY(hipEventElapsedTime(&g_wire_ms, e0, e1), 10);
+  return 0;
 }
 float wire_last_ms() { return g_wire_ms; }
 }  // namespace celo

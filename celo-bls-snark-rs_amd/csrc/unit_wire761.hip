@@ -17,7 +17,6 @@ namespace celo {
 struct ProvingKey;
 int groth16_key_load_dev_761(const uint64_t*, const uint8_t*, size_t, const uint64_t*, const uint8_t*, size_t, const uint64_t*, const uint8_t*, size_t,
                              const uint64_t*, const uint8_t*, size_t, const uint64_t*, const uint64_t*, const uint64_t*, const uint64_t*, int, ProvingKey**);
-void groth16_key_free(ProvingKey*);
 
 // calls from several host threads are serialised per process (they are bulk calls: one fills the GPU); each runs on a stream of its own
 // (host-pointer calls) or on the caller's (the _dev forms)
@@ -67,12 +66,6 @@ static void launch_decode761(int g2, int compressed, const uint8_t* d_in, size_t
   if (check) hipLaunchKernelGGL(k_subgroup761, grid, block, 0, s, d_out, d_st, (uint32_t)n);
 }
 
-#define W761_TRY(x)                                                                                  \
-  do {                                                                                               \
-    hipError_t e_ = (x);                                                                             \
-    if (e_ != hipSuccess) { fprintf(stderr, "[celo-amd] %s: %s\n", #x, hipGetErrorString(e_)); rc = 10; goto done; } \
-  } while (0)
-
 // g2: 0 = G1 (b = -1), 1 = G2 (b = 4); compressed: 1 = 96 B points, 0 = 192 B; dev: all four pointers are device pointers, run on stream_
 int wire761_decode(int g2, int compressed, const uint8_t* in, size_t n, int check, uint64_t* out, uint8_t* status, int dev, void* stream_) {
   if (int rc0 = api_enter()) return rc0;
@@ -80,42 +73,31 @@ int wire761_decode(int g2, int compressed, const uint8_t* in, size_t n, int chec
   if (n == 0) return 0;
   if (!in || !out || !status || n > 0x7fffffffu) return 2;
   const size_t ib = compressed ? 96 : 192;
-  hipStream_t stream = dev ? (hipStream_t)stream_ : nullptr;
-  uint8_t *d_in = nullptr, *d_st = nullptr;
-  uint64_t* d_out = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  int rc = 0;
-  if (!dev) W761_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-  if (dev) { d_in = (uint8_t*)in; d_out = out; d_st = status; }
-  else {
-    W761_TRY(hipMalloc(&d_in, n * ib));
-    W761_TRY(hipMalloc(&d_out, n * 24 * 8));
-    W761_TRY(hipMalloc(&d_st, n));
-    W761_TRY(hipMemcpyAsync(d_in, in, n * ib, hipMemcpyHostToDevice, stream));
+  CallScope cs(dev ? (hipStream_t)stream_ : nullptr);
+  if (!dev) HIP_TRY(cs.create_stream(), 10);
+  const hipStream_t stream = cs.stream();
+  uint8_t *d_in = (uint8_t*)in, *d_st = status;
+  uint64_t* d_out = out;
+  if (!dev) {
+    HIP_TRY(cs.alloc(&d_in, n * ib), 10);
+    HIP_TRY(cs.alloc(&d_out, n * 24 * 8), 10);
+    HIP_TRY(cs.alloc(&d_st, n), 10);
+    HIP_TRY(hipMemcpyAsync(d_in, in, n * ib, hipMemcpyHostToDevice, stream), 10);
   }
-  W761_TRY(hipEventCreate(&e0));
-  W761_TRY(hipEventCreate(&e1));
-  W761_TRY(hipEventRecord(e0, stream));
+  hipEvent_t e0, e1;
+  HIP_TRY(cs.event(&e0), 10);
+  HIP_TRY(cs.event(&e1), 10);
+  HIP_TRY(hipEventRecord(e0, stream), 10);
   launch_decode761(g2, compressed, d_in, n, check, d_out, d_st, stream);
-  W761_TRY(hipGetLastError());
-  W761_TRY(hipEventRecord(e1, stream));
+  HIP_TRY(hipGetLastError(), 10);
+  HIP_TRY(hipEventRecord(e1, stream), 10);
   if (!dev) {
-    W761_TRY(hipMemcpyAsync(out, d_out, n * 24 * 8, hipMemcpyDeviceToHost, stream));
-    W761_TRY(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(out, d_out, n * 24 * 8, hipMemcpyDeviceToHost, stream), 10);
+    HIP_TRY(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, stream), 10);
   }
-  W761_TRY(hipStreamSynchronize(stream));
-  W761_TRY(hipEventElapsedTime(&g_w761_ms[0], e0, e1));
-done:
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  if (!dev) {
-    if (stream) (void)hipStreamSynchronize(stream);
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    if (d_st) (void)hipFree(d_st);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
-  return rc;
+  HIP_TRY(hipStreamSynchronize(stream), 10);
+  HIP_TRY(hipEventElapsedTime(&g_w761_ms[0], e0, e1), 10);
+  return 0;
 }
 
 int wire761_key_layout(const uint8_t* bytes, size_t len, int form, uint64_t out[16]) { return w761_key_layout(bytes, len, form, out); }
@@ -142,71 +124,58 @@ int wire761_key_load(const uint8_t* bytes, size_t len, int form, int window_bits
                        {L[W761_BG1 + 1], L[W761_BG1], 0}, {L[W761_BG2 + 1], L[W761_BG2], 1}, {L[W761_H + 1], L[W761_H], 0}, {L[W761_L + 1], L[W761_L], 0}};
   uint64_t base[9];
   for (uint64_t s = 0, acc = 0; s < 9; s++) { base[s] = acc; acc += secs[s].n; }
-  hipStream_t stream = nullptr;
-  uint8_t *d_bytes = nullptr, *d_st = nullptr;
-  uint64_t* d_xy = nullptr;
-  unsigned long long* d_first = nullptr;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  CallScope cs(nullptr);
+  HIP_TRY(cs.create_stream(), 10);
+  const hipStream_t stream = cs.stream();
+  hipEvent_t ev[3];
+  for (auto& e : ev) HIP_TRY(cs.event(&e), 10);
+  uint8_t *d_bytes, *d_st;
+  uint64_t* d_xy;
+  unsigned long long* d_first;
   unsigned long long first = ~0ull;
-  ProvingKey* key = nullptr;
-  int rc = 0;
-  W761_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-  for (auto& e : ev) W761_TRY(hipEventCreate(&e));
-  W761_TRY(hipMalloc(&d_bytes, len));
-  W761_TRY(hipMalloc(&d_xy, N * 24 * 8));
-  W761_TRY(hipMalloc(&d_st, N));
-  W761_TRY(hipMalloc(&d_first, sizeof(unsigned long long)));
-  W761_TRY(hipEventRecord(ev[0], stream));
-  W761_TRY(hipMemcpyAsync(d_bytes, bytes, len, hipMemcpyHostToDevice, stream));
-  W761_TRY(hipMemcpyAsync(d_first, &first, sizeof first, hipMemcpyHostToDevice, stream));
-  W761_TRY(hipEventRecord(ev[1], stream));
+  HIP_TRY(cs.alloc(&d_bytes, len), 10);
+  HIP_TRY(cs.alloc(&d_xy, N * 24 * 8), 10);
+  HIP_TRY(cs.alloc(&d_st, N), 10);
+  HIP_TRY(cs.alloc(&d_first, sizeof(unsigned long long)), 10);
+  HIP_TRY(hipEventRecord(ev[0], stream), 10);
+  HIP_TRY(hipMemcpyAsync(d_bytes, bytes, len, hipMemcpyHostToDevice, stream), 10);
+  HIP_TRY(hipMemcpyAsync(d_first, &first, sizeof first, hipMemcpyHostToDevice, stream), 10);
+  HIP_TRY(hipEventRecord(ev[1], stream), 10);
   for (int s = 0; s < 9; s++) {
     if (!secs[s].n) continue;
     launch_decode761(secs[s].g2, compressed, d_bytes + secs[s].off, secs[s].n, check, d_xy + base[s] * 24, d_st + base[s], stream);
-    W761_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError(), 10);
   }
   hipLaunchKernelGGL(k_first_bad761, dim3(((uint32_t)N + 255) / 256), dim3(256), 0, stream, d_st, (uint32_t)N, d_first);
-  W761_TRY(hipGetLastError());
-  W761_TRY(hipEventRecord(ev[2], stream));
-  W761_TRY(hipMemcpyAsync(&first, d_first, sizeof first, hipMemcpyDeviceToHost, stream));
-  W761_TRY(hipStreamSynchronize(stream));
-  W761_TRY(hipEventElapsedTime(&g_w761_ms[1], ev[0], ev[1]));
-  W761_TRY(hipEventElapsedTime(&g_w761_ms[2], ev[1], ev[2]));
+  HIP_TRY(hipGetLastError(), 10);
+  HIP_TRY(hipEventRecord(ev[2], stream), 10);
+  HIP_TRY(hipMemcpyAsync(&first, d_first, sizeof first, hipMemcpyDeviceToHost, stream), 10);
+  HIP_TRY(hipStreamSynchronize(stream), 10);
+  HIP_TRY(hipEventElapsedTime(&g_w761_ms[1], ev[0], ev[1]), 10);
+  HIP_TRY(hipEventElapsedTime(&g_w761_ms[2], ev[1], ev[2]), 10);
   if (first != ~0ull) {
     if (first_bad) *first_bad = first;
-    rc = W761_ERR_POINT;
-    goto done;
+    return W761_ERR_POINT;
   }
-  {
-    // the four key elements the composition keeps on the host (ark's identity encoding (0, 1) for the point at infinity)
-    uint64_t host_rows[4][24];
-    const uint64_t where[4] = {secs[4].off, secs[6].off, 0, P};      // a_query[0], b_g2_query[0], alpha_g1, beta_g2
-    const int grp[4] = {0, 1, 0, 1};
-    for (int q = 0; q < 4; q++) {
-      const uint8_t* src = bytes + where[q];
-      WireStatus st;
-      if (grp[q]) st = compressed ? w761_decode_row<4, true>(src, false, host_rows[q]) : w761_decode_row<4, false>(src, false, host_rows[q]);
-      else st = compressed ? w761_decode_row<-1, true>(src, false, host_rows[q]) : w761_decode_row<-1, false>(src, false, host_rows[q]);
-      if (st == WIRE_INFINITY) Fw761::one().to_ark(host_rows[q] + 12);
-      else if (st != WIRE_OK) { rc = 10; goto done; }                 // not reached: the same function accepted these bytes on the device
-    }
-    const auto t0 = std::chrono::steady_clock::now();
-    rc = groth16_key_load_dev_761(d_xy + base[4] * 24, d_st + base[4], L[W761_A], d_xy + base[6] * 24, d_st + base[6], L[W761_BG2],
-                                  d_xy + base[7] * 24, d_st + base[7], L[W761_H], d_xy + base[8] * 24, d_st + base[8], L[W761_L],
-                                  host_rows[0], host_rows[1], host_rows[2], host_rows[3], window_bits, &key);
-    g_w761_ms[3] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  // the four key elements the composition keeps on the host (ark's identity encoding (0, 1) for the point at infinity)
+  uint64_t host_rows[4][24];
+  const uint64_t where[4] = {secs[4].off, secs[6].off, 0, P};      // a_query[0], b_g2_query[0], alpha_g1, beta_g2
+  const int grp[4] = {0, 1, 0, 1};
+  for (int q = 0; q < 4; q++) {
+    const uint8_t* src = bytes + where[q];
+    WireStatus st;
+    if (grp[q]) st = compressed ? w761_decode_row<4, true>(src, false, host_rows[q]) : w761_decode_row<4, false>(src, false, host_rows[q]);
+    else st = compressed ? w761_decode_row<-1, true>(src, false, host_rows[q]) : w761_decode_row<-1, false>(src, false, host_rows[q]);
+    if (st == WIRE_INFINITY) Fw761::one().to_ark(host_rows[q] + 12);
+    else if (st != WIRE_OK) return 10;                                // not reached: the same function accepted these bytes on the device
   }
-done:
-  if (stream) (void)hipStreamSynchronize(stream);
-  for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-  if (d_bytes) (void)hipFree(d_bytes);
-  if (d_xy) (void)hipFree(d_xy);
-  if (d_st) (void)hipFree(d_st);
-  if (d_first) (void)hipFree(d_first);
-  if (stream) (void)hipStreamDestroy(stream);
-  if (rc) { if (key) groth16_key_free(key); return rc; }
-  *out_key = key;
-  return 0;
+  const auto t0 = std::chrono::steady_clock::now();
+  // (frees the key itself when it fails, and sets *out_key only on success: the call's last step)
+  const int rc = groth16_key_load_dev_761(d_xy + base[4] * 24, d_st + base[4], L[W761_A], d_xy + base[6] * 24, d_st + base[6], L[W761_BG2],
+                                          d_xy + base[7] * 24, d_st + base[7], L[W761_H], d_xy + base[8] * 24, d_st + base[8], L[W761_L],
+                                          host_rows[0], host_rows[1], host_rows[2], host_rows[3], window_bits, out_key);
+  g_w761_ms[3] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return rc;
 }
 void wire761_last_timings(float ms[4]) { for (int i = 0; i < 4; i++) ms[i] = g_w761_ms[i]; }
 }  // namespace celo

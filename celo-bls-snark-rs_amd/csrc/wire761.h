@@ -2,8 +2,8 @@
 // of the last byte) as host+device templates over the 28-limb field Fp<P761> the MSM uses.  What ark-groth16 0.1 runs per point when it
 // reads a ProvingKey<BW6_761> / VerifyingKey / Proof (crates/epoch-snark/src/api/setup.rs:12,17-20 Groth16Parameters; the "serialized
 // byte arrays of compressed elements" of crates/bls-snark-sys/src/snark/mod.rs:13-17): GroupAffine::deserialize (compressed, checked),
-// deserialize_uncompressed (checked) and deserialize_unchecked (uncompressed, range only).  The single-point host twin of the checked
-// compressed form is seam_a.hip bw6_decompress (Seam A verify); the bulk form is k_decode761 (unit_wire761.hip), one point per lane.
+// deserialize_uncompressed (checked) and deserialize_unchecked (uncompressed, range only).  One source for both sides: Seam A's verify
+// (seam_a.hip) decodes its vk and proof points on the host with w761_decode_row; the bulk form is k_decode761 (unit_wire761.hip), one point per lane.
 //
 // Curves (both over Fq, q = 3 mod 4):  G1  y^2 = x^3 - 1,   G2 (M-twist)  y^2 = x^3 + 4.   One template, b as its parameter.
 //
@@ -144,7 +144,7 @@ HD bool w761_madd(Xyzz<Fw761>& a, const Affine<Fw761>& p) {
   return true;
 }
 // r P == O with r = q_BLS12-377 (377 bits), MSB-first double-and-add over XYZZ: ark-ec 0.1 is_in_correct_subgroup_assuming_on_curve as
-// written, the predicate of seam_a.hip bw6_decompress.  The XYZZ formulas of curve.h do not depend on b, so one ladder serves both groups.
+// written.  The XYZZ formulas of curve.h do not depend on b, so one ladder serves both groups.
 // One group operation per iteration (stage 0: double for bit i; 1: add p for bit i; 2: acc was p, double instead of adding).
 // (No endomorphism form: that would come with this ladder kept as its twin, as wire.h does for BLS12-377.)
 HD bool w761_in_subgroup(const Affine<Fw761>& p) {
