@@ -17,8 +17,9 @@
 //                runs 12 butterflies in registers, stores them back.  Loads and stores are 64-B vectors, consecutive lanes
 //                touch consecutive elements.
 //   k_ntt_store  bit-reversal gather, optional coset post-scaling x_i *= g^i and final scale, -> arkworks Montgomery
-// Twiddles: one table W[k] = omega^k, k < n/2, in device form, built once per (omega, n) from two 1024-entry power
-// tables and kept by the engine (32 MB at 2^20: stays in the Infinity Cache across passes).
+// Twiddles: one table W[k] = omega^k, k < n/2, in device form, built once per (omega, n) from two power tables and kept by
+// the engine (32 MB at 2^20: stays in the Infinity Cache across passes).  Every power b^k, k < n, is lo[k & 1023] * hi[k >> 10]
+// with lo[i] = b^i (1024 entries) and hi[i] = b^(1024 i) (max(1, n / 1024) entries: 1024 at 2^20, 2^18 at the limit 2^28).
 #pragma once
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -37,20 +38,20 @@ typedef Fp<P253> Fr377;   // the scalar field of BLS12-377: 10 limbs padded to 1
 // elements FR::ARK64 u64, LDS tiles FR::L word planes
 
 #if defined(__HIPCC__)
-// pw[i] = base^(i * stride) for i < 1024 (one lane each: square-and-multiply over the 10 bits of i)
+// pw[i] = base^i for i < count <= 2^nbits (one lane each: square-and-multiply over the nbits bits of i)
 template <class FR>
-__global__ void __launch_bounds__(256) k_ntt_powers(const uint32_t* __restrict__ base_dev, uint32_t* __restrict__ pw) {
+__global__ void __launch_bounds__(256) k_ntt_powers(const uint32_t* __restrict__ base_dev, uint32_t* __restrict__ pw, uint32_t count, int nbits) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= 1024) return;
+  if (i >= count) return;
   const FR b = FR::load(base_dev);
   FR acc = FR::one();
-  for (int bit = 9; bit >= 0; bit--) {
+  for (int bit = nbits - 1; bit >= 0; bit--) {
     acc = FR::sqr(acc);
     if ((i >> bit) & 1) acc = FR::mul(acc, b);
   }
   FR::wred(acc).store(pw + (size_t)i * FR::WORDS);
 }
-// out[k] = lo[k & 1023] * hi[k >> 10]   (lo = base^i, hi = base^(1024 i)); used for the twiddle table and coset powers
+// out[k] = lo[k & 1023] * hi[k >> 10]   (lo = base^i, i < 1024; hi = base^(1024 i), i <= (count - 1) >> 10): the twiddle table
 template <class FR>
 __global__ void __launch_bounds__(256) k_ntt_table(const uint32_t* __restrict__ lo, const uint32_t* __restrict__ hi,
                                                    uint32_t* __restrict__ out, uint32_t count) {
@@ -78,7 +79,7 @@ __global__ void __launch_bounds__(256) k_ntt_load(const uint64_t* __restrict__ a
 struct NttIo {
   const uint64_t* ark_in;    // first launch only
   uint64_t* ark_out;         // last launch only
-  const uint32_t* glo;       // coset power tables g^i, g^(1024 i) (pre-scaling with ark_in, post-scaling with ark_out), or null
+  const uint32_t* glo;       // coset power tables g^i (i < 1024), g^(1024 i) (i < n / 1024): pre-scaling with ark_in, post-scaling with ark_out; or null
   const uint32_t* ghi;
   const uint32_t* scale;     // with ark_out, or null
 };
@@ -241,8 +242,8 @@ template <class FR> class NttEngine {
  public:
   ~NttEngine() { release(); }
   void release() {
-    for (void** p : {(void**)&d_work, (void**)&d_tw, (void**)&d_small, (void**)&d_io}) if (*p) { (void)hipFree(*p); *p = nullptr; }
-    cap_work = cap_tw = cap_io = 0; tw_log_n = 0;
+    for (void** p : {(void**)&d_work, (void**)&d_tw, (void**)&d_small, (void**)&d_hi, (void**)&d_io}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    cap_work = cap_tw = cap_io = cap_hi = 0; tw_log_n = 0;
     for (int i = 0; i < 4; i++) if (ev[i]) { (void)hipEventDestroy(ev[i]); ev[i] = nullptr; }
   }
   NttTimings tm;
@@ -258,8 +259,8 @@ template <class FR> class NttEngine {
     if (log_n > 28) return 2;
     const uint32_t n = 1u << log_n;
     if (prepare(log_n, omega6, coset6, scale6, stream)) return 1;
-    uint32_t* glo = coset6 ? small(2) : nullptr;
-    uint32_t* ghi = coset6 ? small(3) : nullptr;
+    uint32_t* glo = coset6 ? small(1) : nullptr;
+    uint32_t* ghi = coset6 ? hi(1) : nullptr;
     // plan the butterfly launches: (kind, levels): kind 4/3/2 = k_ntt_tile4<kind>, kind 0 = k_ntt_pass<levels>
     int kinds[16], lv[16], np = 0;
     {
@@ -279,7 +280,7 @@ template <class FR> class NttEngine {
     for (int i = 0; i < np; i++) {
       NttIo io = {nullptr, nullptr, nullptr, nullptr, nullptr};
       if (fused && i == 0) { io.ark_in = data_dev; if (coset6 && !coset_after) { io.glo = glo; io.ghi = ghi; } }
-      if (fused && i == np - 1) { io.ark_out = data_dev; if (coset6 && coset_after) { io.glo = glo; io.ghi = ghi; } io.scale = scale6 ? small(4) : nullptr; }
+      if (fused && i == np - 1) { io.ark_out = data_dev; if (coset6 && coset_after) { io.glo = glo; io.ghi = ghi; } io.scale = scale6 ? small(2) : nullptr; }
       const uint32_t blocks = n / NTT_TILE4_ELEMS;
       const size_t lds_bytes = (size_t)FR::L * NTT_TILE4_ELEMS * 4;
       if (kinds[i] == 4) hipLaunchKernelGGL((k_ntt_tile4<FR, 4>), dim3(blocks), dim3(256), lds_bytes, stream, d_work, d_tw, log_n, s, io);
@@ -295,7 +296,7 @@ template <class FR> class NttEngine {
     }
     HIP_TRY(hipEventRecord(ev[2], stream), 1);
     if (!fused) hipLaunchKernelGGL((k_ntt_store<FR>), dim3((n + 255) / 256), dim3(256), 0, stream, d_work, data_dev, log_n, (coset6 && coset_after) ? glo : nullptr, ghi,
-                                   scale6 ? small(4) : nullptr);
+                                   scale6 ? small(2) : nullptr);
     HIP_TRY(hipEventRecord(ev[3], stream), 1);
     HIP_TRY(hipStreamSynchronize(stream), 1);
     HIP_TRY(hipGetLastError(), 1);
@@ -325,12 +326,14 @@ template <class FR> class NttEngine {
  private:
   uint32_t* d_work = nullptr; size_t cap_work = 0;
   uint32_t* d_tw = nullptr; size_t cap_tw = 0;
-  uint32_t* d_small = nullptr;       // 5 x 1024 elements: twiddle lo/hi power tables, coset lo/hi power tables, [4][0] = scale
+  uint32_t* d_small = nullptr;       // 3 x 1024 elements: twiddle lo power table, coset lo power table, [2][0] = scale (staging slots behind it)
+  uint32_t* d_hi = nullptr; size_t cap_hi = 0;   // 2 x cap_hi elements: twiddle hi power table, coset hi power table (cap_hi >= n / 1024, grow-only)
   uint64_t* d_io = nullptr; size_t cap_io = 0;
   unsigned tw_log_n = 0; uint64_t tw_omega[FR::ARK64] = {};
   OwnedStream stream_;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   uint32_t* small(int i) { return d_small + (size_t)i * 1024 * FR::WORDS; }
+  uint32_t* hi(int i) { return d_hi + (size_t)i * cap_hi * FR::WORDS; }
 
   // device-form copy of an arkworks-Montgomery element: done on the host with the same templates
   static void to_dev_words(const uint64_t* ark6, uint32_t* w16) {
@@ -339,23 +342,34 @@ template <class FR> class NttEngine {
     v.store(w16);
   }
   static FR host_pow1024(FR b) { for (int i = 0; i < 10; i++) b = FR::sqr(b); return FR::wred(b); }
-  int upload_pair(const uint64_t* ark6, int slot_lo, int slot_hi, hipStream_t stream) {  // small(slot_lo)[i] = b^i, small(slot_hi)[i] = b^(1024 i)
+  // small(slot)[i] = b^i for i < 1024, hi(slot)[i] = b^(1024 i) for i < max(1, n / 1024) <= cap_hi
+  int upload_pair(const uint64_t* ark6, int slot, unsigned log_n, hipStream_t stream) {
     uint32_t h[2][FR::WORDS];
     to_dev_words(ark6, h[0]);
     FR b = FR::load(h[0]);
     memset(h[1], 0, sizeof h[1]);
     host_pow1024(b).store(h[1]);
-    uint32_t* stage = small(4) + 4 * FR::WORDS;   // scratch slots behind the scale element
+    uint32_t* stage = small(2) + 4 * FR::WORDS;   // scratch slots behind the scale element
     HIP_TRY(hipMemcpyAsync(stage, h, sizeof h, hipMemcpyHostToDevice, stream), 1);
-    hipLaunchKernelGGL((k_ntt_powers<FR>), dim3(4), dim3(256), 0, stream, stage, small(slot_lo));
-    hipLaunchKernelGGL((k_ntt_powers<FR>), dim3(4), dim3(256), 0, stream, stage + FR::WORDS, small(slot_hi));
+    const int hi_bits = log_n > 10 ? (int)log_n - 10 : 0;
+    const uint32_t hi_count = 1u << hi_bits;
+    hipLaunchKernelGGL((k_ntt_powers<FR>), dim3(4), dim3(256), 0, stream, stage, small(slot), 1024u, 10);
+    hipLaunchKernelGGL((k_ntt_powers<FR>), dim3((hi_count + 255) / 256), dim3(256), 0, stream, stage + FR::WORDS, hi(slot), hi_count, hi_bits);
     HIP_TRY(hipStreamSynchronize(stream), 1);     // h lives on this stack frame
     return 0;
   }
   int prepare(unsigned log_n, const uint64_t* omega6, const uint64_t* coset6, const uint64_t* scale6, hipStream_t stream) {
     if (!ev[0]) for (int i = 0; i < 4; i++) HIP_TRY(hipEventCreate(&ev[i]), 1);
     const size_t n = size_t(1) << log_n;
-    if (!d_small) HIP_TRY(hipMalloc(&d_small, (size_t)5 * 1024 * FR::WORDS * 4), 1);
+    if (!d_small) HIP_TRY(hipMalloc(&d_small, (size_t)3 * 1024 * FR::WORDS * 4), 1);
+    const size_t hi_count = n > 1024 ? n / 1024 : 1;
+    if (hi_count > cap_hi) {      // the twiddle table in d_tw is finished by the time this is called again: growing loses nothing
+      if (d_hi) (void)hipFree(d_hi);
+      d_hi = nullptr; cap_hi = 0;
+      const size_t want = hi_count > 1024 ? hi_count : 1024;
+      HIP_TRY(hipMalloc(&d_hi, 2 * want * FR::WORDS * 4), 1);
+      cap_hi = want;
+    }
     if (n * FR::WORDS * 4 > cap_work) {
       if (d_work) (void)hipFree(d_work);
       d_work = nullptr; cap_work = 0;
@@ -370,16 +384,16 @@ template <class FR> class NttEngine {
       cap_tw = tw_count * FR::WORDS * 4;
     }
     if (tw_log_n != log_n || memcmp(tw_omega, omega6, sizeof tw_omega) != 0) {
-      if (upload_pair(omega6, 0, 1, stream)) return 1;
-      hipLaunchKernelGGL((k_ntt_table<FR>), dim3(((uint32_t)tw_count + 255) / 256), dim3(256), 0, stream, small(0), small(1), d_tw, (uint32_t)tw_count);
+      if (upload_pair(omega6, 0, log_n, stream)) return 1;
+      hipLaunchKernelGGL((k_ntt_table<FR>), dim3(((uint32_t)tw_count + 255) / 256), dim3(256), 0, stream, small(0), hi(0), d_tw, (uint32_t)tw_count);
       tw_log_n = log_n;
       memcpy(tw_omega, omega6, sizeof tw_omega);
     }
-    if (coset6 && upload_pair(coset6, 2, 3, stream)) return 1;
+    if (coset6 && upload_pair(coset6, 1, log_n, stream)) return 1;
     if (scale6) {
       uint32_t h[FR::WORDS];
       to_dev_words(scale6, h);
-      HIP_TRY(hipMemcpyAsync(small(4), h, sizeof h, hipMemcpyHostToDevice, stream), 1);
+      HIP_TRY(hipMemcpyAsync(small(2), h, sizeof h, hipMemcpyHostToDevice, stream), 1);
       HIP_TRY(hipStreamSynchronize(stream), 1);
     }
     return 0;

@@ -246,7 +246,8 @@ int celo_amd_pairing_last_timings(float ms[4]);
  * data: n = 2^log_n elements, arkworks Montgomery limbs (6 u64 each).  omega: the domain's group_gen (its inverse for an
  * inverse transform).  coset: NULL, or a generator g: every x_i is multiplied by g^i BEFORE the transform (coset_after =
  * 0: coset_fft with g = the coset offset) or AFTER it (coset_after = 1: coset_ifft with g = offset^-1).  scale: NULL, or a
- * factor applied to every output (size_inv for the inverse transforms).  log_n <= 28. */
+ * factor applied to every output (size_inv for the inverse transforms).  log_n <= 28: a larger log_n returns 2 before anything is
+ * allocated or launched, here and in every entry below that takes a log_n (both fields, the witness maps included). */
 int ntt_bw6_761_fr(uint64_t* data, unsigned log_n, const uint64_t omega[6], const uint64_t* coset, int coset_after, const uint64_t* scale);
 int ntt_bw6_761_fr_dev(uint64_t* d_data, unsigned log_n, const uint64_t omega[6], const uint64_t* coset, int coset_after,
                        const uint64_t* scale, void* hip_stream);
