@@ -88,6 +88,18 @@ int fixed_base_set_window(int);
 void setup_last_timings(float*);
 int groth16_setup(int, const uint64_t*, const uint64_t*, const uint64_t*, size_t, size_t, const uint64_t*, const uint64_t*, size_t, const uint64_t*, const uint64_t*,
                   const uint64_t*, int, uint64_t*, uint64_t*, ProvingKey**);
+struct R1cs;                             // unit_r1cs.hip: constraint matrices on the device
+int r1cs_load(int, size_t, size_t, size_t, const uint64_t* const*, const uint32_t* const*, const uint64_t* const*, const uint64_t*, R1cs**, uint64_t*);
+int r1cs_info(const R1cs*, uint64_t*);
+void r1cs_free(R1cs*);
+int r1cs_rows(const R1cs*, const uint64_t*, unsigned, uint64_t*, uint64_t*, uint64_t*, int, void*);
+int r1cs_check(const R1cs*, const uint64_t*, int64_t*);
+int r1cs_qap_at_tau(const R1cs*, unsigned, const uint64_t*, const uint64_t*, uint64_t*, uint64_t*, uint64_t*, uint64_t*, int, void*);
+void r1cs_last_timings(float*);
+int groth16_prove_r1cs(const ProvingKey*, const R1cs*, const uint64_t*, unsigned, const uint64_t*, const uint64_t*, const uint64_t*, const uint64_t*, const uint64_t*,
+                       const uint64_t*, uint64_t*, uint64_t*, uint64_t*);
+int groth16_setup_r1cs(int, const R1cs*, unsigned, const uint64_t*, const uint64_t*, const uint64_t*, const uint64_t*, const uint64_t*, int, uint64_t*, uint64_t*,
+                       ProvingKey**);
 int hash_to_g1_direct_run(const uint8_t*, const uint8_t*, const uint64_t*, const uint8_t*, const uint64_t*, size_t, uint64_t*, uint8_t*, int);
 float hash_last_ms();
 int pedersen_crh_run(const uint8_t*, const uint64_t*, size_t, uint8_t*);
@@ -471,6 +483,52 @@ int groth16_setup_bls12_377(const uint64_t* qap_a, const uint64_t* qap_b, const 
 }
 int celo_amd_fixed_base_set_window(int window_bits) { return fixed_base_set_window(window_bits); }
 int celo_amd_setup_last_timings(float ms[8]) { if (!ms) return 2; setup_last_timings(ms); return 0; }
+// ---- R1CS matrices on the device (unit_r1cs.hip)
+#define R1CS_LOAD(NAME, CURVE)                                                                                                                              \
+  int NAME(size_t n_constraints, size_t n_vars, size_t n_inputs, const uint64_t* a_row_ptr, const uint32_t* a_col, const uint64_t* a_val, size_t a_nnz,     \
+           const uint64_t* b_row_ptr, const uint32_t* b_col, const uint64_t* b_val, size_t b_nnz, const uint64_t* c_row_ptr, const uint32_t* c_col,          \
+           const uint64_t* c_val, size_t c_nnz, void** out_r1cs, uint64_t* first_bad) {                                                                     \
+    if (!out_r1cs) return 2;                                                                                                                                \
+    *out_r1cs = nullptr;                                                                                                                                    \
+    const uint64_t* const rp[3] = {a_row_ptr, b_row_ptr, c_row_ptr};                                                                                       \
+    const uint32_t* const col[3] = {a_col, b_col, c_col};                                                                                                   \
+    const uint64_t* const val[3] = {a_val, b_val, c_val};                                                                                                   \
+    const uint64_t nnz[3] = {a_nnz, b_nnz, c_nnz};                                                                                                          \
+    return r1cs_load(CURVE, n_constraints, n_vars, n_inputs, rp, col, val, nnz, (R1cs**)out_r1cs, first_bad);                                               \
+  }
+R1CS_LOAD(groth16_r1cs_load_bw6_761, 0) R1CS_LOAD(groth16_r1cs_load_bls12_377, 1)
+#undef R1CS_LOAD
+int groth16_r1cs_info(const void* r1cs, uint64_t out[8]) { return r1cs_info((const R1cs*)r1cs, out); }
+int groth16_r1cs_free(void* r1cs) { if (!r1cs) return 2; r1cs_free((R1cs*)r1cs); return 0; }
+int groth16_r1cs_rows(const void* r1cs, const uint64_t* z, unsigned log_n, uint64_t* out_a, uint64_t* out_b, uint64_t* out_c) {
+  return r1cs_rows((const R1cs*)r1cs, z, log_n, out_a, out_b, out_c, 0, nullptr);
+}
+int groth16_r1cs_rows_dev(const void* r1cs, const uint64_t* d_z, unsigned log_n, uint64_t* d_out_a, uint64_t* d_out_b, uint64_t* d_out_c, void* hip_stream) {
+  return r1cs_rows((const R1cs*)r1cs, d_z, log_n, d_out_a, d_out_b, d_out_c, 1, hip_stream);
+}
+int groth16_r1cs_check(const void* r1cs, const uint64_t* z, int64_t* first_unsatisfied) { return r1cs_check((const R1cs*)r1cs, z, first_unsatisfied); }
+int groth16_r1cs_qap_at_tau(const void* r1cs, unsigned log_n, const uint64_t* omega, const uint64_t* tau, uint64_t* out_a, uint64_t* out_b, uint64_t* out_c,
+                            uint64_t* out_zt) {
+  return r1cs_qap_at_tau((const R1cs*)r1cs, log_n, omega, tau, out_a, out_b, out_c, out_zt, 0, nullptr);
+}
+int groth16_r1cs_qap_at_tau_dev(const void* r1cs, unsigned log_n, const uint64_t* omega, const uint64_t* tau, uint64_t* d_out_a, uint64_t* d_out_b, uint64_t* d_out_c,
+                                uint64_t* out_zt, void* hip_stream) {
+  return r1cs_qap_at_tau((const R1cs*)r1cs, log_n, omega, tau, d_out_a, d_out_b, d_out_c, out_zt, 1, hip_stream);
+}
+int groth16_prove_r1cs_with_key(const void* key, const void* r1cs, const uint64_t* z, unsigned log_n, const uint64_t* omega, const uint64_t* omega_inv,
+                                const uint64_t* coset, const uint64_t* coset_inv, const uint64_t* size_inv, const uint64_t* vanishing_inv, uint64_t* out_a,
+                                uint64_t* out_b, uint64_t* out_c) {
+  return groth16_prove_r1cs((const ProvingKey*)key, (const R1cs*)r1cs, z, log_n, omega, omega_inv, coset, coset_inv, size_inv, vanishing_inv, out_a, out_b, out_c);
+}
+int groth16_setup_r1cs_bw6_761(const void* r1cs, unsigned log_n, const uint64_t omega[6], const uint64_t tau[6], const uint64_t toxic[24], const uint64_t g1_xy[24],
+                               const uint64_t g2_xy[24], int window_bits, uint64_t* out_vk, uint64_t* out_rows, void** out_key) {
+  return groth16_setup_r1cs(0, (const R1cs*)r1cs, log_n, omega, tau, toxic, g1_xy, g2_xy, window_bits, out_vk, out_rows, (ProvingKey**)out_key);
+}
+int groth16_setup_r1cs_bls12_377(const void* r1cs, unsigned log_n, const uint64_t omega[4], const uint64_t tau[4], const uint64_t toxic[16], const uint64_t g1_xy[12],
+                                 const uint64_t g2_xy[24], int window_bits, uint64_t* out_vk, uint64_t* out_rows, void** out_key) {
+  return groth16_setup_r1cs(1, (const R1cs*)r1cs, log_n, omega, tau, toxic, g1_xy, g2_xy, window_bits, out_vk, out_rows, (ProvingKey**)out_key);
+}
+int celo_amd_r1cs_last_timings(float ms[8]) { if (!ms) return 2; r1cs_last_timings(ms); return 0; }
 int celo_amd_decompress_last_ms(float* ms) { if (!ms) return 2; *ms = wire_last_ms(); return 0; }
 int celo_amd_msm_last_timings(int group, float ms[5], int cfg[3]) {
   switch (group) {

@@ -10,6 +10,7 @@
 #include "wire.h"
 #include "wire761.h"
 #include "fixed_base.h"
+#include "r1cs.h"
 #include "hash_direct.h"
 #include "host64.h"
 #include <cstring>
@@ -517,5 +518,56 @@ void ht_setup_scalars(int curve, const uint64_t* qa, const uint64_t* qb, const u
                       const uint64_t* tau, size_t n_h, const uint64_t* toxic, uint64_t* g1s, uint64_t* g2s) {
   if (curve == 0) setup_host<Fp<P377>>(qa, qb, qc, n_vars, n_inputs, zt, tau, n_h, toxic, g1s, g2s);
   else setup_host<Fp<P253>>(qa, qb, qc, n_vars, n_inputs, zt, tau, n_h, toxic, g1s, g2s);
+}
+
+// ---- r1cs.h: the validation of groth16_r1cs_load_*, and the bodies of unit_r1cs.hip's kernels in host loops (the product in the kernels'
+// short / chunk / combine order).  curve 0 = BW6-761 (Fr 6 u64), 1 = BLS12-377 (4 u64).  Matrices: three CSR structures in a, b, c order.
+int ht_r1cs_validate(int curve, size_t rows, size_t n_vars, size_t n_inputs, const uint64_t* const* row_ptr, const uint32_t* const* col, const uint64_t* const* val,
+                     const uint64_t* nnz, uint64_t* first_bad) {
+  const R1csCsr mats[3] = {{row_ptr[0], col[0], val[0], nnz[0]}, {row_ptr[1], col[1], val[1], nnz[1]}, {row_ptr[2], col[2], val[2], nnz[2]}};
+  return curve == 0 ? r1cs_validate<6>(rows, n_vars, n_inputs, mats, P377::P64, first_bad) : r1cs_validate<4>(rows, n_vars, n_inputs, mats, P253::P64, first_bad);
+}
+// the constants the tests' generators must know: the list length above which a list is cut, the chunk size, terms between weak reductions
+void ht_r1cs_params(uint32_t out[3]) { out[0] = R1CS_LONG; out[1] = R1CS_CHUNK; out[2] = R1CS_LAZY; }
+// out = M vec over the matrix's rows (ht_r1cs_rows: vec = the assignment)
+void ht_r1cs_rows(int curve, const uint64_t* row_ptr, const uint32_t* col, const uint64_t* val, size_t rows, const uint64_t* vec, uint64_t* out) {
+  if (curve == 0) r1cs_matvec_host<Fp<P377>>(row_ptr, col, val, rows, vec, out);
+  else r1cs_matvec_host<Fp<P253>>(row_ptr, col, val, rows, vec, out);
+}
+extern "C++" {
+template <class FR> static void lagrange_host(unsigned log_n, const uint64_t* omega, const uint64_t* tau, uint64_t* out, uint64_t* zt) {
+  const R1csLagConsts<FR> k = r1cs_lagrange_consts<FR>(log_n, omega, tau, zt);
+  const uint64_t n = uint64_t(1) << log_n;
+  for (uint64_t j0 = 0; j0 < n; j0 += R1CS_LAG_BLOCK)
+    r1cs_lagrange_block(k.c, k.tau, k.omega, k.omega_inv, j0, n - j0 < R1CS_LAG_BLOCK ? (uint32_t)(n - j0) : R1CS_LAG_BLOCK, out);
+}
+// the transpose of the matrix (r1cs_transpose) times vec, over the n_vars columns; then a_i += extra_i for i < n_extra (the matrix a: L_(rows + i))
+template <class FR> static void cols_host(const uint64_t* row_ptr, const uint32_t* col, const uint64_t* val, size_t rows, size_t n_vars, const uint64_t* vec,
+                                          size_t n_extra, uint64_t* out) {
+  constexpr int A = FR::ARK64;
+  std::vector<uint64_t> t_ptr, t_val;
+  std::vector<uint32_t> t_idx;
+  r1cs_transpose<A>(rows, n_vars, R1csCsr{row_ptr, col, val, row_ptr[rows]}, t_ptr, t_idx, t_val);
+  r1cs_matvec_host<FR>(t_ptr.data(), t_idx.data(), t_val.data(), n_vars, vec, out);
+  for (size_t i = 0; i < n_extra; i++) r1cs_add_input<FR>(out + i * A, vec + (rows + i) * A);
+}
+}  // extern "C++"
+void ht_r1cs_lagrange(int curve, unsigned log_n, const uint64_t* omega, const uint64_t* tau, uint64_t* out, uint64_t* zt) {
+  if (curve == 0) lagrange_host<Fp<P377>>(log_n, omega, tau, out, zt);
+  else lagrange_host<Fp<P253>>(log_n, omega, tau, out, zt);
+}
+void ht_r1cs_cols(int curve, const uint64_t* row_ptr, const uint32_t* col, const uint64_t* val, size_t rows, size_t n_vars, const uint64_t* vec, size_t n_extra,
+                  uint64_t* out) {
+  if (curve == 0) cols_host<Fp<P377>>(row_ptr, col, val, rows, n_vars, vec, n_extra, out);
+  else cols_host<Fp<P253>>(row_ptr, col, val, rows, n_vars, vec, n_extra, out);
+}
+// (A z)_j (B z)_j == (C z)_j over n rows: the smallest failing j, or -1 (the twin of k_r1cs_check)
+int64_t ht_r1cs_check_rows(int curve, const uint64_t* a, const uint64_t* b, const uint64_t* c, size_t n) {
+  const int A = curve == 0 ? 6 : 4;
+  for (size_t j = 0; j < n; j++) {
+    const bool ok = curve == 0 ? r1cs_row_holds<Fp<P377>>(a + j * A, b + j * A, c + j * A) : r1cs_row_holds<Fp<P253>>(a + j * A, b + j * A, c + j * A);
+    if (!ok) return (int64_t)j;
+  }
+  return -1;
 }
 }

@@ -170,6 +170,20 @@ class CallScope {
 };
 
 
+// kernel-time accounting by event pairs per category (read after the call's final synchronisation)
+struct EvLog {
+  struct Rec { int cat; hipEvent_t a, b; };
+  std::vector<Rec> recs;
+  hipStream_t s;
+  explicit EvLog(hipStream_t st) : s(st) {}
+  hipEvent_t open() { hipEvent_t e = nullptr; if (hipEventCreate(&e) != hipSuccess) return nullptr; (void)hipEventRecord(e, s); return e; }
+  void close(int cat, hipEvent_t a) { hipEvent_t e = nullptr; if (a && hipEventCreate(&e) == hipSuccess) { (void)hipEventRecord(e, s); recs.push_back({cat, a, e}); } }
+  void sum(float* ms) {
+    for (auto& r : recs) { float t = 0.f; if (hipEventElapsedTime(&t, r.a, r.b) == hipSuccess) ms[r.cat] += t; }
+  }
+  ~EvLog() { for (auto& r : recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); } }
+};
+
 // ---- chaining engines on the device (batch verification: MSM results -> normalise -> pairing inputs, no host round trip)
 // A batched MSM that has been ENQUEUED on its engine's stream: d_out = m Jacobian results (arkworks form) in the engine's
 // arena; the engine stays leased until msm_batch_end_*.

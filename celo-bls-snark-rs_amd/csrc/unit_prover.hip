@@ -10,11 +10,13 @@
 //        B = b_g2_query[0] + MSM(b_g2_query[1..], assignment) + beta_g2
 //        C = MSM(l_query, aux_assignment) + MSM(h_query, h)
 //      the four MSMs run concurrently on four engines (msm.h); the handful of point additions around them on the host.
-// R1CS synthesis (evaluating the constraint matrices on the witness) is the circuit's business and stays with the caller.
+// R1CS synthesis (running the gadgets) is the circuit's business and stays with the caller.  Evaluating the constraint matrices on the
+// assignment is unit_r1cs.hip: groth16_prove_r1cs below starts from matrices + assignment, the entry points above it from a, b, c.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include "fp.h"
 #include "runtime.h"
+#include <chrono>
 #include <thread>
 #include <vector>
 #include <cstring>
@@ -38,6 +40,10 @@ int msm_fixed_run_g1_377(const FixedTable*, const void*, size_t, int, uint64_t*,
 int msm_fixed_build_g2_377(const void*, const void*, size_t, int, int, FixedTable**);
 int msm_fixed_run_g2_377(const FixedTable*, const void*, size_t, int, uint64_t*, void*);
 int fixed_table_release(FixedTable*);
+struct R1cs;                                         // unit_r1cs.hip: constraint matrices on the device
+int r1cs_rows(const R1cs*, const uint64_t*, unsigned, uint64_t*, uint64_t*, uint64_t*, int, void*);
+void r1cs_shape(const R1cs*, int*, int*, size_t*, size_t*, size_t*);
+void r1cs_note_ms(int, float);
 template <class FR> struct NttOf;
 template <> struct NttOf<Fr761> { static int run(uint64_t* d, unsigned l, const uint64_t* w, const uint64_t* g, int after, const uint64_t* sc, void* st) { return ntt_run(d, l, w, g, after, sc, 1, st); } };
 template <> struct NttOf<Fr377> { static int run(uint64_t* d, unsigned l, const uint64_t* w, const uint64_t* g, int after, const uint64_t* sc, void* st) { return ntt_run_253(d, l, w, g, after, sc, 1, st); } };
@@ -282,8 +288,10 @@ int groth16_key_load_dev_761(const uint64_t* d_a, const uint8_t* d_ainf, size_t 
                              const uint64_t* a0, const uint64_t* b0, const uint64_t* alpha_g1, const uint64_t* beta_g2, int window_bits, ProvingKey** out) {
   return groth16_key_load_dev(0, d_a, d_ainf, na, d_b, d_binf, nb, d_h, d_hinf, nh, d_l, d_linf, nl, a0, b0, alpha_g1, beta_g2, window_bits, out);
 }
-int groth16_prove_keyed(const ProvingKey* k, const uint64_t* assignment, size_t n_assign, size_t n_aux, const uint64_t* h, size_t n_h, uint64_t* out_a, uint64_t* out_b,
-                        uint64_t* out_c) {
+// resident = 0: assignment and h are host pointers; 1: device pointers whose producing stream has been synchronised (the four engine threads
+// read them on their own streams)
+static int prove_keyed(const ProvingKey* k, const uint64_t* assignment, size_t n_assign, size_t n_aux, const uint64_t* h, size_t n_h, int resident, uint64_t* out_a,
+                       uint64_t* out_b, uint64_t* out_c) {
   if (int rc0 = api_enter()) return rc0;
   if (!k || !out_a || !out_b || !out_c || (n_assign && !assignment) || n_aux > n_assign || (n_h && !h)) return 2;
   if (k->device != api_device()) return 101;
@@ -299,8 +307,8 @@ int groth16_prove_keyed(const ProvingKey* k, const uint64_t* assignment, size_t 
     rcs[i] = api_bind_thread(dev);
     if (rcs[i]) return;
     if (!t || n == 0) { ident(acc[i], g2 ? J2 : J1); return; }
-    if (!curve) rcs[i] = msm_fixed_run_761(t, sc, n, 0, acc[i], nullptr);
-    else rcs[i] = g2 ? msm_fixed_run_g2_377(t, sc, n, 0, acc[i], nullptr) : msm_fixed_run_g1_377(t, sc, n, 0, acc[i], nullptr);
+    if (!curve) rcs[i] = msm_fixed_run_761(t, sc, n, resident, acc[i], nullptr);
+    else rcs[i] = g2 ? msm_fixed_run_g2_377(t, sc, n, resident, acc[i], nullptr) : msm_fixed_run_g1_377(t, sc, n, resident, acc[i], nullptr);
   };
   {
     std::thread t0(run, 0, k->a, false, assignment, ka), t1(run, 1, k->b, true, assignment, kb), t2(run, 2, k->l, false, aux, kl);
@@ -326,5 +334,48 @@ int groth16_prove_keyed(const ProvingKey* k, const uint64_t* assignment, size_t 
   if (int rc = curve ? sum_jac_g2_377(&t2[0][0], 3, out_b) : sum_jac_761(&t2[0][0], 3, out_b)) return rc;
   memcpy(pack1, acc[2], J1 * 8); memcpy(pack1 + J1, acc[3], J1 * 8);
   return curve ? sum_jac_g1_377(pack1, 2, out_c) : sum_jac_761(pack1, 2, out_c);
+}
+int groth16_prove_keyed(const ProvingKey* k, const uint64_t* assignment, size_t n_assign, size_t n_aux, const uint64_t* h, size_t n_h, uint64_t* out_a, uint64_t* out_b,
+                        uint64_t* out_c) {
+  return prove_keyed(k, assignment, n_assign, n_aux, h, n_h, 0, out_a, out_b, out_c);
+}
+
+// ---- matrices + assignment -> proof (groth16_prove_r1cs_with_key): z goes up once; the constraint rows (unit_r1cs.hip), the witness map and the
+// canonical assignment are made on the device and the four fixed-base MSMs read them where they lie.
+template <class FR>
+static int prove_r1cs_t(const ProvingKey* k, const R1cs* r, size_t n_vars, size_t n_inputs, const uint64_t* z, unsigned log_n, const uint64_t* omega,
+                        const uint64_t* omega_inv, const uint64_t* coset, const uint64_t* coset_inv, const uint64_t* n_inv, const uint64_t* z_inv, uint64_t* out_a,
+                        uint64_t* out_b, uint64_t* out_c) {
+  constexpr int A = FR::ARK64;
+  const size_t n = size_t(1) << log_n;
+  CallScope cs(nullptr);
+  HIP_TRY(cs.create_stream(), 10);
+  const hipStream_t s = cs.stream();
+  uint64_t *d_z, *d_a, *d_b, *d_c;
+  HIP_TRY(cs.alloc(&d_z, n_vars * A * 8), 10);
+  HIP_TRY(cs.alloc(&d_a, n * A * 8), 10); HIP_TRY(cs.alloc(&d_b, n * A * 8), 10); HIP_TRY(cs.alloc(&d_c, n * A * 8), 10);
+  HIP_TRY(hipMemcpyAsync(d_z, z, n_vars * A * 8, hipMemcpyHostToDevice, s), 10);
+  if (int rc = r1cs_rows(r, d_z, log_n, d_a, d_b, d_c, 1, s)) return rc;
+  if (int rc = witness_map_t<FR>(d_a, d_b, d_c, log_n, omega, omega_inv, coset, coset_inv, n_inv, z_inv, 1, 1, s)) return rc;
+  if (n_vars > 1) hipLaunchKernelGGL((k_to_canonical<FR>), dim3((unsigned)((n_vars - 1 + 255) / 256)), dim3(256), 0, s, d_z + A, (uint32_t)(n_vars - 1));
+  HIP_TRY(hipGetLastError(), 10);
+  HIP_TRY(hipStreamSynchronize(s), 10);
+  return prove_keyed(k, d_z + A, n_vars - 1, n_vars - n_inputs, d_a, n, 1, out_a, out_b, out_c);
+}
+int groth16_prove_r1cs(const ProvingKey* k, const R1cs* r, const uint64_t* z, unsigned log_n, const uint64_t* omega, const uint64_t* omega_inv, const uint64_t* coset,
+                       const uint64_t* coset_inv, const uint64_t* n_inv, const uint64_t* z_inv, uint64_t* out_a, uint64_t* out_b, uint64_t* out_c) {
+  if (int rc0 = api_enter()) return rc0;
+  if (!k || !r || !z || !omega || !omega_inv || !coset || !coset_inv || !n_inv || !z_inv || !out_a || !out_b || !out_c) return 2;
+  int curve, device;
+  size_t m, n_vars, n_inputs;
+  r1cs_shape(r, &curve, &device, &m, &n_vars, &n_inputs);
+  if (curve != k->curve) return 2;
+  if (k->device != api_device() || device != api_device()) return 101;
+  if (log_n > 28 || (size_t(1) << log_n) < m + n_inputs) return 2;
+  const auto t0 = std::chrono::steady_clock::now();
+  const int rc = curve ? prove_r1cs_t<Fr377>(k, r, n_vars, n_inputs, z, log_n, omega, omega_inv, coset, coset_inv, n_inv, z_inv, out_a, out_b, out_c)
+                       : prove_r1cs_t<Fr761>(k, r, n_vars, n_inputs, z, log_n, omega, omega_inv, coset, coset_inv, n_inv, z_inv, out_a, out_b, out_c);
+  r1cs_note_ms(4, std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  return rc;
 }
 }  // namespace celo

@@ -1,5 +1,6 @@
 // Translation unit: batched fixed-base scalar multiplication (fixed_base.h) for the four groups, and Groth16 parameter generation after
-// the QAP evaluation at tau (ark-groth16 0.1 generate_parameters, reached through crates/epoch-snark/src/api/setup.rs:22-46,63-105).
+// the QAP evaluation at tau (ark-groth16 0.1 generate_parameters, reached through crates/epoch-snark/src/api/setup.rs:22-46,63-105) - from
+// the caller's vectors, or from constraint matrices through unit_r1cs.hip (groth16_setup_r1cs).
 // DESIGN.md section 6f.
 #include "fixed_base.h"
 #include "normalize.h"
@@ -14,6 +15,11 @@ namespace celo {
 struct ProvingKey;
 int groth16_key_load_dev(int, const uint64_t*, const uint8_t*, size_t, const uint64_t*, const uint8_t*, size_t, const uint64_t*, const uint8_t*, size_t,
                          const uint64_t*, const uint8_t*, size_t, const uint64_t*, const uint64_t*, const uint64_t*, const uint64_t*, int, ProvingKey**);
+
+struct R1cs;                     // unit_r1cs.hip: constraint matrices on the device
+int r1cs_qap_at_tau(const R1cs*, unsigned, const uint64_t*, const uint64_t*, uint64_t*, uint64_t*, uint64_t*, uint64_t*, int, void*);
+void r1cs_shape(const R1cs*, int*, int*, size_t*, size_t*, size_t*);
+void r1cs_note_ms(int, float);
 
 typedef Fp<P377> FrBw6;          // the scalar field of BW6-761 (the base field of BLS12-377)
 typedef Fp<P253> FrBls;          // the scalar field of BLS12-377
@@ -105,20 +111,6 @@ __global__ void __launch_bounds__(256) k_setup_h(FR zt_dinv, FR tau, uint32_t n_
   const uint32_t cnt = n_h - i0 < SETUP_H_BLOCK ? (uint32_t)(n_h - i0) : SETUP_H_BLOCK;
   setup_h_block<FR>(zt_dinv, tau, i0, cnt, out + i0 * FR::ARK64);
 }
-
-// kernel-time accounting by event pairs per category (read after the call's final synchronisation)
-struct EvLog {
-  struct Rec { int cat; hipEvent_t a, b; };
-  std::vector<Rec> recs;
-  hipStream_t s;
-  explicit EvLog(hipStream_t st) : s(st) {}
-  hipEvent_t open() { hipEvent_t e = nullptr; if (hipEventCreate(&e) != hipSuccess) return nullptr; (void)hipEventRecord(e, s); return e; }
-  void close(int cat, hipEvent_t a) { hipEvent_t e = nullptr; if (a && hipEventCreate(&e) == hipSuccess) { (void)hipEventRecord(e, s); recs.push_back({cat, a, e}); } }
-  void sum(float* ms) {
-    for (auto& r : recs) { float t = 0.f; if (hipEventElapsedTime(&t, r.a, r.b) == hipSuccess) ms[r.cat] += t; }
-  }
-  ~EvLog() { for (auto& r : recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); } }
-};
 
 // ---- one group: G = the group's coordinate field F, N64 u64 per scalar, BITS scalar bits, R the group order's limbs
 template <class F, int N64, int BITS> struct Fbm {
@@ -264,8 +256,9 @@ int fixed_base_set_window(int c) {
 void setup_last_timings(float ms[8]) { for (int i = 0; i < 8; i++) ms[i] = g_setup_ms[i]; }
 
 // ---- Groth16 parameter generation (include/celo_bls_amd.h groth16_setup_*).  curve 0 = BW6-761 (FB1 = FB2 = Fbm761), 1 = BLS12-377.
+// dev_in = 0: qa / qb / qc are host pointers; 1: device pointers, complete before the call (groth16_setup_r1cs).
 template <class FB1, class FB2, class FR>
-static int setup_run(int curve, const uint64_t* qa, const uint64_t* qb, const uint64_t* qc, size_t n_vars, size_t n_inputs, const uint64_t* zt,
+static int setup_run(int curve, int dev_in, const uint64_t* qa, const uint64_t* qb, const uint64_t* qc, size_t n_vars, size_t n_inputs, const uint64_t* zt,
                      const uint64_t* tau, size_t n_h, const uint64_t* toxic, const uint64_t* g1_xy, const uint64_t* g2_xy, int window_bits, uint64_t* out_vk,
                      uint64_t* out_rows, ProvingKey** out_key) {
   constexpr int N = FR::ARK64, R1 = 2 * FB1::A, R2 = 2 * FB2::A;
@@ -293,23 +286,27 @@ static int setup_run(int curve, const uint64_t* qa, const uint64_t* qb, const ui
     const hipStream_t s = cs.stream();
     EvLog log(s);
     const size_t qb_bytes = n_vars * N * 8;
-    uint64_t *d_q, *d_s1, *d_s2, *d_r1, *d_r2;
+    uint64_t *d_s1, *d_s2, *d_r1, *d_r2;
+    const uint64_t *d_qa = qa, *d_qb = qb, *d_qc = qc;
     uint8_t *d_i1, *d_i2;
-    HIP_TRY(cs.alloc(&d_q, 3 * qb_bytes), 10);
     HIP_TRY(cs.alloc(&d_s1, n1 * N * 8), 10);
     HIP_TRY(cs.alloc(&d_s2, n2 * N * 8), 10);
     HIP_TRY(cs.alloc(&d_r1, n1 * R1 * 8), 10);
     HIP_TRY(cs.alloc(&d_r2, n2 * R2 * 8), 10);
     HIP_TRY(cs.alloc(&d_i1, n1), 10);
     HIP_TRY(cs.alloc(&d_i2, n2), 10);
-    HIP_TRY(hipMemcpyAsync(d_q, qa, qb_bytes, hipMemcpyHostToDevice, s), 10);
-    HIP_TRY(hipMemcpyAsync(d_q + n_vars * N, qb, qb_bytes, hipMemcpyHostToDevice, s), 10);
-    HIP_TRY(hipMemcpyAsync(d_q + 2 * n_vars * N, qc, qb_bytes, hipMemcpyHostToDevice, s), 10);
+    if (!dev_in) {
+      uint64_t* d_q;
+      HIP_TRY(cs.alloc(&d_q, 3 * qb_bytes), 10);
+      HIP_TRY(hipMemcpyAsync(d_q, qa, qb_bytes, hipMemcpyHostToDevice, s), 10);
+      HIP_TRY(hipMemcpyAsync(d_q + n_vars * N, qb, qb_bytes, hipMemcpyHostToDevice, s), 10);
+      HIP_TRY(hipMemcpyAsync(d_q + 2 * n_vars * N, qc, qb_bytes, hipMemcpyHostToDevice, s), 10);
+      d_qa = d_q; d_qb = d_q + n_vars * N; d_qc = d_q + 2 * n_vars * N;
+    }
     HIP_TRY(hipMemcpyAsync(d_s1, head1, sizeof head1, hipMemcpyHostToDevice, s), 10);
     HIP_TRY(hipMemcpyAsync(d_s2, head2, sizeof head2, hipMemcpyHostToDevice, s), 10);
     hipEvent_t e0 = log.open();
-    hipLaunchKernelGGL((k_setup_fr<FR>), dim3((unsigned)((n_vars + 255) / 256)), dim3(256), 0, s, d_q, d_q + n_vars * N, d_q + 2 * n_vars * N,
-                       (uint32_t)n_vars, (uint32_t)n_inputs, alpha, beta, ginv, dinv, d_s1, d_s2, (uint32_t)n_h);
+    hipLaunchKernelGGL((k_setup_fr<FR>), dim3((unsigned)((n_vars + 255) / 256)), dim3(256), 0, s, d_qa, d_qb, d_qc, (uint32_t)n_vars, (uint32_t)n_inputs, alpha, beta, ginv, dinv, d_s1, d_s2, (uint32_t)n_h);
     if (n_h) {
       const size_t blocks = (n_h + SETUP_H_BLOCK - 1) / SETUP_H_BLOCK;
       hipLaunchKernelGGL((k_setup_h<FR>), dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, s, zt_dinv, tau_d, (uint32_t)n_h,
@@ -365,8 +362,38 @@ int groth16_setup(int curve, const uint64_t* qa, const uint64_t* qb, const uint6
                   size_t n_h, const uint64_t* toxic, const uint64_t* g1_xy, const uint64_t* g2_xy, int window_bits, uint64_t* out_vk, uint64_t* out_rows,
                   ProvingKey** out_key) {
   if (curve == 0)
-    return setup_run<Fbm761, Fbm761, FrBw6>(0, qa, qb, qc, n_vars, n_inputs, zt, tau, n_h, toxic, g1_xy, g2_xy, window_bits, out_vk, out_rows, out_key);
-  return setup_run<FbmG1_377, FbmG2_377, FrBls>(1, qa, qb, qc, n_vars, n_inputs, zt, tau, n_h, toxic, g1_xy, g2_xy, window_bits, out_vk, out_rows, out_key);
+    return setup_run<Fbm761, Fbm761, FrBw6>(0, 0, qa, qb, qc, n_vars, n_inputs, zt, tau, n_h, toxic, g1_xy, g2_xy, window_bits, out_vk, out_rows, out_key);
+  return setup_run<FbmG1_377, FbmG2_377, FrBls>(1, 0, qa, qb, qc, n_vars, n_inputs, zt, tau, n_h, toxic, g1_xy, g2_xy, window_bits, out_vk, out_rows, out_key);
+}
+
+// ---- matrices + toxic waste -> parameters (groth16_setup_r1cs_*): the QAP at tau on the device (unit_r1cs.hip), then setup_run on the three
+// vectors where they lie; n_h = 2^log_n - 1
+int groth16_setup_r1cs(int curve, const R1cs* r, unsigned log_n, const uint64_t* omega, const uint64_t* tau, const uint64_t* toxic, const uint64_t* g1_xy,
+                       const uint64_t* g2_xy, int window_bits, uint64_t* out_vk, uint64_t* out_rows, ProvingKey** out_key) {
+  if (out_key) *out_key = nullptr;
+  if (int rc0 = api_enter()) return rc0;
+  if (!r || !omega || !tau || log_n > 28) return 2;
+  int r_curve, device;
+  size_t m, n_vars, n_inputs;
+  r1cs_shape(r, &r_curve, &device, &m, &n_vars, &n_inputs);
+  if (r_curve != curve) return 2;
+  if (device != api_device()) return 101;
+  const auto t0 = std::chrono::steady_clock::now();
+  const int N = curve ? 4 : 6;
+  const int rc = [&]() -> int {
+    CallScope cs(nullptr);
+    HIP_TRY(cs.create_stream(), 10);
+    uint64_t *d_q, zt[6];
+    HIP_TRY(cs.alloc(&d_q, 3 * n_vars * N * 8), 10);
+    uint64_t *qa = d_q, *qb = d_q + n_vars * N, *qc = d_q + 2 * n_vars * N;
+    if (int rcq = r1cs_qap_at_tau(r, log_n, omega, tau, qa, qb, qc, zt, 1, cs.stream())) return rcq;
+    const size_t n_h = (size_t(1) << log_n) - 1;
+    if (curve == 0)
+      return setup_run<Fbm761, Fbm761, FrBw6>(0, 1, qa, qb, qc, n_vars, n_inputs, zt, tau, n_h, toxic, g1_xy, g2_xy, window_bits, out_vk, out_rows, out_key);
+    return setup_run<FbmG1_377, FbmG2_377, FrBls>(1, 1, qa, qb, qc, n_vars, n_inputs, zt, tau, n_h, toxic, g1_xy, g2_xy, window_bits, out_vk, out_rows, out_key);
+  }();
+  r1cs_note_ms(5, std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  return rc;
 }
 
 }  // namespace celo

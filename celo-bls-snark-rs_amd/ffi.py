@@ -50,6 +50,9 @@ EXPORTS = [
     "fixed_base_mul_bls12_377_g1_dev", "fixed_base_mul_bls12_377_g2_dev", "fixed_base_mul_bw6_761_g1_dev", "fixed_base_mul_bw6_761_g2_dev",
     "normalize_bw6_761_g1", "normalize_bw6_761_g2", "groth16_setup_bw6_761", "groth16_setup_bls12_377",
     "celo_amd_fixed_base_set_window", "celo_amd_setup_last_timings",
+    "groth16_r1cs_load_bw6_761", "groth16_r1cs_load_bls12_377", "groth16_r1cs_info", "groth16_r1cs_free", "groth16_r1cs_rows", "groth16_r1cs_rows_dev",
+    "groth16_r1cs_check", "groth16_r1cs_qap_at_tau", "groth16_r1cs_qap_at_tau_dev", "groth16_prove_r1cs_with_key", "groth16_setup_r1cs_bw6_761",
+    "groth16_setup_r1cs_bls12_377", "celo_amd_r1cs_last_timings",
     "hash_to_g1_direct_bls12_377", "hash_to_g1_composite_bls12_377", "hash_to_g1_cip22_tail_bls12_377", "composite_crh_bls12_377",
 ]
 
@@ -587,6 +590,18 @@ class ProvingKey:
             raise KeyLoadError(rc, bad.value if rc == KEY_ERR_POINT else None)
         return k
 
+    def prove_r1cs(self, r1cs, z, log_n, consts):
+        """matrices + assignment -> proof (groth16_prove_r1cs_with_key): r1cs an R1CS of this key's curve; z (n_vars, 6 | 4) Montgomery limbs of the
+        full assignment (z[0] = 1); consts as for witness_map.  Returns (A, B, C) Jacobian limbs as prove() does."""
+        zz = np.ascontiguousarray(z, dtype=np.uint64).reshape(-1, self.sw)
+        assert zz.shape[0] == r1cs.n_vars
+        k = [np.ascontiguousarray(consts[n], dtype=np.uint64).reshape(self.sw) for n in ("omega", "omega_inv", "coset", "coset_inv", "size_inv", "vanishing_inv")]
+        out = [np.zeros(w, dtype=np.uint64) for w in self.ow]
+        rc = lib().groth16_prove_r1cs_with_key(self.h, r1cs.h, _p(zz), C.c_uint(log_n), *[_p(x) for x in k], _p(out[0]), _p(out[1]), _p(out[2]))
+        if rc != 0:
+            raise RuntimeError("groth16_prove_r1cs_with_key failed with code %d" % rc)
+        return out
+
     def prove(self, assignment, n_aux, h):
         asg = np.ascontiguousarray(assignment, dtype=np.uint64).reshape(-1, self.sw)
         hh = np.ascontiguousarray(h, dtype=np.uint64).reshape(-1, self.sw)
@@ -914,6 +929,12 @@ def groth16_setup(curve, qap_a, qap_b, qap_c, n_inputs, zt, tau, n_h, toxic, g1_
             C.c_int(window_bits), _p(vk), _p(rows), C.byref(key.h) if key is not None else None)
     if rc != 0:
         raise SetupError(curve, rc)
+    return _setup_outputs(vk, rows, key, n_vars, n_inputs, n_h, R1)
+
+
+def _setup_outputs(vk, rows, key, n_vars, n_inputs, n_h, R1):
+    """the flat vk / rows buffers of groth16_setup_* -> the dict groth16_setup documents"""
+    n_l = max(n_vars - n_inputs, 0)
     out = {"vk": None, "rows": None, "key": key}
     if vk is not None:
         out["vk"] = {"alpha_g1": vk[:R1].copy(), "beta_g2": vk[R1:R1 + 24].copy(), "gamma_g2": vk[R1 + 24:R1 + 48].copy(),
@@ -927,3 +948,146 @@ def groth16_setup(curve, qap_a, qap_b, qap_c, n_inputs, zt, tau, n_h, toxic, g1_
         d["beta_g1"], d["delta_g1"] = d["beta_g1"][0], d["delta_g1"][0]
         out["rows"] = d
     return out
+
+
+# ---- R1CS matrices on the device (include/celo_bls_amd.h: groth16_r1cs_*, groth16_prove_r1cs_with_key, groth16_setup_r1cs_*)
+R1CS_ERR_MATRIX = 34
+# csrc/r1cs.h (tests/test_r1cs_host.py checks them against the built twin): a list of more than R1CS_LONG entries is cut into chunks of R1CS_CHUNK
+R1CS_LONG, R1CS_CHUNK = 128, 1024
+
+
+class R1CSLoadError(RuntimeError):
+    def __init__(self, curve, code, first_bad=None):
+        super().__init__("groth16_r1cs_load_%s failed with code %d%s"
+                         % (curve, code, "" if first_bad is None else " (matrix %d, index %d)" % (first_bad >> 60, first_bad & ((1 << 60) - 1))))
+        self.code = code
+        self.first_bad = first_bad
+
+
+def _csr_args(mats, N):
+    """three (row_ptr, col, val) -> the contiguous arrays and the argument list of groth16_r1cs_load_* / ht_r1cs_validate"""
+    keep, args = [], []
+    for row_ptr, col, val in mats:
+        rp = np.ascontiguousarray(row_ptr, dtype=np.uint64)
+        cc = np.ascontiguousarray(col, dtype=np.uint32)
+        vv = np.ascontiguousarray(val, dtype=np.uint64).reshape(-1, N)
+        keep.append((rp, cc, vv))
+        args += [_p(rp), _p(cc), _p(vv), C.c_size_t(cc.shape[0])]
+    return keep, args
+
+
+class R1CS:
+    """Constraint matrices on the device (groth16_r1cs_load_*): load once, then rows() / check() per assignment and qap_at_tau() per setup.
+    mats: three (row_ptr (m + 1,) uint64, col (nnz,) uint32, val (nnz, 6 | 4) uint64 Montgomery limbs) in a, b, c order."""
+    def __init__(self, curve, n_constraints, n_vars, n_inputs, mats):
+        self.curve, self.m, self.n_vars, self.n_inputs = curve, n_constraints, n_vars, n_inputs
+        self.N = 6 if curve == "bw6_761" else 4
+        self.h = C.c_void_p()
+        keep, args = _csr_args(mats, self.N)
+        for rp, _, _ in keep:
+            assert rp.shape[0] == n_constraints + 1
+        bad = C.c_uint64(0)
+        rc = getattr(lib(), "groth16_r1cs_load_" + curve)(C.c_size_t(n_constraints), C.c_size_t(n_vars), C.c_size_t(n_inputs), *args, C.byref(self.h), C.byref(bad))
+        if rc != 0:
+            self.h = C.c_void_p()
+            raise R1CSLoadError(curve, rc, bad.value if rc == R1CS_ERR_MATRIX else None)
+
+    @classmethod
+    def load(cls, curve, n_constraints, n_vars, n_inputs, mats):
+        return cls(curve, n_constraints, n_vars, n_inputs, mats)
+
+    def info(self):
+        out = np.zeros(8, dtype=np.uint64)
+        rc = lib().groth16_r1cs_info(self.h, _p(out))
+        if rc != 0:
+            raise RuntimeError("groth16_r1cs_info failed with code %d" % rc)
+        return dict(zip(("curve", "n_constraints", "n_vars", "n_inputs", "nnz_a", "nnz_b", "nnz_c", "device_bytes"), (int(v) for v in out)))
+
+    def _z(self, z):
+        zz = np.ascontiguousarray(z, dtype=np.uint64).reshape(-1, self.N)
+        assert zz.shape[0] == self.n_vars
+        return zz
+
+    def rows(self, z, log_n):
+        """(A z, B z, C z) over 2^log_n rows with the input-consistency rows: three (2^log_n, 6 | 4) uint64 arrays (groth16_r1cs_rows)"""
+        zz = self._z(z)
+        out = [np.zeros((1 << log_n, self.N), dtype=np.uint64) for _ in range(3)]
+        rc = lib().groth16_r1cs_rows(self.h, _p(zz), C.c_uint(log_n), _p(out[0]), _p(out[1]), _p(out[2]))
+        if rc != 0:
+            raise RuntimeError("groth16_r1cs_rows failed with code %d" % rc)
+        return out
+
+    def rows_dev(self, d_z, log_n, d_a, d_b, d_c, stream=0):
+        rc = lib().groth16_r1cs_rows_dev(self.h, C.c_void_p(d_z), C.c_uint(log_n), C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_c), C.c_void_p(stream or 0))
+        if rc != 0:
+            raise RuntimeError("groth16_r1cs_rows_dev failed with code %d" % rc)
+
+    def check(self, z):
+        """the smallest unsatisfied constraint, or -1 (groth16_r1cs_check)"""
+        zz = self._z(z)
+        first = C.c_int64(0)
+        rc = lib().groth16_r1cs_check(self.h, _p(zz), C.byref(first))
+        if rc != 0:
+            raise RuntimeError("groth16_r1cs_check failed with code %d" % rc)
+        return first.value
+
+    def qap_at_tau(self, log_n, omega, tau):
+        """(a, b, c (n_vars, 6 | 4), zt (6 | 4,)): the four inputs of groth16_setup (groth16_r1cs_qap_at_tau); omega, tau: Montgomery limbs"""
+        w = np.ascontiguousarray(omega, dtype=np.uint64).reshape(self.N)
+        t = np.ascontiguousarray(tau, dtype=np.uint64).reshape(self.N)
+        out = [np.zeros((self.n_vars, self.N), dtype=np.uint64) for _ in range(3)]
+        zt = np.zeros(self.N, dtype=np.uint64)
+        rc = lib().groth16_r1cs_qap_at_tau(self.h, C.c_uint(log_n), _p(w), _p(t), _p(out[0]), _p(out[1]), _p(out[2]), _p(zt))
+        if rc != 0:
+            raise RuntimeError("groth16_r1cs_qap_at_tau failed with code %d" % rc)
+        return out[0], out[1], out[2], zt
+
+    def qap_at_tau_dev(self, log_n, omega, tau, d_a, d_b, d_c, stream=0):
+        """the same into device buffers; returns zt"""
+        w = np.ascontiguousarray(omega, dtype=np.uint64).reshape(self.N)
+        t = np.ascontiguousarray(tau, dtype=np.uint64).reshape(self.N)
+        zt = np.zeros(self.N, dtype=np.uint64)
+        rc = lib().groth16_r1cs_qap_at_tau_dev(self.h, C.c_uint(log_n), _p(w), _p(t), C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_c), _p(zt), C.c_void_p(stream or 0))
+        if rc != 0:
+            raise RuntimeError("groth16_r1cs_qap_at_tau_dev failed with code %d" % rc)
+        return zt
+
+    def release(self):
+        if self.h:
+            lib().groth16_r1cs_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+def r1cs_timings():
+    """the last R1CS calls: {load, rows, lagrange, columns, prove_r1cs_wall, setup_r1cs_wall} in ms"""
+    ms = (C.c_float * 8)()
+    lib().celo_amd_r1cs_last_timings(ms)
+    return dict(zip(("load", "rows", "lagrange", "columns", "prove_r1cs_wall", "setup_r1cs_wall"), list(ms)[:6]))
+
+
+def groth16_setup_r1cs(r1cs, log_n, omega, tau, toxic, g1_xy, g2_xy, window_bits=0, want_vk=True, want_rows=True, want_key=False):
+    """Groth16 parameters from the matrices (groth16_setup_r1cs_*): the QAP at tau on the device, then groth16_setup with n_h = 2^log_n - 1.
+    Returns what groth16_setup returns."""
+    curve, N = r1cs.curve, r1cs.N
+    R1 = 24 if curve == "bw6_761" else 12
+    n_vars, n_inputs, n_h = r1cs.n_vars, r1cs.n_inputs, (1 << log_n) - 1
+    w = np.ascontiguousarray(omega, dtype=np.uint64).reshape(N)
+    t = np.ascontiguousarray(tau, dtype=np.uint64).reshape(N)
+    tox = np.ascontiguousarray(toxic, dtype=np.uint64).reshape(4 * N)
+    g1 = np.ascontiguousarray(g1_xy, dtype=np.uint64).reshape(R1)
+    g2 = np.ascontiguousarray(g2_xy, dtype=np.uint64).reshape(24)
+    n_l = n_vars - n_inputs
+    vk = np.zeros(R1 + 3 * 24 + n_inputs * R1, dtype=np.uint64) if want_vk else None
+    rows = np.zeros(2 * R1 + 2 * n_vars * R1 + n_vars * 24 + (n_h + n_l) * R1, dtype=np.uint64) if want_rows else None
+    key = ProvingKey(curve, None, None, None, None, None, None) if want_key else None
+    rc = getattr(lib(), "groth16_setup_r1cs_" + curve)(r1cs.h, C.c_uint(log_n), _p(w), _p(t), _p(tox), _p(g1), _p(g2), C.c_int(window_bits), _p(vk), _p(rows),
+                                                       C.byref(key.h) if key is not None else None)
+    if rc != 0:
+        raise SetupError(curve, rc)
+    return _setup_outputs(vk, rows, key, n_vars, n_inputs, n_h, R1)

@@ -258,8 +258,9 @@ int celo_amd_ntt_last_timings(float ms[4], int* passes);
  * with the constraint evaluations and the proving key, as called at crates/epoch-snark/src/api/prover.rs:78,112.
  *
  * groth16_witness_map_bw6_761: R1CStoQAP::witness_map (ark-groth16 0.1 r1cs_to_qap.rs) from the point where a, b, c hold the
- * evaluations of the QAP polynomials over the domain (n = 2^log_n elements each, arkworks Montgomery limbs; the caller builds
- * them from its constraint system, including the input-consistency rows): ifft(a, b, c); coset_fft(a, b, c);
+ * evaluations of the QAP polynomials over the domain (n = 2^log_n elements each, arkworks Montgomery limbs, the input-consistency
+ * rows included: groth16_r1cs_rows below makes them from the constraint matrices and the assignment, and
+ * groth16_prove_r1cs_with_key starts from there; a caller that has a, b, c starts here): ifft(a, b, c); coset_fft(a, b, c);
  * ab = (a o b - c) * vanishing_inv; coset_ifft(ab).  On return a holds h (n coefficients; b and c are scratch) - as field
  * elements, or with out_canonical != 0 as canonical integers (Fr::into_repr(), what the h MSM takes).  Domain constants from the
  * caller (nothing of ark-poly is restated): omega = group_gen, omega_inv, coset = the coset offset (F::multiplicative_generator()),
@@ -514,6 +515,64 @@ int groth16_setup_bls12_377(const uint64_t* qap_a, const uint64_t* qap_b, const 
  * times in ms: [0] table build, [1] Fr preparation, [2] G1 rows, [3] G2 rows, [4] normalisation, [5] key tables, [6] wall, [7] unused */
 int celo_amd_fixed_base_set_window(int window_bits);
 int celo_amd_setup_last_timings(float ms[8]);
+
+/* ---- R1CS matrices on the device: the step of ark-groth16 0.1 between cs.to_matrices() and the entry points above - the constraint evaluation
+ * of R1CStoQAP::witness_map (prover) and R1CStoQAP::instance_map_with_evaluation (setup).  Synthesis (running the gadgets) stays with the caller;
+ * its result is data: three sparse matrices of n_constraints rows and the full assignment.
+ *
+ * One matrix = CSR: row_ptr (n_constraints + 1 offsets, row_ptr[0] = 0, row_ptr[n_constraints] = nnz), col (nnz variable indices: the instance
+ * variables first, index 0 the constant one, then the witness), val (nnz x 6 | 4 u64, arkworks Montgomery Fr), nnz (the length of col and val).
+ * Rows may be empty, repeat a column or hold a zero coefficient.
+ *
+ * groth16_r1cs_load_*: validates on the host, copies the matrices to the device and builds their transposes and the work lists of both
+ * products, once.  Returns 0; 2: n_inputs == 0, n_inputs > n_vars, n_vars, n_constraints or an nnz >= 2^32, a NULL array; 34: a matrix is
+ * malformed - *first_bad (may be NULL) = matrix index (0 a, 1 b, 2 c) << 60 | the row whose end lies before its start (row 0: row_ptr[0] != 0,
+ * row n_constraints: row_ptr[n_constraints] != nnz), or | the entry whose col >= n_vars or whose val >= the modulus; 10: device allocation
+ * failure.  On any failure everything is freed and *out_r1cs is NULL.  A handle is bound to its device (101 from another), is read-only after
+ * the load and may be used from several threads; groth16_r1cs_free releases it.
+ * groth16_r1cs_info: out = curve (0 BW6-761, 1 BLS12-377), n_constraints, n_vars, n_inputs, nnz of a, b, c, device bytes held.
+ *
+ * groth16_r1cs_rows: the witness map's inputs from the assignment z (n_vars x 6 | 4 u64 Montgomery, below the modulus, z[0] = 1):
+ * out_a[j] = sum_k A[j][k] z_k for j < n_constraints, likewise out_b, out_c; out_a[n_constraints + i] = z_i for i < n_inputs (the
+ * input-consistency rows); every other row up to 2^log_n zero.  2: 2^log_n < n_constraints + n_inputs or log_n > 28.  _dev: z and the outputs
+ * are device pointers, the work runs on hip_stream and is complete on return.
+ * groth16_r1cs_check: (A z)_j (B z)_j == (C z)_j for every constraint; *first_unsatisfied = the smallest failing j, or -1.
+ *
+ * groth16_r1cs_qap_at_tau: the four inputs of groth16_setup_*.  L_j = Z(tau) / n * omega^j / (tau - omega^j) over the n = 2^log_n domain points
+ * (omega = the domain's group_gen, from the caller; for tau = omega^k: L_j = [j == k], Z(tau) = 0); out_a[i] = sum_j A[j][i] L_j
+ * (+ L_(n_constraints + i) for i < n_inputs), out_b, out_c without the extra term (n_vars x 6 | 4 u64 each), out_zt = tau^n - 1 (one element, a
+ * HOST pointer in both forms).  _dev: out_a / out_b / out_c are device pointers. */
+int groth16_r1cs_load_bw6_761(size_t n_constraints, size_t n_vars, size_t n_inputs, const uint64_t* a_row_ptr, const uint32_t* a_col, const uint64_t* a_val, size_t a_nnz,
+                              const uint64_t* b_row_ptr, const uint32_t* b_col, const uint64_t* b_val, size_t b_nnz, const uint64_t* c_row_ptr, const uint32_t* c_col,
+                              const uint64_t* c_val, size_t c_nnz, void** out_r1cs, uint64_t* first_bad);
+int groth16_r1cs_load_bls12_377(size_t n_constraints, size_t n_vars, size_t n_inputs, const uint64_t* a_row_ptr, const uint32_t* a_col, const uint64_t* a_val, size_t a_nnz,
+                                const uint64_t* b_row_ptr, const uint32_t* b_col, const uint64_t* b_val, size_t b_nnz, const uint64_t* c_row_ptr, const uint32_t* c_col,
+                                const uint64_t* c_val, size_t c_nnz, void** out_r1cs, uint64_t* first_bad);
+int groth16_r1cs_info(const void* r1cs, uint64_t out[8]);
+int groth16_r1cs_free(void* r1cs);
+int groth16_r1cs_rows(const void* r1cs, const uint64_t* z, unsigned log_n, uint64_t* out_a, uint64_t* out_b, uint64_t* out_c /* 2^log_n x 6 | 4 each */);
+int groth16_r1cs_rows_dev(const void* r1cs, const uint64_t* d_z, unsigned log_n, uint64_t* d_out_a, uint64_t* d_out_b, uint64_t* d_out_c, void* hip_stream);
+int groth16_r1cs_check(const void* r1cs, const uint64_t* z, int64_t* first_unsatisfied);
+int groth16_r1cs_qap_at_tau(const void* r1cs, unsigned log_n, const uint64_t* omega, const uint64_t* tau, uint64_t* out_a, uint64_t* out_b, uint64_t* out_c,
+                            uint64_t* out_zt);
+int groth16_r1cs_qap_at_tau_dev(const void* r1cs, unsigned log_n, const uint64_t* omega, const uint64_t* tau, uint64_t* d_out_a, uint64_t* d_out_b, uint64_t* d_out_c,
+                                uint64_t* out_zt, void* hip_stream);
+/* matrices + assignment -> proof: z goes to the device once; groth16_r1cs_rows_dev, the witness map (canonical h) and the canonical assignment
+ * z[1..] are made there, and the four fixed-base MSMs of groth16_prove_with_key read them where they lie.  Domain constants as for
+ * groth16_witness_map_*.  Same results, identity-row rule and error codes as the piecewise calls; 2 also for a key and a circuit of different
+ * curves, 101 for a key or circuit of another device. */
+int groth16_prove_r1cs_with_key(const void* key, const void* r1cs, const uint64_t* z, unsigned log_n, const uint64_t* omega, const uint64_t* omega_inv,
+                                const uint64_t* coset, const uint64_t* coset_inv, const uint64_t* size_inv, const uint64_t* vanishing_inv, uint64_t* out_a,
+                                uint64_t* out_b, uint64_t* out_c);
+/* matrices + toxic waste -> parameters: groth16_r1cs_qap_at_tau_dev, then groth16_setup_* on the vectors where they lie, with
+ * n_h = 2^log_n - 1.  Outputs and codes as groth16_setup_*; 2 also for a circuit of the other curve or 2^log_n < n_constraints + n_inputs. */
+int groth16_setup_r1cs_bw6_761(const void* r1cs, unsigned log_n, const uint64_t omega[6], const uint64_t tau[6], const uint64_t toxic[24], const uint64_t g1_xy[24],
+                               const uint64_t g2_xy[24], int window_bits, uint64_t* out_vk, uint64_t* out_rows, void** out_key);
+int groth16_setup_r1cs_bls12_377(const void* r1cs, unsigned log_n, const uint64_t omega[4], const uint64_t tau[4], const uint64_t toxic[16], const uint64_t g1_xy[12],
+                                 const uint64_t g2_xy[24], int window_bits, uint64_t* out_vk, uint64_t* out_rows, void** out_key);
+/* the last calls' times in ms: [0] load (host wall: validation, transposition, copies), [1] rows kernels, [2] Lagrange kernel, [3] columns kernels,
+ * [4] groth16_prove_r1cs_with_key wall, [5] groth16_setup_r1cs_* wall, [6..7] unused */
+int celo_amd_r1cs_last_timings(float ms[8]);
 
 #ifdef __cplusplus
 }
