@@ -102,6 +102,7 @@ int groth16_setup_r1cs(int, const R1cs*, unsigned, const uint64_t*, const uint64
                        ProvingKey**);
 int hash_to_g1_direct_run(const uint8_t*, const uint8_t*, const uint64_t*, const uint8_t*, const uint64_t*, size_t, uint64_t*, uint8_t*, int);
 float hash_last_ms();
+int hash_last_rounds();
 int pedersen_crh_run(const uint8_t*, const uint64_t*, size_t, uint8_t*);
 int pairing_run_761(const uint64_t*, const uint8_t*, const uint64_t*, const uint8_t*, const uint32_t*, size_t, uint8_t*, uint64_t*, int);
 int batch_verify_377_run(const void*, const void*, const void*, const void*, const void*, int, const uint32_t*, const void*, const void*, const uint64_t*, size_t, uint8_t*);
@@ -450,6 +451,7 @@ int hash_to_g1_composite_bls12_377(const uint8_t domain[8], const uint8_t* msgs,
 }
 int composite_crh_bls12_377(const uint8_t* msgs, const uint64_t* msg_off, size_t n, uint8_t* out48) { return pedersen_crh_run(msgs, msg_off, n, out48); }
 int celo_amd_hash_last_ms(float* ms) { if (!ms) return 2; *ms = hash_last_ms(); return 0; }
+int celo_amd_hash_last_rounds(int* rounds) { if (!rounds) return 2; *rounds = hash_last_rounds(); return 0; }
 int normalize_bls12_377_g1(const uint64_t* jac, size_t n, uint64_t* out_xy, uint8_t* inf) { return wire_normalize(0, jac, n, out_xy, inf); }
 int normalize_bls12_377_g2(const uint64_t* jac, size_t n, uint64_t* out_xy, uint8_t* inf) { return wire_normalize(1, jac, n, out_xy, inf); }
 // ---- batched fixed-base scalar multiplication and Groth16 setup (unit_setup.hip)

@@ -342,6 +342,49 @@ int ht_hash_to_g1_direct(const uint8_t* dom, const uint8_t* msg, size_t mlen, co
   p.y.to_ark(out_xy + 6);
   return c;
 }
+// the other two modes of the same loop (hash_direct.h: TAI_XOF_ONLY, TAI_COMPOSITE) and the Pedersen CRH (pedersen.h) under bounds tracking.
+// The generator table comes from the caller: gens_ark = nchunks x 4 points (g, 2g, 3g, 4g of chunk ch at rows 4 ch .. 4 ch + 3) x (X, Y, Z, T) x 6 ark
+// limbs, the layout k_pedersen_crh indexes; a byte string longer than the table covers is refused (-2), as the entry points refuse one
+// longer than the full table.
+static std::vector<EdPoint> ht_load_gens(const uint64_t* gens_ark, size_t nchunks) {
+  std::vector<EdPoint> g(nchunks * PEDERSEN_MULTIPLES);
+  for (size_t i = 0; i < g.size(); i++) {
+    const uint64_t* r = gens_ark + i * 24;
+    g[i] = {SF::from(Fq::from_ark(r)), SF::from(Fq::from_ark(r + 6)), SF::from(Fq::from_ark(r + 12)), SF::from(Fq::from_ark(r + 18))};
+  }
+  return g;
+}
+int ht_hash_to_g1(int mode, const uint8_t* dom, const uint8_t* msg, size_t mlen, const uint8_t* extra, size_t elen, const uint64_t* gens_ark, size_t nchunks,
+                  uint64_t* out_xy) {
+  if (mode < TAI_DIRECT || mode > TAI_COMPOSITE) return -2;
+  std::vector<EdPoint> gens;
+  if (mode == TAI_COMPOSITE) {
+    if (!gens_ark || ((1 + elen + mlen) * 8 + 2) / 3 > nchunks) return -2;
+    gens = ht_load_gens(gens_ark, nchunks);
+  }
+  Affine<Fq> p = {Fq::zero(), Fq::zero()};
+  int c = -1;
+  if (!hash_to_g1_direct_tai(dom, msg, mlen, extra, elen, wire_consts(), p, c, 0, mode, gens.data())) return -1;
+  p.x.to_ark(out_xy);
+  p.y.to_ark(out_xy + 6);
+  return c;
+}
+int ht_pedersen_crh(const uint64_t* gens_ark, size_t nchunks, const uint8_t* msg, size_t len, uint8_t* out48) {
+  if ((len * 8 + 2) / 3 > nchunks) return -2;
+  const std::vector<EdPoint> gens = ht_load_gens(gens_ark, nchunks);
+  pedersen_crh(gens.data(), msg, len, out48);
+  return 0;
+}
+// scale_by_cofactor of one affine curve point (ark limbs): 1 and the affine multiple, 0 when the multiple is the identity (points of the
+// cofactor subgroup: what k_hash_finish flags for the serial loop)
+int ht_tai_finish(const uint64_t* xy, uint64_t* out_xy) {
+  const Affine<Fq> p = {Fq::norm(Fq::from_ark(xy)), Fq::norm(Fq::from_ark(xy + 6))};
+  Affine<Fq> r = {Fq::zero(), Fq::zero()};
+  if (!tai_finish(p, r)) return 0;
+  r.x.to_ark(out_xy);
+  r.y.to_ark(out_xy + 6);
+  return 1;
+}
 // table-driven root vs the Tonelli-Shanks loop on one Fq element (ark limbs): returns 1 + 2*(roots agree up to sign) when a root
 // exists for both, 0 when both say non-residue, -1 on disagreement
 int ht_wire_fq_sqrt_both(const uint64_t* a, uint64_t* out) {

@@ -54,6 +54,7 @@ EXPORTS = [
     "groth16_r1cs_check", "groth16_r1cs_qap_at_tau", "groth16_r1cs_qap_at_tau_dev", "groth16_prove_r1cs_with_key", "groth16_setup_r1cs_bw6_761",
     "groth16_setup_r1cs_bls12_377", "celo_amd_r1cs_last_timings",
     "hash_to_g1_direct_bls12_377", "hash_to_g1_composite_bls12_377", "hash_to_g1_cip22_tail_bls12_377", "composite_crh_bls12_377",
+    "celo_amd_hash_last_ms", "celo_amd_hash_last_rounds",
 ]
 
 _lib = None
@@ -829,6 +830,13 @@ def hash_last_ms():
     ms = C.c_float(0)
     assert lib().celo_amd_hash_last_ms(C.byref(ms)) == 0
     return ms.value
+
+
+def hash_last_rounds():
+    """Candidate rounds (kernel launches of the try-and-increment loop) of the last hash_to_g1_* call that hashed a message."""
+    r = C.c_int(0)
+    assert lib().celo_amd_hash_last_rounds(C.byref(r)) == 0
+    return r.value
 
 
 def composite_crh(messages):

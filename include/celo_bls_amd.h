@@ -421,6 +421,9 @@ int hash_to_g1_composite_bls12_377(const uint8_t domain[8], const uint8_t* msgs,
 int composite_crh_bls12_377(const uint8_t* msgs, const uint64_t* msg_off /* n+1 */, size_t n, uint8_t* out48 /* n x 48 */);
 /* kernel time (HIP events) of the last hash_to_g1_* call */
 int celo_amd_hash_last_ms(float* ms);
+/* candidate rounds (launches of the try-and-increment kernel) of the last hash_to_g1_* call that hashed at least one message: each round
+ * gives every message still open 1, 2, 4, 8 or 16 adjacent counters, the width chosen from how many are open */
+int celo_amd_hash_last_rounds(int* rounds);
 
 /* ---- plain sums of k Jacobian points (host pointers, arkworks layout; host-side, for small k): the fold of per-GPU
  * partial MSM results and small aggregates — Signature::aggregate / PublicKey::aggregate

@@ -154,12 +154,32 @@ _GENS = None
 
 def generators(num_windows=NUM_WINDOWS):
     """bowe_hopwood::CRH::create_generators: one random base per window; only the first generator of each window is kept
-    here (the j-th is 16^j times it) and the powers are formed lazily in crh()."""
+    here (the j-th is 16^j times it) and the powers are formed lazily (_window_multiples)."""
     global _GENS
     if _GENS is None or len(_GENS) < num_windows:
         rng = composite_prng()
         _GENS = [ed_rand(rng) for _ in range(num_windows)]
     return _GENS
+
+
+_MULTIPLES = {}     # window -> [(g, 2g, 3g, 4g) of generator j = 16^j * base, j = 0, 1, ...], grown on demand
+
+
+def _window_multiples(gens, s, count):
+    """The four multiples a chunk can select of the first `count` generators of window s, remembered between calls: every hash used to
+    re-derive 16^j * base by four doublings per chunk.  Same affine formulas, same order of operations as the chunk loop had inline:
+    enc = g; b0: enc += g; b1: enc += 2g."""
+    tab = _MULTIPLES.setdefault(s, [])
+    while len(tab) < count:
+        if tab:
+            g = tab[-1][3]                     # 4g of the previous generator ...
+            g = ed_add(g, g)
+            g = ed_add(g, g)                   # ... doubled twice more: 16 * previous
+        else:
+            g = gens[s]
+        g2 = ed_add(g, g)
+        tab.append((g, g2, ed_add(g, g2), ed_add(g2, g2)))
+    return tab
 
 
 def composite_crh(message):
@@ -174,17 +194,11 @@ def composite_crh(message):
     total = ED_ZERO
     for s in range(nseg):
         seg = bits[s * 3 * WINDOW_SIZE:(s + 1) * 3 * WINDOW_SIZE]
-        g = gens[s]
+        tab = _window_multiples(gens, s, len(seg) // 3)
         for j in range(0, len(seg), 3):
             c0, c1, c2 = seg[j], seg[j + 1], seg[j + 2]
-            enc = g
-            if c0:
-                enc = ed_add(enc, g)
-            if c1:
-                enc = ed_add(enc, ed_add(g, g))
+            enc = tab[j // 3][c0 + 2 * c1]
             if c2:
                 enc = ed_neg(enc)
             total = ed_add(total, enc)
-            for _ in range(4):
-                g = ed_add(g, g)
     return total[0].to_bytes(48, "little")

@@ -30,6 +30,16 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), f"missing export {name}"
 
 
+def test_hash_round_count_is_declared_exported_and_wrapped():
+    """celo_amd_hash_last_rounds: the hash tests prove through it that rounds of every width ran (tests/test_hash_gpu.py), so it has to stay
+    in the header, in the library and in ffi.EXPORTS.  It reads a counter: no device needed, a NULL pointer is refused."""
+    from celo_bls_snark_rs_amd import ffi
+    for name in ("celo_amd_hash_last_ms", "celo_amd_hash_last_rounds"):
+        assert name in ffi.EXPORTS and name in declared_symbols()
+    assert ffi.lib().celo_amd_hash_last_rounds(None) == 2
+    assert 0 <= ffi.hash_last_rounds() <= 255
+
+
 def test_no_device_fails_loudly():
     """Without a GPU the product must refuse, not fall back to a CPU path."""
     import numpy as np
