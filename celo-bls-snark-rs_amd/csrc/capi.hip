@@ -333,6 +333,10 @@ int pairing_product_is_one_bw6_761(const uint64_t* g1, const uint8_t* inf1, cons
   if (rc == 0 && is_one) *is_one = one;
   return rc;
 }
+int pairing_product_is_one_batch_bw6_761(const uint64_t* g1, const uint8_t* inf1, const uint64_t* g2, const uint8_t* inf2,
+                                         const uint32_t* offsets, size_t m, uint8_t* is_one) {
+  return pairing_run_761(g1, inf1, g2, inf2, offsets, m, is_one, nullptr, 0);
+}
 int celo_amd_pairing_gt_bw6_761(const uint64_t* g1, const uint8_t* inf1, const uint64_t* g2, const uint8_t* inf2, const uint32_t* offsets,
                                 size_t m, int miller_only, uint64_t* gt72) {
   return pairing_run_761(g1, inf1, g2, inf2, offsets, m, nullptr, gt72, miller_only ? 1 : 0);

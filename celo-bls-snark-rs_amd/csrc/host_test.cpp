@@ -254,19 +254,46 @@ static void pairing_op_lanes(int mode, const uint64_t* g1, const uint64_t* g2, s
                              uint64_t* out72, int* is_one) { pairing_op_lanes_t<HostTri>(mode, g1, g2, k, in72, in72b, out72, is_one); }
 static void pairing_op_hex(int mode, const uint64_t* g1, const uint64_t* g2, size_t k, const uint64_t* in72, const uint64_t* in72b,
                            uint64_t* out72, int* is_one) { pairing_op_lanes_t<HostHex>(mode, g1, g2, k, in72, in72b, out72, is_one); }
+// the lane-parallel BW6-761 pairing on three host lanes.  mode 0 / 1: per-pair Miller values multiplied in input order (GT / Miller value);
+// 10 / 11: the whole product (k <= 4; more is refused) through miller_multi<4>, what k_miller_product_lanes<LP761> runs (GT / Miller value); 12: the value-by-value
+// product tree of k_gt_tree_lanes (an unpaired last value of an odd level is carried), then the final exponentiation
 static void pairing_op_761_lanes(int mode, const uint64_t* g1, const uint64_t* g2, size_t k, uint64_t* out72, int* is_one) {
   typedef QTower<QHost761> T6;
   typedef QPairing761<QHost761> P6;
-  T6::E12 acc = T6::one12();
-  for (size_t i = 0; i < k; i++) {
-    QHost761::V px, py, Qc;
+  auto load_pair = [&](size_t i, QHost761::V& px, QHost761::V& py, QHost761::V& Qc) {
     for (int l = 0; l < 3; l++) {
       px.v[l] = Fw::from_ark(g1 + i * 24); py.v[l] = Fw::from_ark(g1 + i * 24 + 12);
       Qc.v[l] = Fw::from_ark(g2 + i * 24 + (l & 1) * 12);
     }
-    acc = T6::mul12(acc, P6::miller(px, py, Qc));
+  };
+  T6::E12 acc = T6::one12();
+  if (mode == 10 || mode == 11) {
+    QHost761::V px[4], py[4], Qc[4];
+    if (k > 4) {        // miller_multi<4> holds four pairs: refused, not clamped (out72 stays zero, is_one = -1)
+      for (int i = 0; i < 72; i++) out72[i] = 0;
+      if (is_one) *is_one = -1;
+      return;
+    }
+    for (size_t i = 0; i < k; i++) load_pair(i, px[i], py[i], Qc[i]);
+    acc = P6::miller_multi<4>((int)k, px, py, Qc);
+  } else if (mode == 12) {
+    std::vector<T6::E12> m(k ? k : 1, T6::one12());
+    for (size_t i = 0; i < k; i++) {
+      QHost761::V px, py, Qc;
+      load_pair(i, px, py, Qc);
+      m[i] = P6::miller(px, py, Qc);
+    }
+    for (size_t n = k; n > 1; n = (n + 1) / 2)
+      for (size_t t = 0; 2 * t < n; t++) m[t] = 2 * t + 1 < n ? T6::mul12(m[2 * t], m[2 * t + 1]) : m[2 * t];
+    acc = m[0];
+  } else {
+    for (size_t i = 0; i < k; i++) {
+      QHost761::V px, py, Qc;
+      load_pair(i, px, py, Qc);
+      acc = T6::mul12(acc, P6::miller(px, py, Qc));
+    }
   }
-  T6::E12 r = mode == 0 ? P6::final_exponentiation(acc) : acc;
+  T6::E12 r = (mode == 0 || mode == 10 || mode == 12) ? P6::final_exponentiation(acc) : acc;
   Fw6 x;
   Fw* c[6] = {&x.c0.c0, &x.c0.c1, &x.c0.c2, &x.c1.c0, &x.c1.c1, &x.c1.c2};
   for (int j = 0; j < 3; j++) { *c[j] = r.a.v[j]; *c[3 + j] = r.b.v[j]; }

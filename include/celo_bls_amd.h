@@ -235,6 +235,10 @@ int celo_amd_pairing_gt_bls12_377(const uint64_t* g1_xy, const uint8_t* inf1, co
  * g1_xy: k*24 u64, g2_xy: k*24 u64 (G2 coordinates are in Fq: M-type sextic twist). */
 int pairing_product_is_one_bw6_761(const uint64_t* g1_xy, const uint8_t* inf1, const uint64_t* g2_xy, const uint8_t* inf2, size_t k,
                                    int* is_one);
+/* The batch form, as for BLS12-377: m independent products in one call, product p over pairs [offsets[p], offsets[p+1]),
+ * is_one[p] = 1 iff it is the identity (an empty product is) - what a verifier of many proofs calls (m products of four pairs). */
+int pairing_product_is_one_batch_bw6_761(const uint64_t* g1_xy, const uint8_t* inf1, const uint64_t* g2_xy, const uint8_t* inf2,
+                                         const uint32_t* offsets, size_t m, uint8_t* is_one);
 int celo_amd_pairing_gt_bw6_761(const uint64_t* g1_xy, const uint8_t* inf1, const uint64_t* g2_xy, const uint8_t* inf2,
                                 const uint32_t* offsets, size_t m, int miller_only, uint64_t* gt72);
 /* ms[4] = {miller loops, GT products, final exponentiations, total} of the last pairing call (HIP events). */

@@ -179,6 +179,13 @@ def pairing_product_761(g1xy, inf1, g2xy, inf2):
     return gt, bool(one.value)
 
 
+def miller_loop_761(g1xy, inf1, g2xy, inf2):
+    k = g1xy.shape[0]
+    gt = np.zeros(72, dtype=np.uint64)
+    assert lib().orc_miller_loop_bw6_761(_p(g1xy), _p(inf1), _p(g2xy), _p(inf2), C.c_size_t(k), _p(gt)) == 0
+    return gt
+
+
 def gt377_to_flat(gt):
     """72 Montgomery limbs (tower order) -> flat Fq[w]/(w^12+5) coefficient list
     (oracle.py.pairing.tower_to_flat_377 convention)."""

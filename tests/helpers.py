@@ -42,3 +42,25 @@ def build_hosttest():
     csrc = os.path.join(root, "celo-bls-snark-rs_amd", "csrc")
     subprocess.check_call(["make", "-s", "-C", csrc, "../build/libcelo_hosttest.so"])
     return os.path.join(root, "celo-bls-snark-rs_amd", "build", "libcelo_hosttest.so")
+
+
+def groth16_setup(golden):
+    """(vk, proof, public inputs) of the reference's Groth16 known-answer vector (crates/bls-snark-sys/src/snark/mod.rs:52-119) from
+    tests/golden/reference_vectors.json: the inputs are the packed hash of its first and last epoch block"""
+    from oracle.py import epoch as ep
+    g = golden["groth16_bw6_761"]
+    vk = ep.parse_vk(bytes.fromhex(g["vk"]))
+    pr = ep.parse_proof(bytes.fromhex(g["proof"]))
+
+    def pks(hx):
+        b = bytes.fromhex(hx)
+        return [ecc.deser_point(ecc.E2_377, b[96 * i:96 * i + 96]) for i in range(len(b) // 96)]
+
+    first = ep.EpochBlock(g["first"]["index"], g["first"]["round"], bytes.fromhex(g["first_epoch_entropy"]),
+                          bytes.fromhex(g["first_parent_entropy"]), g["first"]["maximum_non_signers"],
+                          g["first"]["maximum_validators"], pks(g["first_pubkeys"]))
+    last = ep.EpochBlock(g["last"]["index"], g["last"]["round"], bytes.fromhex(g["last_epoch_entropy"]),
+                         bytes.fromhex(g["last_parent_entropy"]), g["last"]["maximum_non_signers"],
+                         g["last"]["maximum_validators"], pks(g["last_pubkeys"]))
+    inputs = ep.pack(ep.hash_first_last_epoch_block(first, last))
+    return vk, pr, inputs

@@ -40,6 +40,15 @@ def test_hash_round_count_is_declared_exported_and_wrapped():
     assert 0 <= ffi.hash_last_rounds() <= 255
 
 
+def test_batched_bw6_761_verdict_entry_is_declared_exported_and_wrapped():
+    """pairing_product_is_one_batch_bw6_761: the only way to the per-product verdict bytes of a BW6-761 call with more than one product
+    (tests/test_pairing761_gpu.py), and what a verifier of many Groth16 proofs calls."""
+    from celo_bls_snark_rs_amd import ffi
+    name = "pairing_product_is_one_batch_bw6_761"
+    assert name in ffi.EXPORTS and name in declared_symbols() and hasattr(C.CDLL(ffi.LIB_PATH), name)
+    assert callable(ffi.pairing_product_is_one_batch_bw6)
+
+
 def test_no_device_fails_loudly():
     """Without a GPU the product must refuse, not fall back to a CPU path."""
     import numpy as np

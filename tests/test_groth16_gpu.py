@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 from oracle.py import ecc, epoch as ep
 from oracle import cpu_oracle as co
-from tests.test_oracle_golden import _groth16_setup
+from tests.helpers import groth16_setup
 
 pytestmark = pytest.mark.gpu
 
@@ -22,7 +22,7 @@ def _pairs_via_product_msm(gpu, vk, pr, inputs):
 
 
 def test_groth16_reference_vector_accepts_on_gpu(gpu, golden):
-    vk, pr, inputs = _groth16_setup(golden)
+    vk, pr, inputs = groth16_setup(golden)
     pairs = _pairs_via_product_msm(gpu, vk, pr, inputs)
     assert pairs[1][0] == ep.groth16_pairs(vk, pr, inputs)[1][0]
     g1, i1 = co.pack_761([p for p, _ in pairs])
@@ -39,7 +39,7 @@ def test_groth16_reference_vector_accepts_on_gpu(gpu, golden):
 
 
 def test_bw6_gt_bit_exact(gpu, golden):
-    vk, pr, _ = _groth16_setup(golden)
+    vk, pr, _ = groth16_setup(golden)
     g1, _ = co.pack_761([vk["alpha_g1"], pr["a"]])
     g2, _ = co.pack_761([vk["beta_g2"], pr["b"]])
     offs = np.array([0, 1, 2], dtype=np.uint32)
@@ -56,7 +56,7 @@ def test_bw6_single_product_paths_bit_exact(gpu, golden, k):
     side in lane groups, the long Miller loop cut into a point wave and three iteration ranges, two-wave ladders), k = 8 the
     throughput kernels.  Miller value and GT value against the oracle's restatement of ark-ec's BW6 engine (what
     ark_groth16::verify_proof computes at crates/epoch-snark/src/api/verifier.rs:35), also with a pair at infinity."""
-    vk, pr, _ = _groth16_setup(golden)
+    vk, pr, _ = groth16_setup(golden)
     P = [ecc.E1_761.mul(vk["alpha_g1"], 3 + 2 * j) if j % 2 else ecc.E1_761.mul(pr["a"], 5 + j) for j in range(k)]
     Q = [ecc.E2_761.mul(vk["beta_g2"], 7 + j) if j % 3 else ecc.E2_761.mul(pr["b"], 2 + j) for j in range(k)]
     offs = np.array([0, k], dtype=np.uint32)

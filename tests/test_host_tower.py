@@ -180,3 +180,72 @@ def test_merged_line_product_matches_oracle(ht):
             assert np.array_equal(ml, co.miller_loop_377(g1, None, g2, None)), name
             gt, one = hp(hook, 13, g1, g2, 2)
             assert np.array_equal(gt, co.pairing_product_377(g1, None, g2, None)[0]) and one == (rep == 1), name
+
+
+def _hp761(ht, fn, mode, g1, g2, k):
+    out = np.zeros(72, dtype=np.uint64)
+    one = C.c_int(0)
+    getattr(ht, fn)(mode, _p(np.ascontiguousarray(g1)), _p(np.ascontiguousarray(g2)), C.c_size_t(k), _p(out), C.byref(one))
+    return out, bool(one.value)
+
+
+@pytest.fixture(scope="module")
+def pts761():
+    from tests import pairing761_cases as pc
+    return pc.python_points(24, 0x761A11E)
+
+
+def test_bw6_lane_twin_on_distinct_pairs(ht, pts761):
+    """the three-lane BW6-761 pairing (pairing_lanes.h QPairing761 on the host lanes) and the one-lane functions, per pair, on several
+    DISTINCT point pairs k_i A, k_j B - the lazy-reduction bound assertions of -DCELO_FP_TRACK had seen alpha_g1 / beta_g2 alone."""
+    for i, j in ((0, 1), (2, 2), (5, 3), (7, 11)):
+        g1, g2 = pts761.P[i:i + 1], pts761.Q[j:j + 1]
+        oml = co.miller_loop_761(g1, None, g2, None)
+        ogt, oone = co.pairing_product_761(g1, None, g2, None)
+        for fn in ("ht_pairing_761", "ht_pairing_761_lanes"):
+            assert np.array_equal(_hp761(ht, fn, 1, g1, g2, 1)[0], oml), (fn, i, j)
+            gt, one = _hp761(ht, fn, 0, g1, g2, 1)
+            assert np.array_equal(gt, ogt) and one == oone == False, (fn, i, j)
+
+
+def test_bw6_shared_accumulator_twin_matches_oracle(ht, pts761):
+    """modes 10 / 11: the whole product (k = 1 ... 4) through QPairing761::miller_multi<4>, what k_miller_product_lanes<LP761> runs above
+    16384 products: Miller and GT value bit for bit against the oracle, on unrelated pairs and on accepting products (2 and 4 pairs), for
+    which the host reports is_one and the GT value is the packed one."""
+    from tests import pairing761_cases as pc
+    one_gt = co.pairing_product_761(pts761.P[:0], None, pts761.Q[:0], None)[0]
+    for k in (1, 2, 3, 4):
+        b = pc.layout(pts761, [pc.product(pts761, k, "unrelated", 3 * k)])
+        g1, _, g2, _ = pc.slice_of(b, 0)
+        ml, _ = _hp761(ht, "ht_pairing_761_lanes", 11, g1, g2, k)
+        assert np.array_equal(ml, co.miller_loop_761(g1, None, g2, None)), k
+        gt, one = _hp761(ht, "ht_pairing_761_lanes", 10, g1, g2, k)
+        assert np.array_equal(gt, co.pairing_product_761(g1, None, g2, None)[0]) and not one, k
+    b5 = pc.layout(pts761, [pc.product(pts761, 5, "unrelated", 1)])       # five pairs do not fit miller_multi<4>: refused, not clamped
+    out = np.ones(72, dtype=np.uint64); flag = C.c_int(0)
+    ht.ht_pairing_761_lanes(10, _p(b5[0]), _p(b5[2]), C.c_size_t(5), _p(out), C.byref(flag))
+    assert flag.value == -1 and not out.any()
+    for k, variant, want in ((2, "accept", True), (4, "accept", True), (2, "mismatch", False), (4, "mismatch", False)):
+        s = pc.product(pts761, k, variant, 10 + k)
+        assert not any(s.f1) and not any(s.f2)
+        b = pc.layout(pts761, [s])
+        g1, _, g2, _ = pc.slice_of(b, 0)
+        assert np.array_equal(_hp761(ht, "ht_pairing_761_lanes", 11, g1, g2, k)[0], co.miller_loop_761(g1, None, g2, None)), (k, variant)
+        gt, one = _hp761(ht, "ht_pairing_761_lanes", 10, g1, g2, k)
+        ogt, oone = co.pairing_product_761(g1, None, g2, None)
+        assert np.array_equal(gt, ogt) and one == bool(oone) == want, (k, variant)
+        assert np.array_equal(gt, one_gt) == want
+
+
+def test_bw6_product_tree_twin_matches_oracle(ht, pts761):
+    """mode 12: per-pair Miller values multiplied value by value in the order of k_gt_tree_lanes (k = 2, 3, 5: levels with an unpaired last
+    value), then one final exponentiation; k = 6 as three accepting couples is 1."""
+    from tests import pairing761_cases as pc
+    for k, variant in ((2, "unrelated"), (3, "unrelated"), (5, "extra_live"), (6, "accept")):
+        s = pc.product(pts761, k, variant, 2 * k)
+        assert not any(s.f1) and not any(s.f2)
+        b = pc.layout(pts761, [s])
+        g1, _, g2, _ = pc.slice_of(b, 0)
+        gt, one = _hp761(ht, "ht_pairing_761_lanes", 12, g1, g2, k)
+        ogt, oone = co.pairing_product_761(g1, None, g2, None)
+        assert np.array_equal(gt, ogt) and one == bool(oone) == (variant == "accept"), (k, variant)

@@ -35,29 +35,10 @@ def test_reference_epoch_encodings(golden):
     assert ep.EpochBlock(120, 5, f, g, 3, 11, pk10).encode_first_epoch_to_bytes_cip22().hex() == e["EXPECTED_ENCODING_WITH_ENTROPY_PADDED"]
 
 
-def _groth16_setup(golden):
-    g = golden["groth16_bw6_761"]
-    vk = ep.parse_vk(bytes.fromhex(g["vk"]))
-    pr = ep.parse_proof(bytes.fromhex(g["proof"]))
-
-    def pks(hx):
-        b = bytes.fromhex(hx)
-        return [ecc.deser_point(ecc.E2_377, b[96 * i:96 * i + 96]) for i in range(len(b) // 96)]
-
-    first = ep.EpochBlock(g["first"]["index"], g["first"]["round"], bytes.fromhex(g["first_epoch_entropy"]),
-                          bytes.fromhex(g["first_parent_entropy"]), g["first"]["maximum_non_signers"],
-                          g["first"]["maximum_validators"], pks(g["first_pubkeys"]))
-    last = ep.EpochBlock(g["last"]["index"], g["last"]["round"], bytes.fromhex(g["last_epoch_entropy"]),
-                         bytes.fromhex(g["last_parent_entropy"]), g["last"]["maximum_non_signers"],
-                         g["last"]["maximum_validators"], pks(g["last_pubkeys"]))
-    inputs = ep.pack(ep.hash_first_last_epoch_block(first, last))
-    return vk, pr, inputs
-
-
 def test_reference_groth16_vector_accepts(golden):
     """crates/bls-snark-sys/src/snark/mod.rs:52-119 — the only end-to-end pairing known-answer vector:
     the C++ BW6-761 pairing restatement must ACCEPT it and REJECT any tampering."""
-    vk, pr, inputs = _groth16_setup(golden)
+    vk, pr, inputs = H.groth16_setup(golden)
     for P in [vk["alpha_g1"], pr["a"], pr["c"]] + vk["gamma_abc_g1"]:
         assert ecc.E1_761.in_subgroup(P)
     for P in [vk["beta_g2"], vk["gamma_g2"], vk["delta_g2"], pr["b"]]:
@@ -80,7 +61,7 @@ def test_reference_groth16_vector_accepts(golden):
 
 def test_cpp_bw6_pairing_value_vs_python_textbook(golden):
     """C++ optimal-ate value == (Python flat-field optimal ate)^k, k = (R0(x)+q R1(x)) / ((q^2-q+1)/r)."""
-    vk, _, _ = _groth16_setup(golden)
+    vk, _, _ = H.groth16_setup(golden)
     P, Q = vk["alpha_g1"], vk["beta_g2"]
     x, q, r = ecc.X, ecc.Q761, ecc.R761
     f1 = pp.miller_loop_761(P, Q, loop=x + 1)
@@ -121,7 +102,7 @@ def test_cpp_msm_matches_definition():
 
 
 def test_cpp_msm_bw6(golden):
-    vk, pr, _ = _groth16_setup(golden)
+    vk, pr, _ = H.groth16_setup(golden)
     base_pts = [vk["alpha_g1"], pr["a"], pr["c"]] + vk["gamma_abc_g1"]
     rng = ecc.SplitMix64(3)
     pts = [ecc.E1_761.mul(base_pts[i % len(base_pts)], rng.next() | 1) for i in range(20)]
