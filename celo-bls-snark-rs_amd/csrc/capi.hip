@@ -8,16 +8,9 @@
 #include <cstdio>
 #include "../../include/celo_bls_amd.h"
 #include "runtime.h"
+#include "units.h"
 
 namespace celo {
-struct FixedTable;                       // msm.h: a key's fixed-base tables
-typedef FixedTable FixedTableHandle;
-struct ProvingKey;                       // unit_prover.hip: a loaded Groth16 proving key (fixed-base tables of its four queries)
-int groth16_key_load(int, const uint64_t*, size_t, const uint64_t*, size_t, const uint64_t*, size_t, const uint64_t*, size_t, const uint64_t*, const uint64_t*, int, ProvingKey**);
-int groth16_prove_keyed(const ProvingKey*, const uint64_t*, size_t, size_t, const uint64_t*, size_t, uint64_t*, uint64_t*, uint64_t*);
-void groth16_key_free(ProvingKey*);
-int fixed_table_release(FixedTable*);    // unit_g1_377.hip
-int fixed_table_info(const FixedTable*, size_t*, int*, int*, size_t*, float*);
 // Device binding.  HIP's current device is a per-thread setting, and this library is entered from many host threads (and
 // starts its own): every entry point passes through api_enter(), which applies the calling thread's device - the one bound
 // with celo_amd_use_device(), else the process default chosen by celo_amd_init() (device 0 if init was never called).
@@ -49,67 +42,16 @@ int api_bind_thread(int device) {
   t_bound_device = device;
   return 0;
 }
-#define DECL(TAG)                                                                                     \
-  int msm_host_##TAG(const uint64_t*, const uint8_t*, const uint64_t*, size_t, int, uint64_t*);       \
-  int msm_dev_##TAG(const void*, const void*, const void*, size_t, int, uint64_t*, void*);            \
-  int msm_batch_host_##TAG(const uint64_t*, const uint8_t*, const uint64_t*, const uint32_t*, size_t, int, uint64_t*); \
-  int msm_timings_##TAG(float*, int*);                                                                \
-  int msm_set_c_##TAG(int);                                                                           \
-  int gen_points_##TAG(void*, size_t, uint64_t, const uint64_t*, size_t, uint32_t, void*);                              \
-  int sum_jac_##TAG(const uint64_t*, size_t, uint64_t*);                                              \
-  int msm_multi_host_##TAG(const int*, int, const uint64_t*, const uint8_t*, const uint64_t*, size_t, uint64_t*); \
-  int msm_multi_dev_##TAG(const int*, int, const void* const*, const void* const*, const void* const*, const size_t*, uint64_t*); \
-  int msm_multi_windows_##TAG(const int*, int, int, const void* const*, const void* const*, const void* const*, size_t, int, uint64_t*); \
-  int msm_fixed_build_##TAG(const void*, const void*, size_t, int, int, FixedTableHandle**);          \
-  int msm_fixed_run_##TAG(const FixedTableHandle*, const void*, size_t, int, uint64_t*, void*);       \
-  int msm_window_shard_##TAG(const void*, const void*, const void*, size_t, int, int, int, uint64_t*, int*, void*);   \
-  int msm_join_windows_##TAG(const uint64_t*, const int*, int, uint64_t*);                            \
-  int selftest_accumulate_##TAG(const uint64_t*, uint32_t, uint32_t, uint32_t, uint32_t, int, uint32_t*); \
-  void msm_note_big_call_##TAG();
-DECL(g1_377) DECL(g2_377) DECL(761)
-int pairing_run_377(const uint64_t*, const uint8_t*, const uint64_t*, const uint8_t*, const uint32_t*, size_t, uint8_t*, uint64_t*, int);
-int pairing_timings_377(float*);
-int ntt_run(uint64_t*, unsigned, const uint64_t*, const uint64_t*, int, const uint64_t*, int, void*);
-int ntt_run_253(uint64_t*, unsigned, const uint64_t*, const uint64_t*, int, const uint64_t*, int, void*);
-int ntt_timings(float*, int*);
-int ubench_fp_run(float*);                // unit_ubench.hip
-int witness_map_253_run(uint64_t*, uint64_t*, uint64_t*, unsigned, const uint64_t*, const uint64_t*, const uint64_t*, const uint64_t*, const uint64_t*, const uint64_t*, int, int, void*);
-int groth16_prove_377_run(const uint64_t*, size_t, const uint64_t*, size_t, const uint64_t*, size_t, const uint64_t*, size_t, const uint64_t*, const uint64_t*,
-                          const uint64_t*, size_t, size_t, const uint64_t*, size_t, uint64_t*, uint64_t*, uint64_t*);
-int wire_decompress(int, const uint8_t*, size_t, int, uint64_t*, uint8_t*, int, void*);
-int wire761_decode(int, int, const uint8_t*, size_t, int, uint64_t*, uint8_t*, int, void*);   // unit_wire761.hip
-int wire761_key_layout(const uint8_t*, size_t, int, uint64_t*);
-int wire761_key_load(const uint8_t*, size_t, int, int, ProvingKey**, uint64_t*);
-void wire761_last_timings(float*);
-float wire_last_ms();
-int wire_normalize(int, const uint64_t*, size_t, uint64_t*, uint8_t*);   // group 0 / 1: BLS12-377 G1 / G2, 2: BW6-761
-int fixed_base_mul(int, const uint64_t*, const void*, size_t, void*, void*, int, void*);   // unit_setup.hip
-int fixed_base_set_window(int);
-void setup_last_timings(float*);
-int groth16_setup(int, const uint64_t*, const uint64_t*, const uint64_t*, size_t, size_t, const uint64_t*, const uint64_t*, size_t, const uint64_t*, const uint64_t*,
-                  const uint64_t*, int, uint64_t*, uint64_t*, ProvingKey**);
-struct R1cs;                             // unit_r1cs.hip: constraint matrices on the device
-int r1cs_load(int, size_t, size_t, size_t, const uint64_t* const*, const uint32_t* const*, const uint64_t* const*, const uint64_t*, R1cs**, uint64_t*);
-int r1cs_info(const R1cs*, uint64_t*);
-void r1cs_free(R1cs*);
-int r1cs_rows(const R1cs*, const uint64_t*, unsigned, uint64_t*, uint64_t*, uint64_t*, int, void*);
-int r1cs_check(const R1cs*, const uint64_t*, int64_t*);
-int r1cs_qap_at_tau(const R1cs*, unsigned, const uint64_t*, const uint64_t*, uint64_t*, uint64_t*, uint64_t*, uint64_t*, int, void*);
-void r1cs_last_timings(float*);
-int groth16_prove_r1cs(const ProvingKey*, const R1cs*, const uint64_t*, unsigned, const uint64_t*, const uint64_t*, const uint64_t*, const uint64_t*, const uint64_t*,
-                       const uint64_t*, uint64_t*, uint64_t*, uint64_t*);
-int groth16_setup_r1cs(int, const R1cs*, unsigned, const uint64_t*, const uint64_t*, const uint64_t*, const uint64_t*, const uint64_t*, int, uint64_t*, uint64_t*,
-                       ProvingKey**);
-int hash_to_g1_direct_run(const uint8_t*, const uint8_t*, const uint64_t*, const uint8_t*, const uint64_t*, size_t, uint64_t*, uint8_t*, int);
-float hash_last_ms();
-int hash_last_rounds();
-int pedersen_crh_run(const uint8_t*, const uint64_t*, size_t, uint8_t*);
-int pairing_run_761(const uint64_t*, const uint8_t*, const uint64_t*, const uint8_t*, const uint32_t*, size_t, uint8_t*, uint64_t*, int);
-int batch_verify_377_run(const void*, const void*, const void*, const void*, const void*, int, const uint32_t*, const void*, const void*, const uint64_t*, size_t, uint8_t*);
-int draw_exponents_run(const uint32_t*, const uint32_t*, size_t, uint64_t*);
-int witness_map_run(uint64_t*, uint64_t*, uint64_t*, unsigned, const uint64_t*, const uint64_t*, const uint64_t*, const uint64_t*, const uint64_t*, const uint64_t*, int, int, void*);
-int groth16_prove_761_run(const uint64_t*, size_t, const uint64_t*, size_t, const uint64_t*, size_t, const uint64_t*, size_t, const uint64_t*, const uint64_t*,
-                          const uint64_t*, size_t, size_t, const uint64_t*, size_t, uint64_t*, uint64_t*, uint64_t*);
+// the `group` argument of the celo_amd_msm_* / celo_amd_selftest_* controls: 0 / 1 = BLS12-377 G1 / G2, 2 = BW6-761; anything else returns `bad`
+template <class G> struct GroupTag { typedef G type; };
+template <class F> static int by_group(int group, int bad, F f) {
+  switch (group) {
+    case 0: return f(GroupTag<G1_377>());
+    case 1: return f(GroupTag<G2_377>());
+    case 2: return f(GroupTag<G_761>());
+    default: return bad;
+  }
+}
 }  // namespace celo
 using namespace celo;
 
@@ -151,62 +93,62 @@ int celo_amd_device_name(char* buf, size_t buflen) {
   snprintf(buf, buflen, "%s", p.gcnArchName);
   return 0;
 }
-#define MULTI(NAME, TAG)                                                                                                              \
+#define MULTI(NAME, G)                                                                                                                \
   int NAME##_multi(const int* devices, int ndev, const uint64_t* b, const uint8_t* inf, const uint64_t* s, size_t n, uint64_t* out) { \
-    msm_note_big_call_##TAG();                                                                                                        \
-    return msm_multi_host_##TAG(devices, ndev, b, inf, s, n, out);                                                                    \
+    MsmAuxApi<G>::note_big_call();                                                                                                    \
+    return MsmApi<G>::multi_host(devices, ndev, b, inf, s, n, out);                                                                   \
   }                                                                                                                                   \
   int NAME##_multi_dev(const int* devices, int ndev, const void* const* b, const void* const* inf, const void* const* s,              \
                        const size_t* n_per, uint64_t* out) {                                                                          \
-    msm_note_big_call_##TAG();                                                                                                        \
-    return msm_multi_dev_##TAG(devices, ndev, b, inf, s, n_per, out);                                                                 \
+    MsmAuxApi<G>::note_big_call();                                                                                                    \
+    return MsmApi<G>::multi_dev(devices, ndev, b, inf, s, n_per, out);                                                                \
   }
-MULTI(msm_bls12_377_g1, g1_377) MULTI(msm_bls12_377_g2, g2_377) MULTI(msm_bw6_761_g1, 761) MULTI(msm_bw6_761_g2, 761)
+MULTI(msm_bls12_377_g1, G1_377) MULTI(msm_bls12_377_g2, G2_377) MULTI(msm_bw6_761_g1, G_761) MULTI(msm_bw6_761_g2, G_761)
 #undef MULTI
 // the window partition (include/celo_bls_amd.h): host form = every shard stages the same host arrays; device form = one replica per device
-#define MULTIW(NAME, TAG, SUB)                                                                                                        \
+#define MULTIW(NAME, G, SUB)                                                                                                          \
   int NAME##_multi_windows(const int* devices, int ndev, const uint64_t* b, const uint8_t* inf, const uint64_t* s, size_t n, uint64_t* out) { \
     if (ndev <= 0 || ndev > 64) return 2;                                                                                             \
-    msm_note_big_call_##TAG();                                                                                                        \
+    MsmAuxApi<G>::note_big_call();                                                                                                    \
     std::vector<const void*> pb((size_t)ndev, b), pi((size_t)ndev, inf), ps((size_t)ndev, s);                                         \
-    return msm_multi_windows_##TAG(devices, ndev, 0, pb.data(), inf ? pi.data() : nullptr, ps.data(), n, SUB, out);                   \
+    return MsmApi<G>::multi_windows(devices, ndev, 0, pb.data(), inf ? pi.data() : nullptr, ps.data(), n, SUB, out);                  \
   }                                                                                                                                   \
   int NAME##_multi_windows_dev(const int* devices, int ndev, const void* const* b, const void* const* inf, const void* const* s,      \
                                size_t n, uint64_t* out) {                                                                             \
-    msm_note_big_call_##TAG();                                                                                                        \
-    return msm_multi_windows_##TAG(devices, ndev, 1, b, inf, s, n, SUB, out);                                                         \
+    MsmAuxApi<G>::note_big_call();                                                                                                    \
+    return MsmApi<G>::multi_windows(devices, ndev, 1, b, inf, s, n, SUB, out);                                                        \
   }
-MULTIW(msm_bls12_377_g1, g1_377, 0) MULTIW(msm_bls12_377_g1_subgroup, g1_377, 1) MULTIW(msm_bls12_377_g2, g2_377, 0) MULTIW(msm_bls12_377_g2_subgroup, g2_377, 1)
-MULTIW(msm_bw6_761_g1, 761, 0) MULTIW(msm_bw6_761_g2, 761, 0)
+MULTIW(msm_bls12_377_g1, G1_377, 0) MULTIW(msm_bls12_377_g1_subgroup, G1_377, 1) MULTIW(msm_bls12_377_g2, G2_377, 0) MULTIW(msm_bls12_377_g2_subgroup, G2_377, 1)
+MULTIW(msm_bw6_761_g1, G_761, 0) MULTIW(msm_bw6_761_g2, G_761, 0)
 #undef MULTIW
 int msm_bls12_377_g1_window_shard_dev(const void* b, const void* inf, const void* s, size_t n, int subgroup, int shard, int nshards, uint64_t* o, int* bit_lo, void* st) {
-  msm_note_big_call_g1_377(); return msm_window_shard_g1_377(b, inf, s, n, subgroup, shard, nshards, o, bit_lo, st);
+  MsmAuxApi<G1_377>::note_big_call(); return MsmApi<G1_377>::window_shard(b, inf, s, n, subgroup, shard, nshards, o, bit_lo, st);
 }
 int msm_bls12_377_g2_window_shard_dev(const void* b, const void* inf, const void* s, size_t n, int subgroup, int shard, int nshards, uint64_t* o, int* bit_lo, void* st) {
-  msm_note_big_call_g2_377(); return msm_window_shard_g2_377(b, inf, s, n, subgroup, shard, nshards, o, bit_lo, st);
+  MsmAuxApi<G2_377>::note_big_call(); return MsmApi<G2_377>::window_shard(b, inf, s, n, subgroup, shard, nshards, o, bit_lo, st);
 }
 int msm_bw6_761_window_shard_dev(const void* b, const void* inf, const void* s, size_t n, int shard, int nshards, uint64_t* o, int* bit_lo, void* st) {
-  msm_note_big_call_761(); return msm_window_shard_761(b, inf, s, n, 0, shard, nshards, o, bit_lo, st);
+  MsmAuxApi<G_761>::note_big_call(); return MsmApi<G_761>::window_shard(b, inf, s, n, 0, shard, nshards, o, bit_lo, st);
 }
 // ---- fixed-base MSM: per-key tables (include/celo_bls_amd.h)
-#define FIXED(NAME, TAG)                                                                                                              \
+#define FIXED(NAME, G)                                                                                                                \
   int NAME##_precompute(const uint64_t* b, const uint8_t* inf, size_t n, int window_bits, void** handle) {                            \
     if (!handle) return 2;                                                                                                            \
     *handle = nullptr;                                                                                                                \
-    return msm_fixed_build_##TAG(b, inf, n, 0, window_bits, (FixedTable**)handle);                                                    \
+    return MsmApi<G>::fixed_build(b, inf, n, 0, window_bits, (FixedTable**)handle);                                                   \
   }                                                                                                                                   \
   int NAME##_precompute_dev(const void* b, const void* inf, size_t n, int window_bits, void** handle) {                               \
     if (!handle) return 2;                                                                                                            \
     *handle = nullptr;                                                                                                                \
-    return msm_fixed_build_##TAG(b, inf, n, 1, window_bits, (FixedTable**)handle);                                                    \
+    return MsmApi<G>::fixed_build(b, inf, n, 1, window_bits, (FixedTable**)handle);                                                   \
   }                                                                                                                                   \
   int NAME##_fixed(const void* handle, const uint64_t* s, size_t n, uint64_t* out) {                                                  \
-    msm_note_big_call_##TAG(); return msm_fixed_run_##TAG((const FixedTable*)handle, s, n, 0, out, nullptr);                          \
+    MsmAuxApi<G>::note_big_call(); return MsmApi<G>::fixed_run((const FixedTable*)handle, s, n, 0, out, nullptr);                     \
   }                                                                                                                                   \
   int NAME##_fixed_dev(const void* handle, const void* s, size_t n, uint64_t* out, void* st) {                                        \
-    msm_note_big_call_##TAG(); return msm_fixed_run_##TAG((const FixedTable*)handle, s, n, 1, out, st);                               \
+    MsmAuxApi<G>::note_big_call(); return MsmApi<G>::fixed_run((const FixedTable*)handle, s, n, 1, out, st);                          \
   }
-FIXED(msm_bls12_377_g1, g1_377) FIXED(msm_bls12_377_g2, g2_377) FIXED(msm_bw6_761_g1, 761) FIXED(msm_bw6_761_g2, 761)
+FIXED(msm_bls12_377_g1, G1_377) FIXED(msm_bls12_377_g2, G2_377) FIXED(msm_bw6_761_g1, G_761) FIXED(msm_bw6_761_g2, G_761)
 #undef FIXED
 // ---- Groth16 prover against a loaded key (include/celo_bls_amd.h)
 int groth16_load_key_bw6_761(const uint64_t* a_query, size_t na, const uint64_t* b_g2_query, size_t nb, const uint64_t* h_query, size_t nh, const uint64_t* l_query, size_t nl,
@@ -230,26 +172,26 @@ int celo_amd_msm_fixed_release(void* handle) { return fixed_table_release((Fixed
 int celo_amd_msm_fixed_info(const void* handle, size_t* n, int* window_bits, int* windows, size_t* table_bytes, float* build_ms) {
   return fixed_table_info((const FixedTable*)handle, n, window_bits, windows, table_bytes, build_ms);
 }
-int msm_bls12_377_g1_join_windows(const uint64_t* xyzz, const int* bit_lo, int nshards, uint64_t* out) { return msm_join_windows_g1_377(xyzz, bit_lo, nshards, out); }
-int msm_bls12_377_g2_join_windows(const uint64_t* xyzz, const int* bit_lo, int nshards, uint64_t* out) { return msm_join_windows_g2_377(xyzz, bit_lo, nshards, out); }
-int msm_bw6_761_join_windows(const uint64_t* xyzz, const int* bit_lo, int nshards, uint64_t* out) { return msm_join_windows_761(xyzz, bit_lo, nshards, out); }
-int msm_bls12_377_g1(const uint64_t* b, const uint8_t* inf, const uint64_t* s, size_t n, uint64_t* out) { msm_note_big_call_g1_377(); return msm_host_g1_377(b, inf, s, n, 0, out); }
-int msm_bls12_377_g1_subgroup(const uint64_t* b, const uint8_t* inf, const uint64_t* s, size_t n, uint64_t* out) { msm_note_big_call_g1_377(); return msm_host_g1_377(b, inf, s, n, 1, out); }
-int msm_bls12_377_g1_subgroup_dev(const void* b, const void* inf, const void* s, size_t n, uint64_t* out, void* st) { msm_note_big_call_g1_377(); return msm_dev_g1_377(b, inf, s, n, 1, out, st); }
-int msm_bls12_377_g2(const uint64_t* b, const uint8_t* inf, const uint64_t* s, size_t n, uint64_t* out) { msm_note_big_call_g2_377(); return msm_host_g2_377(b, inf, s, n, 0, out); }
-int msm_bls12_377_g2_subgroup(const uint64_t* b, const uint8_t* inf, const uint64_t* s, size_t n, uint64_t* out) { msm_note_big_call_g2_377(); return msm_host_g2_377(b, inf, s, n, 1, out); }
-int msm_bls12_377_g2_subgroup_dev(const void* b, const void* inf, const void* s, size_t n, uint64_t* out, void* st) { msm_note_big_call_g2_377(); return msm_dev_g2_377(b, inf, s, n, 1, out, st); }
-int msm_bw6_761_g1(const uint64_t* b, const uint8_t* inf, const uint64_t* s, size_t n, uint64_t* out) { msm_note_big_call_761(); return msm_host_761(b, inf, s, n, 0, out); }
-int msm_bw6_761_g2(const uint64_t* b, const uint8_t* inf, const uint64_t* s, size_t n, uint64_t* out) { msm_note_big_call_761(); return msm_host_761(b, inf, s, n, 0, out); }
-int msm_bls12_377_g1_dev(const void* b, const void* inf, const void* s, size_t n, uint64_t* out, void* st) { msm_note_big_call_g1_377(); return msm_dev_g1_377(b, inf, s, n, 0, out, st); }
-int msm_bls12_377_g2_dev(const void* b, const void* inf, const void* s, size_t n, uint64_t* out, void* st) { msm_note_big_call_g2_377(); return msm_dev_g2_377(b, inf, s, n, 0, out, st); }
-int msm_bw6_761_g1_dev(const void* b, const void* inf, const void* s, size_t n, uint64_t* out, void* st) { msm_note_big_call_761(); return msm_dev_761(b, inf, s, n, 0, out, st); }
-int msm_bw6_761_g2_dev(const void* b, const void* inf, const void* s, size_t n, uint64_t* out, void* st) { msm_note_big_call_761(); return msm_dev_761(b, inf, s, n, 0, out, st); }
-int msm_batch_bls12_377_g1(const uint64_t* b, const uint8_t* inf, const uint64_t* s, const uint32_t* off, size_t m, uint64_t* out) { return msm_batch_host_g1_377(b, inf, s, off, m, 0, out); }
-int msm_batch_bls12_377_g2(const uint64_t* b, const uint8_t* inf, const uint64_t* s, const uint32_t* off, size_t m, uint64_t* out) { return msm_batch_host_g2_377(b, inf, s, off, m, 0, out); }
-int msm_batch_bls12_377_g2_subgroup(const uint64_t* b, const uint8_t* inf, const uint64_t* s, const uint32_t* off, size_t m, uint64_t* out) { return msm_batch_host_g2_377(b, inf, s, off, m, 1, out); }
-int msm_batch_bw6_761_g1(const uint64_t* b, const uint8_t* inf, const uint64_t* s, const uint32_t* off, size_t m, uint64_t* out) { return msm_batch_host_761(b, inf, s, off, m, 0, out); }
-int msm_batch_bw6_761_g2(const uint64_t* b, const uint8_t* inf, const uint64_t* s, const uint32_t* off, size_t m, uint64_t* out) { return msm_batch_host_761(b, inf, s, off, m, 0, out); }
+int msm_bls12_377_g1_join_windows(const uint64_t* xyzz, const int* bit_lo, int nshards, uint64_t* out) { return MsmApi<G1_377>::join_windows(xyzz, bit_lo, nshards, out); }
+int msm_bls12_377_g2_join_windows(const uint64_t* xyzz, const int* bit_lo, int nshards, uint64_t* out) { return MsmApi<G2_377>::join_windows(xyzz, bit_lo, nshards, out); }
+int msm_bw6_761_join_windows(const uint64_t* xyzz, const int* bit_lo, int nshards, uint64_t* out) { return MsmApi<G_761>::join_windows(xyzz, bit_lo, nshards, out); }
+int msm_bls12_377_g1(const uint64_t* b, const uint8_t* inf, const uint64_t* s, size_t n, uint64_t* out) { MsmAuxApi<G1_377>::note_big_call(); return MsmApi<G1_377>::host(b, inf, s, n, 0, out); }
+int msm_bls12_377_g1_subgroup(const uint64_t* b, const uint8_t* inf, const uint64_t* s, size_t n, uint64_t* out) { MsmAuxApi<G1_377>::note_big_call(); return MsmApi<G1_377>::host(b, inf, s, n, 1, out); }
+int msm_bls12_377_g1_subgroup_dev(const void* b, const void* inf, const void* s, size_t n, uint64_t* out, void* st) { MsmAuxApi<G1_377>::note_big_call(); return MsmApi<G1_377>::dev(b, inf, s, n, 1, out, st); }
+int msm_bls12_377_g2(const uint64_t* b, const uint8_t* inf, const uint64_t* s, size_t n, uint64_t* out) { MsmAuxApi<G2_377>::note_big_call(); return MsmApi<G2_377>::host(b, inf, s, n, 0, out); }
+int msm_bls12_377_g2_subgroup(const uint64_t* b, const uint8_t* inf, const uint64_t* s, size_t n, uint64_t* out) { MsmAuxApi<G2_377>::note_big_call(); return MsmApi<G2_377>::host(b, inf, s, n, 1, out); }
+int msm_bls12_377_g2_subgroup_dev(const void* b, const void* inf, const void* s, size_t n, uint64_t* out, void* st) { MsmAuxApi<G2_377>::note_big_call(); return MsmApi<G2_377>::dev(b, inf, s, n, 1, out, st); }
+int msm_bw6_761_g1(const uint64_t* b, const uint8_t* inf, const uint64_t* s, size_t n, uint64_t* out) { MsmAuxApi<G_761>::note_big_call(); return MsmApi<G_761>::host(b, inf, s, n, 0, out); }
+int msm_bw6_761_g2(const uint64_t* b, const uint8_t* inf, const uint64_t* s, size_t n, uint64_t* out) { MsmAuxApi<G_761>::note_big_call(); return MsmApi<G_761>::host(b, inf, s, n, 0, out); }
+int msm_bls12_377_g1_dev(const void* b, const void* inf, const void* s, size_t n, uint64_t* out, void* st) { MsmAuxApi<G1_377>::note_big_call(); return MsmApi<G1_377>::dev(b, inf, s, n, 0, out, st); }
+int msm_bls12_377_g2_dev(const void* b, const void* inf, const void* s, size_t n, uint64_t* out, void* st) { MsmAuxApi<G2_377>::note_big_call(); return MsmApi<G2_377>::dev(b, inf, s, n, 0, out, st); }
+int msm_bw6_761_g1_dev(const void* b, const void* inf, const void* s, size_t n, uint64_t* out, void* st) { MsmAuxApi<G_761>::note_big_call(); return MsmApi<G_761>::dev(b, inf, s, n, 0, out, st); }
+int msm_bw6_761_g2_dev(const void* b, const void* inf, const void* s, size_t n, uint64_t* out, void* st) { MsmAuxApi<G_761>::note_big_call(); return MsmApi<G_761>::dev(b, inf, s, n, 0, out, st); }
+int msm_batch_bls12_377_g1(const uint64_t* b, const uint8_t* inf, const uint64_t* s, const uint32_t* off, size_t m, uint64_t* out) { return MsmAuxApi<G1_377>::batch_host(b, inf, s, off, m, 0, out); }
+int msm_batch_bls12_377_g2(const uint64_t* b, const uint8_t* inf, const uint64_t* s, const uint32_t* off, size_t m, uint64_t* out) { return MsmAuxApi<G2_377>::batch_host(b, inf, s, off, m, 0, out); }
+int msm_batch_bls12_377_g2_subgroup(const uint64_t* b, const uint8_t* inf, const uint64_t* s, const uint32_t* off, size_t m, uint64_t* out) { return MsmAuxApi<G2_377>::batch_host(b, inf, s, off, m, 1, out); }
+int msm_batch_bw6_761_g1(const uint64_t* b, const uint8_t* inf, const uint64_t* s, const uint32_t* off, size_t m, uint64_t* out) { return MsmAuxApi<G_761>::batch_host(b, inf, s, off, m, 0, out); }
+int msm_batch_bw6_761_g2(const uint64_t* b, const uint8_t* inf, const uint64_t* s, const uint32_t* off, size_t m, uint64_t* out) { return MsmAuxApi<G_761>::batch_host(b, inf, s, off, m, 0, out); }
 // Single-product checks from concurrent host threads are COMBINED: bls-snark-sys is synchronous and re-entrant and its callers
 // verify from many threads ("Threading"); one product keeps one lane group of the GPU busy for ~11 ms, so
 // serialising callers behind a mutex would cap the library at ~90 verifications/s.  The first caller to arrive becomes the
@@ -352,49 +294,49 @@ int batch_verify_bls12_377_dev(const void* d_pk_xy, const void* d_pk_inf, const 
 int celo_amd_draw_batch_exponents(const uint32_t key[8], const uint32_t* offsets, size_t m, uint64_t* out) { return draw_exponents_run(key, offsets, m, out); }
 int celo_amd_pairing_last_timings(float ms[4]) { return pairing_timings_377(ms); }
 int ntt_bw6_761_fr(uint64_t* data, unsigned log_n, const uint64_t omega[6], const uint64_t* coset, int coset_after, const uint64_t* scale) {
-  return ntt_run(data, log_n, omega, coset, coset_after, scale, 0, nullptr);
+  return ntt_run<Fr761>(data, log_n, omega, coset, coset_after, scale, 0, nullptr);
 }
 int ntt_bw6_761_fr_dev(uint64_t* d_data, unsigned log_n, const uint64_t omega[6], const uint64_t* coset, int coset_after, const uint64_t* scale,
                        void* hip_stream) {
-  return ntt_run(d_data, log_n, omega, coset, coset_after, scale, 1, hip_stream);
+  return ntt_run<Fr761>(d_data, log_n, omega, coset, coset_after, scale, 1, hip_stream);
 }
 int celo_amd_ntt_last_timings(float ms[4], int* passes) { return ntt_timings(ms, passes); }
 int groth16_witness_map_bw6_761(uint64_t* a, uint64_t* b, uint64_t* c, unsigned log_n, const uint64_t omega[6], const uint64_t omega_inv[6], const uint64_t coset[6],
                                 const uint64_t coset_inv[6], const uint64_t size_inv[6], const uint64_t vanishing_inv[6], int out_canonical) {
-  return witness_map_run(a, b, c, log_n, omega, omega_inv, coset, coset_inv, size_inv, vanishing_inv, out_canonical, 0, nullptr);
+  return witness_map_run<Fr761>(a, b, c, log_n, omega, omega_inv, coset, coset_inv, size_inv, vanishing_inv, out_canonical, 0, nullptr);
 }
 int groth16_witness_map_bw6_761_dev(uint64_t* d_a, uint64_t* d_b, uint64_t* d_c, unsigned log_n, const uint64_t omega[6], const uint64_t omega_inv[6],
                                     const uint64_t coset[6], const uint64_t coset_inv[6], const uint64_t size_inv[6], const uint64_t vanishing_inv[6],
                                     int out_canonical, void* hip_stream) {
-  return witness_map_run(d_a, d_b, d_c, log_n, omega, omega_inv, coset, coset_inv, size_inv, vanishing_inv, out_canonical, 1, hip_stream);
+  return witness_map_run<Fr761>(d_a, d_b, d_c, log_n, omega, omega_inv, coset, coset_inv, size_inv, vanishing_inv, out_canonical, 1, hip_stream);
 }
 int groth16_prove_bw6_761(const uint64_t* a_query, size_t na, const uint64_t* b_g2_query, size_t nb, const uint64_t* h_query, size_t nh, const uint64_t* l_query,
                           size_t nl, const uint64_t alpha_g1[24], const uint64_t beta_g2[24], const uint64_t* assignment, size_t n_assignment, size_t n_aux,
                           const uint64_t* h, size_t n_h, uint64_t out_a[36], uint64_t out_b[36], uint64_t out_c[36]) {
-  msm_note_big_call_761();
+  MsmAuxApi<G_761>::note_big_call();
   return groth16_prove_761_run(a_query, na, b_g2_query, nb, h_query, nh, l_query, nl, alpha_g1, beta_g2, assignment, n_assignment, n_aux, h, n_h, out_a, out_b, out_c);
 }
 int ntt_bls12_377_fr(uint64_t* data, unsigned log_n, const uint64_t omega[4], const uint64_t* coset, int coset_after, const uint64_t* scale) {
-  return ntt_run_253(data, log_n, omega, coset, coset_after, scale, 0, nullptr);
+  return ntt_run<Fr377>(data, log_n, omega, coset, coset_after, scale, 0, nullptr);
 }
 int ntt_bls12_377_fr_dev(uint64_t* d_data, unsigned log_n, const uint64_t omega[4], const uint64_t* coset, int coset_after, const uint64_t* scale,
                          void* hip_stream) {
-  return ntt_run_253(d_data, log_n, omega, coset, coset_after, scale, 1, hip_stream);
+  return ntt_run<Fr377>(d_data, log_n, omega, coset, coset_after, scale, 1, hip_stream);
 }
 int groth16_witness_map_bls12_377(uint64_t* a, uint64_t* b, uint64_t* c, unsigned log_n, const uint64_t omega[4], const uint64_t omega_inv[4], const uint64_t coset[4],
                                   const uint64_t coset_inv[4], const uint64_t size_inv[4], const uint64_t vanishing_inv[4], int out_canonical) {
-  return witness_map_253_run(a, b, c, log_n, omega, omega_inv, coset, coset_inv, size_inv, vanishing_inv, out_canonical, 0, nullptr);
+  return witness_map_run<Fr377>(a, b, c, log_n, omega, omega_inv, coset, coset_inv, size_inv, vanishing_inv, out_canonical, 0, nullptr);
 }
 int groth16_witness_map_bls12_377_dev(uint64_t* d_a, uint64_t* d_b, uint64_t* d_c, unsigned log_n, const uint64_t omega[4], const uint64_t omega_inv[4],
                                       const uint64_t coset[4], const uint64_t coset_inv[4], const uint64_t size_inv[4], const uint64_t vanishing_inv[4],
                                       int out_canonical, void* hip_stream) {
-  return witness_map_253_run(d_a, d_b, d_c, log_n, omega, omega_inv, coset, coset_inv, size_inv, vanishing_inv, out_canonical, 1, hip_stream);
+  return witness_map_run<Fr377>(d_a, d_b, d_c, log_n, omega, omega_inv, coset, coset_inv, size_inv, vanishing_inv, out_canonical, 1, hip_stream);
 }
 int groth16_prove_bls12_377(const uint64_t* a_query, size_t na, const uint64_t* b_g2_query, size_t nb, const uint64_t* h_query, size_t nh, const uint64_t* l_query,
                             size_t nl, const uint64_t alpha_g1[12], const uint64_t beta_g2[24], const uint64_t* assignment, size_t n_assignment, size_t n_aux,
                             const uint64_t* h, size_t n_h, uint64_t out_a[18], uint64_t out_b[36], uint64_t out_c[18]) {
-  msm_note_big_call_g1_377();
-  msm_note_big_call_g2_377();
+  MsmAuxApi<G1_377>::note_big_call();
+  MsmAuxApi<G2_377>::note_big_call();
   return groth16_prove_377_run(a_query, na, b_g2_query, nb, h_query, nh, l_query, nl, alpha_g1, beta_g2, assignment, n_assignment, n_aux, h, n_h, out_a, out_b, out_c);
 }
 int decompress_bls12_377_g1(const uint8_t* in, size_t n, int check_subgroup, uint64_t* out_xy, uint8_t* status) {
@@ -537,20 +479,10 @@ int groth16_setup_r1cs_bls12_377(const void* r1cs, unsigned log_n, const uint64_
 int celo_amd_r1cs_last_timings(float ms[8]) { if (!ms) return 2; r1cs_last_timings(ms); return 0; }
 int celo_amd_decompress_last_ms(float* ms) { if (!ms) return 2; *ms = wire_last_ms(); return 0; }
 int celo_amd_msm_last_timings(int group, float ms[5], int cfg[3]) {
-  switch (group) {
-    case 0: return msm_timings_g1_377(ms, cfg);
-    case 1: return msm_timings_g2_377(ms, cfg);
-    case 2: return msm_timings_761(ms, cfg);
-    default: return 1;
-  }
+  return by_group(group, 1, [&](auto g) { return MsmAuxApi<typename decltype(g)::type>::timings(ms, cfg); });
 }
 int celo_amd_selftest_accumulate(int group, const uint64_t* gen_xy, uint32_t runs, uint32_t len, uint32_t seed, uint32_t check, int chunked, uint32_t* differ) {
-  switch (group) {
-    case 0: return selftest_accumulate_g1_377(gen_xy, runs, len, seed, check, chunked, differ);
-    case 1: return selftest_accumulate_g2_377(gen_xy, runs, len, seed, check, chunked, differ);
-    case 2: return selftest_accumulate_761(gen_xy, runs, len, seed, check, chunked, differ);
-    default: return 2;
-  }
+  return by_group(group, 2, [&](auto g) { return MsmApi<typename decltype(g)::type>::selftest_accumulate(gen_xy, runs, len, seed, check, chunked, differ); });
 }
 int celo_amd_ubench_fp(float out[9]) {
   if (!out) return 2;
@@ -572,23 +504,18 @@ int celo_amd_msm_host_chunk_plan(uint64_t n, int chunks, int head_split, int tai
 }
 int celo_amd_msm_set_window_bits(int group, int c) {
   if (c != 0 && (c < 4 || c > 16)) return 1;
-  switch (group) {
-    case 0: return msm_set_c_g1_377(c);
-    case 1: return msm_set_c_g2_377(c);
-    case 2: return msm_set_c_761(c);
-    default: return 1;
-  }
+  return by_group(group, 1, [&](auto g) { return MsmAuxApi<typename decltype(g)::type>::set_c(c); });
 }
-int celo_amd_sum_jacobian_bls12_377_g1(const uint64_t* j, size_t k, uint64_t* out) { return sum_jac_g1_377(j, k, out); }
-int celo_amd_sum_jacobian_bls12_377_g2(const uint64_t* j, size_t k, uint64_t* out) { return sum_jac_g2_377(j, k, out); }
-int celo_amd_sum_jacobian_bw6_761(const uint64_t* j, size_t k, uint64_t* out) { return sum_jac_761(j, k, out); }
-int celo_amd_gen_points_bls12_377_g1_dev(void* d, size_t n, uint64_t seed, const uint64_t* g, void* st) { return gen_points_g1_377(d, n, seed, g, 1, 0, st); }
-int celo_amd_gen_points_bls12_377_g2_dev(void* d, size_t n, uint64_t seed, const uint64_t* g, void* st) { return gen_points_g2_377(d, n, seed, g, 1, 0, st); }
-int celo_amd_gen_points_bw6_761_dev(void* d, size_t n, uint64_t seed, const uint64_t* g, void* st) { return gen_points_761(d, n, seed, g, 1, 0, st); }
+int celo_amd_sum_jacobian_bls12_377_g1(const uint64_t* j, size_t k, uint64_t* out) { return MsmAuxApi<G1_377>::sum_jac(j, k, out); }
+int celo_amd_sum_jacobian_bls12_377_g2(const uint64_t* j, size_t k, uint64_t* out) { return MsmAuxApi<G2_377>::sum_jac(j, k, out); }
+int celo_amd_sum_jacobian_bw6_761(const uint64_t* j, size_t k, uint64_t* out) { return MsmAuxApi<G_761>::sum_jac(j, k, out); }
+int celo_amd_gen_points_bls12_377_g1_dev(void* d, size_t n, uint64_t seed, const uint64_t* g, void* st) { return MsmAuxApi<G1_377>::gen_points(d, n, seed, g, 1, 0, st); }
+int celo_amd_gen_points_bls12_377_g2_dev(void* d, size_t n, uint64_t seed, const uint64_t* g, void* st) { return MsmAuxApi<G2_377>::gen_points(d, n, seed, g, 1, 0, st); }
+int celo_amd_gen_points_bw6_761_dev(void* d, size_t n, uint64_t seed, const uint64_t* g, void* st) { return MsmAuxApi<G_761>::gen_points(d, n, seed, g, 1, 0, st); }
 int celo_amd_gen_points_grouped_bls12_377_g1_dev(void* d, size_t n, uint64_t seed, const uint64_t* gens, size_t ngens, uint32_t per, void* st) {
-  return gen_points_g1_377(d, n, seed, gens, ngens, per, st);
+  return MsmAuxApi<G1_377>::gen_points(d, n, seed, gens, ngens, per, st);
 }
 int celo_amd_gen_points_grouped_bls12_377_g2_dev(void* d, size_t n, uint64_t seed, const uint64_t* gens, size_t ngens, uint32_t per, void* st) {
-  return gen_points_g2_377(d, n, seed, gens, ngens, per, st);
+  return MsmAuxApi<G2_377>::gen_points(d, n, seed, gens, ngens, per, st);
 }
 }

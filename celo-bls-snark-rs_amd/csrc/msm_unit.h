@@ -2,6 +2,7 @@
 #pragma once
 #include "msm.h"
 #include "runtime.h"
+#include "units.h"
 #include <mutex>
 #include <thread>
 #include <atomic>
@@ -303,148 +304,147 @@ int selftest_accumulate_impl(const uint64_t* gen_xy, uint32_t runs, uint32_t len
   *differ = bad;
   return 0;
 }
+// ---- MsmApi<G> / MsmAuxApi<G> (units.h): the large-MSM engine and the auxiliary entry points (batched MSMs, generators, host sums) of a group
+// are instantiated in two translation units, unit_<group>.hip and unit_<group>_aux.hip, which compile in parallel (the 28-limb instantiations
+// are the long pole of the build).  Each half has an engine pool, a "last call" record and a window override of its own.
+template <class G> struct MsmUnit {
+  static EnginePool<MsmEngine<G>>& pool() { static auto* p = new EnginePool<MsmEngine<G>>(); return *p; }
+  static MsmLast& last() { static auto* p = new MsmLast(); return *p; }
+  static std::atomic<int>& force_c() { static std::atomic<int> v{0}; return v; }
+};
+template <class G> int MsmApi<G>::host(const uint64_t* b, const uint8_t* inf, const uint64_t* s, size_t n, int flags, uint64_t* out) {
+  if (int rc = api_enter()) return rc;
+  auto e = MsmUnit<G>::pool().lease();
+  e->force_c = MsmUnit<G>::force_c().load();
+  e->big_subgroup_points = (flags & 1) != 0;
+  e->ark_zero_identity = (flags & 2) != 0;
+  const int rc = e->run_host(b, inf, s, n, out, e->own_stream());
+  e->ark_zero_identity = false;
+  if (!rc && n) MsmUnit<G>::last().note(*e);
+  return rc;
+}
+template <class G> int MsmApi<G>::dev(const void* b, const void* inf, const void* s, size_t n, int subgroup, uint64_t* out, void* st) {
+  if (int rc = api_enter()) return rc;
+  auto e = MsmUnit<G>::pool().lease();
+  e->force_c = MsmUnit<G>::force_c().load();
+  e->big_subgroup_points = subgroup != 0;
+  const int rc = e->run_device((const uint64_t*)b, (const uint8_t*)inf, (const uint32_t*)s, n, out, (hipStream_t)st);
+  if (!rc && n) MsmUnit<G>::last().note(*e);
+  return rc;
+}
+template <class G> int MsmApi<G>::multi_host(const int* devs, int nd, const uint64_t* b, const uint8_t* inf, const uint64_t* s, size_t n, uint64_t* out) {
+  return msm_multi_host_impl<G>(MsmUnit<G>::pool(), MsmUnit<G>::force_c().load(), devs, nd, b, inf, s, n, out, &MsmUnit<G>::last());
+}
+template <class G>
+int MsmApi<G>::multi_dev(const int* devs, int nd, const void* const* b, const void* const* inf, const void* const* s, const size_t* n_per, uint64_t* out) {
+  return msm_multi_impl<G>(MsmUnit<G>::pool(), MsmUnit<G>::force_c().load(), devs, nd, 1, b, inf, s, n_per, out, &MsmUnit<G>::last());
+}
+template <class G>
+int MsmApi<G>::multi_windows(const int* devs, int nd, int resident, const void* const* b, const void* const* inf, const void* const* s, size_t n, int subgroup,
+                             uint64_t* out) {
+  return msm_multi_windows_impl<G>(MsmUnit<G>::pool(), MsmUnit<G>::force_c().load(), devs, nd, resident, b, inf, s, n, subgroup, out, &MsmUnit<G>::last());
+}
+template <class G>
+int MsmApi<G>::window_shard(const void* b, const void* inf, const void* s, size_t n, int subgroup, int shard, int nshards, uint64_t* out_xyzz, int* bit_lo, void* st) {
+  return msm_window_shard_impl<G>(MsmUnit<G>::pool(), MsmUnit<G>::force_c().load(), b, inf, s, n, subgroup, shard, nshards, out_xyzz, bit_lo, st, &MsmUnit<G>::last());
+}
+template <class G> int MsmApi<G>::join_windows(const uint64_t* xyzz, const int* bit_lo, int nshards, uint64_t* out) {
+  return join_windows_impl<G>(xyzz, bit_lo, nshards, out);
+}
+// fixed-base form: per-key tables (msm.h FixedTable).  resident = 1: DEVICE pointers
+template <class G> int MsmApi<G>::fixed_build(const void* b, const void* inf, size_t n, int resident, int cf, FixedTable** out) {
+  if (int rc = api_enter()) return rc;
+  if (!b || !out || n == 0) return 2;
+  typedef PointIO<typename G::F> IO;
+  auto e = MsmUnit<G>::pool().lease();           // an engine's stream; the table itself belongs to the handle
+  void *db = nullptr, *di = nullptr;
+  int rc = 0;
+  if (!resident) {
+    if (hipMalloc(&db, n * 2 * IO::ARK64 * 8) != hipSuccess) return 1;
+    if (hipMemcpyAsync(db, b, n * 2 * IO::ARK64 * 8, hipMemcpyHostToDevice, e->own_stream()) != hipSuccess) rc = 1;
+    if (!rc && inf) {
+      if (hipMalloc(&di, n) != hipSuccess || hipMemcpyAsync(di, inf, n, hipMemcpyHostToDevice, e->own_stream()) != hipSuccess) rc = 1;
+    }
+  }
+  FixedTable* T = new FixedTable();
+  if (!rc) rc = MsmEngine<G>::fixed_build((const uint64_t*)(resident ? b : db), (const uint8_t*)(resident ? inf : di), n, cf, T, e->own_stream());
+  if (db) (void)hipFree(db);
+  if (di) (void)hipFree(di);
+  if (rc) { if (T->table) (void)hipFree(T->table); if (T->tinf) (void)hipFree(T->tinf); delete T; return rc; }
+  *out = T;
+  return 0;
+}
+template <class G> int MsmApi<G>::fixed_run(const FixedTable* T, const void* s, size_t n_sc, int resident, uint64_t* out, void* st) {
+  if (int rc = api_enter()) return rc;
+  if (!T || !T->table || (!s && n_sc) || !out) return 2;
+  if (T->device != api_device()) return 101;        // the table lives on the device it was built on
+  auto e = MsmUnit<G>::pool().lease();
+  e->force_c = 0;
+  e->big_subgroup_points = false;
+  const int rc = e->run_fixed(*T, s, n_sc, resident, out, resident && st ? (hipStream_t)st : e->own_stream());
+  if (!rc && n_sc) MsmUnit<G>::last().note(*e);
+  return rc;
+}
+template <class G>
+int MsmApi<G>::selftest_accumulate(const uint64_t* gen_xy, uint32_t runs, uint32_t len, uint32_t seed, uint32_t check, int chunked, uint32_t* differ) {
+  return selftest_accumulate_impl<G>(gen_xy, runs, len, seed, check, chunked, differ);
+}
+template <class G> void MsmApi<G>::big_timings(float ms[5], int cfg[3]) { MsmUnit<G>::last().read(ms, cfg); }
+template <class G> void MsmApi<G>::big_set_c(int c) { MsmUnit<G>::force_c().store(c); }
+
+template <class G> struct MsmAuxUnit {
+  static EnginePool<MsmEngine<G>>& pool() { static auto* p = new EnginePool<MsmEngine<G>>(); return *p; }
+  static MsmLast& last() { static auto* p = new MsmLast(); return *p; }
+  static std::atomic<int>& force_c() { static std::atomic<int> v{0}; return v; }
+  static std::atomic<int>& last_was_batch() { static std::atomic<int> v{0}; return v; }
+};
+template <class G>
+int MsmAuxApi<G>::batch_host(const uint64_t* b, const uint8_t* inf, const uint64_t* s, const uint32_t* off, size_t m, int subgroup_points, uint64_t* out) {
+  if (int rc = api_enter()) return rc;
+  auto e = MsmAuxUnit<G>::pool().lease();
+  e->force_c = MsmAuxUnit<G>::force_c().load();
+  e->gls_subgroup_points = subgroup_points != 0;    // 0: arbitrary curve points, VariableBaseMSM semantics, no endomorphism
+  MsmAuxUnit<G>::last_was_batch().store(1);
+  const int rc = e->run_batch_host(b, inf, s, off, m, out, e->own_stream());
+  if (!rc && m) MsmAuxUnit<G>::last().note(*e);
+  return rc;
+}
+template <class G>
+int MsmAuxApi<G>::batch_begin(const void* b, const void* inf, const void* s, int resident, const uint32_t* off, size_t m, int subgroup_points, BatchRun* run) {
+  if (int rc = api_enter()) return rc;
+  typedef typename EnginePool<MsmEngine<G>>::Lease L;
+  L* l = new L(MsmAuxUnit<G>::pool().lease());
+  (*l)->force_c = MsmAuxUnit<G>::force_c().load();
+  (*l)->gls_subgroup_points = subgroup_points != 0;
+  (*l)->bits_hint = run->bits > 0 ? run->bits : 0;
+  uint64_t* d_out = nullptr;
+  const int rc = (*l)->run_batch((const uint64_t*)b, (const uint8_t*)inf, (const uint64_t*)s, resident, off, m, nullptr, &d_out, (*l)->own_stream());
+  (*l)->bits_hint = 0;
+  if (rc) { delete l; return rc; }
+  run->lease = l; run->d_out = d_out; run->stream = (*l)->own_stream(); run->bits = (*l)->measured_bits;
+  return 0;
+}
+template <class G> void MsmAuxApi<G>::batch_end(BatchRun* run, int drained) {
+  typedef typename EnginePool<MsmEngine<G>>::Lease L;
+  L* l = (L*)run->lease;
+  if (!l) return;
+  if (drained) { (*l)->collect_batch_timings(); MsmAuxUnit<G>::last_was_batch().store(1); MsmAuxUnit<G>::last().note(**l); }
+  delete l;
+  run->lease = nullptr;
+}
+template <class G> int MsmAuxApi<G>::timings(float ms[5], int cfg[3]) {
+  if (MsmAuxUnit<G>::last_was_batch().load()) MsmAuxUnit<G>::last().read(ms, cfg);
+  else MsmApi<G>::big_timings(ms, cfg);
+  return 0;
+}
+template <class G> void MsmAuxApi<G>::note_big_call() { MsmAuxUnit<G>::last_was_batch().store(0); }
+template <class G> int MsmAuxApi<G>::set_c(int c) {
+  MsmAuxUnit<G>::force_c().store(c);
+  MsmApi<G>::big_set_c(c);
+  return 0;
+}
+template <class G> int MsmAuxApi<G>::gen_points(void* d_out, size_t n, uint64_t seed, const uint64_t* gen_xy, size_t ngens, uint32_t per, void* st) {
+  return gen_points_impl<typename G::F>(d_out, n, seed, gen_xy, ngens, per, st);
+}
+template <class G> int MsmAuxApi<G>::sum_jac(const uint64_t* jac, size_t k, uint64_t* out) { return sum_jacobian_impl<typename G::F>(jac, k, out); }
 }  // namespace celo
-
-// The large-MSM engine and the auxiliary entry points (batched MSMs, generators, host sums) are separate macros so that
-// each group compiles as two translation units in parallel (the 28-limb instantiations are the long pole of the build).
-#define CELO_DEFINE_MSM_UNIT(G, TAG)                                                                                     \
-  namespace celo {                                                                                                       \
-  static EnginePool<MsmEngine<G>>& pool_##TAG() { static auto* p = new EnginePool<MsmEngine<G>>(); return *p; }          \
-  static MsmLast& last_##TAG() { static auto* p = new MsmLast(); return *p; }                                            \
-  static std::atomic<int> force_c_##TAG{0};                                                                              \
-  /* flags: bit 0 = bases vouched to lie in the prime-order subgroup, bit 1 = rows (0, 1) are the identity (the prover's queries) */ \
-  int msm_host_##TAG(const uint64_t* b, const uint8_t* inf, const uint64_t* s, size_t n, int flags, uint64_t* out) {     \
-    if (int rc = api_enter()) return rc;                                                                                 \
-    auto e = pool_##TAG().lease();                                                                                       \
-    e->force_c = force_c_##TAG.load();                                                                                   \
-    e->big_subgroup_points = (flags & 1) != 0;                                                                           \
-    e->ark_zero_identity = (flags & 2) != 0;                                                                             \
-    const int rc = e->run_host(b, inf, s, n, out, e->own_stream());                                                      \
-    e->ark_zero_identity = false;                                                                                        \
-    if (!rc && n) last_##TAG().note(*e);                                                                                 \
-    return rc;                                                                                                           \
-  }                                                                                                                      \
-  int msm_dev_##TAG(const void* b, const void* inf, const void* s, size_t n, int subgroup, uint64_t* out, void* st) {    \
-    if (int rc = api_enter()) return rc;                                                                                 \
-    auto e = pool_##TAG().lease();                                                                                       \
-    e->force_c = force_c_##TAG.load();                                                                                   \
-    e->big_subgroup_points = subgroup != 0;                                                                              \
-    const int rc = e->run_device((const uint64_t*)b, (const uint8_t*)inf, (const uint32_t*)s, n, out, (hipStream_t)st);  \
-    if (!rc && n) last_##TAG().note(*e);                                                                                 \
-    return rc;                                                                                                           \
-  }                                                                                                                      \
-  int msm_multi_host_##TAG(const int* devs, int nd, const uint64_t* b, const uint8_t* inf, const uint64_t* s, size_t n, uint64_t* out) { \
-    return msm_multi_host_impl<G>(pool_##TAG(), force_c_##TAG.load(), devs, nd, b, inf, s, n, out, &last_##TAG());       \
-  }                                                                                                                      \
-  int msm_multi_dev_##TAG(const int* devs, int nd, const void* const* b, const void* const* inf, const void* const* s,   \
-                          const size_t* n_per, uint64_t* out) {                                                          \
-    return msm_multi_impl<G>(pool_##TAG(), force_c_##TAG.load(), devs, nd, 1, b, inf, s, n_per, out, &last_##TAG());     \
-  }                                                                                                                      \
-  int msm_multi_windows_##TAG(const int* devs, int nd, int resident, const void* const* b, const void* const* inf, const void* const* s, \
-                              size_t n, int subgroup, uint64_t* out) {                                                   \
-    return msm_multi_windows_impl<G>(pool_##TAG(), force_c_##TAG.load(), devs, nd, resident, b, inf, s, n, subgroup, out, &last_##TAG()); \
-  }                                                                                                                      \
-  int msm_window_shard_##TAG(const void* b, const void* inf, const void* s, size_t n, int subgroup, int shard, int nshards, \
-                             uint64_t* out_xyzz, int* bit_lo, void* st) {                                                \
-    return msm_window_shard_impl<G>(pool_##TAG(), force_c_##TAG.load(), b, inf, s, n, subgroup, shard, nshards, out_xyzz, bit_lo, st, &last_##TAG()); \
-  }                                                                                                                      \
-  int msm_join_windows_##TAG(const uint64_t* xyzz, const int* bit_lo, int nshards, uint64_t* out) {                      \
-    return join_windows_impl<G>(xyzz, bit_lo, nshards, out);                                                             \
-  }                                                                                                                      \
-  /* fixed-base form: per-key tables (msm.h FixedTable).  resident = 1: DEVICE pointers */                               \
-  int msm_fixed_build_##TAG(const void* b, const void* inf, size_t n, int resident, int cf, FixedTable** out) {          \
-    if (int rc = api_enter()) return rc;                                                                                 \
-    if (!b || !out || n == 0) return 2;                                                                                  \
-    typedef PointIO<G::F> IO_;                                                                                           \
-    auto e = pool_##TAG().lease();           /* an engine's stream; the table itself belongs to the handle */            \
-    void *db = nullptr, *di = nullptr;                                                                                   \
-    int rc = 0;                                                                                                          \
-    if (!resident) {                                                                                                     \
-      if (hipMalloc(&db, n * 2 * IO_::ARK64 * 8) != hipSuccess) return 1;                                                \
-      if (hipMemcpyAsync(db, b, n * 2 * IO_::ARK64 * 8, hipMemcpyHostToDevice, e->own_stream()) != hipSuccess) rc = 1;   \
-      if (!rc && inf) {                                                                                                  \
-        if (hipMalloc(&di, n) != hipSuccess || hipMemcpyAsync(di, inf, n, hipMemcpyHostToDevice, e->own_stream()) != hipSuccess) rc = 1; \
-      }                                                                                                                  \
-    }                                                                                                                    \
-    FixedTable* T = new FixedTable();                                                                                    \
-    if (!rc) rc = MsmEngine<G>::fixed_build((const uint64_t*)(resident ? b : db), (const uint8_t*)(resident ? inf : di), n, cf, T, e->own_stream()); \
-    if (db) (void)hipFree(db);                                                                                           \
-    if (di) (void)hipFree(di);                                                                                           \
-    if (rc) { if (T->table) (void)hipFree(T->table); if (T->tinf) (void)hipFree(T->tinf); delete T; return rc; }         \
-    *out = T;                                                                                                            \
-    return 0;                                                                                                            \
-  }                                                                                                                      \
-  int msm_fixed_run_##TAG(const FixedTable* T, const void* s, size_t n_sc, int resident, uint64_t* out, void* st) {      \
-    if (int rc = api_enter()) return rc;                                                                                 \
-    if (!T || !T->table || (!s && n_sc) || !out) return 2;                                                               \
-    if (T->device != api_device()) return 101;        /* the table lives on the device it was built on */                \
-    auto e = pool_##TAG().lease();                                                                                       \
-    e->force_c = 0;                                                                                                      \
-    e->big_subgroup_points = false;                                                                                      \
-    const int rc = e->run_fixed(*T, s, n_sc, resident, out, resident && st ? (hipStream_t)st : e->own_stream());         \
-    if (!rc && n_sc) last_##TAG().note(*e);                                                                              \
-    return rc;                                                                                                           \
-  }                                                                                                                      \
-  int selftest_accumulate_##TAG(const uint64_t* g, uint32_t runs, uint32_t len, uint32_t seed, uint32_t check, int chunked, uint32_t* differ) { \
-    return selftest_accumulate_impl<G>(g, runs, len, seed, check, chunked, differ);                                      \
-  }                                                                                                                      \
-  void msm_big_timings_##TAG(float ms[5], int cfg[3]) { last_##TAG().read(ms, cfg); }                                    \
-  void msm_big_set_c_##TAG(int c) { force_c_##TAG.store(c); }                                                            \
-  }
-
-#define CELO_DEFINE_MSM_AUX_UNIT(G, TAG)                                                                                 \
-  namespace celo {                                                                                                       \
-  static EnginePool<MsmEngine<G>>& pool_aux_##TAG() { static auto* p = new EnginePool<MsmEngine<G>>(); return *p; }      \
-  static MsmLast& last_aux_##TAG() { static auto* p = new MsmLast(); return *p; }                                        \
-  static std::atomic<int> force_c_aux_##TAG{0};                                                                          \
-  static std::atomic<int> last_was_batch_##TAG{0};                                                                       \
-  void msm_big_timings_##TAG(float ms[5], int cfg[3]);                                                                   \
-  void msm_big_set_c_##TAG(int c);                                                                                       \
-  int msm_batch_host_##TAG(const uint64_t* b, const uint8_t* inf, const uint64_t* s, const uint32_t* off, size_t m, int subgroup_points, uint64_t* out) { \
-    if (int rc = api_enter()) return rc;                                                                                 \
-    auto e = pool_aux_##TAG().lease();                                                                                   \
-    e->force_c = force_c_aux_##TAG.load();                                                                               \
-    e->gls_subgroup_points = subgroup_points != 0;    /* 0: arbitrary curve points, VariableBaseMSM semantics, no endomorphism */ \
-    last_was_batch_##TAG.store(1);                                                                                       \
-    const int rc = e->run_batch_host(b, inf, s, off, m, out, e->own_stream());                                           \
-    if (!rc && m) last_aux_##TAG().note(*e);                                                                             \
-    return rc;                                                                                                           \
-  }                                                                                                                      \
-  int msm_batch_begin_##TAG(const void* b, const void* inf, const void* s, int resident, const uint32_t* off, size_t m, int subgroup_points, BatchRun* run) { \
-    if (int rc = api_enter()) return rc;                                                                                 \
-    typedef EnginePool<MsmEngine<G>>::Lease L;                                                                           \
-    L* l = new L(pool_aux_##TAG().lease());                                                                              \
-    (*l)->force_c = force_c_aux_##TAG.load();                                                                            \
-    (*l)->gls_subgroup_points = subgroup_points != 0;                                                                    \
-    (*l)->bits_hint = run->bits > 0 ? run->bits : 0;                                                                     \
-    uint64_t* d_out = nullptr;                                                                                           \
-    const int rc = (*l)->run_batch((const uint64_t*)b, (const uint8_t*)inf, (const uint64_t*)s, resident, off, m, nullptr, &d_out, (*l)->own_stream()); \
-    (*l)->bits_hint = 0;                                                                                                 \
-    if (rc) { delete l; return rc; }                                                                                     \
-    run->lease = l; run->d_out = d_out; run->stream = (*l)->own_stream(); run->bits = (*l)->measured_bits;               \
-    return 0;                                                                                                            \
-  }                                                                                                                      \
-  void msm_batch_end_##TAG(BatchRun* run, int drained) {                                                                 \
-    typedef EnginePool<MsmEngine<G>>::Lease L;                                                                           \
-    L* l = (L*)run->lease;                                                                                               \
-    if (!l) return;                                                                                                      \
-    if (drained) { (*l)->collect_batch_timings(); last_was_batch_##TAG.store(1); last_aux_##TAG().note(**l); }           \
-    delete l;                                                                                                            \
-    run->lease = nullptr;                                                                                                \
-  }                                                                                                                      \
-  int msm_timings_##TAG(float ms[5], int cfg[3]) {                                                                       \
-    if (last_was_batch_##TAG.load()) last_aux_##TAG().read(ms, cfg);                                                     \
-    else msm_big_timings_##TAG(ms, cfg);                                                                                 \
-    return 0;                                                                                                            \
-  }                                                                                                                      \
-  void msm_note_big_call_##TAG() { last_was_batch_##TAG.store(0); }                                                      \
-  int msm_set_c_##TAG(int c) {                                                                                           \
-    force_c_aux_##TAG.store(c);                                                                                          \
-    msm_big_set_c_##TAG(c);                                                                                              \
-    return 0;                                                                                                            \
-  }                                                                                                                      \
-  int gen_points_##TAG(void* d, size_t n, uint64_t seed, const uint64_t* g, size_t ngens, uint32_t per, void* st) {      \
-    return gen_points_impl<G::F>(d, n, seed, g, ngens, per, st);                                                         \
-  }                                                                                                                      \
-  int sum_jac_##TAG(const uint64_t* jac, size_t k, uint64_t* out) { return sum_jacobian_impl<G::F>(jac, k, out); }       \
-  }

@@ -38,6 +38,7 @@
 #include "pedersen.h"
 #include "host64.h"
 #include "runtime.h"
+#include "units.h"
 #include "../../include/celo_bls_amd.h"
 #include "../../include/celo_bls_snark_sys.h"
 
@@ -789,13 +790,6 @@ void neg_g2_generator(uint64_t out_xy[24]) {
 }  // namespace
 
 namespace celo {
-struct BvJob { BatchRun keys, sigs; };      // unit_batchverify.hip: the chained Batch::verify in three steps
-int bv_begin_keys(BvJob*, const void*, const void*, const void*, int, const uint32_t*, size_t);
-int bv_begin_sigs(BvJob*, const void*, const void*, const void*, int, const uint32_t*, size_t);
-int bv_finish(BvJob*, int, const void*, const void*, int, const uint64_t*, size_t, uint8_t*);
-int bv_mirror_scatter(int, const uint64_t*, const uint8_t*, const uint32_t*, uint64_t*, uint8_t*, size_t, hipStream_t);
-int bv_mirror_gather(int, const uint64_t*, const uint8_t*, const uint32_t*, uint64_t*, uint8_t*, size_t, hipStream_t);
-int bv_draw_exponents(const uint32_t*, const uint32_t*, size_t, size_t, uint64_t*, hipStream_t);
 // the composite hasher's generator table for the bulk GPU kernel (unit_hash.hip: k_pedersen_crh)
 const EdPoint* celo_composite_gens(size_t* count) {
   const CompositeParams& cp = composite_params();
@@ -826,7 +820,6 @@ bool generate_private_key(PrivateKey** out_private_key) {
   *out_private_key = sk;
   return true;
 }
-bool celo_amd_g2_generator(uint64_t out_xy[24]);
 bool private_key_to_public_key(const PrivateKey* in_private_key, PublicKey** out_public_key) {
   if (!in_private_key || !out_public_key) return false;
   uint64_t gen[24];

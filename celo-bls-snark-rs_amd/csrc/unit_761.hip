@@ -1,2 +1,2 @@
 #include "msm_unit.h"
-CELO_DEFINE_MSM_UNIT(celo::G_761, 761)
+template struct celo::MsmApi<celo::G_761>;

@@ -9,16 +9,10 @@
 // The reference does this per batch on the CPU: two MSMs, batch_normalization, product_of_pairings == 1.
 #include "msm.h"
 #include "runtime.h"
+#include "units.h"
 #include <thread>
 
 namespace celo {
-int msm_batch_begin_g1_377(const void*, const void*, const void*, int, const uint32_t*, size_t, int, BatchRun*);
-int msm_batch_begin_g2_377(const void*, const void*, const void*, int, const uint32_t*, size_t, int, BatchRun*);
-void msm_batch_end_g1_377(BatchRun*, int);
-void msm_batch_end_g2_377(BatchRun*, int);
-int pairing_stage_377(uint32_t, size_t, PairingStage*);
-int pairing_run_staged_377(PairingStage*, const uint32_t*, size_t, uint8_t*);
-
 struct NegG2 { uint64_t xy[24]; };   // -g2 generator, affine, arkworks Montgomery limbs
 
 // lanes [0, m): G1 half of batch b = lane; lanes [m_pad, m_pad + m): G2 half (m_pad = m rounded up to the wave size, so a wave
@@ -177,17 +171,16 @@ int draw_exponents_run(const uint32_t key[8], const uint32_t* offsets, size_t m,
 //   bv_begin_keys   enqueue the G2 batch MSM        bv_begin_sigs   enqueue the G1 batch MSM        bv_finish   pairs + products
 // resident = 1: DEVICE pointers; 0: host pointers (staged by the engines).  offsets, out_ok: host.  *_inf: optional byte-per-point
 // "is the identity" arrays (host or device like the points).  bv_finish releases everything, also after a failed begin.
-struct BvJob { BatchRun keys, sigs; };
 int bv_begin_keys(BvJob* j, const void* pk_xy, const void* pk_inf, const void* exponents, int resident, const uint32_t* offsets, size_t m) {
   if (int rc = api_enter()) return rc;
   // the keys of Batch::verify are PublicKey values: elements of the prime-order subgroup G2 by construction (checked deserialisation,
   // secret keys, sums) - what lets the batched MSM split their exponents with the endomorphism psi (msm.h, k_gls_expand)
-  return msm_batch_begin_g2_377(pk_xy, pk_inf, exponents, resident, offsets, m, 1, &j->keys);
+  return MsmAuxApi<G2_377>::batch_begin(pk_xy, pk_inf, exponents, resident, offsets, m, 1, &j->keys);
 }
 int bv_begin_sigs(BvJob* j, const void* sig_xy, const void* sig_inf, const void* exponents, int resident, const uint32_t* offsets, size_t m) {
   if (int rc = api_enter()) return rc;
   j->sigs.bits = j->keys.lease ? j->keys.bits : 0;     // the same exponents: the key leg has measured their length already
-  return msm_batch_begin_g1_377(sig_xy, sig_inf, exponents, resident, offsets, m, 0, &j->sigs);
+  return MsmAuxApi<G1_377>::batch_begin(sig_xy, sig_inf, exponents, resident, offsets, m, 0, &j->sigs);
 }
 int bv_finish(BvJob* j, int begun_ok, const void* hash_xy, const void* hash_inf, int resident, const uint64_t neg_g2_xy[24], size_t m, uint8_t* out_ok) {
   BatchRun& r1 = j->sigs;
@@ -227,8 +220,8 @@ done:
     if (r1.stream) (void)hipStreamSynchronize(r1.stream);
     if (r2.stream) (void)hipStreamSynchronize(r2.stream);
   }
-  msm_batch_end_g1_377(&r1, drained ? 1 : 0);
-  msm_batch_end_g2_377(&r2, drained ? 1 : 0);
+  MsmAuxApi<G1_377>::batch_end(&r1, drained ? 1 : 0);
+  MsmAuxApi<G2_377>::batch_end(&r2, drained ? 1 : 0);
   if (e1) (void)hipEventDestroy(e1);
   if (e2) (void)hipEventDestroy(e2);
   if (d_hash) (void)hipFree(d_hash);

@@ -1,5 +1,5 @@
 #include "msm_unit.h"
-CELO_DEFINE_MSM_UNIT(celo::G1_377, g1_377)
+template struct celo::MsmApi<celo::G1_377>;
 
 // group-agnostic ends of a fixed-base handle (msm.h FixedTable; capi.hip celo_amd_msm_fixed_release / _info)
 namespace celo {

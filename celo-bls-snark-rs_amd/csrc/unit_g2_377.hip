@@ -1,2 +1,2 @@
 #include "msm_unit.h"
-CELO_DEFINE_MSM_UNIT(celo::G2_377, g2_377)
+template struct celo::MsmApi<celo::G2_377>;

@@ -9,13 +9,13 @@
 #include <cstdio>
 
 #include "runtime.h"
+#include "units.h"
 // two waves per SIMD (scratch instead of AGPRs for what does not fit 256 VGPRs) unless overridden: -DFROW_OCC= for the A/B
 #ifndef FROW_OCC
 #define FROW_OCC __attribute__((amdgpu_waves_per_eu(2, 2)))
 #endif
 namespace celo {
 static std::mutex hash_mu;                 // bulk calls, serialised per process (each fills the GPU; buffers are per call)
-int wire_consts_device(WireConsts& out);   // unit_wire.hip
 
 struct HashDom { uint8_t b[8]; };
 struct HashIn { const uint8_t* msgs; const uint64_t* msg_off; const uint8_t* extras; const uint64_t* extra_off; };
@@ -77,7 +77,7 @@ k_hash_finish(const uint64_t* __restrict__ cand_xy, const uint8_t* __restrict__ 
   else { redo[i] = 1; for (int j = 0; j < 12; j++) o[j] = 0; }
 }
 
-const EdPoint* celo_composite_gens(size_t* count);   // seam_a.hip: the generator table (built once, ChaCha20 stream of the reference)
+// celo_composite_gens (seam_a.hip): the generator table, built once from the ChaCha20 stream of the reference
 static EdPoint* g_d_gens_dev[MAX_DEVICES] = {};      // its device copies (11.7 MB each), uploaded on first use (under hash_mu)
 #define g_d_gens g_d_gens_dev[api_device()]
 static int ensure_device_gens(const EdPoint* h_gens, size_t ngens) {

@@ -1,5 +1,6 @@
 // Translation unit: BLS12-377 pairing kernels + engine (see pairing.h).
 #include "pairing.h"
+#include "units.h"
 #include <mutex>
 
 namespace celo {

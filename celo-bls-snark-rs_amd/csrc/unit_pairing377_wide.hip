@@ -13,6 +13,7 @@
 //   * k377_wide_final: the product of the partial values, then ark-ec's final exponentiation chain on the side-by-side operations.
 // Exact arithmetic: the same field elements as the throughput path (GT values against the oracle, tests/test_pairing_gpu.py).
 #include "pairing_lanes_kernels.h"
+#include "units.h"
 
 namespace celo {
 namespace {

@@ -1,8 +1,8 @@
 // Translation unit: lane-parallel (six lanes per pairing) BLS12-377 final exponentiation kernel (pairing_lanes.h).
 #include "pairing_lanes_kernels.h"
+#include "units.h"
 namespace celo {
-void final_exp_w3_377(const uint32_t* prod, uint8_t* is_one, uint64_t* gt, uint32_t m, hipStream_t s);   // unit_pairing377_wide.hip
-void final_exp_w2_377(const uint32_t* prod, uint8_t* is_one, uint64_t* gt, uint32_t m, hipStream_t s);
+// final_exp_w3_377 / _w2_377: unit_pairing377_wide.hip
 // up to 3072 products (three per wave: at most one wave per SIMD): every Fq12 operation's independent products side by side - measured
 // 1.47 against 2.17 ms at 2048 products.  Above, SIMDs take a second wave and the side-by-side form's extra instructions cost more than
 // its shorter chains save (4096 products: 2.39 against 2.24 ms; 6144: 2.50 against 2.31): one six-lane group per product from there on

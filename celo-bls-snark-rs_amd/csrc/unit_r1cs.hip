@@ -8,6 +8,7 @@
 #include <mutex>
 #include <vector>
 #include "runtime.h"
+#include "units.h"
 
 namespace celo {
 

@@ -10,17 +10,9 @@
 #include <mutex>
 #include <vector>
 #include "runtime.h"
+#include "units.h"
 
 namespace celo {
-struct ProvingKey;
-int groth16_key_load_dev(int, const uint64_t*, const uint8_t*, size_t, const uint64_t*, const uint8_t*, size_t, const uint64_t*, const uint8_t*, size_t,
-                         const uint64_t*, const uint8_t*, size_t, const uint64_t*, const uint64_t*, const uint64_t*, const uint64_t*, int, ProvingKey**);
-
-struct R1cs;                     // unit_r1cs.hip: constraint matrices on the device
-int r1cs_qap_at_tau(const R1cs*, unsigned, const uint64_t*, const uint64_t*, uint64_t*, uint64_t*, uint64_t*, uint64_t*, int, void*);
-void r1cs_shape(const R1cs*, int*, int*, size_t*, size_t*, size_t*);
-void r1cs_note_ms(int, float);
-
 typedef Fp<P377> FrBw6;          // the scalar field of BW6-761 (the base field of BLS12-377)
 typedef Fp<P253> FrBls;          // the scalar field of BLS12-377
 

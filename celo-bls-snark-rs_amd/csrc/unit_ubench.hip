@@ -11,6 +11,7 @@
 #include <vector>
 #include "fp.h"
 #include "runtime.h"
+#include "units.h"
 
 namespace celo {
 

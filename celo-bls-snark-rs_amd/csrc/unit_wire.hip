@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <mutex>
 #include "runtime.h"
+#include "units.h"
 
 // two waves per SIMD (scratch instead of AGPRs for what does not fit 256 VGPRs) unless overridden: -DFROW_OCC= for the A/B
 #ifndef FROW_OCC

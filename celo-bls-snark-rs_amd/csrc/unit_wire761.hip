@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <mutex>
 #include "runtime.h"
+#include "units.h"
 
 // one wave per SIMD: the square root (four odd powers and the running power, 5 x 28 registers) and the ladder (XYZZ accumulator 4 x 28, the
 // point 2 x 28, the addition's temporaries) do not fit 256 VGPRs.  With the AGPR half of the file k_decode761 needs no scratch and
@@ -14,10 +15,6 @@
 #define W761_OCC __attribute__((amdgpu_waves_per_eu(1, 1)))
 #endif
 namespace celo {
-struct ProvingKey;
-int groth16_key_load_dev_761(const uint64_t*, const uint8_t*, size_t, const uint64_t*, const uint8_t*, size_t, const uint64_t*, const uint8_t*, size_t,
-                             const uint64_t*, const uint8_t*, size_t, const uint64_t*, const uint64_t*, const uint64_t*, const uint64_t*, int, ProvingKey**);
-
 // calls from several host threads are serialised per process (they are bulk calls: one fills the GPU); each runs on a stream of its own
 // (host-pointer calls) or on the caller's (the _dev forms)
 static std::mutex w761_mu;
@@ -171,9 +168,9 @@ int wire761_key_load(const uint8_t* bytes, size_t len, int form, int window_bits
   }
   const auto t0 = std::chrono::steady_clock::now();
   // (frees the key itself when it fails, and sets *out_key only on success: the call's last step)
-  const int rc = groth16_key_load_dev_761(d_xy + base[4] * 24, d_st + base[4], L[W761_A], d_xy + base[6] * 24, d_st + base[6], L[W761_BG2],
-                                          d_xy + base[7] * 24, d_st + base[7], L[W761_H], d_xy + base[8] * 24, d_st + base[8], L[W761_L],
-                                          host_rows[0], host_rows[1], host_rows[2], host_rows[3], window_bits, out_key);
+  const int rc = groth16_key_load_dev(0, d_xy + base[4] * 24, d_st + base[4], L[W761_A], d_xy + base[6] * 24, d_st + base[6], L[W761_BG2],
+                                      d_xy + base[7] * 24, d_st + base[7], L[W761_H], d_xy + base[8] * 24, d_st + base[8], L[W761_L],
+                                      host_rows[0], host_rows[1], host_rows[2], host_rows[3], window_bits, out_key);
   g_w761_ms[3] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return rc;
 }

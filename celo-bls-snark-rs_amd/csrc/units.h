@@ -1,0 +1,145 @@
+// Every function that one translation unit defines and another calls, declared once.  The units are linked into a shared library, where an
+// undefined celo:: symbol is no link error: a prototype re-typed at the caller that drifts from its definition builds cleanly and fails at
+// load time, or at the first call.  So no .hip file declares another unit's function itself: callers and the defining unit include this header,
+// a member of MsmApi / MsmAuxApi that is defined differently does not compile.  A plain function defined differently DOES compile (it is an
+// overload, and the declared one stays undefined): the guard for those is tests/test_abi_symbols.py, which checks that the library is left
+// with no undefined celo:: symbol.
+// Light on purpose (capi.hip and seam_a.hip include it): no field, curve or kernel header; the groups, fields and handles are opaque here.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include "runtime.h"
+
+namespace celo {
+struct G1_377; struct G2_377; struct G_761;      // msm.h: the three group configurations
+struct P377; struct P253;                        // fp_consts.h
+template <class P> struct Fp;                    // fp.h
+typedef Fp<P377> Fr761;                          // the scalar field of BW6-761 is the base field of BLS12-377 (ntt.h)
+typedef Fp<P253> Fr377;                          // the scalar field of BLS12-377
+struct FixedTable;                               // msm_fixed.h: a key's fixed-base tables
+struct ProvingKey;                               // unit_prover.hip: a loaded Groth16 proving key (fixed-base tables of its four queries)
+struct R1cs;                                     // unit_r1cs.hip: constraint matrices on the device
+struct WireConsts;                               // wire.h
+struct EdPoint;                                  // pedersen.h
+struct BvJob { BatchRun keys, sigs; };           // unit_batchverify.hip: the chained Batch::verify in three steps
+
+// ---- the MSM of group G (msm_unit.h holds the definitions; unit_<group>.hip and unit_<group>_aux.hip instantiate them).  Two templates because
+// each group is built as two translation units: the halves own separate engine pools and separate "last call" records.
+template <class G> struct MsmApi {
+  // flags: bit 0 = bases vouched to lie in the prime-order subgroup, bit 1 = rows (0, 1) are the identity (the prover's queries)
+  static int host(const uint64_t* b, const uint8_t* inf, const uint64_t* s, size_t n, int flags, uint64_t* out);
+  static int dev(const void* b, const void* inf, const void* s, size_t n, int subgroup, uint64_t* out, void* st);
+  static int multi_host(const int* devs, int nd, const uint64_t* b, const uint8_t* inf, const uint64_t* s, size_t n, uint64_t* out);
+  static int multi_dev(const int* devs, int nd, const void* const* b, const void* const* inf, const void* const* s, const size_t* n_per, uint64_t* out);
+  static int multi_windows(const int* devs, int nd, int resident, const void* const* b, const void* const* inf, const void* const* s, size_t n, int subgroup,
+                           uint64_t* out);
+  static int window_shard(const void* b, const void* inf, const void* s, size_t n, int subgroup, int shard, int nshards, uint64_t* out_xyzz, int* bit_lo, void* st);
+  static int join_windows(const uint64_t* xyzz, const int* bit_lo, int nshards, uint64_t* out);
+  // fixed-base form: per-key tables.  resident = 1: DEVICE pointers
+  static int fixed_build(const void* b, const void* inf, size_t n, int resident, int cf, FixedTable** out);
+  static int fixed_run(const FixedTable* T, const void* s, size_t n_sc, int resident, uint64_t* out, void* st);
+  static int selftest_accumulate(const uint64_t* gen_xy, uint32_t runs, uint32_t len, uint32_t seed, uint32_t check, int chunked, uint32_t* differ);
+  static void big_timings(float ms[5], int cfg[3]);
+  static void big_set_c(int c);
+};
+template <class G> struct MsmAuxApi {
+  static int batch_host(const uint64_t* b, const uint8_t* inf, const uint64_t* s, const uint32_t* off, size_t m, int subgroup_points, uint64_t* out);
+  static int batch_begin(const void* b, const void* inf, const void* s, int resident, const uint32_t* off, size_t m, int subgroup_points, BatchRun* run);
+  static void batch_end(BatchRun* run, int drained);
+  static int timings(float ms[5], int cfg[3]);
+  static void note_big_call();
+  static int set_c(int c);
+  static int gen_points(void* d_out, size_t n, uint64_t seed, const uint64_t* gen_xy, size_t ngens, uint32_t per, void* st);
+  static int sum_jac(const uint64_t* jac, size_t k, uint64_t* out);
+};
+extern template struct MsmApi<G1_377>; extern template struct MsmApi<G2_377>; extern template struct MsmApi<G_761>;
+extern template struct MsmAuxApi<G1_377>; extern template struct MsmAuxApi<G2_377>; extern template struct MsmAuxApi<G_761>;
+int fixed_table_release(FixedTable* T);          // unit_g1_377.hip: the group-agnostic ends of a fixed-base handle
+int fixed_table_info(const FixedTable* T, size_t* n, int* window_bits, int* windows, size_t* table_bytes, float* build_ms);
+
+// ---- NTT and witness map over FR = Fr761 / Fr377 (unit_ntt.hip, unit_prover.hip)
+template <class FR> int ntt_run(uint64_t* data, unsigned log_n, const uint64_t* omega, const uint64_t* coset, int coset_after, const uint64_t* scale, int dev, void* stream);
+int ntt_timings(float ms[4], int* passes);
+template <class FR>
+int witness_map_run(uint64_t* a, uint64_t* b, uint64_t* c, unsigned log_n, const uint64_t* omega, const uint64_t* omega_inv, const uint64_t* coset,
+                    const uint64_t* coset_inv, const uint64_t* n_inv, const uint64_t* z_inv, int out_canonical, int dev, void* stream);
+
+// ---- pairing (unit_pairing.hip, unit_pairing761.hip, unit_pairing377_wide.hip)
+int pairing_run_377(const uint64_t* g1, const uint8_t* inf1, const uint64_t* g2, const uint8_t* inf2, const uint32_t* offsets, size_t m, uint8_t* is_one, uint64_t* gt, int mode);
+int pairing_run_761(const uint64_t* g1, const uint8_t* inf1, const uint64_t* g2, const uint8_t* inf2, const uint32_t* offsets, size_t m, uint8_t* is_one, uint64_t* gt, int mode);
+int pairing_stage_377(uint32_t k, size_t m, PairingStage* st);
+int pairing_run_staged_377(PairingStage* st, const uint32_t* offsets, size_t m, uint8_t* is_one);
+int pairing_timings_377(float ms[4]);
+void final_exp_w3_377(const uint32_t* prod, uint8_t* is_one, uint64_t* gt, uint32_t m, hipStream_t s);
+void final_exp_w2_377(const uint32_t* prod, uint8_t* is_one, uint64_t* gt, uint32_t m, hipStream_t s);
+
+// ---- chained Batch::verify (unit_batchverify.hip)
+int batch_verify_377_run(const void* pk_xy, const void* pk_inf, const void* sig_xy, const void* sig_inf, const void* exponents, int resident, const uint32_t* offsets,
+                         const void* hash_xy, const void* hash_inf, const uint64_t neg_g2_xy[24], size_t m, uint8_t* out_ok);
+int draw_exponents_run(const uint32_t key[8], const uint32_t* offsets, size_t m, uint64_t* out);
+int bv_begin_keys(BvJob* j, const void* pk_xy, const void* pk_inf, const void* exponents, int resident, const uint32_t* offsets, size_t m);
+int bv_begin_sigs(BvJob* j, const void* sig_xy, const void* sig_inf, const void* exponents, int resident, const uint32_t* offsets, size_t m);
+int bv_finish(BvJob* j, int begun_ok, const void* hash_xy, const void* hash_inf, int resident, const uint64_t neg_g2_xy[24], size_t m, uint8_t* out_ok);
+int bv_mirror_scatter(int words, const uint64_t* up_xy, const uint8_t* up_inf, const uint32_t* slots, uint64_t* mirror_xy, uint8_t* mirror_inf, size_t k, hipStream_t stream);
+int bv_mirror_gather(int words, const uint64_t* mirror_xy, const uint8_t* mirror_inf, const uint32_t* slots, uint64_t* out_xy, uint8_t* out_inf, size_t n, hipStream_t stream);
+int bv_draw_exponents(const uint32_t key[8], const uint32_t* d_offsets, size_t m, size_t tot, uint64_t* d_out, hipStream_t stream);
+
+// ---- point decoding and normalisation (unit_wire.hip, unit_wire761.hip).  group 0 / 1: BLS12-377 G1 / G2, 2: BW6-761
+int wire_decompress(int g2, const uint8_t* in, size_t n, int check, uint64_t* out, uint8_t* status, int dev, void* stream);
+int wire_normalize(int group, const uint64_t* jac, size_t n, uint64_t* out_xy, uint8_t* inf);
+int wire_consts_device(WireConsts& out);
+float wire_last_ms();
+int wire761_decode(int g2, int compressed, const uint8_t* in, size_t n, int check, uint64_t* out, uint8_t* status, int dev, void* stream);
+int wire761_key_layout(const uint8_t* bytes, size_t len, int form, uint64_t out[16]);
+int wire761_key_load(const uint8_t* bytes, size_t len, int form, int window_bits, ProvingKey** out_key, uint64_t* first_bad);
+void wire761_last_timings(float ms[4]);
+
+// ---- hash to G1 (unit_hash.hip; the composite hasher's generator table is seam_a.hip's)
+int hash_to_g1_direct_run(const uint8_t* domain, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off, size_t n, uint64_t* out_xy,
+                          uint8_t* attempts, int mode);
+int pedersen_crh_run(const uint8_t* msgs, const uint64_t* msg_off, size_t n, uint8_t* out48);
+float hash_last_ms();
+int hash_last_rounds();
+const EdPoint* celo_composite_gens(size_t* count);
+
+// ---- batched fixed-base scalar multiplication and Groth16 setup (unit_setup.hip)
+int fixed_base_mul(int group, const uint64_t* gen, const void* scalars, size_t n, void* out_xy, void* inf, int dev, void* stream);
+int fixed_base_set_window(int c);
+void setup_last_timings(float ms[8]);
+int groth16_setup(int curve, const uint64_t* qa, const uint64_t* qb, const uint64_t* qc, size_t n_vars, size_t n_inputs, const uint64_t* zt, const uint64_t* tau, size_t n_h,
+                  const uint64_t* toxic, const uint64_t* g1_xy, const uint64_t* g2_xy, int window_bits, uint64_t* out_vk, uint64_t* out_rows, ProvingKey** out_key);
+int groth16_setup_r1cs(int curve, const R1cs* r, unsigned log_n, const uint64_t* omega, const uint64_t* tau, const uint64_t* toxic, const uint64_t* g1_xy,
+                       const uint64_t* g2_xy, int window_bits, uint64_t* out_vk, uint64_t* out_rows, ProvingKey** out_key);
+
+// ---- constraint matrices (unit_r1cs.hip)
+int r1cs_load(int curve, size_t m, size_t n_vars, size_t n_inputs, const uint64_t* const row_ptr[3], const uint32_t* const col[3], const uint64_t* const val[3],
+              const uint64_t nnz[3], R1cs** out, uint64_t* first_bad);
+int r1cs_info(const R1cs* r, uint64_t out[8]);
+void r1cs_free(R1cs* r);
+void r1cs_shape(const R1cs* r, int* curve, int* device, size_t* m, size_t* n_vars, size_t* n_inputs);
+int r1cs_rows(const R1cs* r, const uint64_t* z, unsigned log_n, uint64_t* oa, uint64_t* ob, uint64_t* oc, int dev, void* stream);
+int r1cs_check(const R1cs* r, const uint64_t* z, int64_t* first_unsatisfied);
+int r1cs_qap_at_tau(const R1cs* r, unsigned log_n, const uint64_t* omega, const uint64_t* tau, uint64_t* oa, uint64_t* ob, uint64_t* oc, uint64_t* ozt, int dev, void* stream);
+void r1cs_note_ms(int slot, float v);
+void r1cs_last_timings(float ms[8]);
+
+// ---- Groth16 prover (unit_prover.hip).  curve 0 = BW6-761, 1 = BLS12-377
+int groth16_prove_761_run(const uint64_t* a_query, size_t na, const uint64_t* b_g2_query, size_t nb, const uint64_t* h_query, size_t nh, const uint64_t* l_query, size_t nl,
+                          const uint64_t* alpha_g1, const uint64_t* beta_g2, const uint64_t* assignment, size_t n_assign, size_t n_aux, const uint64_t* h, size_t n_h,
+                          uint64_t* out_a, uint64_t* out_b, uint64_t* out_c);
+int groth16_prove_377_run(const uint64_t* a_query, size_t na, const uint64_t* b_g2_query, size_t nb, const uint64_t* h_query, size_t nh, const uint64_t* l_query, size_t nl,
+                          const uint64_t* alpha_g1, const uint64_t* beta_g2, const uint64_t* assignment, size_t n_assign, size_t n_aux, const uint64_t* h, size_t n_h,
+                          uint64_t* out_a, uint64_t* out_b, uint64_t* out_c);
+int groth16_key_load(int curve, const uint64_t* a_query, size_t na, const uint64_t* b_g2_query, size_t nb, const uint64_t* h_query, size_t nh, const uint64_t* l_query,
+                     size_t nl, const uint64_t* alpha_g1, const uint64_t* beta_g2, int window_bits, ProvingKey** out);
+int groth16_key_load_dev(int curve, const uint64_t* d_a, const uint8_t* d_ainf, size_t na, const uint64_t* d_b, const uint8_t* d_binf, size_t nb, const uint64_t* d_h,
+                         const uint8_t* d_hinf, size_t nh, const uint64_t* d_l, const uint8_t* d_linf, size_t nl, const uint64_t* a0, const uint64_t* b0,
+                         const uint64_t* alpha_g1, const uint64_t* beta_g2, int window_bits, ProvingKey** out);
+void groth16_key_free(ProvingKey* k);
+int groth16_prove_keyed(const ProvingKey* k, const uint64_t* assignment, size_t n_assign, size_t n_aux, const uint64_t* h, size_t n_h, uint64_t* out_a, uint64_t* out_b,
+                        uint64_t* out_c);
+int groth16_prove_r1cs(const ProvingKey* k, const R1cs* r, const uint64_t* z, unsigned log_n, const uint64_t* omega, const uint64_t* omega_inv, const uint64_t* coset,
+                       const uint64_t* coset_inv, const uint64_t* n_inv, const uint64_t* z_inv, uint64_t* out_a, uint64_t* out_b, uint64_t* out_c);
+
+int ubench_fp_run(float out[9]);                 // unit_ubench.hip
+}  // namespace celo

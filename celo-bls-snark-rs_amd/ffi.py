@@ -75,6 +75,12 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _rows(x, width):
+    """x as a contiguous (k, width) uint64 array; k may be 0 (a query without rows, an empty h), which reshape(-1, width) refuses."""
+    a = np.ascontiguousarray(x, dtype=np.uint64)
+    return a.reshape(a.size // width, width)
+
+
 def init(device=0):
     rc = lib().celo_amd_init(C.c_int(device))
     if rc != 0:
@@ -522,10 +528,9 @@ def witness_map_dev(d_a, d_b, d_c, log_n, consts, canonical=False, stream=0):
 def groth16_prove(a_query, b_g2_query, h_query, l_query, alpha_g1, beta_g2, assignment, n_aux, h):
     """create_proof_no_zk's group arithmetic (groth16_prove_bw6_761).  queries: (k, 24) uint64; alpha / beta: (24,); assignment,
     h: (k, 6) uint64 canonical scalars.  Returns (A, B, C) Jacobian limbs (36 u64 each)."""
-    arrs = [np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, 24) for x in (a_query, b_g2_query, h_query, l_query)]
+    arrs = [_rows(x, 24) for x in (a_query, b_g2_query, h_query, l_query)]
     al, be = (np.ascontiguousarray(x, dtype=np.uint64).reshape(24) for x in (alpha_g1, beta_g2))
-    asg = np.ascontiguousarray(assignment, dtype=np.uint64).reshape(-1, 6)
-    hh = np.ascontiguousarray(h, dtype=np.uint64).reshape(-1, 6)
+    asg, hh = _rows(assignment, 6), _rows(h, 6)
     out = [np.zeros(36, dtype=np.uint64) for _ in range(3)]
     rc = lib().groth16_prove_bw6_761(_p(arrs[0]), C.c_size_t(arrs[0].shape[0]), _p(arrs[1]), C.c_size_t(arrs[1].shape[0]), _p(arrs[2]), C.c_size_t(arrs[2].shape[0]),
                                      _p(arrs[3]), C.c_size_t(arrs[3].shape[0]), _p(al), _p(be), _p(asg), C.c_size_t(asg.shape[0]), C.c_size_t(n_aux),
@@ -568,8 +573,7 @@ class ProvingKey:
         self.h = C.c_void_p()
         if a_query is None:                 # from_serialized fills the handle
             return
-        q = [np.ascontiguousarray(a_query, dtype=np.uint64).reshape(-1, g1w), np.ascontiguousarray(b_g2_query, dtype=np.uint64).reshape(-1, 24),
-             np.ascontiguousarray(h_query, dtype=np.uint64).reshape(-1, g1w), np.ascontiguousarray(l_query, dtype=np.uint64).reshape(-1, g1w)]
+        q = [_rows(a_query, g1w), _rows(b_g2_query, 24), _rows(h_query, g1w), _rows(l_query, g1w)]
         al = np.ascontiguousarray(alpha_g1, dtype=np.uint64).reshape(g1w)
         be = np.ascontiguousarray(beta_g2, dtype=np.uint64).reshape(24)
         fn = lib().groth16_load_key_bw6_761 if curve == "bw6_761" else lib().groth16_load_key_bls12_377
@@ -604,8 +608,7 @@ class ProvingKey:
         return out
 
     def prove(self, assignment, n_aux, h):
-        asg = np.ascontiguousarray(assignment, dtype=np.uint64).reshape(-1, self.sw)
-        hh = np.ascontiguousarray(h, dtype=np.uint64).reshape(-1, self.sw)
+        asg, hh = _rows(assignment, self.sw), _rows(h, self.sw)
         out = [np.zeros(w, dtype=np.uint64) for w in self.ow]
         rc = lib().groth16_prove_with_key(self.h, _p(asg), C.c_size_t(asg.shape[0]), C.c_size_t(n_aux), _p(hh), C.c_size_t(hh.shape[0]), _p(out[0]), _p(out[1]), _p(out[2]))
         if rc != 0:
@@ -669,12 +672,11 @@ def witness_map_fr377_dev(d_a, d_b, d_c, log_n, consts, canonical=False, stream=
 def groth16_prove_bls12_377(a_query, b_g2_query, h_query, l_query, alpha_g1, beta_g2, assignment, n_aux, h):
     """create_proof_no_zk's group arithmetic over BLS12-377 (groth16_prove_bls12_377).  a / h / l queries: (k, 12) uint64, b_g2_query:
     (k, 24); alpha (12,), beta (24,); assignment, h: (k, 4) canonical scalars.  Returns (A (18,), B (36,), C (18,)) Jacobian limbs."""
-    aq, hq, lq = (np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, 12) for x in (a_query, h_query, l_query))
-    bq = np.ascontiguousarray(b_g2_query, dtype=np.uint64).reshape(-1, 24)
+    aq, hq, lq = (_rows(x, 12) for x in (a_query, h_query, l_query))
+    bq = _rows(b_g2_query, 24)
     al = np.ascontiguousarray(alpha_g1, dtype=np.uint64).reshape(12)
     be = np.ascontiguousarray(beta_g2, dtype=np.uint64).reshape(24)
-    asg = np.ascontiguousarray(assignment, dtype=np.uint64).reshape(-1, 4)
-    hh = np.ascontiguousarray(h, dtype=np.uint64).reshape(-1, 4)
+    asg, hh = _rows(assignment, 4), _rows(h, 4)
     out = [np.zeros(18, dtype=np.uint64), np.zeros(36, dtype=np.uint64), np.zeros(18, dtype=np.uint64)]
     rc = lib().groth16_prove_bls12_377(_p(aq), C.c_size_t(aq.shape[0]), _p(bq), C.c_size_t(bq.shape[0]), _p(hq), C.c_size_t(hq.shape[0]),
                                        _p(lq), C.c_size_t(lq.shape[0]), _p(al), _p(be), _p(asg), C.c_size_t(asg.shape[0]), C.c_size_t(n_aux),

@@ -112,6 +112,16 @@ def test_no_stray_c_symbols_exported():
     assert stray == [], stray
 
 
+def test_no_undefined_symbol_of_the_library_itself():
+    """The library is linked -shared, where a celo:: function that a unit calls and no unit defines is no link error: it would fail at load
+    time or at the first call.  csrc/units.h declares every cross-unit function once; this is the check that each has its definition."""
+    import subprocess
+    from celo_bls_snark_rs_amd import ffi
+    out = subprocess.run(["nm", "-D", "--undefined-only", ffi.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    own = [ln.split()[-1] for ln in out.splitlines() if re.search(r"\b_ZNK?4celo", ln)]
+    assert own == [], own
+
+
 def test_accumulate_kernels_are_out_of_the_sgpr_spill_regime():
     """rounds 2-4 shipped k_accumulate with 107-211 spilled SGPRs (the K p tables of the cold canonical reduction, hoisted
     into the prologue and parked in VGPR lanes) - the register shape next to which the round-3 signed-pass instantiation miscompiled.  Round 5

@@ -320,3 +320,62 @@ def test_prove_bls12_377_identity_rows_under_the_glv_split(gpu):
     A, B, Cc = key.prove(asg, n_aux, h)
     assert co.jac_to_affine(A, "g1_377") == wa and co.jac_to_affine(B, "g2_377") == wb and co.jac_to_affine(Cc, "g1_377") == wc
     key.release()
+
+
+# ------------------------------------------------------------------------------------------------ proofs with an empty MSM
+_EMPTY_SIDE_CURVES = {
+    "bw6_761": dict(g1="bw6_761_g1", g2="bw6_761_g2", g1_words=24, scalar_words=6, q=ecc.Q761, kinds=("761", "761", "761"),
+                    prove="groth16_prove", oracle=gp.prove_no_zk),
+    "bls12_377": dict(g1="bls12_377_g1", g2="bls12_377_g2", g1_words=12, scalar_words=4, q=ecc.Q377, kinds=("g1_377", "g2_377", "g1_377"),
+                      prove="groth16_prove_bls12_377", oracle=gp.prove_no_zk_bls12_377),
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("curve", ["bw6_761", "bls12_377"])
+def test_prove_with_an_empty_msm_matches_oracle(gpu, curve):
+    """The proof composition where one of its four MSMs has no terms (VariableBaseMSM zips bases with scalars: the shorter side decides, and
+    it may be empty): a circuit without auxiliary variables, an empty h, both (C is the identity), queries that hold row 0 only - and an
+    l_query of arkworks identity rows (0, 1) under full-size scalars.  Every case through the variable-base entry point and through a
+    loaded key (one key per distinct set of queries), A, B and C equal to the oracle's as affine points."""
+    from celo_bls_snark_rs_amd import synthetic as syn
+    c = _EMPTY_SIDE_CURVES[curve]
+    n_inputs, n_aux = 2, 4
+    n_assign = n_inputs + n_aux
+    w1, sw = c["g1_words"], c["scalar_words"]
+    def pts(group, k, seed):
+        return syn.device_points(group, k, seed).cpu().numpy().view(np.uint64).reshape(k, -1)
+    a_query, b_query = pts(c["g1"], n_assign + 1, 41), pts(c["g2"], n_assign + 1, 42)
+    l_query, h_query = pts(c["g1"], n_aux, 43), pts(c["g1"], 7, 44)
+    alpha, beta = pts(c["g1"], 1, 45)[0], pts(c["g2"], 1, 46)[0]
+    asg, h = syn.uniform_scalars(c["g1"], n_assign, 47), syn.uniform_scalars(c["g1"], 7, 48)
+    asg_ints, h_ints = co.limbs_to_ints(asg, sw), co.limbs_to_ints(h, sw)
+    assert a_query.shape == (7, w1) and b_query.shape == (7, 24) and l_query.shape == (4, w1)
+    zero_row = np.concatenate([np.zeros(w1 // 2, dtype=np.uint64), co.to_mont([1], c["q"])[0]])
+    no_rows, no_h = np.zeros((0, w1), dtype=np.uint64), np.zeros((0, sw), dtype=np.uint64)
+    queries = {                                     # (a, b_g2, h, l)
+        "full": (a_query, b_query, h_query, l_query),
+        "no l": (a_query, b_query, h_query, no_rows),
+        "row 0 only": (a_query[:1], b_query[:1], h_query, l_query),
+        "identity l": (a_query, b_query, h_query, np.tile(zero_row, (n_aux, 1))),
+    }
+    cases = [                                       # (name, queries, n_aux, h, its ints)
+        ("everything present", "full", n_aux, h, h_ints),
+        ("no auxiliary variables", "no l", 0, h, h_ints),
+        ("empty h", "full", n_aux, no_h, []),
+        ("no auxiliary variables and empty h", "no l", 0, no_h, []),
+        ("a and b of one row", "row 0 only", n_aux, h, h_ints),
+        ("l of identity rows", "identity l", n_aux, h, h_ints),
+    ]
+    keys = {name: gpu.ProvingKey(curve, *q, alpha, beta, window_bits=0) for name, q in queries.items()}
+    affine = lambda proof: tuple(co.jac_to_affine(p, kind) for p, kind in zip(proof, c["kinds"]))
+    for name, qname, aux, hh, hh_ints in cases:
+        q = queries[qname]
+        want = c["oracle"](*q, alpha, beta, asg_ints, aux, hh_ints)
+        assert want[0] is not None and want[1] is not None, name
+        if name == "no auxiliary variables and empty h":
+            assert want[2] is None                  # ... which the library returns as Z = 0
+        assert affine(getattr(gpu, c["prove"])(*q, alpha, beta, asg, aux, hh)) == want, name
+        assert affine(keys[qname].prove(asg, aux, hh)) == want, name + " (loaded key)"
+    for key in keys.values():
+        key.release()
