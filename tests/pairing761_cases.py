@@ -21,9 +21,52 @@ MAX_PAIRS = 9          # pair counts of the ragged batches: 0 ... 9
 VARIANTS = ("accept", "mismatch", "extra_live", "unrelated", "all_off", "half_off")
 
 
+class Curve:
+    """what binds the cases to a curve: the row widths, the generators A / B and their groups, the packers, the library's generator
+    kernel groups and the two oracle calls.  Everything else in this module is curve-independent (tests/pairing377_cases.py binds BLS12-377)."""
+
+    def __init__(self, name, w1, w2, q, E1, E2, generators, pack1, pack2, device_groups, gt, miller):
+        self.name, self.w1, self.w2, self.q, self.E1, self.E2 = name, w1, w2, q, E1, E2
+        self.generators, self.pack1, self.pack2, self.device_groups, self.gt, self.miller = generators, pack1, pack2, device_groups, gt, miller
+
+    def python_rows(self, seed, indices):
+        """rows of P_i and Q_i for the given i, by the Python oracle's scalar multiplication"""
+        A, B = self.generators()
+        g1, _ = self.pack1([self.E1.mul(A, scalar(seed, i)) for i in indices])
+        g2, _ = self.pack2([self.E2.mul(B, scalar(seed, i)) for i in indices])
+        return g1, g2
+
+    def python_points(self, n, seed):
+        return Points(*self.python_rows(seed, range(n)), seed, self)
+
+    def device_points(self, n, seed):
+        """the same rows from the library's generator kernel (needs the GPU)"""
+        from celo_bls_snark_rs_amd import synthetic as syn
+        P = syn.device_points(self.device_groups[0], n, seed).view(n, self.w1).cpu().numpy().view(np.uint64)
+        Q = syn.device_points(self.device_groups[1], n, seed).view(n, self.w2).cpu().numpy().view(np.uint64)
+        return Points(P, Q, seed, self)
+
+    def neg_g1_rows(self, rows):
+        """the rows of -P for G1 rows of P (Montgomery limbs: -(y R) = q - y R); a zero row stays zero"""
+        rows = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, self.w1)
+        n = self.w1 // 2
+        y = co.limbs_to_ints(rows[:, n:], n)
+        out = rows.copy()
+        out[:, n:] = co.ints_to_limbs([(self.q - v) % self.q for v in y], n)
+        return out
+
+
 def generators():
     from celo_bls_snark_rs_amd import synthetic as syn        # (imports torch: kept out of module level)
     return syn.BW6_G1_POINT, syn.BW6_G2_POINT
+
+
+def _pack_761(points):
+    return co.pack_761(points)
+
+
+CURVE = Curve("bw6_761", 24, 24, ecc.Q761, ecc.E1_761, ecc.E2_761, generators, _pack_761, _pack_761, ("bw6_761_g1", "bw6_761_g2"),
+              lambda *a: co.pairing_product_761(*a), lambda *a: co.miller_loop_761(*a))
 
 
 def scalar(seed, i):
@@ -31,16 +74,17 @@ def scalar(seed, i):
 
 
 class Points:
-    """P (n, 24), Q (n, 24): arkworks Montgomery rows of P_i, Q_i; table1 / table2 add the fixed rows A, -A, B, an all-zero row (what
-    pack_761 writes for a point at infinity) and any rows added later (the reference vector's)."""
+    """P (n, w1), Q (n, w2): arkworks Montgomery rows of P_i, Q_i; table1 / table2 add the fixed rows A, -A, B, an all-zero row (what
+    the packers write for a point at infinity) and any rows added later (the reference vector's)."""
 
-    def __init__(self, P, Q, seed):
-        A, B = generators()
+    def __init__(self, P, Q, seed, curve=None):
+        self.curve = curve = CURVE if curve is None else curve
+        A, B = curve.generators()
         self.n, self.seed = P.shape[0], seed
-        fixed1, _ = co.pack_761([A, ecc.E1_761.neg(A), None])
-        fixed2, _ = co.pack_761([B, None])
-        self.table1 = np.concatenate([np.ascontiguousarray(P, dtype=np.uint64).reshape(-1, 24), fixed1])
-        self.table2 = np.concatenate([np.ascontiguousarray(Q, dtype=np.uint64).reshape(-1, 24), fixed2])
+        fixed1, _ = curve.pack1([A, curve.E1.neg(A), None])
+        fixed2, _ = curve.pack2([B, None])
+        self.table1 = np.concatenate([np.ascontiguousarray(P, dtype=np.uint64).reshape(-1, curve.w1), fixed1])
+        self.table2 = np.concatenate([np.ascontiguousarray(Q, dtype=np.uint64).reshape(-1, curve.w2), fixed2])
         self.A, self.NEG_A, self.ZERO1 = self.n, self.n + 1, self.n + 2
         self.B, self.ZERO2 = self.n, self.n + 1
 
@@ -58,29 +102,21 @@ class Points:
         import copy
         q = copy.copy(self)
         at = (self.table1.shape[0], self.table2.shape[0])
-        q.table1 = np.concatenate([self.table1, np.asarray(g1rows, dtype=np.uint64).reshape(-1, 24)])
-        q.table2 = np.concatenate([self.table2, np.asarray(g2rows, dtype=np.uint64).reshape(-1, 24)])
+        q.table1 = np.concatenate([self.table1, np.asarray(g1rows, dtype=np.uint64).reshape(-1, self.curve.w1)])
+        q.table2 = np.concatenate([self.table2, np.asarray(g2rows, dtype=np.uint64).reshape(-1, self.curve.w2)])
         return q, at
 
 
 def python_rows(seed, indices):
-    """rows of P_i and Q_i for the given i, by the Python oracle's scalar multiplication"""
-    A, B = generators()
-    g1, _ = co.pack_761([ecc.E1_761.mul(A, scalar(seed, i)) for i in indices])
-    g2, _ = co.pack_761([ecc.E2_761.mul(B, scalar(seed, i)) for i in indices])
-    return g1, g2
+    return CURVE.python_rows(seed, indices)
 
 
 def python_points(n, seed):
-    return Points(*python_rows(seed, range(n)), seed)
+    return CURVE.python_points(n, seed)
 
 
 def device_points(n, seed):
-    """the same rows from the library's generator kernel (needs the GPU)"""
-    from celo_bls_snark_rs_amd import synthetic as syn
-    P = syn.device_points("bw6_761_g1", n, seed).view(n, 24).cpu().numpy().view(np.uint64)
-    Q = syn.device_points("bw6_761_g2", n, seed).view(n, 24).cpu().numpy().view(np.uint64)
-    return Points(P, Q, seed)
+    return CURVE.device_points(n, seed)
 
 
 class Spec:
@@ -180,15 +216,15 @@ def fixed_product(at, k, expect, kind):
 
 
 def layout(pts, specs):
-    """-> g1 (k, 24), i1 (k), g2 (k, 24), i2 (k), offsets (m + 1) uint32, expect (m) uint8"""
+    """-> g1 (k, w1), i1 (k), g2 (k, w2), i2 (k), offsets (m + 1) uint32, expect (m) uint8"""
     i1 = np.array([r for s in specs for r in s.i1], dtype=np.int64)
     i2 = np.array([r for s in specs for r in s.i2], dtype=np.int64)
     f1 = np.array([r for s in specs for r in s.f1], dtype=np.uint8)
     f2 = np.array([r for s in specs for r in s.f2], dtype=np.uint8)
     offs = np.zeros(len(specs) + 1, dtype=np.uint32)
     offs[1:] = np.cumsum([len(s) for s in specs])
-    g1 = pts.table1[i1] if i1.size else np.zeros((0, 24), dtype=np.uint64)
-    g2 = pts.table2[i2] if i2.size else np.zeros((0, 24), dtype=np.uint64)
+    g1 = pts.table1[i1] if i1.size else np.zeros((0, pts.curve.w1), dtype=np.uint64)
+    g2 = pts.table2[i2] if i2.size else np.zeros((0, pts.curve.w2), dtype=np.uint64)
     return np.ascontiguousarray(g1), f1, np.ascontiguousarray(g2), f2, offs, np.array([s.expect for s in specs], dtype=np.uint8)
 
 
@@ -196,21 +232,23 @@ def has_flag(s):
     return any(s.f1) or any(s.f2)
 
 
-def ragged_specs(pts, counts, seed, first=0, flag_share=None):
+def ragged_specs(pts, counts, seed, first=0, flag_share=None, variants=VARIANTS, build=None):
     """one product per entry of counts (0 ... MAX_PAIRS pairs each), variants drawn by a seeded generator, every product over point
     indices of its own (a stride of max(counts) + 1).  flag_share: keep only about that share of the products that came out with a flag
-    and rebuild the others as a flagless variant of the same count (for calls whose flagged products must all go to the oracle)."""
+    and rebuild the others as a flagless variant of the same count (for calls whose flagged products must all go to the oracle).
+    variants / build: another list of variants and the function that builds them (default: VARIANTS, product)."""
+    build = product if build is None else build
     rng = np.random.default_rng(seed)
     stride = max(max(counts), 1) + 1
     assert max(counts) <= MAX_PAIRS and first + stride * len(counts) <= pts.n, "not enough points for distinct products"
-    draw = rng.integers(0, len(VARIANTS), size=len(counts))
+    draw = rng.integers(0, len(variants), size=len(counts))
     keep = rng.random(len(counts))
     specs = []
     for p, (c, v) in enumerate(zip(counts, draw)):
-        s = product(pts, int(c), VARIANTS[int(v)], first + p * stride)
+        s = build(pts, int(c), variants[int(v)], first + p * stride)
         if flag_share is not None and has_flag(s) and keep[p] >= flag_share:
             flagless = ("extra_live", "unrelated") if c % 2 else ("accept", "mismatch", "unrelated")
-            s = product(pts, int(c), flagless[int(v) % len(flagless)], first + p * stride)
+            s = build(pts, int(c), flagless[int(v) % len(flagless)], first + p * stride)
             assert not has_flag(s)
         specs.append(s)
     return specs
@@ -241,9 +279,9 @@ def slice_of(batch, p):
     return g1[lo:hi], (None if i1 is None else i1[lo:hi]), g2[lo:hi], (None if i2 is None else i2[lo:hi])
 
 
-def oracle_gt(batch, p):
-    return co.pairing_product_761(*slice_of(batch, p))
+def oracle_gt(batch, p, curve=CURVE):
+    return curve.gt(*slice_of(batch, p))
 
 
-def oracle_miller(batch, p):
-    return co.miller_loop_761(*slice_of(batch, p))
+def oracle_miller(batch, p, curve=CURVE):
+    return curve.miller(*slice_of(batch, p))
