@@ -3,7 +3,7 @@
 // WINDOW_SIZE = 93, NUM_WINDOWS = 560), host+device templates.  The message is cut into 3-bit chunks (LSB-first, zero
 // padded); chunk ch uses generator ch of the window-major table (generator j of a window = 16^j * its base) and contributes
 // (1 + b0 + 2 b1) * g, negated when b2 is set; the hash is the affine x coordinate of the sum, 48 bytes little-endian.
-// The generator table itself is built on the host (seam_a.hip: ChaCha20 stream exactly as the reference consumes it) and
+// The generator table itself is built on the host (seam_hash.hip: ChaCha20 stream exactly as the reference consumes it) and
 // handed to the device once.  It holds FOUR entries per chunk - g, 2g, 3g, 4g (PEDERSEN_MULTIPLES) - so that a chunk's contribution
 // (1 + b0 + 2 b1) g is one table entry and costs ONE point addition; round 2 kept g alone and formed the multiple per chunk (up to two
 // additions and a doubling before the one that counts: 2.5 point operations per chunk on average).  Same group element, same hash.  One source for Seam A's host path (hash_crh, the composite hashers) and the bulk GPU kernel

@@ -59,7 +59,7 @@ k_pack_verify_pairs(const uint64_t* __restrict__ sig_sum /* m x 18 */, const uin
   }
 }
 
-// ---- the per-device mirror of Seam A's handle arenas (seam_a.hip, batch_verify_strict): W u64 of affine coordinates + an identity
+// ---- the per-device mirror of Seam A's handle arenas (seam_strict.hip, batch_verify_strict): W u64 of affine coordinates + an identity
 // byte per arena slot.  scatter: freshly staged entries go to their slots; gather: the call's slot numbers become the dense point
 // arrays the batch MSMs read.  One lane per 64-bit word: both sides of either copy move whole 96 / 192-byte rows.
 template <int W>

@@ -77,7 +77,7 @@ k_hash_finish(const uint64_t* __restrict__ cand_xy, const uint8_t* __restrict__ 
   else { redo[i] = 1; for (int j = 0; j < 12; j++) o[j] = 0; }
 }
 
-// celo_composite_gens (seam_a.hip): the generator table, built once from the ChaCha20 stream of the reference
+// celo_composite_gens (seam_hash.hip): the generator table, built once from the ChaCha20 stream of the reference
 static EdPoint* g_d_gens_dev[MAX_DEVICES] = {};      // its device copies (11.7 MB each), uploaded on first use (under hash_mu)
 #define g_d_gens g_d_gens_dev[api_device()]
 static int ensure_device_gens(const EdPoint* h_gens, size_t ngens) {

@@ -4,7 +4,7 @@
 // a member of MsmApi / MsmAuxApi that is defined differently does not compile.  A plain function defined differently DOES compile (it is an
 // overload, and the declared one stays undefined): the guard for those is tests/test_abi_symbols.py, which checks that the library is left
 // with no undefined celo:: symbol.
-// Light on purpose (capi.hip and seam_a.hip include it): no field, curve or kernel header; the groups, fields and handles are opaque here.
+// Light on purpose (capi.hip and the seam_*.hip units include it): no field, curve or kernel header; the groups, fields and handles are opaque here.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -94,7 +94,7 @@ int wire761_key_layout(const uint8_t* bytes, size_t len, int form, uint64_t out[
 int wire761_key_load(const uint8_t* bytes, size_t len, int form, int window_bits, ProvingKey** out_key, uint64_t* first_bad);
 void wire761_last_timings(float ms[4]);
 
-// ---- hash to G1 (unit_hash.hip; the composite hasher's generator table is seam_a.hip's)
+// ---- hash to G1 (unit_hash.hip; the composite hasher's generator table is seam_hash.hip's)
 int hash_to_g1_direct_run(const uint8_t* domain, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off, size_t n, uint64_t* out_xy,
                           uint8_t* attempts, int mode);
 int pedersen_crh_run(const uint8_t* msgs, const uint64_t* msg_off, size_t n, uint8_t* out48);

@@ -5,7 +5,7 @@
 // reference does once per key in PublicKey::deserialize / Signature::deserialize (crates/bls-crypto/src/bls/public.rs:123-149,
 // signature.rs:31-57) and per validator in EpochBlock::from FFI bytes (crates/bls-snark-sys/src/snark/epoch_block.rs:187-196).
 //
-// One source for both sides: seam_a.hip calls these functions on the host for single keys (a 1 ms latency path), the
+// One source for both sides: the seam_*.hip units call these functions on the host for single keys (a 1 ms latency path), the
 // k_decompress kernels (unit_wire.hip) run them one point per lane for bulk wire data.  A square root is unique up to
 // sign and the sign is fixed by the flag, so every correct implementation decodes to the same canonical coordinates.
 #pragma once

@@ -3,7 +3,7 @@
 // reads a ProvingKey<BW6_761> / VerifyingKey / Proof (crates/epoch-snark/src/api/setup.rs:12,17-20 Groth16Parameters; the "serialized
 // byte arrays of compressed elements" of crates/bls-snark-sys/src/snark/mod.rs:13-17): GroupAffine::deserialize (compressed, checked),
 // deserialize_uncompressed (checked) and deserialize_unchecked (uncompressed, range only).  One source for both sides: Seam A's verify
-// (seam_a.hip) decodes its vk and proof points on the host with w761_decode_row; the bulk form is k_decode761 (unit_wire761.hip), one point per lane.
+// (seam_epoch.hip) decodes its vk and proof points on the host with w761_decode_row; the bulk form is k_decode761 (unit_wire761.hip), one point per lane.
 //
 // Curves (both over Fq, q = 3 mod 4):  G1  y^2 = x^3 - 1,   G2 (M-twist)  y^2 = x^3 + 4.   One template, b as its parameter.
 //

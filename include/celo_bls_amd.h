@@ -368,7 +368,7 @@ int decode_uncompressed_bw6_761_g2(const uint8_t* in /* n x 192 */, size_t n, in
  * in the derive order of the struct; a Vec is a u64 little-endian length followed by its elements:
  *   vk { alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1: Vec<G1> }, beta_g1, delta_g1,
  *   a_query: Vec<G1>, b_g1_query: Vec<G1>, b_g2_query: Vec<G2>, h_query: Vec<G1>, l_query: Vec<G1>
- * (the VK prefix is the one csrc/seam_a.hip verify parses).  form: 0 = compressed, checked (ProvingKey::deserialize); 1 = uncompressed,
+ * (the VK prefix is the one csrc/seam_epoch.hip verify parses).  form: 0 = compressed, checked (ProvingKey::deserialize); 1 = uncompressed,
  * checked (deserialize_uncompressed); 2 = uncompressed, unchecked (deserialize_unchecked).  Points are 96 B (form 0) or 192 B.
  *
  * groth16_key_layout_bw6_761: a host walk of that structure (no device call).  out[16]:

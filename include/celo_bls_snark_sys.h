@@ -15,7 +15,7 @@
  * Differences from the reference, all deliberate:
  *   - hash_composite / hash_composite_cip22 return ToBytes of a G1Projective (x || y || z, 144 B).  Since round 5 these are the bytes of the
  *     Jacobian representative arkworks' scale_by_cofactor leaves (MSB-first double-and-add with its dbl-2009-l / madd-2007-bl formulas,
- *     restated in csrc/seam_a.hip ark_scale_by_cofactor_tobytes); rounds 1-4 returned (x, y, 1).  No reference vector pins these bytes
+ *     restated in csrc/seam_hash.hip ark_scale_by_cofactor_tobytes); rounds 1-4 returned (x, y, 1).  No reference vector pins these bytes
  *     (the reference's tests compare points), so the restatement is checked against the pinned hash POINTS and an independent big-integer
  *     replay of the same schedule - until a vector exists, callers should still compare after into_affine().
  *   - an epoch block that lists the point at infinity as a validator key is refused by encode_epoch_block_to_bytes* and verify

@@ -1,7 +1,7 @@
 """Test-side arkworks 0.1 serialization of BW6-761 points and of a Groth16 ProvingKey<BW6_761> (ark-groth16 0.1 derive order), shared by
 tests/test_wire761_host.py, tests/test_wire761_gpu.py and tests/test_groth16_key_load_gpu.py.
 
-The reference ships no serialized ProvingKey: past the VerifyingKey prefix (which seam_a.hip verify and oracle/py/epoch.parse_vk parse from the
+The reference ships no serialized ProvingKey: past the VerifyingKey prefix (which seam_epoch.hip verify and oracle/py/epoch.parse_vk parse from the
 reference's own vector) the layout below restates ark-groth16 0.1's field order, as the loader does."""
 import json
 import os

@@ -5,7 +5,7 @@ the identity branch of tai_finish.
 
 The generator table of the Pedersen tests is NOT the library's: it is built here from the oracle's generators (oracle/py/composite.py,
 pinned on the reference's CRH vectors by tests/test_oracle_golden.py) for the first three windows, as g, 2g, 3g, 4g per chunk in
-extended coordinates - so these tests also state, independently of csrc/seam_a.hip, the layout k_pedersen_crh indexes.
+extended coordinates - so these tests also state, independently of csrc/seam_hash.hip, the layout k_pedersen_crh indexes.
 
 Not covered anywhere: counter exhaustion (attempts = 255).  No findable input fails 255 counters in a row, and there is no hook to force
 it."""

@@ -961,7 +961,7 @@ def test_batch_verify_strict_config3_scale_through_the_ffi(sys_lib, gpu):
 def test_batch_verify_strict_two_host_threads_overlap(sys_lib, gpu):
     """The reference's batch_verify_strict is re-entrant (crates/bls-snark-sys/src/signatures.rs:343: no shared state but the key cache).  Two
     host threads, each verifying its own 2048 batches x 256 signers (one spoiled batch each): the verdicts are those of the calls made one
-    after the other, and the two calls overlap: the per-device lock covers the mirror phase only (csrc/seam_a.hip DevStage), the MSMs and
+    after the other, and the two calls overlap: the per-device lock covers the mirror phase only (csrc/seam_strict.hip DevStage), the MSMs and
     pairing checks of the two calls run on pooled engines side by side.  What bounds the pair is the GPU, not a lock:
     a warm call of this size is 0.8 ms of host passes + 2.6 ms waiting for the message hashes + 13.9 ms of device chain (CELO_AMD_LOG=1,
     profiles/r5_strict_two_threads.txt) = 17.3 ms, i.e. 80 % GPU-busy, so two calls cannot finish in less than ~1.6-1.7 x one; measured
@@ -1035,7 +1035,7 @@ def test_batch_verify_strict_two_host_threads_overlap(sys_lib, gpu):
 
 @pytest.mark.gpu
 def test_batch_verify_strict_device_mirror_follows_the_handles(sys_lib, gpu):
-    """batch_verify_strict keeps the points of the handles it has seen in HBM, by arena slot (csrc/seam_a.hip HandleArena / Mirror), and
+    """batch_verify_strict keeps the points of the handles it has seen in HBM, by arena slot (csrc/seam_handles.hip HandleArena, csrc/seam_strict.hip Mirror), and
     ships slot numbers.  What must hold whatever the mirror holds: a repeated call over the same handles gives the same verdicts; a
     slot that is destroyed and handed out again carries its NEW point (the reused slot's stale row must not be paired with the new
     handle); a destroyed handle in a list makes the call fail instead of verifying against a stale row; handles that are not affine
@@ -1111,8 +1111,20 @@ def test_batch_verify_strict_device_mirror_follows_the_handles(sys_lib, gpu):
     assert call(lambda b, i: agg_pk, lambda b, i: agg_sigs[(b + 1) % m]) == (False, [False] * m)
 
 
+@pytest.mark.gpu
+def test_batch_verify_strict_mirror_growth_keeps_rows(gpu):
+    """A device mirror that grows (csrc/seam_strict.hip Mirror::grow) copies its rows device to device and carries the tags over: handles
+    the device saw before the growth keep verifying although nothing uploads them again, a handle beyond the first capacity (65 536
+    slots) gets a row, and a reused slot up there takes its new tenant's point.  In a fresh process (tests/seam_a_mirror_worker.py has
+    the steps), so that arenas and mirrors start empty and the slot numbers are known."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "seam_a_mirror_worker.py")], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "mirror growth ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+
+
 def test_handle_arena_allocation_and_reuse(sys_lib, golden):
-    """Handles live in chunked arenas (csrc/seam_a.hip HandleArena): addresses are stable, a destroyed handle's slot is handed out again
+    """Handles live in chunked arenas (csrc/seam_handles.hip HandleArena): addresses are stable, a destroyed handle's slot is handed out again
     (LIFO), contents never leak from one tenant of a slot to the next, and more handles than one chunk holds (2^14) keep their
     contents - host only, through the reference-named symbols.  Concurrent create / destroy from several threads ends consistent."""
     import threading
