@@ -376,6 +376,43 @@ int groth16_load_key_bw6_761_serialized(const uint8_t* bytes, size_t len, int fo
   return wire761_key_load(bytes, len, form, window_bits, (ProvingKey**)out_key, first_bad_point);
 }
 int celo_amd_wire761_last_timings(float ms[4]) { if (!ms) return 2; wire761_last_timings(ms); return 0; }
+// ---- the encoders (unit_wire_encode.hip): group 0 / 1 = BLS12-377 G1 / G2, 2 = BW6-761
+int compress_bls12_377_g1(const uint64_t* rows, const uint8_t* inf, size_t n, uint8_t* out, uint8_t* status) { return wire_encode(0, 1, rows, inf, n, out, status, 0, nullptr); }
+int compress_bls12_377_g2(const uint64_t* rows, const uint8_t* inf, size_t n, uint8_t* out, uint8_t* status) { return wire_encode(1, 1, rows, inf, n, out, status, 0, nullptr); }
+int compress_bw6_761(const uint64_t* rows, const uint8_t* inf, size_t n, uint8_t* out, uint8_t* status) { return wire_encode(2, 1, rows, inf, n, out, status, 0, nullptr); }
+int encode_uncompressed_bls12_377_g1(const uint64_t* rows, const uint8_t* inf, size_t n, uint8_t* out, uint8_t* status) { return wire_encode(0, 0, rows, inf, n, out, status, 0, nullptr); }
+int encode_uncompressed_bls12_377_g2(const uint64_t* rows, const uint8_t* inf, size_t n, uint8_t* out, uint8_t* status) { return wire_encode(1, 0, rows, inf, n, out, status, 0, nullptr); }
+int encode_uncompressed_bw6_761(const uint64_t* rows, const uint8_t* inf, size_t n, uint8_t* out, uint8_t* status) { return wire_encode(2, 0, rows, inf, n, out, status, 0, nullptr); }
+int compress_bls12_377_g1_dev(const uint64_t* d_rows, const uint8_t* d_inf, size_t n, uint8_t* d_out, uint8_t* d_status, void* hip_stream) {
+  return wire_encode(0, 1, d_rows, d_inf, n, d_out, d_status, 1, hip_stream);
+}
+int compress_bls12_377_g2_dev(const uint64_t* d_rows, const uint8_t* d_inf, size_t n, uint8_t* d_out, uint8_t* d_status, void* hip_stream) {
+  return wire_encode(1, 1, d_rows, d_inf, n, d_out, d_status, 1, hip_stream);
+}
+int compress_bw6_761_dev(const uint64_t* d_rows, const uint8_t* d_inf, size_t n, uint8_t* d_out, uint8_t* d_status, void* hip_stream) {
+  return wire_encode(2, 1, d_rows, d_inf, n, d_out, d_status, 1, hip_stream);
+}
+int encode_uncompressed_bls12_377_g1_dev(const uint64_t* d_rows, const uint8_t* d_inf, size_t n, uint8_t* d_out, uint8_t* d_status, void* hip_stream) {
+  return wire_encode(0, 0, d_rows, d_inf, n, d_out, d_status, 1, hip_stream);
+}
+int encode_uncompressed_bls12_377_g2_dev(const uint64_t* d_rows, const uint8_t* d_inf, size_t n, uint8_t* d_out, uint8_t* d_status, void* hip_stream) {
+  return wire_encode(1, 0, d_rows, d_inf, n, d_out, d_status, 1, hip_stream);
+}
+int encode_uncompressed_bw6_761_dev(const uint64_t* d_rows, const uint8_t* d_inf, size_t n, uint8_t* d_out, uint8_t* d_status, void* hip_stream) {
+  return wire_encode(2, 0, d_rows, d_inf, n, d_out, d_status, 1, hip_stream);
+}
+int groth16_serialized_key_size_bw6_761(size_t n_inputs, size_t n_vars, size_t n_h, int form, int vk_only, uint64_t* len) {
+  return wire761_key_size(n_inputs, n_vars, n_h, form, vk_only, len);
+}
+int groth16_serialize_key_bw6_761(const uint64_t* vk, size_t n_inputs, const uint64_t* rows, size_t n_vars, size_t n_h, int form, uint8_t* out, size_t cap, uint64_t* out_len,
+                                  uint64_t* first_bad_point) {
+  return wire761_key_serialize(vk, n_inputs, rows, n_vars, n_h, form, out, cap, out_len, first_bad_point);
+}
+int groth16_serialize_proof_bw6_761(const uint64_t a_xyz[36], const uint64_t b_xyz[36], const uint64_t c_xyz[36], uint8_t out[288]) {
+  return wire761_proof_serialize(a_xyz, b_xyz, c_xyz, out);
+}
+int celo_amd_wire_encode_last_ms(float* ms) { if (!ms) return 2; *ms = wire_encode_last_ms(); return 0; }
+int celo_amd_wire_encode_key_timings(float ms[3]) { if (!ms) return 2; wire_encode_key_timings(ms); return 0; }
 int hash_to_g1_direct_bls12_377(const uint8_t domain[8], const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off,
                                 size_t n, uint64_t* out_xy, uint8_t* attempts) {
   return hash_to_g1_direct_run(domain, msgs, msg_off, extras, extra_off, n, out_xy, attempts, 0);

@@ -348,6 +348,37 @@ void ht_wire761_decode(int g2, int compressed, int check, const uint8_t* in, siz
     else status[i] = compressed ? w761_decode_row<-1, true>(src, check != 0, o) : w761_decode_row<-1, false>(src, check != 0, o);
   }
 }
+// the encoders (wire.h WireEnc, wire761.h) under bounds tracking: n rows -> wire bytes + status, what k_encode runs per lane.
+// group 0 / 1: BLS12-377 G1 / G2 (rows 12 / 24 u64), 2: BW6-761 (24 u64); ark_zero: a row (0, 1 in Montgomery form) is the identity (the key writer's rule)
+extern "C++" {
+template <class E> static void encode_host(const uint64_t* rows, const uint8_t* inf, size_t n, int ark_zero, uint8_t* out, uint8_t* status) {
+  for (size_t i = 0; i < n; i++) {
+    uint64_t w[E::OUT_WORDS];
+    status[i] = E::row(rows + i * E::ROW_WORDS, inf && inf[i], ark_zero != 0, w);
+    memcpy(out + i * E::OUT_WORDS * 8, w, E::OUT_WORDS * 8);
+  }
+}
+}  // extern "C++"
+int ht_wire_encode(int group, int compressed, const uint64_t* rows, const uint8_t* inf, size_t n, int ark_zero, uint8_t* out, uint8_t* status) {
+  switch (group * 2 + (compressed ? 1 : 0)) {
+    case 0: encode_host<WireEncG1u>(rows, inf, n, ark_zero, out, status); break;
+    case 1: encode_host<WireEncG1c>(rows, inf, n, ark_zero, out, status); break;
+    case 2: encode_host<WireEncG2u>(rows, inf, n, ark_zero, out, status); break;
+    case 3: encode_host<WireEncG2c>(rows, inf, n, ark_zero, out, status); break;
+    case 4: encode_host<W761EncU>(rows, inf, n, ark_zero, out, status); break;
+    case 5: encode_host<W761EncC>(rows, inf, n, ark_zero, out, status); break;
+    default: return 2;
+  }
+  return 0;
+}
+// one arkworks Jacobian BW6-761 point (36 u64) -> 96 compressed bytes (the proof writer's per-point step); returns the status
+int ht_wire761_encode_jacobian(const uint64_t* xyz, uint8_t* out96) {
+  uint64_t w[12];
+  const int st = w761_encode_jacobian(xyz, w);
+  memcpy(out96, w, 96);
+  return st;
+}
+int ht_wire761_key_size(size_t n_inputs, size_t n_vars, size_t n_h, int form, int vk_only, uint64_t* len) { return w761_key_size(n_inputs, n_vars, n_h, form, vk_only, len); }
 // the two forms of the subgroup test on one affine on-curve point (ark limbs): bit 0 = endomorphism form (what the decoders run),
 // bit 1 = the r * P ladder (the reference's definition)
 int ht_wire_subgroup_both(int g2, const uint64_t* xy) {

@@ -93,6 +93,14 @@ int wire761_decode(int g2, int compressed, const uint8_t* in, size_t n, int chec
 int wire761_key_layout(const uint8_t* bytes, size_t len, int form, uint64_t out[16]);
 int wire761_key_load(const uint8_t* bytes, size_t len, int form, int window_bits, ProvingKey** out_key, uint64_t* first_bad);
 void wire761_last_timings(float ms[4]);
+// ---- point encoding and the key / proof writers (unit_wire_encode.hip).  group as above; compressed: 1 = x with the sign flag, 0 = x || y
+int wire_encode(int group, int compressed, const uint64_t* rows, const uint8_t* inf, size_t n, uint8_t* out, uint8_t* status, int dev, void* stream);
+float wire_encode_last_ms();
+void wire_encode_key_timings(float ms[3]);
+int wire761_key_size(size_t n_inputs, size_t n_vars, size_t n_h, int form, int vk_only, uint64_t* len);
+int wire761_key_serialize(const uint64_t* vk, size_t n_inputs, const uint64_t* rows, size_t n_vars, size_t n_h, int form, uint8_t* out, size_t cap, uint64_t* out_len,
+                          uint64_t* first_bad);
+int wire761_proof_serialize(const uint64_t* a_xyz, const uint64_t* b_xyz, const uint64_t* c_xyz, uint8_t* out);
 
 // ---- hash to G1 (unit_hash.hip; the composite hasher's generator table is seam_hash.hip's)
 int hash_to_g1_direct_run(const uint8_t* domain, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off, size_t n, uint64_t* out_xy,

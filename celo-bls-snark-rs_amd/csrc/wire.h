@@ -305,6 +305,81 @@ HD WireStatus wire_decode_g2(const uint8_t* in, const WireConsts& k, bool check_
   return WIRE_OK;
 }
 
+// ---- encoding (arkworks 0.1 CanonicalSerialize for GroupAffine: serialize / serialize_uncompressed), the twin of the decoders above and of
+// wire761.h's.  One template for every group: a row is two coordinates of K components (K = 1: Fq, K = 2: Fq2 as c0 || c1) of P::N64 u64
+// each, arkworks Montgomery limbs; the output is x (compressed) or x || y (uncompressed) as canonical little-endian integers, handed over as
+// u64 words (both sides are little-endian: word j is bytes 8 j .. 8 j + 7).  Flags sit in the two top bits of the last word.
+//   the identity (inf, or the all-zero row that normalize_* and the decoders emit; ark_zero: also arkworks' GroupAffine::zero(), x = 0 and
+//   y = 1 in Montgomery form, the identity rule of groth16_load_key_*)       -> zero words, 0x40 on the last byte, WIRE_INFINITY (1)
+//   a component whose limbs are not below q (no field element)                -> zero words, no flag, WIRE_INVALID (2)
+//   otherwise                                                                 -> WIRE_OK (0); compressed: 0x80 on the last byte when y > -y
+// Neither the curve equation nor the subgroup is looked at: arkworks does not when it serializes.  A row (0, 1) is a pair of field
+// elements like any other unless ark_zero.
+// Montgomery limbs -> canonical integer: one Montgomery product of the repacked limbs by C_WIRE = R_d / 2^(64 N) (fp_consts.h) and the
+// full reduction below q - no detour through the device form.
+template <class P> HD void wire_ark_to_canonical(const uint64_t* ark, uint64_t* w) {
+  typedef Fp<P> F;
+  F::reduce(F::mul(F::repack_from64(ark), F::from_limbs(P::C_WIRE))).repack_to64(w);
+}
+// a < b over N words, without a branch: the borrow of a - b (the encoders' comparisons are the same instructions in every lane)
+template <int N> HD bool wire_less(const uint64_t* a, const uint64_t* b) {
+  uint64_t borrow = 0;
+#pragma unroll
+  for (int i = 0; i < N; i++) {
+    const uint64_t d = a[i] - b[i];
+    borrow = (uint64_t)(a[i] < b[i]) | (uint64_t)(d < borrow);
+  }
+  return borrow != 0;
+}
+template <class P, int K, bool COMPRESSED> struct WireEnc {
+  static constexpr int N = P::N64, XW = K * N;           // words of one component, of one coordinate
+  static constexpr int OUT_WORDS = COMPRESSED ? XW : 2 * XW;
+  static constexpr int ROW_WORDS = 2 * XW;
+  static constexpr uint64_t FLAG_INF = 0x40ull << 56, FLAG_NEG = 0x80ull << 56;
+  // component C of x and of y to canonical words (a template, not a loop: every index into the lane's row is a constant)
+  template <int C> HD static void component(const uint64_t* in, uint64_t* out, uint64_t* y) {
+    wire_ark_to_canonical<P>(in + C * N, out + C * N);
+    if constexpr (COMPRESSED) wire_ark_to_canonical<P>(in + XW + C * N, y + C * N);
+    else wire_ark_to_canonical<P>(in + XW + C * N, out + XW + C * N);
+  }
+  HD static WireStatus row(const uint64_t* in, bool inf, bool ark_zero, uint64_t* out) {
+    uint64_t x_or = 0, y_or = 0, y_one = 0;                // y_one: the difference of y from (1, 0 ...) in Montgomery form
+    uint64_t one[N];
+    Fp<P>::from_limbs(P::C_OUT).repack_to64(one);          // 2^(64 N) mod q in the field's own limbs: the compiler folds it
+    bool in_range = true;
+#pragma unroll
+    for (int j = 0; j < XW; j++) {
+      x_or |= in[j];
+      y_or |= in[XW + j];
+      y_one |= in[XW + j] ^ (j < N ? one[j] : 0);
+    }
+#pragma unroll
+    for (int c = 0; c < 2 * K; c++) in_range = in_range & wire_less<N>(in + c * N, P::P64);
+#pragma unroll
+    for (int j = 0; j < OUT_WORDS; j++) out[j] = 0;
+    if (inf || (x_or | y_or) == 0 || (ark_zero && x_or == 0 && y_one == 0)) { out[OUT_WORDS - 1] = FLAG_INF; return WIRE_INFINITY; }
+    if (!in_range) return WIRE_INVALID;
+    uint64_t y[XW];
+    component<0>(in, out, y);
+    if constexpr (K == 2) component<1>(in, out, y);
+    if constexpr (COMPRESSED) {
+      // y > -y  <=>  canonical(y) > (q - 1) / 2; Fq2 is ordered by c1 first, then c0 (wire_lex_largest), and y = 0 is not larger
+      bool larger = wire_less<N>(P::PM1_HALF64, y);
+      if constexpr (K == 2) {
+        uint64_t c1_or = 0;
+#pragma unroll
+        for (int j = 0; j < N; j++) c1_or |= y[N + j];
+        const bool larger1 = wire_less<N>(P::PM1_HALF64, y + N);
+        larger = c1_or ? larger1 : larger;
+      }
+      if (larger) out[OUT_WORDS - 1] |= FLAG_NEG;
+    }
+    return WIRE_OK;
+  }
+};
+typedef WireEnc<P377, 1, true> WireEncG1c;   typedef WireEnc<P377, 1, false> WireEncG1u;
+typedef WireEnc<P377, 2, true> WireEncG2c;   typedef WireEnc<P377, 2, false> WireEncG2u;
+
 // ---- host: the constants (one search for the smallest non-residue, three exponentiations; first use only)
 inline WireConsts wire_consts_build() {
   WireConsts k;

@@ -200,12 +200,31 @@ template <int B, bool COMPRESSED> HD WireStatus w761_decode_row(const uint8_t* i
   return st;
 }
 
+// ---- encoding (GroupAffine::serialize / serialize_uncompressed): wire.h's WireEnc over the 12-word field.  G1 and G2 share the
+// coordinate field and the encoder never touches the curve constant, so one instantiation per form serves both groups.
+typedef WireEnc<P761, 1, true> W761EncC;     // 24 u64 -> 12 words (96 B)
+typedef WireEnc<P761, 1, false> W761EncU;    // 24 u64 -> 24 words (192 B)
+// an arkworks Jacobian point (X, Y, Z: 36 u64, what groth16_prove_* returns) -> its compressed encoding; Z == 0 is the identity
+HD WireStatus w761_encode_jacobian(const uint64_t* xyz, uint64_t* out12) {
+  const Fw761 Z = Fw761::norm(Fw761::from_ark(xyz + 24));
+  uint64_t row[24];
+  for (int j = 0; j < 24; j++) row[j] = 0;
+  const bool inf = Z.is_zero_mod_p();
+  if (!inf) {
+    const Fw761 zi = Fw761::norm(Fw761::inv(Z)), zi2 = Fw761::sqr(zi);
+    Fw761::mul(Fw761::from_ark(xyz), zi2).to_ark(row);
+    Fw761::mul(Fw761::from_ark(xyz + 12), Fw761::mul(zi2, zi)).to_ark(row + 12);
+  }
+  return W761EncC::row(row, inf, false, out12);
+}
+
 // ---- host: the layout of a serialized ark-groth16 0.1 ProvingKey<BW6_761> (its derive order; Vec = u64 LE length, then the elements):
 //   vk { alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1: Vec<G1> }, beta_g1, delta_g1,
 //   a_query: Vec<G1>, b_g1_query: Vec<G1>, b_g2_query: Vec<G2>, h_query: Vec<G1>, l_query: Vec<G1>
 // The length fields are input: no count * size is formed before count is known to fit what is left.
 enum W761Layout { W761_PT = 0, W761_LEN = 1, W761_ABC = 2, W761_A = 4, W761_BG1 = 6, W761_BG2 = 8, W761_H = 10, W761_L = 12, W761_BETA_G1 = 14, W761_NPOINTS = 15 };
 constexpr int W761_ERR_TRUNCATED = 30, W761_ERR_TRAILING = 31, W761_ERR_LENGTH = 32, W761_ERR_POINT = 33;
+constexpr int W761_ERR_CAPACITY = 35;             // the key writer: the output buffer is smaller than the serialization (34 is the R1CS loader's)
 inline int w761_key_layout(const uint8_t* bytes, size_t len, int form, uint64_t out[16]) {
   if (!out || (!bytes && len) || form < 0 || form > 2) return 2;
   for (int i = 0; i < 16; i++) out[i] = 0;
@@ -240,6 +259,18 @@ inline int w761_key_layout(const uint8_t* bytes, size_t len, int form, uint64_t 
   out[W761_PT] = P;
   out[W761_LEN] = len;
   out[W761_NPOINTS] = points;
+  return 0;
+}
+
+// The byte length of what w761_key_layout parses, from the counts (the key writer's side): form 0 = 96 B points, 1 = 192 B; vk_only: the
+// VerifyingKey prefix alone (n_vars and n_h are not looked at).  l_query has n_vars - n_inputs rows.  2: no such key, or a length past 64 bits.
+inline int w761_key_size(uint64_t n_inputs, uint64_t n_vars, uint64_t n_h, int form, int vk_only, uint64_t* len) {
+  if (!len || form < 0 || form > 1 || n_inputs == 0 || (!vk_only && n_inputs > n_vars)) return 2;
+  const unsigned __int128 P = form == 0 ? 96 : 192;
+  unsigned __int128 t = (4 + (unsigned __int128)n_inputs) * P + 8;
+  if (!vk_only) t += (2 + 3 * (unsigned __int128)n_vars + n_h + (n_vars - n_inputs)) * P + 5 * 8;
+  if (t > UINT64_MAX) return 2;
+  *len = (uint64_t)t;
   return 0;
 }
 

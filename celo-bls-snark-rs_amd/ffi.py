@@ -45,6 +45,11 @@ EXPORTS = [
     "decompress_bw6_761_g1", "decompress_bw6_761_g2", "decompress_bw6_761_g1_dev", "decompress_bw6_761_g2_dev",
     "decode_uncompressed_bw6_761_g1", "decode_uncompressed_bw6_761_g2", "groth16_key_layout_bw6_761", "groth16_load_key_bw6_761_serialized",
     "celo_amd_wire761_last_timings",
+    "compress_bls12_377_g1", "compress_bls12_377_g2", "compress_bw6_761", "compress_bls12_377_g1_dev", "compress_bls12_377_g2_dev", "compress_bw6_761_dev",
+    "encode_uncompressed_bls12_377_g1", "encode_uncompressed_bls12_377_g2", "encode_uncompressed_bw6_761",
+    "encode_uncompressed_bls12_377_g1_dev", "encode_uncompressed_bls12_377_g2_dev", "encode_uncompressed_bw6_761_dev",
+    "groth16_serialized_key_size_bw6_761", "groth16_serialize_key_bw6_761", "groth16_serialize_proof_bw6_761",
+    "celo_amd_wire_encode_last_ms", "celo_amd_wire_encode_key_timings",
     "normalize_bls12_377_g1", "normalize_bls12_377_g2",
     "fixed_base_mul_bls12_377_g1", "fixed_base_mul_bls12_377_g2", "fixed_base_mul_bw6_761_g1", "fixed_base_mul_bw6_761_g2",
     "fixed_base_mul_bls12_377_g1_dev", "fixed_base_mul_bls12_377_g2_dev", "fixed_base_mul_bw6_761_g1_dev", "fixed_base_mul_bw6_761_g2_dev",
@@ -792,6 +797,113 @@ def decode_uncompressed(group, data, check=True):
     if rc != 0:
         raise RuntimeError("%s failed with code %d" % (fn, rc))
     return xy, st
+
+
+# ---- encoding into the wire form (include/celo_bls_amd.h: compress_*, encode_uncompressed_*, groth16_serialize_*)
+KEY_ERR_CAPACITY = 35
+_ENCODE_GROUPS = {"g1": (12, 48, "bls12_377_g1"), "g2": (24, 96, "bls12_377_g2"), "bw6_761": (24, 96, "bw6_761"),
+                  "bw6_761_g1": (24, 96, "bw6_761"), "bw6_761_g2": (24, 96, "bw6_761")}
+
+
+class WireEncodeError(RuntimeError):
+    def __init__(self, fn, code):
+        super().__init__("%s failed with code %d" % (fn, code))
+        self.code = code
+
+
+def _encode_fn(group, compressed, dev):
+    words, size, suffix = _ENCODE_GROUPS[group]
+    return words, size * (1 if compressed else 2), ("compress_" if compressed else "encode_uncompressed_") + suffix + ("_dev" if dev else "")
+
+
+def encode_points(group, rows, inf=None, compressed=True):
+    """Bulk encoding of affine points (compress_* / encode_uncompressed_*).  group: "g1" / "g2" (BLS12-377, rows (n, 12) / (n, 24) uint64
+    arkworks Montgomery limbs) or "bw6_761" (both groups of BW6-761, rows (n, 24); "bw6_761_g1" / "bw6_761_g2" are accepted as names of the
+    same); inf: uint8 (n,) or None.  Returns (out (n, 48 | 96 | 192) uint8, status (n,) uint8: 0 encoded, 1 identity, 2 not a field element)."""
+    words, size, fn = _encode_fn(group, compressed, False)
+    r = _rows(rows, words)
+    n = r.shape[0]
+    i = None if inf is None else np.ascontiguousarray(inf, dtype=np.uint8).reshape(n)
+    out = np.zeros((n, size), dtype=np.uint8)
+    st = np.zeros(n, dtype=np.uint8)
+    rc = getattr(lib(), fn)(_p(r), _p(i), C.c_size_t(n), _p(out), _p(st))
+    if rc != 0:
+        raise WireEncodeError(fn, rc)
+    return out, st
+
+
+def encode_points_dev(group, d_rows, d_inf, n, d_out, d_status, compressed=True, stream=0):
+    """The same on device buffers (integer device addresses; d_inf 0 / None: no identity bytes), on `stream`."""
+    fn = _encode_fn(group, compressed, True)[2]
+    rc = getattr(lib(), fn)(C.c_void_p(d_rows), C.c_void_p(d_inf or None), C.c_size_t(n), C.c_void_p(d_out), C.c_void_p(d_status), C.c_void_p(stream))
+    if rc != 0:
+        raise WireEncodeError(fn, rc)
+
+
+class KeySerializeError(RuntimeError):
+    def __init__(self, code, out_len=None, first_bad_point=None):
+        super().__init__("groth16_serialize_key_bw6_761 failed with code %d%s" % (code, "" if first_bad_point is None else " (first bad point: %d)" % first_bad_point))
+        self.code = code
+        self.out_len = out_len
+        self.first_bad_point = first_bad_point
+
+
+def groth16_serialized_key_size(n_inputs, n_vars, n_h, form=0, vk_only=False):
+    """Byte length of the serialized ProvingKey<BW6_761> (or VerifyingKey) with these counts (groth16_serialized_key_size_bw6_761); no device call."""
+    ln = C.c_uint64(0)
+    rc = lib().groth16_serialized_key_size_bw6_761(C.c_size_t(n_inputs), C.c_size_t(n_vars), C.c_size_t(n_h), C.c_int(form), C.c_int(1 if vk_only else 0), C.byref(ln))
+    if rc != 0:
+        raise KeySerializeError(rc)
+    return ln.value
+
+
+def _key_rows(x, names):
+    """a flat buffer of 24-u64 rows, or the dict groth16_setup returns for it (sections concatenated in serialization order)"""
+    if isinstance(x, dict):
+        x = np.concatenate([np.ascontiguousarray(x[k], dtype=np.uint64).reshape(-1) for k in names])
+    return _rows(x, 24)
+
+
+def groth16_serialize_key(vk, rows=None, n_vars=0, n_h=0, form=0, cap=None):
+    """ProvingKey::<BW6_761>::serialize (form 0) / serialize_uncompressed (1) of groth16_setup's "vk" and "rows" (dicts or flat buffers), or
+    VerifyingKey::serialize when rows is None (groth16_serialize_key_bw6_761).  cap: the output buffer's size (default: what is needed).
+    Returns bytes; raises KeySerializeError (.code 35 with .out_len, 33 with .first_bad_point)."""
+    v = _key_rows(vk, ("alpha_g1", "beta_g2", "gamma_g2", "delta_g2", "gamma_abc_g1"))
+    n_inputs = v.shape[0] - 4
+    r = None if rows is None else _key_rows(rows, ("beta_g1", "delta_g1", "a_query", "b_g1_query", "b_g2_query", "h_query", "l_query"))
+    if r is not None:
+        assert r.shape[0] == 2 + 3 * n_vars + n_h + (n_vars - n_inputs), "rows do not match n_vars / n_h"
+    need = groth16_serialized_key_size(n_inputs, n_vars, n_h, form, rows is None)
+    out = np.zeros(need if cap is None else cap, dtype=np.uint8)
+    ln, bad = C.c_uint64(0), C.c_uint64(0)
+    rc = lib().groth16_serialize_key_bw6_761(_p(v), C.c_size_t(n_inputs), _p(r), C.c_size_t(n_vars), C.c_size_t(n_h), C.c_int(form), _p(out), C.c_size_t(out.size),
+                                             C.byref(ln), C.byref(bad))
+    if rc != 0:
+        raise KeySerializeError(rc, ln.value, bad.value if rc == KEY_ERR_POINT else None)
+    return out[:ln.value].tobytes()
+
+
+def groth16_serialize_proof(a_xyz, b_xyz, c_xyz):
+    """Proof::<BW6_761>::serialize (288 B) from the three Jacobian points groth16_prove / ProvingKey.prove return (groth16_serialize_proof_bw6_761)."""
+    pts = [np.ascontiguousarray(x, dtype=np.uint64).reshape(36) for x in (a_xyz, b_xyz, c_xyz)]
+    out = np.zeros(288, dtype=np.uint8)
+    rc = lib().groth16_serialize_proof_bw6_761(_p(pts[0]), _p(pts[1]), _p(pts[2]), _p(out))
+    if rc != 0:
+        raise RuntimeError("groth16_serialize_proof_bw6_761 failed with code %d" % rc)
+    return out.tobytes()
+
+
+def wire_encode_last_ms():
+    ms = C.c_float(0)
+    assert lib().celo_amd_wire_encode_last_ms(C.byref(ms)) == 0
+    return ms.value
+
+
+def wire_encode_key_timings():
+    """the last groth16_serialize_key call: (rows to the device, encoding, bytes back) in ms"""
+    ms = (C.c_float * 3)()
+    assert lib().celo_amd_wire_encode_key_timings(ms) == 0
+    return tuple(ms)
 
 
 def wire761_last_timings():

@@ -394,6 +394,53 @@ int groth16_load_key_bw6_761_serialized(const uint8_t* bytes, size_t len, int fo
  * transfer of the bytes, decoding (all sections and the rejection scan) and fixed-base table build */
 int celo_amd_wire761_last_timings(float ms[4]);
 
+/* ---- bulk ENCODING into the same wire form: n affine points (arkworks Montgomery limbs, the rows the decoders, normalize_* and the MSM
+ * entry points use) -> n encodings, one point per GPU lane.  Replaces n calls of GroupAffine::serialize (compress_*: x little-endian with
+ * 0x80 on the last byte when y is the lexicographically larger of (y, -y)) or serialize_uncompressed (encode_uncompressed_*: x then y, no
+ * sign bit) - ark-serialize 0.1 CanonicalSerialize; the identity is all-zero bytes with 0x40 on the last byte in both forms.
+ * A row is the identity when inf != NULL && inf[i] != 0, or when the row is all zero (what normalize_* and the decoders emit; never a
+ * point of these curves).  A row (0, 1) is a pair of field elements like any other here.  inf may be NULL.
+ * status[i]: 0 encoded; 1 identity written; 2 a coordinate's limbs are not below q - not a field element: the output row is all zero,
+ * no flag.  Neither the curve equation nor the subgroup is checked, as arkworks checks neither when it serializes.
+ * compress_bw6_761 / encode_uncompressed_bw6_761 serve G1 and G2 of BW6-761 (one coordinate field, and the encoding does not involve the
+ * curve constant).  Returns 0; 2: n > 2^31 - 1, a required pointer NULL, or a _dev rows / output pointer that is not 8-byte aligned (the
+ * kernels move 64-bit words); 10: allocation failure; 100: no device.  n == 0 returns 0.  The _dev forms take device pointers and run
+ * on hip_stream (0: the null stream); calls are serialised per process. */
+int compress_bls12_377_g1(const uint64_t* rows /* n x 12 */, const uint8_t* inf, size_t n, uint8_t* out /* n x 48 */, uint8_t* status /* n */);
+int compress_bls12_377_g2(const uint64_t* rows /* n x 24 */, const uint8_t* inf, size_t n, uint8_t* out /* n x 96 */, uint8_t* status /* n */);
+int encode_uncompressed_bls12_377_g1(const uint64_t* rows /* n x 12 */, const uint8_t* inf, size_t n, uint8_t* out /* n x 96 */, uint8_t* status /* n */);
+int encode_uncompressed_bls12_377_g2(const uint64_t* rows /* n x 24 */, const uint8_t* inf, size_t n, uint8_t* out /* n x 192 */, uint8_t* status /* n */);
+int compress_bw6_761(const uint64_t* rows /* n x 24 */, const uint8_t* inf, size_t n, uint8_t* out /* n x 96 */, uint8_t* status /* n */);
+int encode_uncompressed_bw6_761(const uint64_t* rows /* n x 24 */, const uint8_t* inf, size_t n, uint8_t* out /* n x 192 */, uint8_t* status /* n */);
+int compress_bls12_377_g1_dev(const uint64_t* d_rows, const uint8_t* d_inf, size_t n, uint8_t* d_out, uint8_t* d_status, void* hip_stream);
+int compress_bls12_377_g2_dev(const uint64_t* d_rows, const uint8_t* d_inf, size_t n, uint8_t* d_out, uint8_t* d_status, void* hip_stream);
+int encode_uncompressed_bls12_377_g1_dev(const uint64_t* d_rows, const uint8_t* d_inf, size_t n, uint8_t* d_out, uint8_t* d_status, void* hip_stream);
+int encode_uncompressed_bls12_377_g2_dev(const uint64_t* d_rows, const uint8_t* d_inf, size_t n, uint8_t* d_out, uint8_t* d_status, void* hip_stream);
+int compress_bw6_761_dev(const uint64_t* d_rows, const uint8_t* d_inf, size_t n, uint8_t* d_out, uint8_t* d_status, void* hip_stream);
+int encode_uncompressed_bw6_761_dev(const uint64_t* d_rows, const uint8_t* d_inf, size_t n, uint8_t* d_out, uint8_t* d_status, void* hip_stream);
+/* ---- the writers of what groth16_load_key_bw6_761_serialized and Seam A's verify read.
+ * groth16_serialize_key_bw6_761: ProvingKey::<BW6_761>::serialize (form 0) / serialize_uncompressed (form 1) from the out_vk / out_rows
+ * buffers of groth16_setup_bw6_761 (vk: alpha_g1, beta_g2, gamma_g2, delta_g2, n_inputs rows of gamma_abc_g1; rows: beta_g1, delta_g1,
+ * a_query[n_vars], b_g1_query[n_vars], b_g2_query[n_vars], h_query[n_h], l_query[n_vars - n_inputs]; 24 u64 each), in the layout
+ * groth16_key_layout_bw6_761 parses.  rows == NULL: VerifyingKey::serialize of vk alone (n_vars and n_h are not looked at).  The rows cross
+ * to the device once, every contiguous run of points is encoded there straight to its byte offset, the bytes cross back once.  Here a row
+ * (0, 1 in Montgomery form) - arkworks' GroupAffine::zero(), what groth16_setup_* emits - is the identity too, as for groth16_load_key_*.
+ * *out_len is the size of the serialization whenever the counts are valid.  Returns 0; 2: a NULL vk / out / out_len, form not 0 or 1,
+ * n_inputs == 0, n_inputs > n_vars, more than 2^31 - 1 points; 35: cap < *out_len; 33: a row that is no pair of field elements (limbs not
+ * below q), *first_bad_point (may be NULL) = its index in serialization order, the index space of groth16_load_key_bw6_761_serialized -
+ * with 35 and with 33 nothing is written to out; 10: allocation failure; 100: no device.  Nothing is kept allocated on any path.
+ * groth16_serialized_key_size_bw6_761: that size from the counts alone (no device call); vk_only != 0: the VerifyingKey's.
+ * groth16_serialize_proof_bw6_761: Proof::serialize (A, B, C compressed, 288 B: the `proof` argument of verify) from the arkworks Jacobian
+ * points groth16_prove_* returns; Z == 0 encodes the identity.  Host only (three points, the same encoder).  2: a NULL pointer. */
+int groth16_serialized_key_size_bw6_761(size_t n_inputs, size_t n_vars, size_t n_h, int form, int vk_only, uint64_t* len);
+int groth16_serialize_key_bw6_761(const uint64_t* vk, size_t n_inputs, const uint64_t* rows /* NULL: the VerifyingKey alone */, size_t n_vars, size_t n_h,
+                                  int form /* 0 compressed, 1 uncompressed */, uint8_t* out, size_t cap, uint64_t* out_len, uint64_t* first_bad_point /* NULL allowed */);
+int groth16_serialize_proof_bw6_761(const uint64_t a_xyz[36], const uint64_t b_xyz[36], const uint64_t c_xyz[36], uint8_t out[288]);
+/* kernel time in ms of the last compress_* / encode_uncompressed_* call (or of the last key writer's launches); the last
+ * groth16_serialize_key_bw6_761 call's three phases: rows to the device, encoding, bytes back (what tools/bench_wire_encode.py reports). */
+int celo_amd_wire_encode_last_ms(float* ms);
+int celo_amd_wire_encode_key_timings(float ms[3]);
+
 /* ---- batched hash-to-G1, DIRECT hasher: n messages per launch, one per GPU lane.
  * Replaces n calls of TryAndIncrement<DirectHasher, G1>::hash_with_attempt(domain, message, extra_data)
  * (crates/bls-crypto/src/hash_to_curve/try_and_increment.rs:87-139; DirectHasher = Blake2s CRH + Blake2Xs XOF,

@@ -8,6 +8,8 @@ arkworks hands over / expects x * 2^(64*N) mod p in 64-bit limbs; conversion is 
 multiplication by a constant each way plus a bit repack:
    in :  dev = montmul_d(repack(ark), C_IN )   with C_IN  = 2^(2*W*L - 64*N) mod p   (raw limbs)
    out:  ark = repack(montmul_d(dev, C_OUT))   with C_OUT = 2^(64*N) mod p             (raw limbs)
+and straight to the canonical integer the wire format writes (wire.h / wire761.h encoders), without passing through the device form:
+   x   = repack(montmul_d(repack(ark), C_WIRE)) with C_WIRE = 2^(W*L - 64*N) mod p     (raw limbs)
 """
 import os
 
@@ -56,6 +58,7 @@ def emit(name, p, W, L, N64, subs):
     s += arr("C_IN", limbs(pow(2, 2 * W * L - 64 * N64, p), W, L))
     s += arr("C_OUT", limbs(pow(2, 64 * N64, p), W, L))
     s += arr("RAW_ONE", limbs(1, W, L))
+    s += arr("C_WIRE", limbs(pow(2, W * L - 64 * N64, p), W, L))  # arkworks Montgomery limbs -> canonical integer in one product
     s += arr("R2", limbs(pow(Rd, 2, p), W, L))  # canonical int -> device form: montmul(x, R2)
     for (K, m) in subs:
         s += arr(f"KP{K}_M{m}", redundant(K * p, W, L, m))
