@@ -540,7 +540,7 @@ int celo_amd_msm_host_chunk_plan(uint64_t n, int chunks, int head_split, int tai
   return (int)celo::host_chunk_plan((size_t)n, (uint32_t)chunks, (uint32_t)head_split, (uint32_t)tail_split, *cm, lens);
 }
 int celo_amd_msm_set_window_bits(int group, int c) {
-  if (c != 0 && (c < 4 || c > 16)) return 1;
+  if (c != 0 && (c < 3 || c > 16)) return 1;
   return by_group(group, 1, [&](auto g) { return MsmAuxApi<typename decltype(g)::type>::set_c(c); });
 }
 int celo_amd_sum_jacobian_bls12_377_g1(const uint64_t* j, size_t k, uint64_t* out) { return MsmAuxApi<G1_377>::sum_jac(j, k, out); }

@@ -39,6 +39,14 @@ __global__ void __launch_bounds__(256) k_scalar_or(const uint32_t* __restrict__ 
   __syncthreads();
   if (threadIdx.x < SW && blk[threadIdx.x]) atomicOr(out + threadIdx.x, blk[threadIdx.x]);
 }
+// A scalar is its container modulo 2^SCALAR_BITS: the bits from Fr::MODULUS_BITS up (253..255 of BigInteger256, 377..383 of BigInteger384) are
+// ignored, as on the single-MSM paths (msm_sort.h k_digits, k_glv_expand below) and in ark-ec.  The batched windows reach past them -
+// (SCALAR_BITS + c) / c windows of c bits cover 255..259 bits on BLS12-377 - so the top word is cleared where it is loaded (k_batch_sort,
+// k_gls_expand) and where the longest scalar is measured (run_batch, on k_scalar_or's result).  The 4-word containers are the 64-bit GLS
+// digits: nothing to clear.
+template <int SW> struct BatchTopWord { static constexpr uint32_t MASK = 0xffffffffu; };
+template <> struct BatchTopWord<8> { static constexpr uint32_t MASK = (1u << (253 - 224)) - 1u; };
+template <> struct BatchTopWord<12> { static constexpr uint32_t MASK = (1u << (377 - 352)) - 1u; };
 template <int SW, int CB, int PT>
 __global__ void __launch_bounds__(256) k_batch_sort(const uint32_t* __restrict__ scalars, const uint8_t* __restrict__ inf,
                                                     const uint32_t* __restrict__ offsets, uint32_t* __restrict__ sorted,
@@ -66,6 +74,7 @@ __global__ void __launch_bounds__(256) k_batch_sort(const uint32_t* __restrict__
         uint4 v = sp[k];
         s[q][4 * k] = v.x; s[q][4 * k + 1] = v.y; s[q][4 * k + 2] = v.z; s[q][4 * k + 3] = v.w;
       }
+      if constexpr (BatchTopWord<SW>::MASK != 0xffffffffu) s[q][SW - 1] &= BatchTopWord<SW>::MASK;
     }
   }
 #pragma unroll 1
@@ -317,7 +326,11 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
   for (uint32_t t = blockIdx.y * 64u + threadIdx.x; t < n; t += gridDim.y * 64u) {
     const uint64_t* s = ark + (size_t)(lo + t) * 2 * IO::ARK64;
     uint32_t d[4][2];
-    gls_digits_base_x<NW, ND>(scalars + (size_t)(lo + t) * 8, d);
+    uint32_t k[NW];
+#pragma unroll
+    for (int i = 0; i < NW; i++) k[i] = scalars[(size_t)(lo + t) * 8 + i];
+    if constexpr (NW == 8) k[7] &= BatchTopWord<8>::MASK;      // (fewer words: the caller measured the scalars without those bits, and they are not read)
+    gls_digits_base_x<NW, ND>(k, d);
     const uint8_t fl = inf ? inf[lo + t] : 0;
 #pragma unroll
     for (int j = 0; j < 4; j++) {

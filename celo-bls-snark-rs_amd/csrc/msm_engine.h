@@ -795,7 +795,7 @@ template <class G> class MsmEngine {
   int batch_bits = 0;   // length of the longest scalar of the last batched call
   // bits_hint > 0: the length of the longest scalar of the NEXT batched call, measured by the caller on the same scalars (spares the
   // k_scalar_or round trip: with the chip full of another engine's accumulation that small kernel and its synchronisation waited 16 ms
-  // inside batch_verify_strict, and the G1 leg was enqueued only then); measured_bits: what the last call used, before clamping
+  // inside batch_verify_strict, and the G1 leg was enqueued only then); measured_bits: what the last call used (bits from SCALAR_BITS up not counted)
   int bits_hint = 0, measured_bits = 0;
   int run_batch_host(const uint64_t* bases, const uint8_t* inf, const uint64_t* scalars, const uint32_t* offsets, size_t m,
                      uint64_t* out, hipStream_t stream) {
@@ -865,7 +865,7 @@ template <class G> class MsmEngine {
     // a Horner chain of 66 doublings instead of 140.
     const int gls_max = (GlsExpand<G>::AVAILABLE && (gls_subgroup_points || gls_force) && use_gls) ? 4 : 1;
     auto gls_digits = [&](int bits) {
-      if (gls_max == 1 || bits <= 64 || bits > G::SCALAR_BITS) return 1;
+      if (gls_max == 1 || bits <= 64) return 1;
       const int nd_ = bits <= 126 ? 2 : bits <= 189 ? 3 : 4;
       return (size_t)nd_ * max_n <= BATCH_MAX_N ? nd_ : 1;
     };
@@ -918,15 +918,17 @@ template <class G> class MsmEngine {
         uint32_t h_or[SW];
         HIP_TRY(hipMemcpyAsync(h_or, A0 + o_or, SW * 4, hipMemcpyDeviceToHost, stream), 1);
         HIP_TRY(hipStreamSynchronize(stream), 1);
+        static_assert(BatchTopWord<SW>::MASK == (1u << (G::SCALAR_BITS - 32 * (SW - 1))) - 1u, "the container's bits from SCALAR_BITS up");
+        h_or[SW - 1] &= BatchTopWord<SW>::MASK;     // not part of any scalar (msm_batch.h): they neither add windows nor switch the split off
         for (int k = SW - 1; k >= 0; k--) if (h_or[k]) { bits = 32 * k + 32 - __builtin_clz(h_or[k]); break; }
       }
+      if (bits > G::SCALAR_BITS) bits = G::SCALAR_BITS;     // (a caller's hint)
       measured_bits = bits;
-      if (bits > G::SCALAR_BITS && gls_digits(bits) == 1) bits = G::SCALAR_BITS;
       batch_bits = bits;
     }
     const int nd = gls_digits(batch_bits);
     const uint32_t eff_max_n = (uint32_t)nd * max_n, eff_total = (uint32_t)nd * total_pts;
-    const int eff_bits = nd > 1 ? 64 : (batch_bits > G::SCALAR_BITS ? G::SCALAR_BITS : batch_bits);
+    const int eff_bits = nd > 1 ? 64 : batch_bits;
     const int c = window_for(eff_max_n);
     const uint32_t B = 1u << (c - 1);
     const int nw = (eff_bits + c) / c;

@@ -440,7 +440,7 @@ template <class G> int MsmAuxApi<G>::timings(float ms[5], int cfg[3]) {
 template <class G> void MsmAuxApi<G>::note_big_call() { MsmAuxUnit<G>::last_was_batch().store(0); }
 template <class G> int MsmAuxApi<G>::set_c(int c) {
   MsmAuxUnit<G>::force_c().store(c);
-  MsmApi<G>::big_set_c(c);
+  MsmApi<G>::big_set_c(c == 3 ? 0 : c);      // 3 bits is a window of the batched kernels only (3..7 there); the large pipeline stays automatic
   return 0;
 }
 template <class G> int MsmAuxApi<G>::gen_points(void* d_out, size_t n, uint64_t seed, const uint64_t* gen_xy, size_t ngens, uint32_t per, void* st) {

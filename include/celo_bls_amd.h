@@ -170,14 +170,21 @@ int celo_amd_msm_fixed_info(const void* handle, size_t* n, int* window_bits, int
  * (offsets has m+1 entries), out_xyz holds m Jacobian results back to back.  This is the shape of Batch::verify
  * (crates/bls-crypto/src/bls/batch.rs:69,76 — one G2 and one G1 MSM over the batch's signers) when
  * batch_verify_strict (crates/bls-snark-sys/src/signatures.rs:343-400) is handed many batches; the reference loops over
- * them serially (signatures.rs:358).  Instances of up to 1024 points run on the batched kernels; larger ones are
- * processed one at a time on the large-MSM pipeline. */
+ * them serially (signatures.rs:358).  Instances of up to 1024 points run on the batched kernels; a call with a larger instance
+ * (or with no point at all) is processed one instance at a time on the large-MSM pipeline.
+ * Dispatch of the batched kernels (reported by celo_amd_msm_last_timings): the window c is 3 bits, one more
+ * from 128, 256, 512 and 1024 points in the call's largest instance; the number of windows is (bits + c) / c for bits = the
+ * length of the longest scalar present.  A scalar is its container modulo 2^SCALAR_BITS (253 for BLS12-377, 377 for BW6-761):
+ * container bits from there up are ignored - they neither change the result nor count towards `bits` - on the batched kernels as
+ * on the large pipeline and on msm_<group>. */
 int msm_batch_bls12_377_g1(const uint64_t* bases_xy, const uint8_t* inf, const uint64_t* scalars, const uint32_t* offsets, size_t m, uint64_t* out_xyz /* m*18 */);
 int msm_batch_bls12_377_g2(const uint64_t* bases_xy, const uint8_t* inf, const uint64_t* scalars, const uint32_t* offsets, size_t m, uint64_t* out_xyz /* m*36 */);
 /* The same call for bases the caller vouches to be elements of the prime-order subgroup G2 - public keys: a PublicKey of the reference is
  * one by construction (checked deserialisation crates/bls-crypto/src/bls/public.rs:123-149, secret keys, sums) - which is what
  * Batch::verify hands over (batch.rs:69).  Same result; the library may then split every scalar with the endomorphism psi (psi(P) = [x]P
- * on G2): an instance of n points with up to 253-bit scalars becomes one of up to 4 n points with 64-bit scalars (csrc/msm.h, k_gls_expand).
+ * on G2): an instance of n points with up to 253-bit scalars becomes one of up to 4 n points with 64-bit scalars (csrc/msm.h, k_gls_expand):
+ * nd = 2 digits for a longest scalar of 65..126 bits, 3 up to 189, 4 beyond, wherever nd times the largest instance stays within 1024 points
+ * (the window then follows the expanded size and there are (64 + c) / c windows); no split up to 64 bits or beyond that size.
  * For a base outside the subgroup the result is unspecified (use msm_batch_bls12_377_g2, which is VariableBaseMSM on any curve point). */
 int msm_batch_bls12_377_g2_subgroup(const uint64_t* bases_xy, const uint8_t* inf, const uint64_t* scalars, const uint32_t* offsets, size_t m, uint64_t* out_xyz /* m*36 */);
 int msm_batch_bw6_761_g1(const uint64_t* bases_xy, const uint8_t* inf, const uint64_t* scalars, const uint32_t* offsets, size_t m, uint64_t* out_xyz /* m*36 */);
@@ -496,7 +503,8 @@ int celo_amd_selftest_accumulate(int group, const uint64_t* gen_xy, uint32_t run
  * bodies in register-resident loops (csrc/unit_ubench.hip; ~0.3 s).  out[0..3] = 1e9 products/s: Fq(BLS12-377) mul, sqr, Fq(BW6-761) mul,
  * sqr; out[4] = shader clock in MHz during the first loop (s_memtime against the 100 MHz s_memrealtime); out[5..8] = the loops' kernel ms. */
 int celo_amd_ubench_fp(float out[9]);
-/* Forces the Pippenger window size (0 = automatic) — tuning and test hook. */
+/* Forces the Pippenger window size (0 = automatic) — tuning and test hook.  c = 4..16 for the large pipeline; the batched kernels
+ * (msm_batch_*) clamp it to their 3..7, and c = 3 applies to them alone (the large pipeline stays automatic). */
 int celo_amd_msm_set_window_bits(int group, int c);
 /* Host-pointer entry points (msm_<group>, from 2^18 terms - 2^17 when the count is set here): the number of index chunks in which scalars and bases cross PCIe while the
  * chunks already on the device are sorted and accumulated (csrc/msm.h HostIn).  0 = the unpipelined form (three transfers, then
