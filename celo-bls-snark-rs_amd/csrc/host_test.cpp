@@ -10,6 +10,7 @@
 #include "wire.h"
 #include "wire761.h"
 #include "fixed_base.h"
+#include "groth16_verify.h"
 #include "r1cs.h"
 #include "hash_direct.h"
 #include "host64.h"
@@ -589,6 +590,71 @@ void ht_fixed_base_mul(int group, const uint64_t* gen, const uint64_t* sc, size_
   else if (group == 1) fbm_host<Fp2<P377>, 4>(gen, sc, n, c, 253, out, inf);
   else fbm_host<Fp<P761>, 6>(gen, sc, n, c, 377, out, inf);
 }
+// ---- groth16_verify.h: the lane routines of unit_groth16_verify.hip's kernels in host loops.
+// ht_g16_input_row: abc n_abc x 24 u64 (affine arkworks limbs, none the identity), inputs n x (n_abc - 1) x 6 canonical u64, window bits c ->
+// out n x 24 (a zero row and inf = 1 for the identity), status[i] = 1 for a row with an input that is not below r.  The tables are built as
+// k_fbm_bases / k_fbm_table build them, one per base.
+void ht_g16_input_row(const uint64_t* abc, size_t n_abc, const uint64_t* inputs, size_t n, int c, uint64_t* out, uint8_t* inf, uint8_t* status) {
+  typedef Fp<P761> F;
+  constexpr int FW = F::WORDS;
+  const size_t n_in = n_abc - 1;
+  const int W = fb_windows(G16_SCALAR_BITS, c);
+  const uint32_t H = 1u << (c - 1), E = (uint32_t)W * H;
+  std::vector<uint32_t> table((size_t)(n_in ? n_in : 1) * E * 2 * FW), abc0(2 * FW);
+  std::vector<uint8_t> tinf((size_t)(n_in ? n_in : 1) * E);
+  fb_store_entry(abc0.data(), Affine<F>{F::norm(F::from_ark(abc)), F::norm(F::from_ark(abc + 12))});
+  for (size_t j = 0; j < n_in; j++) {
+    const uint64_t* gen = abc + (j + 1) * 24;
+    const Affine<F> g = {F::norm(F::from_ark(gen)), F::norm(F::from_ark(gen + 12))};
+    for (int w = 0; w < W; w++) {
+      Affine<F> b = {F::zero(), F::zero()};
+      const bool okb = fb_to_affine(fb_window_base(g, w, c), b);
+      for (uint32_t d = 1; d <= H; d++) {
+        const size_t e = j * E + (size_t)w * H + d - 1;
+        Affine<F> r = {F::zero(), F::zero()};
+        const bool ok = okb && fb_to_affine(fb_table_entry(b, d), r);
+        fb_store_entry(&table[e * 2 * FW], r);
+        tinf[e] = ok ? 0 : 1;
+      }
+    }
+  }
+  for (size_t i = 0; i < n; i++) {
+    uint32_t bad = 0;
+    const Xyzz<F> a = g16_input_row<F, 6>(inputs + i * n_in * 6, (uint32_t)n_in, abc0.data(), false, table.data(), tinf.data(), c, W, &bad);
+    Affine<F> r;
+    uint64_t* o = out + i * 24;
+    if (fb_to_affine(a, r)) { r.x.to_ark(o); r.y.to_ark(o + 12); inf[i] = 0; }
+    else { for (int k = 0; k < 24; k++) o[k] = 0; inf[i] = 1; }
+    status[i] = bad ? 1 : 0;
+  }
+}
+// ht_g16_scale: out[i] = (2^127 | low 127 bits of r2[i]) xy[i] for n affine points and n pairs of u64
+void ht_g16_scale(const uint64_t* xy, const uint64_t* r2, size_t n, uint64_t* out, uint8_t* inf) {
+  typedef Fp<P761> F;
+  for (size_t i = 0; i < n; i++) {
+    const Affine<F> p = {F::norm(F::from_ark(xy + i * 24)), F::norm(F::from_ark(xy + i * 24 + 12))};
+    uint64_t lo, hi;
+    g16_exponent(r2[2 * i], r2[2 * i + 1], lo, hi);
+    const Xyzz<F> a = g16_scale128(p, lo, hi);
+    Affine<F> r;
+    uint64_t* o = out + i * 24;
+    if (fb_to_affine(a, r)) { r.x.to_ark(o); r.y.to_ark(o + 12); inf[i] = 0; }
+    else { for (int k = 0; k < 24; k++) o[k] = 0; inf[i] = 1; }
+  }
+}
+// ht_g16_vk_parse: groth16_vk_load_bw6_761_serialized's host parse.  rows: (4 + n_abc) x 24 u64 with room for cap rows; *n_abc out
+int ht_g16_vk_parse(const uint8_t* bytes, size_t len, size_t cap, uint64_t* rows, uint8_t* inf, uint64_t* n_abc) {
+  std::vector<uint64_t> r;
+  std::vector<uint8_t> f;
+  const int rc = g16_vk_parse(bytes, len, r, f, nullptr);
+  if (rc) return rc;
+  if (f.size() > cap) return 2;
+  memcpy(rows, r.data(), r.size() * 8);
+  memcpy(inf, f.data(), f.size());
+  *n_abc = f.size() - 4;
+  return 0;
+}
+int ht_g16_window_bits(size_t n_in) { return g16_window_bits(n_in); }
 // the setup's scalar lists as unit_setup.hip lays them out: G1 [alpha, beta, delta, gamma_abc, a, b, h, l], G2 [beta, gamma, delta, b]
 extern "C++" {
 template <class FR> static void setup_host(const uint64_t* qa, const uint64_t* qb, const uint64_t* qc, size_t n_vars, size_t n_inputs, const uint64_t* zt,

@@ -16,4 +16,31 @@ int pairing_run_761(const uint64_t* g1, const uint8_t* inf1, const uint64_t* g2,
   if (!rc && m) { std::lock_guard<std::mutex> lk(tm_mu_761); tm_last_761 = e->tm; }
   return rc;
 }
+int pairing_stage_761(uint32_t k, size_t m, PairingStage* st) {
+  if (int rc = api_enter()) return rc;
+  typedef EnginePool<PairingEngine<PP761>>::Lease L;
+  L* l = new L(pool_761().lease());
+  PairingEngine<PP761>::Staged sg;
+  if ((*l)->stage(k, m, &sg)) { delete l; return 1; }
+  *st = {l, sg.d_g1, sg.d_g2, sg.d_i1, sg.d_i2, (*l)->own_stream()};
+  return 0;
+}
+int pairing_run_staged_761(PairingStage* st, const uint32_t* offsets, size_t m, uint8_t* is_one) {
+  typedef EnginePool<PairingEngine<PP761>>::Lease L;
+  L* l = (L*)st->lease;
+  if (!l) return 2;
+  int rc = 0;
+  if (offsets) {
+    rc = (*l)->run_staged(offsets, m, true, true, is_one, nullptr, 0, st->stream);
+    if (!rc && m) { std::lock_guard<std::mutex> lk(tm_mu_761); tm_last_761 = (*l)->tm; }
+  }
+  delete l;
+  st->lease = nullptr;
+  return rc;
+}
+int pairing_timings_761(float ms[4]) {
+  std::lock_guard<std::mutex> lk(tm_mu_761);
+  ms[0] = tm_last_761.miller; ms[1] = tm_last_761.product; ms[2] = tm_last_761.final_exp; ms[3] = tm_last_761.total;
+  return 0;
+}
 }  // namespace celo

@@ -247,6 +247,40 @@ int fixed_base_set_window(int c) {
 }
 void setup_last_timings(float ms[8]) { for (int i = 0; i < 8; i++) ms[i] = g_setup_ms[i]; }
 
+// The table of k_fbm_bases / k_fbm_table for each of n BW6-761 bases instead of one generator (the Groth16 verifier's gamma_abc rows,
+// unit_groth16_verify.hip): gens n x 24 u64 affine arkworks limbs and inf their identity flags, both on the HOST; d_table n x W 2^(c-1)
+// entries and d_tinf their flags on the device, base-major.  An identity base's entries are all flagged.  Enqueued on s; returns after
+// the stream has drained (the window bases are the call's own scratch).
+int fixed_base_tables_761(const uint64_t* gens, const uint8_t* inf, size_t n, int c, uint32_t* d_table, uint8_t* d_tinf, hipStream_t s) {
+  typedef Fp<P761> F;
+  constexpr int A = F::ARK64;
+  if (n == 0) return 0;
+  if (!gens || !d_table || !d_tinf || c < 2 || c > 14) return 2;
+  const int W = fb_windows(377, c);
+  const uint32_t H = 1u << (c - 1), E = (uint32_t)W * H;
+  CallScope cs(s);
+  uint32_t* bases;
+  uint8_t* binf;
+  HIP_TRY(cs.alloc(&bases, (size_t)W * 2 * F::WORDS * 4), 10);
+  HIP_TRY(cs.alloc(&binf, W), 10);
+  for (size_t b = 0; b < n; b++) {
+    uint32_t* t = d_table + b * (size_t)E * 2 * F::WORDS;
+    uint8_t* ti = d_tinf + b * (size_t)E;
+    if ((inf && inf[b]) || gen_is_identity<F>(gens + b * 2 * A)) {
+      HIP_TRY(hipMemsetAsync(t, 0, (size_t)E * 2 * F::WORDS * 4, s), 10);
+      HIP_TRY(hipMemsetAsync(ti, 1, E, s), 10);
+      continue;
+    }
+    ArkWords<2 * A> g;
+    memcpy(g.v, gens + b * 2 * A, sizeof g.v);
+    hipLaunchKernelGGL((k_fbm_bases<F>), dim3((W + 63) / 64), dim3(64), 0, s, g, bases, binf, W, c);
+    hipLaunchKernelGGL((k_fbm_table<F>), dim3((E + 63) / 64), dim3(64), 0, s, bases, binf, t, ti, H, E);
+    HIP_TRY(hipGetLastError(), 10);
+  }
+  HIP_TRY(hipStreamSynchronize(s), 10);
+  return 0;
+}
+
 // ---- Groth16 parameter generation (include/celo_bls_amd.h groth16_setup_*).  curve 0 = BW6-761 (FB1 = FB2 = Fbm761), 1 = BLS12-377.
 // dev_in = 0: qa / qb / qc are host pointers; 1: device pointers, complete before the call (groth16_setup_r1cs).
 template <class FB1, class FB2, class FR>

@@ -19,6 +19,7 @@ typedef Fp<P253> Fr377;                          // the scalar field of BLS12-37
 struct FixedTable;                               // msm_fixed.h: a key's fixed-base tables
 struct ProvingKey;                               // unit_prover.hip: a loaded Groth16 proving key (fixed-base tables of its four queries)
 struct R1cs;                                     // unit_r1cs.hip: constraint matrices on the device
+struct VerifyingKey;                             // unit_groth16_verify.hip: a loaded Groth16 verifying key (its input bases' window tables)
 struct WireConsts;                               // wire.h
 struct EdPoint;                                  // pedersen.h
 struct BvJob { BatchRun keys, sigs; };           // unit_batchverify.hip: the chained Batch::verify in three steps
@@ -70,6 +71,9 @@ int pairing_run_761(const uint64_t* g1, const uint8_t* inf1, const uint64_t* g2,
 int pairing_stage_377(uint32_t k, size_t m, PairingStage* st);
 int pairing_run_staged_377(PairingStage* st, const uint32_t* offsets, size_t m, uint8_t* is_one);
 int pairing_timings_377(float ms[4]);
+int pairing_stage_761(uint32_t k, size_t m, PairingStage* st);
+int pairing_run_staged_761(PairingStage* st, const uint32_t* offsets, size_t m, uint8_t* is_one);
+int pairing_timings_761(float ms[4]);
 void final_exp_w3_377(const uint32_t* prod, uint8_t* is_one, uint64_t* gt, uint32_t m, hipStream_t s);
 void final_exp_w2_377(const uint32_t* prod, uint8_t* is_one, uint64_t* gt, uint32_t m, hipStream_t s);
 
@@ -113,6 +117,7 @@ const EdPoint* celo_composite_gens(size_t* count);
 // ---- batched fixed-base scalar multiplication and Groth16 setup (unit_setup.hip)
 int fixed_base_mul(int group, const uint64_t* gen, const void* scalars, size_t n, void* out_xy, void* inf, int dev, void* stream);
 int fixed_base_set_window(int c);
+int fixed_base_tables_761(const uint64_t* gens, const uint8_t* inf, size_t n, int c, uint32_t* d_table, uint8_t* d_tinf, hipStream_t s);
 void setup_last_timings(float ms[8]);
 int groth16_setup(int curve, const uint64_t* qa, const uint64_t* qb, const uint64_t* qc, size_t n_vars, size_t n_inputs, const uint64_t* zt, const uint64_t* tau, size_t n_h,
                   const uint64_t* toxic, const uint64_t* g1_xy, const uint64_t* g2_xy, int window_bits, uint64_t* out_vk, uint64_t* out_rows, ProvingKey** out_key);
@@ -148,6 +153,16 @@ int groth16_prove_keyed(const ProvingKey* k, const uint64_t* assignment, size_t 
                         uint64_t* out_c);
 int groth16_prove_r1cs(const ProvingKey* k, const R1cs* r, const uint64_t* z, unsigned log_n, const uint64_t* omega, const uint64_t* omega_inv, const uint64_t* coset,
                        const uint64_t* coset_inv, const uint64_t* n_inv, const uint64_t* z_inv, uint64_t* out_a, uint64_t* out_b, uint64_t* out_c);
+
+// ---- Groth16 verification of many proofs under one key (unit_groth16_verify.hip).  BW6-761 only
+int groth16_vk_load_761(const uint64_t* alpha_g1, const uint64_t* beta_g2, const uint64_t* gamma_g2, const uint64_t* delta_g2, const uint64_t* gamma_abc_g1, size_t n_abc,
+                        VerifyingKey** out);
+int groth16_vk_load_761_serialized(const uint8_t* bytes, size_t len, VerifyingKey** out);
+int groth16_vk_release(VerifyingKey* vk);
+int groth16_verify_761(const VerifyingKey* vk, const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf, const uint64_t* c_xy,
+                       const uint8_t* c_inf, const uint8_t* proofs, const uint64_t* inputs, size_t m, int mode, const uint32_t* key, uint8_t* out_ok);
+int groth16_draw_exponents_run(const uint32_t key[8], size_t m, uint64_t* out);
+int groth16_verify_last(int* path, int* window_bits, float ms[8]);
 
 int ubench_fp_run(float out[9]);                 // unit_ubench.hip
 }  // namespace celo

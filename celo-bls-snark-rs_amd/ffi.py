@@ -60,6 +60,8 @@ EXPORTS = [
     "groth16_setup_r1cs_bls12_377", "celo_amd_r1cs_last_timings",
     "hash_to_g1_direct_bls12_377", "hash_to_g1_composite_bls12_377", "hash_to_g1_cip22_tail_bls12_377", "composite_crh_bls12_377",
     "celo_amd_hash_last_ms", "celo_amd_hash_last_rounds",
+    "groth16_vk_load_bw6_761", "groth16_vk_load_bw6_761_serialized", "groth16_vk_free", "groth16_verify_batch_bw6_761",
+    "groth16_verify_batch_bw6_761_serialized", "celo_amd_groth16_draw_exponents", "celo_amd_groth16_verify_last",
 ]
 
 _lib = None
@@ -630,6 +632,110 @@ class ProvingKey:
             self.release()
         except Exception:
             pass
+
+
+class VerifyError(RuntimeError):
+    def __init__(self, what, code):
+        super().__init__("%s failed with code %d" % (what, code))
+        self.code = code
+
+
+VERIFY_PATHS = {0: "each", 1: "combined accepted", 2: "combined then each"}
+VK_ERR_INPUTS = 36
+
+
+class VerifyingKey:
+    """A loaded Groth16 verifying key over BW6-761 (groth16_vk_load_bw6_761): verify() checks m proofs under it in one call.
+    alpha_g1 / beta_g2 / gamma_g2 / delta_g2: 24 u64 each; gamma_abc_g1: (n_abc, 24); affine arkworks limbs.  Raises VerifyError (.code)."""
+    def __init__(self, alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1):
+        self.h = C.c_void_p()
+        if alpha_g1 is None:                # from_serialized fills the handle
+            return
+        pts = [np.ascontiguousarray(x, dtype=np.uint64).reshape(24) for x in (alpha_g1, beta_g2, gamma_g2, delta_g2)]
+        abc = _rows(gamma_abc_g1, 24)
+        self.n_inputs = abc.shape[0] - 1
+        rc = lib().groth16_vk_load_bw6_761(*[_p(x) for x in pts], _p(abc), C.c_size_t(abc.shape[0]), C.byref(self.h))
+        if rc != 0:
+            self.h = C.c_void_p()
+            raise VerifyError("groth16_vk_load_bw6_761", rc)
+
+    @classmethod
+    def from_serialized(cls, data):
+        """from VerifyingKey::serialize bytes (compressed; decoded and checked as VerifyingKey::deserialize does)"""
+        k = cls(None, None, None, None, None)
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        rc = lib().groth16_vk_load_bw6_761_serialized(_p(buf), C.c_size_t(buf.size), C.byref(k.h))
+        if rc != 0:
+            k.h = C.c_void_p()
+            raise VerifyError("groth16_vk_load_bw6_761_serialized", rc)
+        k.n_inputs = int.from_bytes(bytes(data)[384:392], "little") - 1
+        return k
+
+    def _inputs(self, inputs, m):
+        if self.n_inputs == 0:
+            return None
+        x = np.ascontiguousarray(inputs, dtype=np.uint64)
+        assert x.size == m * self.n_inputs * 6, "inputs: m x n_inputs x 6 canonical u64"
+        return x
+
+    def verify(self, a_xy, b_xy, c_xy, inputs, mode=0, key=None, a_inf=None, b_inf=None, c_inf=None):
+        """m proofs as rows (m, 24) of A, B, C and inputs (m, n_inputs, 6) canonical integers -> uint8 [m] verdicts.  mode 0: each;
+        1: combined (A, C in G1 and B in G2 required), key: 8 uint32 for the exponent stream or None for the operating system's."""
+        a, b, c = _rows(a_xy, 24), _rows(b_xy, 24), _rows(c_xy, 24)
+        m = a.shape[0]
+        assert b.shape[0] == m and c.shape[0] == m
+        x = self._inputs(inputs, m)
+        flags = [None if f is None else np.ascontiguousarray(f, dtype=np.uint8) for f in (a_inf, b_inf, c_inf)]
+        k = None if key is None else np.ascontiguousarray(key, dtype=np.uint32).reshape(8)
+        out = np.zeros(m, dtype=np.uint8)
+        rc = lib().groth16_verify_batch_bw6_761(self.h, _p(a), _p(flags[0]), _p(b), _p(flags[1]), _p(c), _p(flags[2]), _p(x), C.c_size_t(m), C.c_int(mode), _p(k), _p(out))
+        if rc != 0:
+            raise VerifyError("groth16_verify_batch_bw6_761", rc)
+        return out
+
+    def verify_serialized(self, proofs, inputs, mode=0, key=None):
+        """m proofs as m x 288 bytes (Proof::serialize: A | B | C compressed), decoded and checked on the device"""
+        buf = np.frombuffer(bytes(proofs), dtype=np.uint8)
+        assert buf.size % 288 == 0
+        m = buf.size // 288
+        x = self._inputs(inputs, m)
+        k = None if key is None else np.ascontiguousarray(key, dtype=np.uint32).reshape(8)
+        out = np.zeros(m, dtype=np.uint8)
+        rc = lib().groth16_verify_batch_bw6_761_serialized(self.h, _p(buf), _p(x), C.c_size_t(m), C.c_int(mode), _p(k), _p(out))
+        if rc != 0:
+            raise VerifyError("groth16_verify_batch_bw6_761_serialized", rc)
+        return out
+
+    def release(self):
+        if self.h:
+            rc = lib().groth16_vk_free(self.h)
+            self.h = C.c_void_p()
+            return rc
+        return 0
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+def groth16_draw_exponents(key, m):
+    """The exponents a combined verify call under `key` (8 uint32) gives its m proofs (celo_amd_groth16_draw_exponents): uint64 [m, 2]."""
+    key = np.ascontiguousarray(key, dtype=np.uint32).reshape(8)
+    out = np.zeros((m, 2), dtype=np.uint64)
+    rc = lib().celo_amd_groth16_draw_exponents(_p(key), C.c_size_t(m), _p(out))
+    if rc != 0:
+        raise RuntimeError(f"celo_amd_groth16_draw_exponents failed rc={rc}")
+    return out
+
+
+def groth16_verify_last():
+    """(path name, window bits, ms[8]) of the last verify call (celo_amd_groth16_verify_last)"""
+    path, c = C.c_int(-1), C.c_int(0)
+    ms = (C.c_float * 8)()
+    lib().celo_amd_groth16_verify_last(C.byref(path), C.byref(c), ms)
+    return VERIFY_PATHS.get(path.value, "none"), c.value, list(ms)
 
 
 # ---- the hash-helper proof's field and curve: Fr(BLS12-377) elements are 4 u64, G1 points 12 u64 affine / 18 Jacobian, G2 24 / 36

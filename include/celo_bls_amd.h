@@ -401,6 +401,66 @@ int groth16_load_key_bw6_761_serialized(const uint8_t* bytes, size_t len, int fo
  * transfer of the bytes, decoding (all sections and the rejection scan) and fixed-base table build */
 int celo_amd_wire761_last_timings(float ms[4]);
 
+/* ---- Groth16 verification over BW6-761 for m proofs under ONE verifying key: ark_groth16::prepare_verifying_key + verify_proof
+ * (crates/epoch-snark/src/api/verifier.rs:35, what the FFI `verify` runs per proof) from the inputs to the verdict bytes on the device -
+ * what a light client checking many epoch proofs, or a service checking proofs of many provers, calls instead of one msm_bw6_761_g1 and one
+ * pairing_product_is_one_bw6_761 per proof.  The Groth16 counterpart of batch_verify_bls12_377.
+ *
+ * groth16_vk_load_bw6_761: the key from affine arkworks limbs (24 u64 per point; gamma_abc_g1: n_abc rows, n_abc - 1 public inputs).  Kept on
+ * the device: -alpha, beta, -gamma, -delta and, per input base gamma_abc[j], j >= 1, one signed-digit window table (csrc/fixed_base.h,
+ * generalised from one generator to n_abc - 1 bases) - an input's multiple is then one mixed addition per window and no doubling.  The window
+ * width c is the widest of 10 .. 4 bits whose tables fit 64 MiB (10 bits up to 15 inputs, 7 bits at 64); celo_amd_groth16_verify_last
+ * reports it.  A row that is all zero, or arkworks' (0, 1), is the point at infinity.
+ * groth16_vk_load_bw6_761_serialized: the same from VerifyingKey::serialize bytes (alpha_g1 | beta_g2 | gamma_g2 | delta_g2 | u64 n_abc |
+ * gamma_abc_g1, compressed), decoded and CHECKED as VerifyingKey::deserialize does (curve, prime-order subgroup).
+ * Returns 0; 2: a NULL pointer or n_abc == 0; 36: n_abc - 1 > 64 public inputs (out of scope); 30 / 31: the serialized key ends early /
+ * has bytes left over; 33: a point of it does not decode or is outside the subgroup; 10: allocation failure; 100: no device.  The argument
+ * and length checks come first and need no device.  The handle is bound to the device it was loaded on (101 from a thread bound to another),
+ * is read-only after the load and may be used from several host threads at once; groth16_vk_free releases it (2: not a live handle).
+ *
+ * groth16_verify_batch_bw6_761: out_ok[i] = 1 iff verify_proof(pvk, (A_i, B_i, C_i), inputs_i) would return true:
+ *   e(A_i, B_i) e(acc_i, -gamma) e(C_i, -delta) e(-alpha, beta) == 1,   acc_i = gamma_abc[0] + sum_j inputs_i[j] gamma_abc[j + 1].
+ * a_xy / b_xy / c_xy: m rows of 24 u64 (affine arkworks limbs); *_inf: optional identity bytes (NULL = none) - a pair with a point at
+ * infinity contributes 1, as in ark-ec; inputs: m x (n_abc - 1) x 6 u64, CANONICAL integers (may be NULL when n_abc == 1).  An input that
+ * is not below r makes that proof's verdict 0: ark cannot represent such a value, and treating x and x + r alike would let one statement
+ * be presented under two encodings.
+ * groth16_verify_batch_bw6_761_serialized: proofs = m x 288 B, Proof::serialize (A | B | C compressed).  The bytes cross once; every point
+ * is decoded and checked on the device (decompress_bw6_761_*_dev, check_subgroup = 1) into the rows the verifier reads; a proof with a point
+ * that does not decode or is outside the prime-order subgroup gets verdict 0 - that proof alone.
+ * mode 0 ("each"): m independent products of four pairs in one batched pairing call.  No precondition.
+ * mode 1 ("combined"): the random linear combination
+ *   prod_i e(r_i A_i, B_i) * e(sum r_i acc_i, -gamma) * e(sum r_i C_i, -delta) * e(-(sum r_i) alpha, beta) == 1
+ * - m + 3 Miller loops and ONE final exponentiation instead of 4 m and m, paid for with m 128-bit ladders and two m-term MSMs.  If it holds,
+ * every proof whose status is clean gets 1; if not, the call runs mode 0 and returns its verdicts: out_ok means the same in both modes
+ * (up to the soundness error 2^-127 of the combination).  PRECONDITION of mode 1, as for batch_verify_bls12_377: every A_i, C_i is an element
+ * of G1 and every B_i of G2 (the prime-order subgroups) - the combination argument holds in a group of prime order only.  The serialized
+ * entry always guarantees it; a caller of the limb entry holding unchecked points uses mode 0 or decodes them with check_subgroup = 1.
+ * Exponents: r_i = 2^127 | (the low 127 bits of the first 16 bytes, little-endian, of block i of the ChaCha20 stream under `key`) - the
+ * block function of celo_amd_draw_batch_exponents.  The top bit is fixed: every ladder has the same length.  key: 8 x u32, or NULL for
+ * 32 bytes from the operating system per call (getrandom, as batch_verify_strict seeds its stream) - what a verifier uses; a fixed key
+ * is for tests.  celo_amd_groth16_draw_exponents returns them (m x 2 u64, host).
+ * Choosing a mode (one MI355X, two inputs, profiles/bench_groth16_verify.json): a call has a floor of 65-90 ms in either
+ * mode.  Mode 0 takes 79 / 67 / 146 ms for 64 / 1 024 / 16 421 proofs, mode 1 92 / 87 / 92 ms: combined / each = 1.16, 1.30, 0.63.  Use mode 0
+ * up to a few thousand proofs and mode 1 above (the crossover lies between 1 024 and 16 421 proofs and was not bracketed further).
+ * Returns 0; 2: a NULL pointer, mode not 0 / 1, m > 2^24, a handle that is not live; 101; 10; 100.  m == 0 returns 0 and touches nothing.
+ * Limits: at most 64 public inputs, m <= 2^24 proofs per call; products are laid out at offsets 0, 4, 8, ... (each) or as one product of
+ * m + 3 pairs (combined) in the pairing engine's own input slots.
+ *
+ * celo_amd_groth16_verify_last: of the last successful verify call of the process - *path: 0 each, 1 combined accepted, 2 combined rejected
+ * then each; *window_bits: c of its key; ms[8]: [0] decoding, [1] input sums, [2] exponents and ladders, [4] pairing products, [6] transfers
+ * to the device (HIP events), [3] the two MSMs and (sum r) alpha, [5] the whole call (wall).  Any pointer may be NULL. */
+int groth16_vk_load_bw6_761(const uint64_t alpha_g1[24], const uint64_t beta_g2[24], const uint64_t gamma_g2[24], const uint64_t delta_g2[24],
+                            const uint64_t* gamma_abc_g1 /* n_abc x 24 */, size_t n_abc, void** out_vk);
+int groth16_vk_load_bw6_761_serialized(const uint8_t* bytes, size_t len, void** out_vk);
+int groth16_vk_free(void* vk);
+int groth16_verify_batch_bw6_761(const void* vk, const uint64_t* a_xy /* m x 24 */, const uint8_t* a_inf, const uint64_t* b_xy /* m x 24 */, const uint8_t* b_inf,
+                                 const uint64_t* c_xy /* m x 24 */, const uint8_t* c_inf, const uint64_t* inputs /* m x (n_abc - 1) x 6 */, size_t m, int mode,
+                                 const uint32_t* key /* 8, or NULL */, uint8_t* out_ok /* m */);
+int groth16_verify_batch_bw6_761_serialized(const void* vk, const uint8_t* proofs /* m x 288 */, const uint64_t* inputs, size_t m, int mode,
+                                            const uint32_t* key /* 8, or NULL */, uint8_t* out_ok /* m */);
+int celo_amd_groth16_draw_exponents(const uint32_t key[8], size_t m, uint64_t* out /* m x 2 */);
+int celo_amd_groth16_verify_last(int* path, int* window_bits, float ms[8]);
+
 /* ---- bulk ENCODING into the same wire form: n affine points (arkworks Montgomery limbs, the rows the decoders, normalize_* and the MSM
  * entry points use) -> n encodings, one point per GPU lane.  Replaces n calls of GroupAffine::serialize (compress_*: x little-endian with
  * 0x80 on the last byte when y is the lexicographically larger of (y, -y)) or serialize_uncompressed (encode_uncompressed_*: x then y, no
