@@ -375,21 +375,35 @@ int groth16_load_key_bw6_761_serialized(const uint8_t* bytes, size_t len, int fo
   *out_key = nullptr;
   return wire761_key_load(bytes, len, form, window_bits, (ProvingKey**)out_key, first_bad_point);
 }
-// ---- Groth16 verification of many proofs under one key (unit_groth16_verify.hip)
+// ---- Groth16 verification of many proofs under one key (unit_groth16_verify.hip, unit_groth16_verify377.hip)
 int groth16_vk_load_bw6_761(const uint64_t alpha_g1[24], const uint64_t beta_g2[24], const uint64_t gamma_g2[24], const uint64_t delta_g2[24], const uint64_t* gamma_abc_g1,
                             size_t n_abc, void** out_vk) {
-  return groth16_vk_load_761(alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1, n_abc, (VerifyingKey**)out_vk);
+  return G16Api<G16Bw6>::vk_load(alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1, n_abc, (VerifyingKey**)out_vk);
 }
-int groth16_vk_load_bw6_761_serialized(const uint8_t* bytes, size_t len, void** out_vk) { return groth16_vk_load_761_serialized(bytes, len, (VerifyingKey**)out_vk); }
+int groth16_vk_load_bw6_761_serialized(const uint8_t* bytes, size_t len, void** out_vk) { return G16Api<G16Bw6>::vk_load_serialized(bytes, len, (VerifyingKey**)out_vk); }
 int groth16_vk_free(void* vk) { return groth16_vk_release((VerifyingKey*)vk); }
 int groth16_verify_batch_bw6_761(const void* vk, const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf, const uint64_t* c_xy,
                                  const uint8_t* c_inf, const uint64_t* inputs, size_t m, int mode, const uint32_t* key, uint8_t* out_ok) {
   if (m && (!a_xy || !b_xy || !c_xy)) return 2;
-  return groth16_verify_761((const VerifyingKey*)vk, a_xy, a_inf, b_xy, b_inf, c_xy, c_inf, nullptr, inputs, m, mode, key, out_ok);
+  return G16Api<G16Bw6>::verify((const VerifyingKey*)vk, a_xy, a_inf, b_xy, b_inf, c_xy, c_inf, nullptr, inputs, m, mode, key, out_ok);
 }
 int groth16_verify_batch_bw6_761_serialized(const void* vk, const uint8_t* proofs, const uint64_t* inputs, size_t m, int mode, const uint32_t* key, uint8_t* out_ok) {
   if (m && !proofs) return 2;
-  return groth16_verify_761((const VerifyingKey*)vk, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, proofs, inputs, m, mode, key, out_ok);
+  return G16Api<G16Bw6>::verify((const VerifyingKey*)vk, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, proofs, inputs, m, mode, key, out_ok);
+}
+int groth16_vk_load_bls12_377(const uint64_t alpha_g1[12], const uint64_t beta_g2[24], const uint64_t gamma_g2[24], const uint64_t delta_g2[24], const uint64_t* gamma_abc_g1,
+                              size_t n_abc, void** out_vk) {
+  return G16Api<G16Bls>::vk_load(alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1, n_abc, (VerifyingKey**)out_vk);
+}
+int groth16_vk_load_bls12_377_serialized(const uint8_t* bytes, size_t len, void** out_vk) { return G16Api<G16Bls>::vk_load_serialized(bytes, len, (VerifyingKey**)out_vk); }
+int groth16_verify_batch_bls12_377(const void* vk, const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf, const uint64_t* c_xy,
+                                   const uint8_t* c_inf, const uint64_t* inputs, size_t m, int mode, const uint32_t* key, uint8_t* out_ok) {
+  if (m && (!a_xy || !b_xy || !c_xy)) return 2;
+  return G16Api<G16Bls>::verify((const VerifyingKey*)vk, a_xy, a_inf, b_xy, b_inf, c_xy, c_inf, nullptr, inputs, m, mode, key, out_ok);
+}
+int groth16_verify_batch_bls12_377_serialized(const void* vk, const uint8_t* proofs, const uint64_t* inputs, size_t m, int mode, const uint32_t* key, uint8_t* out_ok) {
+  if (m && !proofs) return 2;
+  return G16Api<G16Bls>::verify((const VerifyingKey*)vk, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, proofs, inputs, m, mode, key, out_ok);
 }
 int celo_amd_groth16_draw_exponents(const uint32_t key[8], size_t m, uint64_t* out) { return groth16_draw_exponents_run(key, m, out); }
 int celo_amd_groth16_verify_last(int* path, int* window_bits, float ms[8]) { return groth16_verify_last(path, window_bits, ms); }
@@ -428,6 +442,9 @@ int groth16_serialize_key_bw6_761(const uint64_t* vk, size_t n_inputs, const uin
 }
 int groth16_serialize_proof_bw6_761(const uint64_t a_xyz[36], const uint64_t b_xyz[36], const uint64_t c_xyz[36], uint8_t out[288]) {
   return wire761_proof_serialize(a_xyz, b_xyz, c_xyz, out);
+}
+int groth16_serialize_proof_bls12_377(const uint64_t a_xyz[18], const uint64_t b_xyz[36], const uint64_t c_xyz[18], uint8_t out[192]) {
+  return wire377_proof_serialize(a_xyz, b_xyz, c_xyz, out);
 }
 int celo_amd_wire_encode_last_ms(float* ms) { if (!ms) return 2; *ms = wire_encode_last_ms(); return 0; }
 int celo_amd_wire_encode_key_timings(float ms[3]) { if (!ms) return 2; wire_encode_key_timings(ms); return 0; }

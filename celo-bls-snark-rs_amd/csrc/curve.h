@@ -102,6 +102,35 @@ template <class F> HD void xyzz_madd(Xyzz<F>& a, const Affine<F>& p) {
   a.Y = Y3;
 }
 
+// acc += p (madd-2008-s, as xyzz_madd) - except when acc == p, where it returns false and leaves acc for the caller to double: a ladder
+// then runs its one doubling site instead of xyzz_madd's inlined xyzz_dbl_affine, whose extra live range is what spilled the BW6-761 ladder
+// kernel to ~1 KB of scratch per lane (wire761.h w761_in_subgroup, groth16_verify.h g16_scale128).
+template <class F> HD bool xyzz_madd_unless_equal(Xyzz<F>& a, const Affine<F>& p) {
+  if (a.is_identity()) { a = Xyzz<F>::from_affine(p); return true; }
+  F U2 = F::mul_nn(p.x, a.ZZ);                        // [1, 2]
+  F S2 = F::mul_nn(p.y, a.ZZZ);
+  F Pd = F::prep(F::template sub<32, 1>(U2, a.X));    // [3, 18]
+  F R = F::prep(F::template sub<16, 1>(S2, a.Y));     // [3, 18]
+  if (Pd.is_zero_mod_p()) {
+    if (R.is_zero_mod_p()) return false;
+    a = Xyzz<F>::identity();
+    return true;
+  }
+  F PP = F::sqr_nn(Pd);
+  F PPP = F::mul_nn(Pd, PP);
+  F Q = F::mul_nn(a.X, PP);
+  F R2 = F::sqr_nn(R);
+  F s = F::add(F::add(PPP, Q), Q);                    // [3, 6]
+  F X3 = F::norm(F::template sub<16, 3>(R2, s));       // [1, 10]
+  F t = F::prep(F::template sub<32, 1>(Q, X3));       // [3, 18]
+  F Y3 = F::template mul_sub_nn_at<2>(R, t, a.Y, PPP);
+  a.ZZ = F::mul_nn(a.ZZ, PP);
+  a.ZZZ = F::mul_nn(a.ZZZ, PPP);
+  a.X = X3;
+  a.Y = Y3;
+  return true;
+}
+
 // p + q for two AFFINE points, result XYZZ (mmadd-2007-bl's shape: U2 = x2, S2 = y2, ZZ3 = PP, ZZZ3 = PPP): 4 products + 2 squares
 // where xyzz_madd on from_affine(p) spends 8 + 2.  The first addition of every bucket run (k_accumulate).  x < 2 p (stored
 // bases); y < 2 p, or in (2 p, 4 p) after affine_neg - which is why the y difference takes 8 p of slack: a subtrahend of up to K p

@@ -1,6 +1,7 @@
-// Groth16 verification over BW6-761 for many proofs under one verifying key (ark_groth16::prepare_verifying_key + verify_proof,
-// crates/epoch-snark/src/api/verifier.rs:35): the lane routines of unit_groth16_verify.hip as host+device templates, and the host parse
-// of a serialized VerifyingKey.  The kernels and the host twins of host_test.cpp (-DCELO_FP_TRACK) run the same code.
+// Groth16 verification for many proofs under one verifying key (ark_groth16::prepare_verifying_key + verify_proof), over BW6-761
+// (crates/epoch-snark/src/api/verifier.rs:35) and over BLS12-377 (the hash-helper proof of crates/epoch-snark/src/api/prover.rs:83-118):
+// the curve descriptions, the lane routines of groth16_verify_unit.h's kernels as host+device templates, and the host parse of a serialized
+// VerifyingKey.  The kernels and the host twins of host_test.cpp (-DCELO_FP_TRACK) run the same code.
 //
 //   acc_i = abc_0 + sum_j x_ij abc_j     g16_input_row: one signed-digit window table per input base (fixed_base.h, generalised from one
 //                                        generator to n_abc - 1 bases), one mixed addition per non-zero digit, no doublings
@@ -17,18 +18,53 @@ namespace celo {
 
 constexpr size_t G16_MAX_INPUTS = 64;                 // n_abc - 1; more is refused with G16_ERR_INPUTS
 constexpr int G16_ERR_INPUTS = 36;                    // (30 .. 35: the serialized-key and R1CS codes of wire761.h / r1cs.h)
-constexpr int G16_SCALAR_BITS = 377;                  // bits of r, the order of the groups
 constexpr size_t G16_TABLE_BUDGET = size_t(64) << 20; // bytes of window tables per key
 constexpr int G16_C_MAX = 10, G16_C_MIN = 4;
 
-// bytes of the tables of n_in bases at c window bits: W 2^(c-1) affine entries of 2 x 28 words each
-inline size_t g16_table_bytes(size_t n_in, int c) {
-  return n_in * (size_t)fb_windows(G16_SCALAR_BITS, c) * (size_t(1) << (c - 1)) * 2 * Fw761::WORDS * 4;
+// ---- what the verifier needs to know of a curve.  F / F2: the coordinate fields of G1 / G2; G1W / G2W: u64 of an affine row of arkworks
+// limbs; N64: limbs of a scalar; order() / SCALAR_BITS: r, the order of the groups; G1_BYTES / G2_BYTES: a compressed point.
+// decode_g1 / decode_g2: one compressed point, checked as GroupAffine::deserialize checks it (host side of the key parse).
+struct G16Bw6 {
+  typedef Fw761 F;
+  typedef Fw761 F2;
+  static constexpr int ID = 0, G1W = 24, G2W = 24, N64 = 6, SCALAR_BITS = 377, G1_BYTES = 96, G2_BYTES = 96;
+  HD static const uint64_t* order() { return P377::P64; }
+  static WireStatus decode_g1(const uint8_t* in, uint64_t* row) { return w761_decode_row<-1, true>(in, true, row); }
+  static WireStatus decode_g2(const uint8_t* in, uint64_t* row) { return w761_decode_row<4, true>(in, true, row); }
+};
+struct G16Bls {
+  typedef Fq F;
+  typedef Fq2 F2;
+  static constexpr int ID = 1, G1W = 12, G2W = 24, N64 = 4, SCALAR_BITS = 253, G1_BYTES = 48, G2_BYTES = 96;
+  HD static const uint64_t* order() { return P253::P64; }
+  static WireStatus decode_g1(const uint8_t* in, uint64_t* row) {
+    Affine<Fq> p = {Fq::zero(), Fq::zero()};
+    const WireStatus st = wire_decode_g1(in, wire_consts(), true, p);
+    for (int j = 0; j < G1W; j++) row[j] = 0;
+    if (st == WIRE_OK) { p.x.to_ark(row); p.y.to_ark(row + 6); }
+    return st;
+  }
+  static WireStatus decode_g2(const uint8_t* in, uint64_t* row) {
+    Affine<Fq2> p = {Fq2::zero(), Fq2::zero()};
+    const WireStatus st = wire_decode_g2(in, wire_consts(), true, p);
+    for (int j = 0; j < G2W; j++) row[j] = 0;
+    if (st == WIRE_OK) { p.x.to_ark(row); p.y.to_ark(row + 12); }
+    return st;
+  }
+};
+// rows of the key and of a parsed key are KW u64 apart on both curves (a G1 row of BLS12-377 fills the first half of its slot)
+constexpr int G16_KW = 24;
+
+// bytes of the tables of n_in bases at c window bits: W 2^(c-1) affine entries of 2 x F::WORDS words each (28 for BW6-761; the 14 limbs
+// of BLS12-377 are stored as 16 words, the field's own stored form)
+template <class C> inline size_t g16_table_bytes(size_t n_in, int c) {
+  return n_in * (size_t)fb_windows(C::SCALAR_BITS, c) * (size_t(1) << (c - 1)) * 2 * C::F::WORDS * 4;
 }
-// the widest window (fewest additions per input) whose tables stay within the budget: 10 bits up to 15 inputs ... 7 bits at 64
-inline int g16_window_bits(size_t n_in) {
+// the widest window (fewest additions per input) whose tables stay within the budget.  BW6-761: 10 bits up to 15 inputs ... 7 bits at
+// 64; BLS12-377: 10 bits up to 39 inputs, 9 bits from 40 to 64
+template <class C> inline int g16_window_bits(size_t n_in) {
   int c = G16_C_MAX;
-  while (c > G16_C_MIN && g16_table_bytes(n_in, c) > G16_TABLE_BUDGET) c--;
+  while (c > G16_C_MIN && g16_table_bytes<C>(n_in, c) > G16_TABLE_BUDGET) c--;
   return c;
 }
 
@@ -63,8 +99,10 @@ template <class F, int N64> HD void g16_add_input(Xyzz<F>& acc, const uint64_t* 
 }
 // One proof's input sum.  x: n_in inputs of N64 limbs; abc0: gamma_abc[0] as a table entry (2 F::WORDS canonical words), abc0_inf its
 // identity flag; table / tinf: n_in tables of W 2^(c-1) entries, base-major.  An input that is not below r sets *bad and enters as zero.
-template <class F, int N64>
-HD Xyzz<F> g16_input_row(const uint64_t* x, uint32_t n_in, const uint32_t* abc0, bool abc0_inf, const uint32_t* table, const uint8_t* tinf, int c, int W, uint32_t* bad) {
+template <class C>
+HD Xyzz<typename C::F> g16_input_row(const uint64_t* x, uint32_t n_in, const uint32_t* abc0, bool abc0_inf, const uint32_t* table, const uint8_t* tinf, int c, int W, uint32_t* bad) {
+  typedef typename C::F F;
+  constexpr int N64 = C::N64;
   const size_t E = (size_t)W << (c - 1);
   Xyzz<F> acc = Xyzz<F>::identity();
   if (!abc0_inf) acc = Xyzz<F>::from_affine(fb_load_entry<F>(abc0));
@@ -75,7 +113,7 @@ HD Xyzz<F> g16_input_row(const uint64_t* x, uint32_t n_in, const uint32_t* abc0,
 #pragma unroll
 #endif
     for (int k = 0; k < N64; k++) s[k] = x[(size_t)j * N64 + k];
-    const uint64_t keep = (uint64_t)0 - (uint64_t)g16_below<N64>(s, P377::P64);      // all ones when x < r
+    const uint64_t keep = (uint64_t)0 - (uint64_t)g16_below<N64>(s, C::order());      // all ones when x < r
     b |= (uint32_t)(~keep & 1u);
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
@@ -90,8 +128,8 @@ HD Xyzz<F> g16_input_row(const uint64_t* x, uint32_t n_in, const uint32_t* abc0,
 // k p for k = 2^127 + (hi : lo without its top bit) - 128 bits, the top one always set, so the ladder starts from p and every exponent
 // takes 127 doublings.  One group operation per turn and one doubling site, as w761_in_subgroup: stage 0 doubles, stage 1 adds p where
 // bit i is set, stage 2 is the doubling that replaces an addition of acc == p (p of small order only).
-HD Xyzz<Fw761> g16_scale128(const Affine<Fw761>& p, uint64_t lo, uint64_t hi) {
-  Xyzz<Fw761> acc = Xyzz<Fw761>::from_affine(p);
+template <class F> HD Xyzz<F> g16_scale128(const Affine<F>& p, uint64_t lo, uint64_t hi) {
+  Xyzz<F> acc = Xyzz<F>::from_affine(p);
   int i = 126, stage = 0;
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll 1
@@ -100,7 +138,7 @@ HD Xyzz<Fw761> g16_scale128(const Affine<Fw761>& p, uint64_t lo, uint64_t hi) {
     if (stage == 1) {
       const uint64_t w = i >= 64 ? hi : lo;
       const bool bit = (w >> (i & 63)) & 1;
-      if (!bit || w761_madd(acc, p)) { stage = 0; i--; continue; }
+      if (!bit || xyzz_madd_unless_equal(acc, p)) { stage = 0; i--; continue; }
       stage = 2;
     }
     acc = xyzz_dbl(acc);
@@ -113,37 +151,43 @@ HD Xyzz<Fw761> g16_scale128(const Affine<Fw761>& p, uint64_t lo, uint64_t hi) {
 // the exponent of proof i from the first 16 bytes of its ChaCha20 block (two little-endian u64): 2^127 | the low 127 bits
 HD void g16_exponent(uint64_t w0, uint64_t w1, uint64_t& lo, uint64_t& hi) { lo = w0; hi = w1 | (1ull << 63); }
 
-// arkworks' identity as a row of limbs: all zero (what the decoders and normalize_* write) or GroupAffine::zero() = (0, 1)
-inline bool g16_row_is_identity(const uint64_t* xy) {
-  uint64_t one[12];
-  Fw761::one().to_ark(one);
+// arkworks' identity as a row of limbs of the field F (Fq2: c0 then c1 per coordinate): all zero (what the decoders and normalize_* write)
+// or GroupAffine::zero() = (0, 1)
+template <class F> inline bool g16_row_is_identity(const uint64_t* xy) {
+  constexpr int A = F::ARK64;
+  uint64_t one[A];
+  F::one().to_ark(one);
   bool x0 = true, y0 = true, y1 = true;
-  for (int k = 0; k < 12; k++) { x0 = x0 && xy[k] == 0; y0 = y0 && xy[12 + k] == 0; y1 = y1 && xy[12 + k] == one[k]; }
+  for (int k = 0; k < A; k++) { x0 = x0 && xy[k] == 0; y0 = y0 && xy[A + k] == 0; y1 = y1 && xy[A + k] == one[k]; }
   return x0 && (y0 || y1);
 }
-inline void g16_negate_row(uint64_t* xy) { w761_neg(Fw761::from_ark(xy + 12)).to_ark(xy + 12); }
+HD Fw761 g16_neg(const Fw761& a) { return w761_neg(a); }
+HD Fq g16_neg(const Fq& a) { return wire_neg(a); }
+HD Fq2 g16_neg(const Fq2& a) { return {wire_neg(a.c0), wire_neg(a.c1)}; }
+template <class F> inline void g16_negate_row(uint64_t* xy) { g16_neg(F::from_ark(xy + F::ARK64)).to_ark(xy + F::ARK64); }
 
-// ---- host: VerifyingKey::<BW6_761>::deserialize (compressed, checked):
-//   alpha_g1 | beta_g2 | gamma_g2 | delta_g2 | u64 LE n_abc | gamma_abc_g1[n_abc]      96 B per point
+// ---- host: VerifyingKey::deserialize (compressed, checked):
+//   alpha_g1 | beta_g2 | gamma_g2 | delta_g2 | u64 LE n_abc | gamma_abc_g1[n_abc]      96 B per point (BW6-761); 48 / 96 B (BLS12-377)
 // rows: (4 + n_abc) x 24 u64 in that order, inf: their identity flags (the encoding of the point at infinity is a valid one).
 // 2: a NULL pointer or n_abc == 0; 30 / 31: the bytes end early / go on after the last point; 36: more than 64 public inputs; 33: a point
 // that does not decode or lies outside the prime-order subgroup, *first_bad = its index in serialization order.
-inline int g16_vk_parse(const uint8_t* bytes, size_t len, std::vector<uint64_t>& rows, std::vector<uint8_t>& inf, uint64_t* first_bad) {
+template <class C> inline int g16_vk_parse(const uint8_t* bytes, size_t len, std::vector<uint64_t>& rows, std::vector<uint8_t>& inf, uint64_t* first_bad) {
+  constexpr size_t B1 = C::G1_BYTES, B2 = C::G2_BYTES, HEAD = B1 + 3 * B2;
   if (!bytes) return 2;
-  if (len < 392) return W761_ERR_TRUNCATED;
+  if (len < HEAD + 8) return W761_ERR_TRUNCATED;
   uint64_t n_abc = 0;
-  for (int b = 7; b >= 0; b--) n_abc = (n_abc << 8) | bytes[384 + b];
+  for (int b = 7; b >= 0; b--) n_abc = (n_abc << 8) | bytes[HEAD + b];
   if (n_abc == 0) return 2;
   if (n_abc - 1 > G16_MAX_INPUTS) return G16_ERR_INPUTS;
-  if (len - 392 < 96 * n_abc) return W761_ERR_TRUNCATED;
-  if (len - 392 > 96 * n_abc) return W761_ERR_TRAILING;
-  rows.assign((size_t)(4 + n_abc) * 24, 0);
+  if (len - (HEAD + 8) < B1 * n_abc) return W761_ERR_TRUNCATED;
+  if (len - (HEAD + 8) > B1 * n_abc) return W761_ERR_TRAILING;
+  rows.assign((size_t)(4 + n_abc) * G16_KW, 0);
   inf.assign((size_t)(4 + n_abc), 0);
   for (uint64_t i = 0; i < 4 + n_abc; i++) {
-    const uint8_t* src = bytes + (i < 4 ? 96 * i : 392 + 96 * (i - 4));
+    const uint8_t* src = bytes + (i == 0 ? 0 : i < 4 ? B1 + B2 * (i - 1) : HEAD + 8 + B1 * (i - 4));
     const bool g2 = i >= 1 && i <= 3;
-    uint64_t* row = rows.data() + i * 24;
-    const WireStatus st = g2 ? w761_decode_row<4, true>(src, true, row) : w761_decode_row<-1, true>(src, true, row);
+    uint64_t* row = rows.data() + i * G16_KW;
+    const WireStatus st = g2 ? C::decode_g2(src, row) : C::decode_g1(src, row);
     if (st == WIRE_INFINITY) inf[i] = 1;
     else if (st != WIRE_OK) { if (first_bad) *first_bad = i; return W761_ERR_POINT; }
   }

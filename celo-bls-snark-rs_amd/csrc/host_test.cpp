@@ -590,22 +590,25 @@ void ht_fixed_base_mul(int group, const uint64_t* gen, const uint64_t* sc, size_
   else if (group == 1) fbm_host<Fp2<P377>, 4>(gen, sc, n, c, 253, out, inf);
   else fbm_host<Fp<P761>, 6>(gen, sc, n, c, 377, out, inf);
 }
-// ---- groth16_verify.h: the lane routines of unit_groth16_verify.hip's kernels in host loops.
-// ht_g16_input_row: abc n_abc x 24 u64 (affine arkworks limbs, none the identity), inputs n x (n_abc - 1) x 6 canonical u64, window bits c ->
-// out n x 24 (a zero row and inf = 1 for the identity), status[i] = 1 for a row with an input that is not below r.  The tables are built as
+// ---- groth16_verify.h: the lane routines of groth16_verify_unit.h's kernels in host loops, one template over the curve description; the
+// exported twins are its two instantiations (BW6-761: rows of 24 u64, inputs of 6; BLS12-377: G1 rows of 12 u64, inputs of 4).
+// g16_input_row_host: abc n_abc G1 rows (affine arkworks limbs, none the identity), inputs n x (n_abc - 1) canonical scalars, window bits c ->
+// out n G1 rows (a zero row and inf = 1 for the identity), status[i] = 1 for a row with an input that is not below r.  The tables are built as
 // k_fbm_bases / k_fbm_table build them, one per base.
-void ht_g16_input_row(const uint64_t* abc, size_t n_abc, const uint64_t* inputs, size_t n, int c, uint64_t* out, uint8_t* inf, uint8_t* status) {
-  typedef Fp<P761> F;
-  constexpr int FW = F::WORDS;
+extern "C++" {
+template <class C>
+static void g16_input_row_host(const uint64_t* abc, size_t n_abc, const uint64_t* inputs, size_t n, int c, uint64_t* out, uint8_t* inf, uint8_t* status) {
+  typedef typename C::F F;
+  constexpr int FW = F::WORDS, A = F::ARK64, W1 = C::G1W;
   const size_t n_in = n_abc - 1;
-  const int W = fb_windows(G16_SCALAR_BITS, c);
+  const int W = fb_windows(C::SCALAR_BITS, c);
   const uint32_t H = 1u << (c - 1), E = (uint32_t)W * H;
   std::vector<uint32_t> table((size_t)(n_in ? n_in : 1) * E * 2 * FW), abc0(2 * FW);
   std::vector<uint8_t> tinf((size_t)(n_in ? n_in : 1) * E);
-  fb_store_entry(abc0.data(), Affine<F>{F::norm(F::from_ark(abc)), F::norm(F::from_ark(abc + 12))});
+  fb_store_entry(abc0.data(), Affine<F>{F::norm(F::from_ark(abc)), F::norm(F::from_ark(abc + A))});
   for (size_t j = 0; j < n_in; j++) {
-    const uint64_t* gen = abc + (j + 1) * 24;
-    const Affine<F> g = {F::norm(F::from_ark(gen)), F::norm(F::from_ark(gen + 12))};
+    const uint64_t* gen = abc + (j + 1) * W1;
+    const Affine<F> g = {F::norm(F::from_ark(gen)), F::norm(F::from_ark(gen + A))};
     for (int w = 0; w < W; w++) {
       Affine<F> b = {F::zero(), F::zero()};
       const bool okb = fb_to_affine(fb_window_base(g, w, c), b);
@@ -620,33 +623,35 @@ void ht_g16_input_row(const uint64_t* abc, size_t n_abc, const uint64_t* inputs,
   }
   for (size_t i = 0; i < n; i++) {
     uint32_t bad = 0;
-    const Xyzz<F> a = g16_input_row<F, 6>(inputs + i * n_in * 6, (uint32_t)n_in, abc0.data(), false, table.data(), tinf.data(), c, W, &bad);
+    const Xyzz<F> a = g16_input_row<C>(inputs + i * n_in * C::N64, (uint32_t)n_in, abc0.data(), false, table.data(), tinf.data(), c, W, &bad);
     Affine<F> r;
-    uint64_t* o = out + i * 24;
-    if (fb_to_affine(a, r)) { r.x.to_ark(o); r.y.to_ark(o + 12); inf[i] = 0; }
-    else { for (int k = 0; k < 24; k++) o[k] = 0; inf[i] = 1; }
+    uint64_t* o = out + i * W1;
+    if (fb_to_affine(a, r)) { r.x.to_ark(o); r.y.to_ark(o + A); inf[i] = 0; }
+    else { for (int k = 0; k < W1; k++) o[k] = 0; inf[i] = 1; }
     status[i] = bad ? 1 : 0;
   }
 }
-// ht_g16_scale: out[i] = (2^127 | low 127 bits of r2[i]) xy[i] for n affine points and n pairs of u64
-void ht_g16_scale(const uint64_t* xy, const uint64_t* r2, size_t n, uint64_t* out, uint8_t* inf) {
-  typedef Fp<P761> F;
+// out[i] = (2^127 | low 127 bits of r2[i]) xy[i] for n affine G1 points and n pairs of u64
+template <class C> static void g16_scale_host(const uint64_t* xy, const uint64_t* r2, size_t n, uint64_t* out, uint8_t* inf) {
+  typedef typename C::F F;
+  constexpr int A = F::ARK64, W1 = C::G1W;
   for (size_t i = 0; i < n; i++) {
-    const Affine<F> p = {F::norm(F::from_ark(xy + i * 24)), F::norm(F::from_ark(xy + i * 24 + 12))};
+    const Affine<F> p = {F::norm(F::from_ark(xy + i * W1)), F::norm(F::from_ark(xy + i * W1 + A))};
     uint64_t lo, hi;
     g16_exponent(r2[2 * i], r2[2 * i + 1], lo, hi);
     const Xyzz<F> a = g16_scale128(p, lo, hi);
     Affine<F> r;
-    uint64_t* o = out + i * 24;
-    if (fb_to_affine(a, r)) { r.x.to_ark(o); r.y.to_ark(o + 12); inf[i] = 0; }
-    else { for (int k = 0; k < 24; k++) o[k] = 0; inf[i] = 1; }
+    uint64_t* o = out + i * W1;
+    if (fb_to_affine(a, r)) { r.x.to_ark(o); r.y.to_ark(o + A); inf[i] = 0; }
+    else { for (int k = 0; k < W1; k++) o[k] = 0; inf[i] = 1; }
   }
 }
-// ht_g16_vk_parse: groth16_vk_load_bw6_761_serialized's host parse.  rows: (4 + n_abc) x 24 u64 with room for cap rows; *n_abc out
-int ht_g16_vk_parse(const uint8_t* bytes, size_t len, size_t cap, uint64_t* rows, uint8_t* inf, uint64_t* n_abc) {
+// the host parse of a serialized verifying key.  rows: (4 + n_abc) x 24 u64 on both curves, with room for cap rows; *n_abc out; *first_bad
+// (may be NULL): the index of the point that was refused with 33
+template <class C> static int g16_vk_parse_host(const uint8_t* bytes, size_t len, size_t cap, uint64_t* rows, uint8_t* inf, uint64_t* n_abc, uint64_t* first_bad) {
   std::vector<uint64_t> r;
   std::vector<uint8_t> f;
-  const int rc = g16_vk_parse(bytes, len, r, f, nullptr);
+  const int rc = g16_vk_parse<C>(bytes, len, r, f, first_bad);
   if (rc) return rc;
   if (f.size() > cap) return 2;
   memcpy(rows, r.data(), r.size() * 8);
@@ -654,7 +659,23 @@ int ht_g16_vk_parse(const uint8_t* bytes, size_t len, size_t cap, uint64_t* rows
   *n_abc = f.size() - 4;
   return 0;
 }
-int ht_g16_window_bits(size_t n_in) { return g16_window_bits(n_in); }
+}  // extern "C++"
+void ht_g16_input_row(const uint64_t* abc, size_t n_abc, const uint64_t* inputs, size_t n, int c, uint64_t* out, uint8_t* inf, uint8_t* status) {
+  g16_input_row_host<G16Bw6>(abc, n_abc, inputs, n, c, out, inf, status);
+}
+void ht_g16_input_row_377(const uint64_t* abc, size_t n_abc, const uint64_t* inputs, size_t n, int c, uint64_t* out, uint8_t* inf, uint8_t* status) {
+  g16_input_row_host<G16Bls>(abc, n_abc, inputs, n, c, out, inf, status);
+}
+void ht_g16_scale(const uint64_t* xy, const uint64_t* r2, size_t n, uint64_t* out, uint8_t* inf) { g16_scale_host<G16Bw6>(xy, r2, n, out, inf); }
+void ht_g16_scale_377(const uint64_t* xy, const uint64_t* r2, size_t n, uint64_t* out, uint8_t* inf) { g16_scale_host<G16Bls>(xy, r2, n, out, inf); }
+int ht_g16_vk_parse(const uint8_t* bytes, size_t len, size_t cap, uint64_t* rows, uint8_t* inf, uint64_t* n_abc) {
+  return g16_vk_parse_host<G16Bw6>(bytes, len, cap, rows, inf, n_abc, nullptr);
+}
+int ht_g16_vk_parse_377(const uint8_t* bytes, size_t len, size_t cap, uint64_t* rows, uint8_t* inf, uint64_t* n_abc, uint64_t* first_bad) {
+  return g16_vk_parse_host<G16Bls>(bytes, len, cap, rows, inf, n_abc, first_bad);
+}
+int ht_g16_window_bits(size_t n_in) { return g16_window_bits<G16Bw6>(n_in); }
+int ht_g16_window_bits_377(size_t n_in) { return g16_window_bits<G16Bls>(n_in); }
 // the setup's scalar lists as unit_setup.hip lays them out: G1 [alpha, beta, delta, gamma_abc, a, b, h, l], G2 [beta, gamma, delta, b]
 extern "C++" {
 template <class FR> static void setup_host(const uint64_t* qa, const uint64_t* qb, const uint64_t* qc, size_t n_vars, size_t n_inputs, const uint64_t* zt,

@@ -247,16 +247,16 @@ int fixed_base_set_window(int c) {
 }
 void setup_last_timings(float ms[8]) { for (int i = 0; i < 8; i++) ms[i] = g_setup_ms[i]; }
 
-// The table of k_fbm_bases / k_fbm_table for each of n BW6-761 bases instead of one generator (the Groth16 verifier's gamma_abc rows,
-// unit_groth16_verify.hip): gens n x 24 u64 affine arkworks limbs and inf their identity flags, both on the HOST; d_table n x W 2^(c-1)
-// entries and d_tinf their flags on the device, base-major.  An identity base's entries are all flagged.  Enqueued on s; returns after
-// the stream has drained (the window bases are the call's own scratch).
-int fixed_base_tables_761(const uint64_t* gens, const uint8_t* inf, size_t n, int c, uint32_t* d_table, uint8_t* d_tinf, hipStream_t s) {
-  typedef Fp<P761> F;
+// The table of k_fbm_bases / k_fbm_table for each of n bases over the field F instead of one generator (the Groth16 verifier's gamma_abc rows,
+// groth16_verify_unit.h): gens n x 2 F::ARK64 u64 affine arkworks limbs and inf their identity flags, both on the HOST; d_table n x W 2^(c-1)
+// entries and d_tinf their flags on the device, base-major, W = fb_windows(scalar_bits, c).  An identity base's entries are all flagged.
+// Enqueued on s; returns after the stream has drained (the window bases are the call's own scratch).
+template <class F>
+int fixed_base_tables(const uint64_t* gens, const uint8_t* inf, size_t n, int scalar_bits, int c, uint32_t* d_table, uint8_t* d_tinf, hipStream_t s) {
   constexpr int A = F::ARK64;
   if (n == 0) return 0;
   if (!gens || !d_table || !d_tinf || c < 2 || c > 14) return 2;
-  const int W = fb_windows(377, c);
+  const int W = fb_windows(scalar_bits, c);
   const uint32_t H = 1u << (c - 1), E = (uint32_t)W * H;
   CallScope cs(s);
   uint32_t* bases;
@@ -280,6 +280,9 @@ int fixed_base_tables_761(const uint64_t* gens, const uint8_t* inf, size_t n, in
   HIP_TRY(hipStreamSynchronize(s), 10);
   return 0;
 }
+
+template int fixed_base_tables<Fp<P761>>(const uint64_t*, const uint8_t*, size_t, int, int, uint32_t*, uint8_t*, hipStream_t);
+template int fixed_base_tables<Fp<P377>>(const uint64_t*, const uint8_t*, size_t, int, int, uint32_t*, uint8_t*, hipStream_t);
 
 // ---- Groth16 parameter generation (include/celo_bls_amd.h groth16_setup_*).  curve 0 = BW6-761 (FB1 = FB2 = Fbm761), 1 = BLS12-377.
 // dev_in = 0: qa / qb / qc are host pointers; 1: device pointers, complete before the call (groth16_setup_r1cs).

@@ -202,4 +202,15 @@ int wire761_proof_serialize(const uint64_t* a_xyz, const uint64_t* b_xyz, const 
   }
   return 0;
 }
+// Proof::<Bls12_377>::serialize: A (G1, 48 B), B (G2, 96 B), C (G1, 48 B) compressed, from the arkworks Jacobian points groth16_prove_*
+// returns (18 / 36 / 18 u64).  Host only, through the encoders of groups 0 / 1.
+int wire377_proof_serialize(const uint64_t* a_xyz, const uint64_t* b_xyz, const uint64_t* c_xyz, uint8_t* out) {
+  if (!a_xyz || !b_xyz || !c_xyz || !out) return 2;
+  uint64_t w[24];
+  (void)wire_encode_jacobian<Fq, WireEncG1c>(a_xyz, w);
+  (void)wire_encode_jacobian<Fq2, WireEncG2c>(b_xyz, w + 6);
+  (void)wire_encode_jacobian<Fq, WireEncG1c>(c_xyz, w + 18);
+  for (int j = 0; j < 192; j++) out[j] = (uint8_t)(w[j >> 3] >> (8 * (j & 7)));
+  return 0;
+}
 }  // namespace celo

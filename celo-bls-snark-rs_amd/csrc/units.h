@@ -12,14 +12,15 @@
 
 namespace celo {
 struct G1_377; struct G2_377; struct G_761;      // msm.h: the three group configurations
-struct P377; struct P253;                        // fp_consts.h
+struct P377; struct P253; struct P761;           // fp_consts.h
 template <class P> struct Fp;                    // fp.h
 typedef Fp<P377> Fr761;                          // the scalar field of BW6-761 is the base field of BLS12-377 (ntt.h)
 typedef Fp<P253> Fr377;                          // the scalar field of BLS12-377
 struct FixedTable;                               // msm_fixed.h: a key's fixed-base tables
 struct ProvingKey;                               // unit_prover.hip: a loaded Groth16 proving key (fixed-base tables of its four queries)
 struct R1cs;                                     // unit_r1cs.hip: constraint matrices on the device
-struct VerifyingKey;                             // unit_groth16_verify.hip: a loaded Groth16 verifying key (its input bases' window tables)
+struct VerifyingKey;                             // groth16_verify_unit.h: a loaded Groth16 verifying key (its input bases' window tables)
+struct G16Bw6; struct G16Bls;                    // groth16_verify.h: the two curves of the Groth16 verifier
 struct WireConsts;                               // wire.h
 struct EdPoint;                                  // pedersen.h
 struct BvJob { BatchRun keys, sigs; };           // unit_batchverify.hip: the chained Batch::verify in three steps
@@ -117,7 +118,8 @@ const EdPoint* celo_composite_gens(size_t* count);
 // ---- batched fixed-base scalar multiplication and Groth16 setup (unit_setup.hip)
 int fixed_base_mul(int group, const uint64_t* gen, const void* scalars, size_t n, void* out_xy, void* inf, int dev, void* stream);
 int fixed_base_set_window(int c);
-int fixed_base_tables_761(const uint64_t* gens, const uint8_t* inf, size_t n, int c, uint32_t* d_table, uint8_t* d_tinf, hipStream_t s);
+template <class F>                               // F = Fp<P761> (BW6-761, both groups) or Fp<P377> (BLS12-377 G1); scalar_bits: of the group order
+int fixed_base_tables(const uint64_t* gens, const uint8_t* inf, size_t n, int scalar_bits, int c, uint32_t* d_table, uint8_t* d_tinf, hipStream_t s);
 void setup_last_timings(float ms[8]);
 int groth16_setup(int curve, const uint64_t* qa, const uint64_t* qb, const uint64_t* qc, size_t n_vars, size_t n_inputs, const uint64_t* zt, const uint64_t* tau, size_t n_h,
                   const uint64_t* toxic, const uint64_t* g1_xy, const uint64_t* g2_xy, int window_bits, uint64_t* out_vk, uint64_t* out_rows, ProvingKey** out_key);
@@ -154,15 +156,24 @@ int groth16_prove_keyed(const ProvingKey* k, const uint64_t* assignment, size_t 
 int groth16_prove_r1cs(const ProvingKey* k, const R1cs* r, const uint64_t* z, unsigned log_n, const uint64_t* omega, const uint64_t* omega_inv, const uint64_t* coset,
                        const uint64_t* coset_inv, const uint64_t* n_inv, const uint64_t* z_inv, uint64_t* out_a, uint64_t* out_b, uint64_t* out_c);
 
-// ---- Groth16 verification of many proofs under one key (unit_groth16_verify.hip).  BW6-761 only
-int groth16_vk_load_761(const uint64_t* alpha_g1, const uint64_t* beta_g2, const uint64_t* gamma_g2, const uint64_t* delta_g2, const uint64_t* gamma_abc_g1, size_t n_abc,
-                        VerifyingKey** out);
-int groth16_vk_load_761_serialized(const uint8_t* bytes, size_t len, VerifyingKey** out);
+// ---- Groth16 verification of many proofs under one key (groth16_verify_unit.h holds the definitions; unit_groth16_verify.hip instantiates
+// them for C = G16Bw6 and unit_groth16_verify377.hip for C = G16Bls).  Rows: affine arkworks limbs, C::G1W / C::G2W u64 each
+template <class C> struct G16Api {
+  static int vk_load(const uint64_t* alpha_g1, const uint64_t* beta_g2, const uint64_t* gamma_g2, const uint64_t* delta_g2, const uint64_t* gamma_abc_g1, size_t n_abc,
+                     VerifyingKey** out);
+  static int vk_load_serialized(const uint8_t* bytes, size_t len, VerifyingKey** out);
+  static int verify(const VerifyingKey* vk, const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf, const uint64_t* c_xy,
+                    const uint8_t* c_inf, const uint8_t* proofs, const uint64_t* inputs, size_t m, int mode, const uint32_t* key, uint8_t* out_ok);
+};
+extern template struct G16Api<G16Bw6>; extern template struct G16Api<G16Bls>;
+// what the two curves share (unit_groth16_verify.hip): the handles that are alive, the last call's record, the exponent draw
+void groth16_vk_adopt(VerifyingKey* vk);
+bool groth16_vk_is_live(const VerifyingKey* vk, int curve);
 int groth16_vk_release(VerifyingKey* vk);
-int groth16_verify_761(const VerifyingKey* vk, const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf, const uint64_t* c_xy,
-                       const uint8_t* c_inf, const uint8_t* proofs, const uint64_t* inputs, size_t m, int mode, const uint32_t* key, uint8_t* out_ok);
+void groth16_verify_note(int path, int window_bits, const float ms[8]);
 int groth16_draw_exponents_run(const uint32_t key[8], size_t m, uint64_t* out);
 int groth16_verify_last(int* path, int* window_bits, float ms[8]);
+int wire377_proof_serialize(const uint64_t* a_xyz, const uint64_t* b_xyz, const uint64_t* c_xyz, uint8_t* out);      // unit_wire_encode.hip
 
 int ubench_fp_run(float out[9]);                 // unit_ubench.hip
 }  // namespace celo

@@ -380,6 +380,22 @@ template <class P, int K, bool COMPRESSED> struct WireEnc {
 typedef WireEnc<P377, 1, true> WireEncG1c;   typedef WireEnc<P377, 1, false> WireEncG1u;
 typedef WireEnc<P377, 2, true> WireEncG2c;   typedef WireEnc<P377, 2, false> WireEncG2u;
 
+// an arkworks Jacobian point over F (X, Y, Z: 3 F::ARK64 u64, what groth16_prove_* returns) -> its compressed encoding by E; Z == 0 is the
+// identity (wire761.h's w761_encode_jacobian for the BLS12-377 groups)
+template <class F, class E> HD WireStatus wire_encode_jacobian(const uint64_t* xyz, uint64_t* out) {
+  constexpr int A = F::ARK64;
+  const F Z = F::norm(F::from_ark(xyz + 2 * A));
+  uint64_t row[2 * A];
+  for (int j = 0; j < 2 * A; j++) row[j] = 0;
+  const bool inf = Z.is_zero_mod_p();
+  if (!inf) {
+    const F zi = F::norm(F::inv(Z)), zi2 = F::norm(F::sqr(zi));
+    F::mul(F::norm(F::from_ark(xyz)), zi2).to_ark(row);
+    F::mul(F::norm(F::from_ark(xyz + A)), F::norm(F::mul(zi2, zi))).to_ark(row + A);
+  }
+  return E::row(row, inf, false, out);
+}
+
 // ---- host: the constants (one search for the smallest non-residue, three exponentiations; first use only)
 inline WireConsts wire_consts_build() {
   WireConsts k;

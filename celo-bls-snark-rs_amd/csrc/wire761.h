@@ -114,35 +114,8 @@ HD bool w761_sqrt(const Fw761& a_, Fw761& out) {
   out = r;
   return true;
 }
-// acc += p (madd-2008-s, curve.h xyzz_madd) - except when acc == p, where it returns false and leaves acc for the caller to double: the
-// ladder below then runs its one doubling site instead of xyzz_madd's inlined xyzz_dbl_affine, whose extra live range is what spilled the
-// ladder kernel to ~1 KB of scratch per lane.
-HD bool w761_madd(Xyzz<Fw761>& a, const Affine<Fw761>& p) {
-  typedef Fw761 F;
-  if (a.is_identity()) { a = Xyzz<F>::from_affine(p); return true; }
-  F U2 = F::mul_nn(p.x, a.ZZ);                        // [1, 2]
-  F S2 = F::mul_nn(p.y, a.ZZZ);
-  F Pd = F::prep(F::template sub<32, 1>(U2, a.X));    // [3, 18]
-  F R = F::prep(F::template sub<16, 1>(S2, a.Y));     // [3, 18]
-  if (Pd.is_zero_mod_p()) {
-    if (R.is_zero_mod_p()) return false;
-    a = Xyzz<F>::identity();
-    return true;
-  }
-  F PP = F::sqr_nn(Pd);
-  F PPP = F::mul_nn(Pd, PP);
-  F Q = F::mul_nn(a.X, PP);
-  F R2 = F::sqr_nn(R);
-  F s = F::add(F::add(PPP, Q), Q);                    // [3, 6]
-  F X3 = F::norm(F::template sub<16, 3>(R2, s));       // [1, 10]
-  F t = F::prep(F::template sub<32, 1>(Q, X3));       // [3, 18]
-  F Y3 = F::template mul_sub_nn_at<2>(R, t, a.Y, PPP);
-  a.ZZ = F::mul_nn(a.ZZ, PP);
-  a.ZZZ = F::mul_nn(a.ZZZ, PPP);
-  a.X = X3;
-  a.Y = Y3;
-  return true;
-}
+// acc += p, except when acc == p: false, and acc is left for the caller to double (curve.h xyzz_madd_unless_equal, which began here)
+HD bool w761_madd(Xyzz<Fw761>& a, const Affine<Fw761>& p) { return xyzz_madd_unless_equal(a, p); }
 // r P == O with r = q_BLS12-377 (377 bits), MSB-first double-and-add over XYZZ: ark-ec 0.1 is_in_correct_subgroup_assuming_on_curve as
 // written.  The XYZZ formulas of curve.h do not depend on b, so one ladder serves both groups.
 // One group operation per iteration (stage 0: double for bit i; 1: add p for bit i; 2: acc was p, double instead of adding).

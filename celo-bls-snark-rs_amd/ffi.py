@@ -62,6 +62,8 @@ EXPORTS = [
     "celo_amd_hash_last_ms", "celo_amd_hash_last_rounds",
     "groth16_vk_load_bw6_761", "groth16_vk_load_bw6_761_serialized", "groth16_vk_free", "groth16_verify_batch_bw6_761",
     "groth16_verify_batch_bw6_761_serialized", "celo_amd_groth16_draw_exponents", "celo_amd_groth16_verify_last",
+    "groth16_vk_load_bls12_377", "groth16_vk_load_bls12_377_serialized", "groth16_verify_batch_bls12_377", "groth16_verify_batch_bls12_377_serialized",
+    "groth16_serialize_proof_bls12_377",
 ]
 
 _lib = None
@@ -644,66 +646,76 @@ VERIFY_PATHS = {0: "each", 1: "combined accepted", 2: "combined then each"}
 VK_ERR_INPUTS = 36
 
 
+# per curve of the verifier: u64 of a G1 / G2 row, of one input, bytes of a compressed G1 / G2 point
+VERIFY_CURVES = {"bw6_761": (24, 24, 6, 96, 96), "bls12_377": (12, 24, 4, 48, 96)}
+
+
 class VerifyingKey:
-    """A loaded Groth16 verifying key over BW6-761 (groth16_vk_load_bw6_761): verify() checks m proofs under it in one call.
-    alpha_g1 / beta_g2 / gamma_g2 / delta_g2: 24 u64 each; gamma_abc_g1: (n_abc, 24); affine arkworks limbs.  Raises VerifyError (.code)."""
-    def __init__(self, alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1):
+    """A loaded Groth16 verifying key over BW6-761 or BLS12-377 (groth16_vk_load_<curve>): verify() checks m proofs under it in one call.
+    alpha_g1 and the rows of gamma_abc_g1 (n_abc of them): 24 u64 each over BW6-761, 12 over BLS12-377; beta_g2 / gamma_g2 / delta_g2: 24 u64;
+    affine arkworks limbs.  Raises VerifyError (.code)."""
+    def __init__(self, alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1, curve="bw6_761"):
         self.h = C.c_void_p()
+        self.curve = curve
+        self.w1, self.w2, self.n64, b1, b2 = VERIFY_CURVES[curve]
+        self.proof_bytes, self.key_head = 2 * b1 + b2, b1 + 3 * b2
         if alpha_g1 is None:                # from_serialized fills the handle
             return
-        pts = [np.ascontiguousarray(x, dtype=np.uint64).reshape(24) for x in (alpha_g1, beta_g2, gamma_g2, delta_g2)]
-        abc = _rows(gamma_abc_g1, 24)
+        pts = [np.ascontiguousarray(x, dtype=np.uint64).reshape(w) for x, w in zip((alpha_g1, beta_g2, gamma_g2, delta_g2), (self.w1, self.w2, self.w2, self.w2))]
+        abc = _rows(gamma_abc_g1, self.w1)
         self.n_inputs = abc.shape[0] - 1
-        rc = lib().groth16_vk_load_bw6_761(*[_p(x) for x in pts], _p(abc), C.c_size_t(abc.shape[0]), C.byref(self.h))
+        rc = getattr(lib(), "groth16_vk_load_" + curve)(*[_p(x) for x in pts], _p(abc), C.c_size_t(abc.shape[0]), C.byref(self.h))
         if rc != 0:
             self.h = C.c_void_p()
-            raise VerifyError("groth16_vk_load_bw6_761", rc)
+            raise VerifyError("groth16_vk_load_" + curve, rc)
 
     @classmethod
-    def from_serialized(cls, data):
+    def from_serialized(cls, data, curve="bw6_761"):
         """from VerifyingKey::serialize bytes (compressed; decoded and checked as VerifyingKey::deserialize does)"""
-        k = cls(None, None, None, None, None)
+        k = cls(None, None, None, None, None, curve=curve)
         buf = np.frombuffer(bytes(data), dtype=np.uint8)
-        rc = lib().groth16_vk_load_bw6_761_serialized(_p(buf), C.c_size_t(buf.size), C.byref(k.h))
+        rc = getattr(lib(), "groth16_vk_load_%s_serialized" % curve)(_p(buf), C.c_size_t(buf.size), C.byref(k.h))
         if rc != 0:
             k.h = C.c_void_p()
-            raise VerifyError("groth16_vk_load_bw6_761_serialized", rc)
-        k.n_inputs = int.from_bytes(bytes(data)[384:392], "little") - 1
+            raise VerifyError("groth16_vk_load_%s_serialized" % curve, rc)
+        k.n_inputs = int.from_bytes(bytes(data)[k.key_head:k.key_head + 8], "little") - 1
         return k
 
     def _inputs(self, inputs, m):
         if self.n_inputs == 0:
             return None
         x = np.ascontiguousarray(inputs, dtype=np.uint64)
-        assert x.size == m * self.n_inputs * 6, "inputs: m x n_inputs x 6 canonical u64"
+        assert x.size == m * self.n_inputs * self.n64, "inputs: m x n_inputs x %d canonical u64" % self.n64
         return x
 
     def verify(self, a_xy, b_xy, c_xy, inputs, mode=0, key=None, a_inf=None, b_inf=None, c_inf=None):
-        """m proofs as rows (m, 24) of A, B, C and inputs (m, n_inputs, 6) canonical integers -> uint8 [m] verdicts.  mode 0: each;
-        1: combined (A, C in G1 and B in G2 required), key: 8 uint32 for the exponent stream or None for the operating system's."""
-        a, b, c = _rows(a_xy, 24), _rows(b_xy, 24), _rows(c_xy, 24)
+        """m proofs as rows of A, B, C (BW6-761: (m, 24) each; BLS12-377: (m, 12), (m, 24), (m, 12)) and inputs (m, n_inputs, 6 or 4)
+        canonical integers -> uint8 [m] verdicts.  mode 0: each; 1: combined (A, C in G1 and B in G2 required), key: 8 uint32 for the
+        exponent stream or None for the operating system's."""
+        a, b, c = _rows(a_xy, self.w1), _rows(b_xy, self.w2), _rows(c_xy, self.w1)
         m = a.shape[0]
         assert b.shape[0] == m and c.shape[0] == m
         x = self._inputs(inputs, m)
         flags = [None if f is None else np.ascontiguousarray(f, dtype=np.uint8) for f in (a_inf, b_inf, c_inf)]
         k = None if key is None else np.ascontiguousarray(key, dtype=np.uint32).reshape(8)
         out = np.zeros(m, dtype=np.uint8)
-        rc = lib().groth16_verify_batch_bw6_761(self.h, _p(a), _p(flags[0]), _p(b), _p(flags[1]), _p(c), _p(flags[2]), _p(x), C.c_size_t(m), C.c_int(mode), _p(k), _p(out))
+        rc = getattr(lib(), "groth16_verify_batch_" + self.curve)(self.h, _p(a), _p(flags[0]), _p(b), _p(flags[1]), _p(c), _p(flags[2]), _p(x), C.c_size_t(m), C.c_int(mode),
+                                                                  _p(k), _p(out))
         if rc != 0:
-            raise VerifyError("groth16_verify_batch_bw6_761", rc)
+            raise VerifyError("groth16_verify_batch_" + self.curve, rc)
         return out
 
     def verify_serialized(self, proofs, inputs, mode=0, key=None):
-        """m proofs as m x 288 bytes (Proof::serialize: A | B | C compressed), decoded and checked on the device"""
+        """m proofs as m x 288 bytes (BLS12-377: m x 192; Proof::serialize: A | B | C compressed), decoded and checked on the device"""
         buf = np.frombuffer(bytes(proofs), dtype=np.uint8)
-        assert buf.size % 288 == 0
-        m = buf.size // 288
+        assert buf.size % self.proof_bytes == 0
+        m = buf.size // self.proof_bytes
         x = self._inputs(inputs, m)
         k = None if key is None else np.ascontiguousarray(key, dtype=np.uint32).reshape(8)
         out = np.zeros(m, dtype=np.uint8)
-        rc = lib().groth16_verify_batch_bw6_761_serialized(self.h, _p(buf), _p(x), C.c_size_t(m), C.c_int(mode), _p(k), _p(out))
+        rc = getattr(lib(), "groth16_verify_batch_%s_serialized" % self.curve)(self.h, _p(buf), _p(x), C.c_size_t(m), C.c_int(mode), _p(k), _p(out))
         if rc != 0:
-            raise VerifyError("groth16_verify_batch_bw6_761_serialized", rc)
+            raise VerifyError("groth16_verify_batch_%s_serialized" % self.curve, rc)
         return out
 
     def release(self):
@@ -989,13 +1001,15 @@ def groth16_serialize_key(vk, rows=None, n_vars=0, n_h=0, form=0, cap=None):
     return out[:ln.value].tobytes()
 
 
-def groth16_serialize_proof(a_xyz, b_xyz, c_xyz):
-    """Proof::<BW6_761>::serialize (288 B) from the three Jacobian points groth16_prove / ProvingKey.prove return (groth16_serialize_proof_bw6_761)."""
-    pts = [np.ascontiguousarray(x, dtype=np.uint64).reshape(36) for x in (a_xyz, b_xyz, c_xyz)]
-    out = np.zeros(288, dtype=np.uint8)
-    rc = lib().groth16_serialize_proof_bw6_761(_p(pts[0]), _p(pts[1]), _p(pts[2]), _p(out))
+def groth16_serialize_proof(a_xyz, b_xyz, c_xyz, curve="bw6_761"):
+    """Proof::serialize (BW6-761: 288 B; BLS12-377: 192 B) from the three Jacobian points groth16_prove / ProvingKey.prove return
+    (groth16_serialize_proof_<curve>)."""
+    w1, w2, nbytes = (36, 36, 288) if curve == "bw6_761" else (18, 36, 192)
+    pts = [np.ascontiguousarray(x, dtype=np.uint64).reshape(w) for x, w in zip((a_xyz, b_xyz, c_xyz), (w1, w2, w1))]
+    out = np.zeros(nbytes, dtype=np.uint8)
+    rc = getattr(lib(), "groth16_serialize_proof_" + curve)(_p(pts[0]), _p(pts[1]), _p(pts[2]), _p(out))
     if rc != 0:
-        raise RuntimeError("groth16_serialize_proof_bw6_761 failed with code %d" % rc)
+        raise RuntimeError("groth16_serialize_proof_%s failed with code %d" % (curve, rc))
     return out.tobytes()
 
 

@@ -401,7 +401,7 @@ int groth16_load_key_bw6_761_serialized(const uint8_t* bytes, size_t len, int fo
  * transfer of the bytes, decoding (all sections and the rejection scan) and fixed-base table build */
 int celo_amd_wire761_last_timings(float ms[4]);
 
-/* ---- Groth16 verification over BW6-761 for m proofs under ONE verifying key: ark_groth16::prepare_verifying_key + verify_proof
+/* ---- Groth16 verification over BW6-761 for m proofs under ONE verifying key (BLS12-377: the next block): ark_groth16::prepare_verifying_key + verify_proof
  * (crates/epoch-snark/src/api/verifier.rs:35, what the FFI `verify` runs per proof) from the inputs to the verdict bytes on the device -
  * what a light client checking many epoch proofs, or a service checking proofs of many provers, calls instead of one msm_bw6_761_g1 and one
  * pairing_product_is_one_bw6_761 per proof.  The Groth16 counterpart of batch_verify_bls12_377.
@@ -460,6 +460,39 @@ int groth16_verify_batch_bw6_761_serialized(const void* vk, const uint8_t* proof
                                             const uint32_t* key /* 8, or NULL */, uint8_t* out_ok /* m */);
 int celo_amd_groth16_draw_exponents(const uint32_t key[8], size_t m, uint64_t* out /* m x 2 */);
 int celo_amd_groth16_verify_last(int* path, int* window_bits, float ms[8]);
+
+/* ---- The same verifier over BLS12-377: ark_groth16::prepare_verifying_key + verify_proof over Bls12_377, the check of the hash-helper
+ * proof (crates/epoch-snark/src/api/prover.rs:83-118) that a prover pipeline makes BEFORE it computes the BW6-761 proof over it - a helper
+ * proof that does not verify makes the outer circuit unsatisfiable.  One template with the BW6-761 entries above (csrc/groth16_verify_unit.h):
+ * the contract, the modes, the exponents, the limits and the return codes are theirs word for word; what differs is the shape of the data.
+ * Rows: G1 12 u64, G2 24 u64 (c0 then c1 per coordinate, as msm_bls12_377_g2 takes them); inputs: m x (n_abc - 1) x 4 u64, canonical
+ * integers below the 253-bit r.  Serialized key: alpha_g1 (48 B) | beta_g2 (96) | gamma_g2 (96) | delta_g2 (96) | u64 LE n_abc |
+ * gamma_abc_g1 (48 each); serialized proof: A (48) | B (96) | C (48) = 192 B; decoded and checked as `deserialize` does
+ * (decompress_bls12_377_*_dev, check_subgroup = 1).
+ * Window tables: entries are 2 x 16 words (the 14 limbs of a coordinate in the field's stored form), 128 B; the widest of 10 .. 4 bits whose
+ * tables fit 64 MiB is 10 bits up to 39 inputs and 9 bits from 40 to 64.
+ * groth16_vk_free, celo_amd_groth16_draw_exponents and celo_amd_groth16_verify_last serve both curves.  A handle knows its curve: a
+ * BLS12-377 handle given to a BW6-761 entry, or the reverse, returns 2 before anything is read.
+ * Dispatch: a product of four pairs is one more than the BLS12-377 latency path takes, so mode 0 runs the per-pair lane kernels below
+ * 16 384 proofs and the shared-accumulator kernel from there; the combined product of m + 3 pairs takes the 8-pair product up to m = 5 and the
+ * pairwise tree from m = 6.
+ * Choosing a mode (one MI355X, two inputs, profiles/bench_groth16_verify_377.json): a call has a floor of
+ * about 4.7 ms (each) and 8.2 ms (combined).  Mode 0 takes 4.76 / 4.87 / 22.9 ms for 64 / 1 024 / 16 421 proofs, mode 1 8.21 / 8.92 / 11.5 ms:
+ * combined / each = 1.73, 1.83, 0.50.  Use mode 0 up to a few thousand proofs and mode 1 above (the crossover lies between 1 024 and 16 421
+ * proofs and was not bracketed further).  Against the loop of one msm_bls12_377_g1 and one four-pair pairing_product_is_one_bls12_377 per
+ * proof (3.80 ms per proof), mode 0 is 51 x cheaper per proof at 64 proofs.
+ * groth16_serialize_proof_bls12_377: Proof::serialize (192 B) from the arkworks Jacobian points groth16_prove_bls12_377 /
+ * groth16_prove_with_key return (18 / 36 / 18 u64); Z == 0 encodes the identity.  Host only, through the encoders of compress_bls12_377_*.
+ * 2: a NULL pointer. */
+int groth16_vk_load_bls12_377(const uint64_t alpha_g1[12], const uint64_t beta_g2[24], const uint64_t gamma_g2[24], const uint64_t delta_g2[24],
+                              const uint64_t* gamma_abc_g1 /* n_abc x 12 */, size_t n_abc, void** out_vk);
+int groth16_vk_load_bls12_377_serialized(const uint8_t* bytes, size_t len, void** out_vk);
+int groth16_verify_batch_bls12_377(const void* vk, const uint64_t* a_xy /* m x 12 */, const uint8_t* a_inf, const uint64_t* b_xy /* m x 24 */, const uint8_t* b_inf,
+                                   const uint64_t* c_xy /* m x 12 */, const uint8_t* c_inf, const uint64_t* inputs /* m x (n_abc - 1) x 4 */, size_t m, int mode,
+                                   const uint32_t* key /* 8, or NULL */, uint8_t* out_ok /* m */);
+int groth16_verify_batch_bls12_377_serialized(const void* vk, const uint8_t* proofs /* m x 192 */, const uint64_t* inputs, size_t m, int mode,
+                                              const uint32_t* key /* 8, or NULL */, uint8_t* out_ok /* m */);
+int groth16_serialize_proof_bls12_377(const uint64_t a_xyz[18], const uint64_t b_xyz[36], const uint64_t c_xyz[18], uint8_t out[192]);
 
 /* ---- bulk ENCODING into the same wire form: n affine points (arkworks Montgomery limbs, the rows the decoders, normalize_* and the MSM
  * entry points use) -> n encodings, one point per GPU lane.  Replaces n calls of GroupAffine::serialize (compress_*: x little-endian with

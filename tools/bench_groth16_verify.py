@@ -1,11 +1,12 @@
-"""Batch Groth16 verification over BW6-761 (csrc/unit_groth16_verify.hip): each against combined against the per-proof loop.
+"""Batch Groth16 verification over BW6-761 or BLS12-377 (csrc/groth16_verify_unit.h): each against combined against the per-proof loop.
 
-  python tools/bench_groth16_verify.py [--sizes 64,1024,16421] [--reps 5] [--out FILE]
+  python tools/bench_groth16_verify.py [--curve bw6_761|bls12_377] [--sizes 64,1024,16421] [--reps 5] [--out FILE]
 
-One process, one constructed key with two public inputs (tests/groth16_verify_cases.py; the proofs' points come from the library's
-fixed-base rows), all proofs valid.  Per size m, after a warm-up round, `reps` rounds with the modes interleaved (each, combined, serialized
-each; at m = 64 also the piecewise loop: one msm_bw6_761_g1 and one pairing_product_is_one_bw6_761 per proof, the only way before this
-entry point existed).  Reported: the median wall time per mode, the per-proof time, the HIP-event phase times of the `last` record of the
+One process, one constructed key with two public inputs (tests/groth16_verify_cases.py, tests/groth16_verify377_cases.py; the proofs'
+points come from the library's fixed-base rows), all proofs valid.  Per size m, after a warm-up round, `reps` rounds with the modes
+interleaved (each, combined, serialized each; at m = 64 also the piecewise loop: one msm_<curve>_g1 and one pairing_product_is_one per
+proof, the only way before these entry points existed).  --curve bls12_377 writes profiles/bench_groth16_verify_377.json unless --out
+names another file, and leaves out the multiply-add model of k_g16_inputs, which is BW6-761's.  Reported: the median wall time per mode, the per-proof time, the HIP-event phase times of the `last` record of the
 median round, combined / each, the decode share of the serialized entry, and the rate of k_g16_inputs against the celo_amd_ubench_fp
 peak of the same run under DESIGN 6f's model (windows x (1 - 2^-c) digits x 14 140 multiply-adds per mixed addition; peak = Fq761
 products/s x 1 540).  Prints one JSON document."""
@@ -23,13 +24,17 @@ import torch  # noqa: E402  (before the library: both must share one HIP runtime
 from oracle.py import ecc  # noqa: E402
 from oracle import cpu_oracle as co  # noqa: E402
 from celo_bls_snark_rs_amd import ffi  # noqa: E402
-from tests import groth16_verify_cases as gc  # noqa: E402
+from tests import groth16_verify_cases as gc761  # noqa: E402
+from tests import groth16_verify377_cases as gc377  # noqa: E402
 
 KEY8 = np.arange(8, dtype=np.uint32) + 1
+gc = gc761                                   # the case module of the curve under test (main() sets it)
+CURVE = "bw6_761"
+N64 = {"bw6_761": 6, "bls12_377": 4}
 
 
 def device_mul(gen, scalars, on_g2):
-    xy, inf = ffi.fixed_base_mul("bw6_761_g2" if on_g2 else "bw6_761_g1", gen, co.ints_to_limbs([int(k) % gc.R for k in scalars], 6))
+    xy, inf = ffi.fixed_base_mul(CURVE + ("_g2" if on_g2 else "_g1"), gen, co.ints_to_limbs([int(k) % gc.R for k in scalars], N64[CURVE]))
     xy[inf != 0] = 0
     return xy, inf
 
@@ -37,30 +42,40 @@ def device_mul(gen, scalars, on_g2):
 def piecewise(key, b):
     """what a caller did before: per proof, the 3-term input MSM and the 4-pair product"""
     ng, nd, na = gc.neg_row(key.gamma), gc.neg_row(key.delta), gc.neg_row(key.alpha)
-    one = co.ints_to_limbs([1], 6)
+    one = co.ints_to_limbs([1], N64[CURVE])
     ok = []
     for i in range(b.m):
-        acc = co.pack_761([co.jac_to_affine(ffi.msm("bw6_761_g1", key.abc, None, np.concatenate([one, b.inputs[i]])), "761")])[0][0]      # (affine on the host, as Seam A's verify)
+        jac = ffi.msm(CURVE + "_g1", key.abc, None, np.concatenate([one, b.inputs[i]]))
+        if CURVE == "bw6_761":
+            acc = co.pack_761([co.jac_to_affine(jac, "761")])[0][0]      # (affine on the host, as Seam A's verify)
+        else:
+            acc = co.pack_g1_377([co.jac_to_affine(jac, "g1_377")])[0][0]
         g1 = np.stack([b.a[i], acc, b.c[i], na])
         g2 = np.stack([b.b[i], ng, nd, key.beta])
-        ok.append(ffi.pairing_product_is_one_bw6(g1, None, g2, None))
+        ok.append((ffi.pairing_product_is_one_bw6 if CURVE == "bw6_761" else ffi.pairing_product_is_one)(g1, None, g2, None))
     return ok
 
 
 def main():
+    global gc, CURVE
     ap = argparse.ArgumentParser()
+    ap.add_argument("--curve", default="bw6_761", choices=["bw6_761", "bls12_377"])
     ap.add_argument("--sizes", default="64,1024,16421")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     sizes = [int(s) for s in args.sizes.split(",")]
+    CURVE = args.curve
+    gc = gc761 if CURVE == "bw6_761" else gc377
+    if CURVE == "bls12_377" and args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "bench_groth16_verify_377.json")
     ffi.init(0)
     peak = ffi.ubench_fp()
     key = gc.Key(2, 0x6116)
-    vk = ffi.VerifyingKey(key.alpha, key.beta, key.gamma, key.delta, key.abc)
+    vk = ffi.VerifyingKey(key.alpha, key.beta, key.gamma, key.delta, key.abc, curve=CURVE)
     rng = ecc.SplitMix64(1)
     allb = gc.Batch(key, [gc.valid_proof(key, rng) for _ in range(max(sizes))], mul=device_mul)
-    doc = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "n_inputs": 2, "ubench_fp": peak, "sizes": {}}
+    doc = {"curve": CURVE, "device": torch.cuda.get_device_name(0), "reps": args.reps, "n_inputs": 2, "ubench_fp": peak, "sizes": {}}
     for m in sizes:
         b = gc.take(allb, range(m))
         ser = b.serialize() if m <= 1024 else None
@@ -90,15 +105,17 @@ def main():
                 row[name].update({"path": path, "window_bits": c, "phase_ms": dict(zip(("decode", "inputs", "scale", "msm_and_alpha_wall", "pairing", "wall", "transfers"),
                                                                                       [round(x, 3) for x in ms[:7]]))})
         row["combined_over_each"] = round(row["combined"]["wall_ms_median"] / row["each"]["wall_ms_median"], 3)
-        c = row["each"]["window_bits"]
-        windows = (377 + 1 + c - 1) // c
-        madds = m * 2 * windows * (1 - 2.0 ** -c) * 14140
-        in_ms = row["each"]["phase_ms"]["inputs"]
-        row["inputs_kernel_share_of_peak"] = round(madds / (in_ms * 1e-3) / (peak["fq761_mul_G"] * 1e9 * 1540), 4) if in_ms > 0 else None
+        if CURVE == "bw6_761":
+            c = row["each"]["window_bits"]
+            windows = (377 + 1 + c - 1) // c
+            madds = m * 2 * windows * (1 - 2.0 ** -c) * 14140
+            in_ms = row["each"]["phase_ms"]["inputs"]
+            row["inputs_kernel_share_of_peak"] = round(madds / (in_ms * 1e-3) / (peak["fq761_mul_G"] * 1e9 * 1540), 4) if in_ms > 0 else None
         if "serialized_each" in row:
             row["serialized_decode_share"] = round(row["serialized_each"]["phase_ms"]["decode"] / row["serialized_each"]["wall_ms_median"], 3)
         if m == 64:
             row["each_per_proof_below_piecewise"] = row["each"]["per_proof_ms"] < row["piecewise_loop"]["per_proof_ms"]
+            row["piecewise_over_each"] = round(row["piecewise_loop"]["per_proof_ms"] / row["each"]["per_proof_ms"], 2)
         doc["sizes"][str(m)] = row
     vk.release()
     doc["note"] = ("wall_ms: host wall time of the whole call, median of the rounds after one warm-up round, modes interleaved; phase_ms: the last record of the "
