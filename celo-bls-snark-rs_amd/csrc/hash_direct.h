@@ -195,4 +195,105 @@ HD bool hash_to_g1_direct_tai(const uint8_t dom[8], const uint8_t* msg, size_t m
   return false;
 }
 
+// ---- hash to G2: the same loops onto the twist E'(Fq2): y^2 = x^3 + 1/u (TryAndIncrement<H, G2> / TryAndIncrementCIP22<H, G2>; the reference
+// pins ten outputs, hash_to_curve/mod.rs:490-513).  The field element takes 96 bytes, hash_length(96) = 96, so a candidate is THREE XOF blocks
+// and every node offset (the XOF's and the direct CRH's) carries 96.
+//
+// 96 XOF bytes (24 little-endian words) -> the point they select, before the cofactor.  c0 = bytes 0..47, c1 = bytes 48..95, each cut to 377
+// bits; the flags are bits 7 (y sign) and 6 (infinity) of byte 95 as the XOF gives them (compat == 0: what the reference's G2 vectors pin) or
+// with the sign flag copied from bit 1 of byte 95 first (compat != 0: the deployed remap, try_and_increment.rs:107-120).  false: a half is no
+// field element, the flagged zero, or x^3 + B' is no square.  An infinity flag beside x != 0 is ignored.
+HD bool tai_point_from_xof_g2(const uint32_t w24[24], int compat, const WireConsts& k, Affine<Fq2>& p) {
+  uint32_t b95 = w24[23] >> 24;
+  if (compat) { if (b95 & 2) b95 |= 0x80; else b95 &= 0x7F; }
+  const uint32_t flags = b95 & 0xC0;
+  Fq2 x;
+  for (int h = 0; h < 2; h++) {
+    const uint32_t* w12 = w24 + 12 * h;
+    uint64_t w[6];
+    for (int i = 0; i < 5; i++) w[i] = (uint64_t)w12[2 * i] | ((uint64_t)w12[2 * i + 1] << 32);
+    w[5] = (uint64_t)w12[10] | ((uint64_t)(w12[11] & 0x01FFFFFFu) << 32);     // bits below MODULUS_BITS = 377
+    if (wire_cmp(w, P377::P64, 6) >= 0) return false;
+    (h ? x.c1 : x.c0) = Fq::from_canonical(w);
+  }
+  if (x.is_zero_mod_p() && (flags & 0x40)) return false;                       // the zero point scales to zero
+  const Fq2 tb = {Fq::zero(), wire_neg(k.inv5)};                                // B' = 1 / u = -u / 5
+  Fq2 y;
+  if (!wire_fq2_sqrt(Fq2::norm(Fq2::add(Fq2::mul(Fq2::sqr(x), x), tb)), k, y)) return false;
+  if (wire_lex_largest(y) != ((flags & 0x80) != 0)) y = {wire_neg(y.c0), wire_neg(y.c1)};   // get_point_from_x(x, greatest)
+  p = {Fq2::norm(x), Fq2::norm(y)};
+  return true;
+}
+// one attempt, the modes of tai_candidate
+HD bool tai_candidate_g2(const uint8_t dom[8], const uint8_t* msg, size_t mlen, const uint8_t* extra, size_t elen, int c, int compat, const WireConsts& k,
+                         Affine<Fq2>& p, int mode = TAI_DIRECT, const EdPoint* gens = nullptr) {
+  uint32_t w24[24];
+  const TaiBytes src = {(uint8_t)c, extra, elen, msg, mlen};
+  if (mode == TAI_XOF_ONLY) {
+    for (int b = 0; b < 3; b++) {
+      b2s_init(w24 + 8 * b, 32, 0, 0, 32, b2x_node_offset(b, 96), 0, 32, dom);
+      b2s_stream(w24 + 8 * b, src);
+    }
+  } else if (mode == TAI_COMPOSITE) {
+    uint8_t pre[48];
+    pedersen_crh_src(gens, src, pre);
+    const PtrBytes ps = {pre, 48};
+    for (int b = 0; b < 3; b++) {
+      b2s_init(w24 + 8 * b, 32, 0, 0, 32, b2x_node_offset(b, 96), 0, 32, dom);
+      b2s_stream(w24 + 8 * b, ps);
+    }
+  } else {
+    uint32_t h[8], m[16];
+    b2s_init(h, 32, 1, 1, 0, b2x_node_offset(0, 96), 0, 0, dom);            // DirectHasher::crh with hash_length(96) = 96
+    b2s_stream(h, src);
+    for (int i = 0; i < 8; i++) { m[i] = h[i]; m[i + 8] = 0; }
+    for (int b = 0; b < 3; b++) {
+      b2s_init(w24 + 8 * b, 32, 0, 0, 32, b2x_node_offset(b, 96), 0, 32, dom);
+      b2s_compress(w24 + 8 * b, m, 32, true);
+    }
+  }
+  return tai_point_from_xof_g2(w24, compat, k, p);
+}
+// H2 = #E'(Fq2) / r, 502 bits (bit 501 set): the cofactor arkworks' scale_by_cofactor multiplies by.  tests/hash_g2_ref.py derives it
+// from the six orders a sextic twist can have; tests/test_hash_g2_host.py pins the ladder below on it.
+struct TaiG2Cofactor {
+  static constexpr int TOP = 501;
+  static constexpr uint64_t H2[8] = {0x0000000000000001ULL, 0x452217cc90000000ULL, 0xa0f3622fba094800ULL, 0xd693e8c36676bd09ULL,
+                                     0x8c505634fae2e189ULL, 0xfbb36b00e1dcc40cULL, 0xddd88d99a6f6a829ULL, 0x0026ba558ae9562aULL};
+};
+// [H2]P, MSB-first double-and-add over the 502 bits: the DEFINITION of the cofactor multiple, and what runs (no faster form ships; the
+// Budroni-Pintore h_eff clearing is a different multiple and would not reproduce the reference's points)
+WIRE_FN Xyzz<Fq2> tai_cofactor_ladder_g2(const Affine<Fq2>& p) {
+  Xyzz<Fq2> s = Xyzz<Fq2>::from_affine(p);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+  for (int i = TaiG2Cofactor::TOP - 1; i >= 0; i--) {
+    s = xyzz_dbl(s);      // inlined, as in wire_in_subgroup_ladder
+    if ((TaiG2Cofactor::H2[i >> 6] >> (i & 63)) & 1) xyzz_madd(s, p);
+  }
+  return s;
+}
+// scale_by_cofactor + affine normalisation; false when the multiple is the identity (the reference then tries the next counter)
+HD bool tai_finish_g2(const Affine<Fq2>& p, Affine<Fq2>& out) {
+  const Xyzz<Fq2> s = tai_cofactor_ladder_g2(p);
+  if (s.is_identity() || s.ZZ.is_zero_mod_p()) return false;
+  const Fq2 t = Fq2::inv(Fq2::mul(s.ZZ, s.ZZZ));
+  out.x = Fq2::norm(Fq2::mul(s.X, Fq2::mul(t, s.ZZZ)));
+  out.y = Fq2::norm(Fq2::mul(s.Y, Fq2::mul(t, s.ZZ)));
+  return true;
+}
+// the serial loop: the host path (hash_to_g2_one_bls12_377) and the GPU path's fallback from counter c_start
+HD bool hash_to_g2_tai(const uint8_t dom[8], const uint8_t* msg, size_t mlen, const uint8_t* extra, size_t elen, int compat, const WireConsts& k,
+                       Affine<Fq2>& out, int& attempt, int c_start = 0, int mode = TAI_DIRECT, const EdPoint* gens = nullptr) {
+  for (int c = c_start; c < 255; c++) {
+    Affine<Fq2> p = {Fq2::zero(), Fq2::zero()};
+    if (!tai_candidate_g2(dom, msg, mlen, extra, elen, c, compat, k, p, mode, gens)) continue;
+    if (!tai_finish_g2(p, out)) continue;
+    attempt = c;
+    return true;
+  }
+  return false;
+}
+
 }  // namespace celo

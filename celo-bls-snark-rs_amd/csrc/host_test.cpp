@@ -444,6 +444,30 @@ int ht_tai_finish(const uint64_t* xy, uint64_t* out_xy) {
   r.y.to_ark(out_xy + 6);
   return 1;
 }
+// the G2 twins (hash_direct.h: hash_to_g2_tai, tai_finish_g2): rows of 24 ark limbs x.c0, x.c1, y.c0, y.c1; compat as in the entry points
+int ht_hash_to_g2(int mode, int compat, const uint8_t* dom, const uint8_t* msg, size_t mlen, const uint8_t* extra, size_t elen, const uint64_t* gens_ark,
+                  size_t nchunks, uint64_t* out_xy) {
+  if (mode < TAI_DIRECT || mode > TAI_COMPOSITE) return -2;
+  std::vector<EdPoint> gens;
+  if (mode == TAI_COMPOSITE) {
+    if (!gens_ark || ((1 + elen + mlen) * 8 + 2) / 3 > nchunks) return -2;
+    gens = ht_load_gens(gens_ark, nchunks);
+  }
+  Affine<Fq2> p = {Fq2::zero(), Fq2::zero()};
+  int c = -1;
+  if (!hash_to_g2_tai(dom, msg, mlen, extra, elen, compat, wire_consts(), p, c, 0, mode, gens.data())) return -1;
+  p.x.to_ark(out_xy);
+  p.y.to_ark(out_xy + 12);
+  return c;
+}
+int ht_tai_finish_g2(const uint64_t* xy, uint64_t* out_xy) {
+  const Affine<Fq2> p = {Fq2::norm(Fq2::from_ark(xy)), Fq2::norm(Fq2::from_ark(xy + 12))};
+  Affine<Fq2> r = {Fq2::zero(), Fq2::zero()};
+  if (!tai_finish_g2(p, r)) return 0;
+  r.x.to_ark(out_xy);
+  r.y.to_ark(out_xy + 12);
+  return 1;
+}
 // table-driven root vs the Tonelli-Shanks loop on one Fq element (ark limbs): returns 1 + 2*(roots agree up to sign) when a root
 // exists for both, 0 when both say non-residue, -1 on disagreement
 int ht_wire_fq_sqrt_both(const uint64_t* a, uint64_t* out) {

@@ -1,8 +1,9 @@
-// Translation unit: batched hash-to-G1 over the direct hasher (see hash_direct.h): rounds of candidate counters, then the
-// cofactor ladder.
+// Translation unit: batched hash-to-G1 and hash-to-G2 (see hash_direct.h): rounds of candidate counters, then the cofactor ladder.  The two
+// groups have kernels of their own and share the round loop (hash_rounds), the scratch, the stream and the mutex.
 #include "hash_direct.h"
 #include "pedersen.h"
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <mutex>
 #include <vector>
 #include <cstring>
@@ -77,6 +78,58 @@ k_hash_finish(const uint64_t* __restrict__ cand_xy, const uint8_t* __restrict__ 
   else { redo[i] = 1; for (int j = 0; j < 12; j++) o[j] = 0; }
 }
 
+// ---- the same two kernels for G2: candidates are points of the twist over Fq2 (three XOF blocks, an Fq2 root: hash_direct.h
+// tai_candidate_g2), rows are 24 limbs (x.c0, x.c1, y.c0, y.c1: the layout of msm_bls12_377_g2's bases), the cofactor ladder has 501 steps.
+// Siblings, not instantiations of one template: the G1 kernels stay the source they were measured as.
+__global__ void __launch_bounds__(64) FROW_OCC
+k_hash_candidates_g2(HashDom dom, HashIn in, const uint32_t* __restrict__ list, uint32_t count, uint32_t cand_log, uint32_t base, int mode, int compat,
+                     const EdPoint* __restrict__ gens, uint64_t* __restrict__ cand_xy, uint8_t* __restrict__ attempts, uint32_t* __restrict__ next_list,
+                     uint32_t* __restrict__ next_count, WireConsts k) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t j = t >> cand_log, s = t & ((1u << cand_log) - 1);
+  const bool live = j < count;
+  const uint32_t i = live ? (list ? list[j] : j) : 0;
+  const uint32_t c = base + s;
+  bool ok = false;
+  Affine<Fq2> p = {Fq2::zero(), Fq2::zero()};
+  if (live && c < 255) {
+    const uint8_t* msg = in.msgs + in.msg_off[i];
+    const size_t mlen = (size_t)(in.msg_off[i + 1] - in.msg_off[i]);
+    const uint8_t* extra = in.extra_off ? in.extras + in.extra_off[i] : nullptr;
+    const size_t elen = in.extra_off ? (size_t)(in.extra_off[i + 1] - in.extra_off[i]) : 0;
+    ok = tai_candidate_g2(dom.b, msg, mlen, extra, elen, (int)c, compat, k, p, mode, gens);
+  }
+  const uint64_t mask = __ballot(ok);
+  const uint32_t lane = threadIdx.x & 63, g0 = lane & ~((1u << cand_log) - 1);
+  const uint64_t gm = (mask >> g0) & (cand_log == 6 ? ~0ull : ((1ull << (1u << cand_log)) - 1));
+  if (!live) return;
+  if (gm) {
+    const uint32_t win = (uint32_t)__builtin_ctzll(gm);
+    if (s == win) {
+      uint64_t* o = cand_xy + (size_t)i * 24;
+      p.x.to_ark(o);
+      p.y.to_ark(o + 12);
+      attempts[i] = (uint8_t)c;
+    }
+  } else if (s == 0) {
+    if (base + (1u << cand_log) >= 255) attempts[i] = 255;                // every counter tried: the reference errs
+    else next_list[atomicAdd(next_count, 1u)] = i;
+  }
+}
+__global__ void __launch_bounds__(64) FROW_OCC
+k_hash_finish_g2(const uint64_t* __restrict__ cand_xy, const uint8_t* __restrict__ attempts, uint64_t* __restrict__ out, uint8_t* __restrict__ redo, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint64_t* o = out + (size_t)i * 24;
+  redo[i] = 0;
+  if (attempts[i] == 255) { for (int j = 0; j < 24; j++) o[j] = 0; return; }
+  const uint64_t* ci = cand_xy + (size_t)i * 24;
+  const Affine<Fq2> p = {Fq2::norm(Fq2::from_ark(ci)), Fq2::norm(Fq2::from_ark(ci + 12))};
+  Affine<Fq2> r = {Fq2::zero(), Fq2::zero()};
+  if (tai_finish_g2(p, r)) { r.x.to_ark(o); r.y.to_ark(o + 12); }
+  else { redo[i] = 1; for (int j = 0; j < 24; j++) o[j] = 0; }
+}
+
 // celo_composite_gens (seam_hash.hip): the generator table, built once from the ChaCha20 stream of the reference
 static EdPoint* g_d_gens_dev[MAX_DEVICES] = {};      // its device copies (11.7 MB each), uploaded on first use (under hash_mu)
 #define g_d_gens g_d_gens_dev[api_device()]
@@ -108,8 +161,52 @@ static int hash_scratch(size_t need, HashScratch** out) {
 static float g_hash_ms = 0.f;
 static int g_hash_rounds = 0;
 
-int hash_to_g1_direct_run(const uint8_t* domain, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off,
-                          size_t n, uint64_t* out_xy, uint8_t* attempts, int mode) {
+static float g_hash_g2_ms[2] = {0.f, 0.f};      // the last G2 call's candidate rounds / finish kernel
+static std::atomic<int> g_g2_budget_log{17};    // celo_amd_hash_g2_set_lane_budget_log
+
+// What differs between the groups: the row width, the two kernels, the serial loop, the lane budget.  compat reaches only G2.
+struct HashG1 {
+  static constexpr int ROW = 12;
+  static int budget_log() { return 17; }
+  static void candidates(dim3 grid, hipStream_t st, const HashDom& dom, const HashIn& in, const uint32_t* list, uint32_t count, uint32_t cand_log, uint32_t base, int mode,
+                         int, const EdPoint* gens, uint64_t* cand, uint8_t* att, uint32_t* next, uint32_t* cnt, const WireConsts& k) {
+    hipLaunchKernelGGL(k_hash_candidates, grid, dim3(64), 0, st, dom, in, list, count, cand_log, base, mode, gens, cand, att, next, cnt, k);
+  }
+  static void finish(dim3 grid, hipStream_t st, const uint64_t* cand, const uint8_t* att, uint64_t* out, uint8_t* redo, uint32_t n) {
+    hipLaunchKernelGGL(k_hash_finish, grid, dim3(64), 0, st, cand, att, out, redo, n);
+  }
+  static bool serial(const uint8_t* dom, const uint8_t* msg, size_t mlen, const uint8_t* extra, size_t elen, int, const WireConsts& kh, uint64_t* o, int& c, int c_start,
+                     int mode, const EdPoint* gens) {
+    Affine<Fq> p = {Fq::zero(), Fq::zero()};
+    if (!hash_to_g1_direct_tai(dom, msg, mlen, extra, elen, kh, p, c, c_start, mode, gens)) return false;
+    p.x.to_ark(o); p.y.to_ark(o + 6);
+    return true;
+  }
+};
+struct HashG2 {
+  static constexpr int ROW = 24;
+  static int budget_log() { return g_g2_budget_log.load(); }
+  static void candidates(dim3 grid, hipStream_t st, const HashDom& dom, const HashIn& in, const uint32_t* list, uint32_t count, uint32_t cand_log, uint32_t base, int mode,
+                         int compat, const EdPoint* gens, uint64_t* cand, uint8_t* att, uint32_t* next, uint32_t* cnt, const WireConsts& k) {
+    hipLaunchKernelGGL(k_hash_candidates_g2, grid, dim3(64), 0, st, dom, in, list, count, cand_log, base, mode, compat, gens, cand, att, next, cnt, k);
+  }
+  static void finish(dim3 grid, hipStream_t st, const uint64_t* cand, const uint8_t* att, uint64_t* out, uint8_t* redo, uint32_t n) {
+    hipLaunchKernelGGL(k_hash_finish_g2, grid, dim3(64), 0, st, cand, att, out, redo, n);
+  }
+  static bool serial(const uint8_t* dom, const uint8_t* msg, size_t mlen, const uint8_t* extra, size_t elen, int compat, const WireConsts& kh, uint64_t* o, int& c,
+                     int c_start, int mode, const EdPoint* gens) {
+    Affine<Fq2> p = {Fq2::zero(), Fq2::zero()};
+    if (!hash_to_g2_tai(dom, msg, mlen, extra, elen, compat, kh, p, c, c_start, mode, gens)) return false;
+    p.x.to_ark(o); p.y.to_ark(o + 12);
+    return true;
+  }
+};
+
+// The round loop of both groups.  split_ms (optional): kernel time of the candidate rounds and of the finish kernel.
+template <class G>
+static int hash_rounds(const uint8_t* domain, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off, size_t n, int compat,
+                       uint64_t* out_xy, uint8_t* attempts, int mode, float* split_ms) {
+  constexpr int ROW = G::ROW;
   size_t ngens = 0;
   const EdPoint* h_gens = mode == TAI_COMPOSITE ? celo_composite_gens(&ngens) : nullptr;   // before the lock: 0.5 s on first use
   if (int rc0 = api_enter()) return rc0;
@@ -135,7 +232,7 @@ int hash_to_g1_direct_run(const uint8_t* domain, const uint8_t* msgs, const uint
   std::vector<uint8_t> redo(n);
   size_t off = 0;
   auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~size_t(255); return o; };
-  const size_t o_off = take((n + 1) * 2 * 8), o_out = take(n * 12 * 8), o_cand = take(n * 12 * 8), o_list = take(2 * n * 4), o_cnt = take(256 * 4),
+  const size_t o_off = take((n + 1) * 2 * 8), o_out = take(n * ROW * 8), o_cand = take(n * ROW * 8), o_list = take(2 * n * 4), o_cnt = take(256 * 4),
                o_att = take(n), o_redo = take(n), o_bytes = take(mb + eb + 8);
   HashScratch* hs = nullptr;
   if (hash_scratch(off, &hs)) return 10;
@@ -149,21 +246,22 @@ int hash_to_g1_direct_run(const uint8_t* domain, const uint8_t* msgs, const uint
   HIP_TRY(hipMemcpyAsync(d_off, msg_off, (n + 1) * 8, hipMemcpyHostToDevice, st), 10);
   if (extra_off) HIP_TRY(hipMemcpyAsync(d_off + n + 1, extra_off, (n + 1) * 8, hipMemcpyHostToDevice, st), 10);
   HIP_TRY(hipMemsetAsync(d_cnt, 0, 256 * 4, st), 10);
-  hipEvent_t e0, e1;
+  hipEvent_t e0, e1, em = nullptr;
   HIP_TRY(cs.event(&e0), 10);
   HIP_TRY(cs.event(&e1), 10);
+  if (split_ms) HIP_TRY(cs.event(&em), 10);
   HIP_TRY(hipEventRecord(e0, st), 10);
   const HashIn in = {d_bytes, d_off, d_bytes + mb, extra_off ? d_off + n + 1 : nullptr};
+  const size_t budget = size_t(1) << G::budget_log();
   uint32_t count = (uint32_t)n, base = 0;
   int round = 0;
   while (count && base < 255) {
     uint32_t cand_log = 0;
-    while (cand_log < 4 && ((size_t)count << (cand_log + 1)) <= (1u << 17)) cand_log++;     // fill ~2^17 lanes, at most 16 counters
+    while (cand_log < 4 && ((size_t)count << (cand_log + 1)) <= budget) cand_log++;     // fill the lane budget (2^17), at most 16 counters
     const uint32_t* list = round ? d_list + (size_t)(round & 1) * n : nullptr;
     uint32_t* next = d_list + (size_t)((round + 1) & 1) * n;
     const size_t lanes = (size_t)count << cand_log;
-    hipLaunchKernelGGL(k_hash_candidates, dim3((uint32_t)((lanes + 63) / 64)), dim3(64), 0, st, dom, in, list, count, cand_log, base, mode, d_gens, d_cand, d_att,
-                       next, d_cnt + round, k);
+    G::candidates(dim3((uint32_t)((lanes + 63) / 64)), st, dom, in, list, count, cand_log, base, mode, compat, d_gens, d_cand, d_att, next, d_cnt + round, k);
     HIP_TRY(hipGetLastError(), 10);
     HIP_TRY(hipMemcpyAsync(&count, d_cnt + round, 4, hipMemcpyDeviceToHost, st), 10);
     HIP_TRY(hipStreamSynchronize(st), 10);
@@ -171,26 +269,64 @@ int hash_to_g1_direct_run(const uint8_t* domain, const uint8_t* msgs, const uint
     round++;
   }
   g_hash_rounds = round;
-  hipLaunchKernelGGL(k_hash_finish, dim3(((uint32_t)n + 63) / 64), dim3(64), 0, st, d_cand, d_att, d_out, d_redo, (uint32_t)n);
+  if (split_ms) HIP_TRY(hipEventRecord(em, st), 10);
+  G::finish(dim3(((uint32_t)n + 63) / 64), st, d_cand, d_att, d_out, d_redo, (uint32_t)n);
   HIP_TRY(hipGetLastError(), 10);
   HIP_TRY(hipEventRecord(e1, st), 10);
-  HIP_TRY(hipMemcpyAsync(out_xy, d_out, n * 12 * 8, hipMemcpyDeviceToHost, st), 10);
+  HIP_TRY(hipMemcpyAsync(out_xy, d_out, n * ROW * 8, hipMemcpyDeviceToHost, st), 10);
   HIP_TRY(hipMemcpyAsync(attempts, d_att, n, hipMemcpyDeviceToHost, st), 10);
   HIP_TRY(hipMemcpyAsync(redo.data(), d_redo, n, hipMemcpyDeviceToHost, st), 10);
   HIP_TRY(hipStreamSynchronize(st), 10);
   HIP_TRY(hipEventElapsedTime(&g_hash_ms, e0, e1), 10);
+  if (split_ms) {
+    HIP_TRY(hipEventElapsedTime(&split_ms[0], e0, em), 10);
+    HIP_TRY(hipEventElapsedTime(&split_ms[1], em, e1), 10);
+  }
   // the counter whose cofactor multiple was the identity is skipped like the reference's loop does: continue serially after it
   for (size_t i = 0; i < n; i++) {
     if (!redo[i]) continue;
-    Affine<Fq> p = {Fq::zero(), Fq::zero()};
     int c = 255;
-    uint64_t* o = out_xy + i * 12;
-    if (hash_to_g1_direct_tai(domain, msgs + msg_off[i], msg_off[i + 1] - msg_off[i], extra_off ? extras + extra_off[i] : nullptr,
-                              extra_off ? extra_off[i + 1] - extra_off[i] : 0, kh, p, c, attempts[i] + 1, mode, h_gens)) { p.x.to_ark(o); p.y.to_ark(o + 6); attempts[i] = (uint8_t)c; }
-    else { attempts[i] = 255; memset(o, 0, 96); }
+    uint64_t* o = out_xy + i * ROW;
+    if (G::serial(domain, msgs + msg_off[i], msg_off[i + 1] - msg_off[i], extra_off ? extras + extra_off[i] : nullptr, extra_off ? extra_off[i + 1] - extra_off[i] : 0,
+                  compat, kh, o, c, attempts[i] + 1, mode, h_gens)) attempts[i] = (uint8_t)c;
+    else { attempts[i] = 255; memset(o, 0, ROW * 8); }
   }
   return 0;
 }
+int hash_to_g1_direct_run(const uint8_t* domain, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off,
+                          size_t n, uint64_t* out_xy, uint8_t* attempts, int mode) {
+  return hash_rounds<HashG1>(domain, msgs, msg_off, extras, extra_off, n, 0, out_xy, attempts, mode, nullptr);
+}
+int hash_to_g2_run(const uint8_t* domain, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off, size_t n, int compat,
+                   uint64_t* out_xy, uint8_t* attempts, int mode) {
+  if (compat != 0 && compat != 1) return 2;
+  return hash_rounds<HashG2>(domain, msgs, msg_off, extras, extra_off, n, compat, out_xy, attempts, mode, g_hash_g2_ms);
+}
+// one message on the host, no device touched: mode 0 direct, 1 the CIP22 tail (`msg` is the inner CRH), 2 composite, 3 composite CIP22
+int hash_to_g2_one_run(const uint8_t* domain, const uint8_t* msg, size_t mlen, const uint8_t* extra, size_t elen, int mode, int compat, uint64_t* out_xy, int* attempt) {
+  if (!domain || !out_xy || !attempt || (mlen && !msg) || (elen && !extra) || mode < 0 || mode > 3 || (compat != 0 && compat != 1)) return 2;
+  size_t ngens = 0;
+  const EdPoint* gens = mode >= 2 ? celo_composite_gens(&ngens) : nullptr;
+  uint8_t inner[48];
+  if (mode == 3) {
+    if (mlen * 8 > PEDERSEN_MAX_BITS) return 2;
+    pedersen_crh(gens, msg, mlen, inner);
+    msg = inner;
+    mlen = 48;
+  } else if (mode == 2 && (1 + mlen + elen) * 8 > PEDERSEN_MAX_BITS) return 2;
+  int c = 255;
+  *attempt = 255;
+  memset(out_xy, 0, 24 * 8);
+  if (!HashG2::serial(domain, msg, mlen, extra, elen, compat, wire_consts(), out_xy, c, 0, mode == 0 ? TAI_DIRECT : mode == 2 ? TAI_COMPOSITE : TAI_XOF_ONLY, gens)) return 0;
+  *attempt = c;
+  return 0;
+}
+int hash_g2_set_lane_budget_log(int log) {
+  if (log < 4 || log > 17) return 2;
+  g_g2_budget_log.store(log);
+  return 0;
+}
+void hash_g2_last_split(float ms[2]) { ms[0] = g_hash_g2_ms[0]; ms[1] = g_hash_g2_ms[1]; }
 // ---- bulk Pedersen CRH (pedersen.h): one message per lane; the 52080-generator table (11.7 MB) is uploaded on first use
 __global__ void __launch_bounds__(64) FROW_OCC
 k_pedersen_crh(const EdPoint* __restrict__ gens, const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ off, uint8_t* __restrict__ out, uint32_t n) {

@@ -111,6 +111,12 @@ int wire761_proof_serialize(const uint64_t* a_xyz, const uint64_t* b_xyz, const 
 int hash_to_g1_direct_run(const uint8_t* domain, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off, size_t n, uint64_t* out_xy,
                           uint8_t* attempts, int mode);
 int pedersen_crh_run(const uint8_t* msgs, const uint64_t* msg_off, size_t n, uint8_t* out48);
+// ---- hash to G2 (unit_hash.hip): the same round loop, rows of 24 limbs; compat 0 / 1: the flags as the XOF gives them / the deployed remap
+int hash_to_g2_run(const uint8_t* domain, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off, size_t n, int compat,
+                   uint64_t* out_xy, uint8_t* attempts, int mode);
+int hash_to_g2_one_run(const uint8_t* domain, const uint8_t* msg, size_t mlen, const uint8_t* extra, size_t elen, int mode, int compat, uint64_t* out_xy, int* attempt);
+int hash_g2_set_lane_budget_log(int log);
+void hash_g2_last_split(float ms[2]);
 float hash_last_ms();
 int hash_last_rounds();
 const EdPoint* celo_composite_gens(size_t* count);

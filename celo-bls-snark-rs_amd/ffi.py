@@ -60,6 +60,8 @@ EXPORTS = [
     "groth16_setup_r1cs_bls12_377", "celo_amd_r1cs_last_timings",
     "hash_to_g1_direct_bls12_377", "hash_to_g1_composite_bls12_377", "hash_to_g1_cip22_tail_bls12_377", "composite_crh_bls12_377",
     "celo_amd_hash_last_ms", "celo_amd_hash_last_rounds",
+    "hash_to_g2_direct_bls12_377", "hash_to_g2_cip22_tail_bls12_377", "hash_to_g2_composite_bls12_377", "hash_to_g2_one_bls12_377",
+    "celo_amd_hash_g2_set_lane_budget_log", "celo_amd_hash_g2_last_split",
     "groth16_vk_load_bw6_761", "groth16_vk_load_bw6_761_serialized", "groth16_vk_free", "groth16_verify_batch_bw6_761",
     "groth16_verify_batch_bw6_761_serialized", "celo_amd_groth16_draw_exponents", "celo_amd_groth16_verify_last",
     "groth16_vk_load_bls12_377", "groth16_vk_load_bls12_377_serialized", "groth16_verify_batch_bls12_377", "groth16_verify_batch_bls12_377_serialized",
@@ -1073,6 +1075,65 @@ def hash_to_g1_direct(domain, messages, extras=None, cip22_tail=False, composite
     return xy, att
 
 
+def hash_to_g2_composite(domain, messages, extras=None, cip22=False, compat=0):
+    """Batched hash-to-G2 with the composite hasher (include/celo_bls_amd.h: hash_to_g2_composite_bls12_377); same conventions as
+    hash_to_g2_direct."""
+    return hash_to_g2_direct(domain, messages, extras, composite=(2 if cip22 else 1), compat=compat)
+
+
+def hash_to_g2_direct(domain, messages, extras=None, cip22_tail=False, composite=0, compat=0):
+    """Batched try-and-increment hash-to-G2 (include/celo_bls_amd.h: hash_to_g2_direct_bls12_377; cip22_tail: hash_to_g2_cip22_tail_bls12_377
+    over precomputed inner CRHs).  Arguments as hash_to_g1_direct; compat 0: the flags as the XOF gives them (the reference's vectors), 1: the
+    deployed remap.  Returns (xy (n, 24) uint64: x.c0, x.c1, y.c0, y.c1 as arkworks Montgomery limbs, attempts (n,) uint8; 255 = no point)."""
+    n = len(messages)
+    assert len(domain) == 8 and (extras is None or len(extras) == n)
+
+    def pack(items):
+        off = np.zeros(n + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(b) for b in items], dtype=np.uint64) if n else []
+        data = np.frombuffer(b"".join(items) or b"\0", dtype=np.uint8)
+        return data, off
+    mdat, moff = pack(messages)
+    edat, eoff = pack(extras) if extras is not None else (None, None)
+    dom = np.frombuffer(bytes(domain), dtype=np.uint8)
+    xy = np.zeros((n, 24), dtype=np.uint64)
+    att = np.zeros(n, dtype=np.uint8)
+    if composite:
+        rc = lib().hash_to_g2_composite_bls12_377(_p(dom), _p(mdat), _p(moff), _p(edat), _p(eoff), C.c_size_t(n), C.c_int(composite - 1), C.c_int(compat), _p(xy), _p(att))
+    else:
+        fn = lib().hash_to_g2_cip22_tail_bls12_377 if cip22_tail else lib().hash_to_g2_direct_bls12_377
+        rc = fn(_p(dom), _p(mdat), _p(moff), _p(edat), _p(eoff), C.c_size_t(n), C.c_int(compat), _p(xy), _p(att))
+    if rc != 0:
+        raise RuntimeError("hash_to_g2 (%s) failed with code %d" % ("composite" if composite else "cip22 tail" if cip22_tail else "direct", rc))
+    return xy, att
+
+
+def hash_to_g2_one(domain, message, extra=b"", mode=0, compat=0):
+    """One message through the serial loop on the host (hash_to_g2_one_bls12_377: no device is touched).  mode 0 direct, 1 the CIP22 tail
+    (message = the inner CRH), 2 composite, 3 composite CIP22.  Returns (xy (24,) uint64, attempt; 255 = no point)."""
+    assert len(domain) == 8
+    xy = np.zeros(24, dtype=np.uint64)
+    att = C.c_int(0)
+    rc = lib().hash_to_g2_one_bls12_377(bytes(domain), bytes(message), C.c_size_t(len(message)), bytes(extra), C.c_size_t(len(extra)), C.c_int(mode), C.c_int(compat),
+                                        _p(xy), C.byref(att))
+    if rc != 0:
+        raise RuntimeError("hash_to_g2_one failed with code %d" % rc)
+    return xy, att.value
+
+
+def hash_g2_set_lane_budget_log(log):
+    """celo_amd_hash_g2_set_lane_budget_log: rounds give each open message the widest power of two of counters <= 16 with open * width <=
+    2^log (4 ... 17, default 17).  Returns the code: 0, or 2 for a value outside the range (nothing changes then)."""
+    return lib().celo_amd_hash_g2_set_lane_budget_log(C.c_int(log))
+
+
+def hash_g2_last_split():
+    """(candidate rounds ms, cofactor kernel ms) of the last hash_to_g2_* call"""
+    ms = (C.c_float * 2)()
+    assert lib().celo_amd_hash_g2_last_split(ms) == 0
+    return tuple(ms)
+
+
 def hash_last_ms():
     ms = C.c_float(0)
     assert lib().celo_amd_hash_last_ms(C.byref(ms)) == 0
@@ -1080,7 +1141,7 @@ def hash_last_ms():
 
 
 def hash_last_rounds():
-    """Candidate rounds (kernel launches of the try-and-increment loop) of the last hash_to_g1_* call that hashed a message."""
+    """Candidate rounds (kernel launches of the try-and-increment loop) of the last hash_to_g1_* or hash_to_g2_* call that hashed a message."""
     r = C.c_int(0)
     assert lib().celo_amd_hash_last_rounds(C.byref(r)) == 0
     return r.value

@@ -570,10 +570,35 @@ int hash_to_g1_composite_bls12_377(const uint8_t domain[8], const uint8_t* msgs,
  * signatures.rs:169, is the one-message form).  out48: n x 48 bytes, the affine x coordinate little-endian.  A message longer
  * than 93 * 560 * 3 bits is an error for the whole call (the reference panics). */
 int composite_crh_bls12_377(const uint8_t* msgs, const uint64_t* msg_off /* n+1 */, size_t n, uint8_t* out48 /* n x 48 */);
-/* kernel time (HIP events) of the last hash_to_g1_* call */
+/* ---- batched hash-to-G2: the same hashers and loops onto the twist over Fq2 - TryAndIncrement<H, G2> / TryAndIncrementCIP22<H, G2>
+ * (try_and_increment.rs:63-140, try_and_increment_cip22.rs:75-135; the reference pins ten outputs, hash_to_curve/mod.rs:490-513).  A candidate
+ * is 96 XOF bytes (hash_length(96) = 96: every node offset carries 96); the winning point is multiplied by the 502-bit cofactor of the twist.
+ * Arguments, layouts and return codes are those of the hash_to_g1_* entries, except: out_xy is n x 24 u64 (x.c0, x.c1, y.c0, y.c1 in arkworks
+ * Montgomery limbs, the G2 layout of the MSM / pairing entry points), and compat selects the flag logic: 0 = the y-sign flag is bit 7 of byte
+ * 95 as the XOF gives it (the reference's vectors), 1 = the deployed remap, bit 1 of byte 95 copied into bit 7 first
+ * (try_and_increment.rs:107-120).  Any other compat value returns 2. */
+int hash_to_g2_direct_bls12_377(const uint8_t domain[8], const uint8_t* msgs, const uint64_t* msg_off /* n+1 */, const uint8_t* extras,
+                                const uint64_t* extra_off /* n+1 or NULL */, size_t n, int compat, uint64_t* out_xy /* n x 24 */, uint8_t* attempts /* n */);
+int hash_to_g2_cip22_tail_bls12_377(const uint8_t domain[8], const uint8_t* inner, const uint64_t* inner_off /* n+1 */, const uint8_t* extras,
+                                    const uint64_t* extra_off /* n+1 or NULL */, size_t n, int compat, uint64_t* out_xy /* n x 24 */, uint8_t* attempts /* n */);
+int hash_to_g2_composite_bls12_377(const uint8_t domain[8], const uint8_t* msgs, const uint64_t* msg_off /* n+1 */, const uint8_t* extras,
+                                   const uint64_t* extra_off /* n+1 or NULL */, size_t n, int cip22, int compat, uint64_t* out_xy /* n x 24 */,
+                                   uint8_t* attempts /* n */);
+/* One message through the serial loop on the HOST: no device is touched, so it works on a machine without a GPU.  mode: 0 direct, 1 the
+ * CIP22 tail (msg is the inner CRH), 2 composite, 3 composite CIP22.  *attempt = 255 and a zero row when no counter below 255 gives a point. */
+int hash_to_g2_one_bls12_377(const uint8_t domain[8], const uint8_t* msg, size_t mlen, const uint8_t* extra, size_t elen, int mode, int compat,
+                             uint64_t out_xy[24], int* attempt);
+/* The lane budget of the hash_to_g2_* rounds: every round gives each open message the widest power of two of counters, at most 16, with
+ * open * width <= 2^log.  Default 17 (what hash_to_g1_* uses); 4 ... 17 accepted, anything else returns 2.  A test hook: at 8 the widths
+ * 16 / 8 / 4 / 2 / 1 are reached at 16 / 32 / 64 / 128 / 129+ messages. */
+int celo_amd_hash_g2_set_lane_budget_log(int log);
+/* the last hash_to_g2_* call's kernel time in two parts: ms[0] the candidate rounds (with the host's round trips between them), ms[1] the
+ * cofactor kernel */
+int celo_amd_hash_g2_last_split(float ms[2]);
+/* kernel time (HIP events) of the last hash_to_g1_* or hash_to_g2_* call */
 int celo_amd_hash_last_ms(float* ms);
-/* candidate rounds (launches of the try-and-increment kernel) of the last hash_to_g1_* call that hashed at least one message: each round
- * gives every message still open 1, 2, 4, 8 or 16 adjacent counters, the width chosen from how many are open */
+/* candidate rounds (launches of the try-and-increment kernel) of the last hash_to_g1_* or hash_to_g2_* call that hashed at least one
+ * message: each round gives every message still open 1, 2, 4, 8 or 16 adjacent counters, the width chosen from how many are open */
 int celo_amd_hash_last_rounds(int* rounds);
 
 /* ---- plain sums of k Jacobian points (host pointers, arkworks layout; host-side, for small k): the fold of per-GPU
