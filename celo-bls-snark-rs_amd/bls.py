@@ -53,6 +53,19 @@ def signature_batch(exponents, signatures):
     return codec.jacobian_to_affine(out, codec.Q377)
 
 
+def sign_batch(secret_keys, messages, extras=None, pop=False, composite=False, cip22=False):
+    """PrivateKey::sign / sign_pop for many messages in one call (secret.rs:42-70; the sign_batch helper of test_helpers.rs:20).  secret_keys: one
+    int below r (it signs every message) or a list of one per message; messages / extras: lists of bytes.  pop: hash under POP_DOMAIN instead of
+    SIG_DOMAIN.  Returns the list of 48-byte compressed signatures (serialize_signature's bytes); a message whose hash found no counter raises
+    BLSError, as the reference's HashToCurveError does."""
+    keys = [secret_keys] if isinstance(secret_keys, int) else list(secret_keys)
+    mode = 3 if cip22 else 2 if composite else 0
+    sig, att = ffi.sign_batch(codec.ints_to_limbs(keys, 4), ffi.POP_DOMAIN if pop else ffi.SIG_DOMAIN, list(messages), extras, mode)
+    if (att == 255).any():
+        raise BLSError("hash to curve found no point for message %d" % int(np.argmax(att == 255)))
+    return [sig[i].tobytes() for i in range(len(messages))]
+
+
 def verify_hash(public_key, message_hash, signature):
     """PublicKey::verify_sig with the hash already computed (public.rs:94-120): e(sig,-g2) * e(H(m),pk) == 1."""
     g1, i1 = codec.pack_affine([signature, message_hash], codec.Q377)

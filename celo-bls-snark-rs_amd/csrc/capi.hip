@@ -529,6 +529,28 @@ int groth16_setup_bls12_377(const uint64_t* qap_a, const uint64_t* qap_b, const 
 }
 int celo_amd_fixed_base_set_window(int window_bits) { return fixed_base_set_window(window_bits); }
 int celo_amd_setup_last_timings(float ms[8]) { if (!ms) return 2; setup_last_timings(ms); return 0; }
+// ---- batched variable-base scalar multiplication and batched signing (unit_varbase.hip)
+#define SCALAR_MUL(NAME, GROUP, SUBGROUP)                                                                                                                   \
+  int scalar_mul_batch_##NAME(const uint64_t* xy, const uint8_t* inf, const uint64_t* scalars, size_t n_scalars, size_t n, uint64_t* out_xy, uint8_t* out_inf) { \
+    return scalar_mul_batch(GROUP, SUBGROUP, xy, inf, scalars, n_scalars, n, out_xy, out_inf, 0, nullptr);                                                 \
+  }                                                                                                                                                        \
+  int scalar_mul_batch_##NAME##_dev(const void* d_xy, const void* d_inf, const void* d_scalars, size_t n_scalars, size_t n, void* d_out_xy, void* d_out_inf, \
+                                    void* hip_stream) {                                                                                                    \
+    return scalar_mul_batch(GROUP, SUBGROUP, d_xy, d_inf, d_scalars, n_scalars, n, d_out_xy, d_out_inf, 1, hip_stream);                                    \
+  }
+SCALAR_MUL(bls12_377_g1, 0, 0)
+SCALAR_MUL(bls12_377_g1_subgroup, 0, 1)
+SCALAR_MUL(bls12_377_g2, 1, 0)
+SCALAR_MUL(bw6_761_g1, 2, 0)
+SCALAR_MUL(bw6_761_g2, 2, 0)
+#undef SCALAR_MUL
+int sign_batch_bls12_377(const uint64_t* sk, size_t n_sk, const uint8_t domain[8], const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras,
+                         const uint64_t* extra_off, size_t n, int mode, uint8_t* out_sig48, uint8_t* attempts) {
+  return sign_batch_377(sk, n_sk, domain, msgs, msg_off, extras, extra_off, n, mode, out_sig48, attempts);
+}
+int celo_amd_scalar_mul_set_window(int c) { return scalar_mul_set_window(c); }
+int celo_amd_scalar_mul_set_chunk_rows(uint32_t rows) { return scalar_mul_set_chunk_rows(rows); }
+int celo_amd_scalar_mul_last_ms(float ms[4]) { if (!ms) return 2; scalar_mul_last_ms(ms); return 0; }
 // ---- R1CS matrices on the device (unit_r1cs.hip)
 #define R1CS_LOAD(NAME, CURVE)                                                                                                                              \
   int NAME(size_t n_constraints, size_t n_vars, size_t n_inputs, const uint64_t* a_row_ptr, const uint32_t* a_col, const uint64_t* a_val, size_t a_nnz,     \

@@ -10,6 +10,7 @@
 #include "wire.h"
 #include "wire761.h"
 #include "fixed_base.h"
+#include "var_base.h"
 #include "groth16_verify.h"
 #include "r1cs.h"
 #include "hash_direct.h"
@@ -613,6 +614,65 @@ void ht_fixed_base_mul(int group, const uint64_t* gen, const uint64_t* sc, size_
   if (group == 0) fbm_host<Fp<P377>, 4>(gen, sc, n, c, 253, out, inf);
   else if (group == 1) fbm_host<Fp2<P377>, 4>(gen, sc, n, c, 253, out, inf);
   else fbm_host<Fp<P761>, 6>(gen, sc, n, c, 377, out, inf);
+}
+// ---- var_base.h: the per-lane table, the plain ladder, the subgroup (GLV) ladder and the shared-scalar form of unit_varbase.hip's kernels, run in
+// host loops over the SAME lane-interleaved workspace (stride = n lanes); the affine form of each row by its own inversion, where the device
+// batches them.  group: 0 BLS12-377 G1, 1 BLS12-377 G2, 2 BW6-761.  n_sc: n, or 1 for one scalar shared by every row.
+extern "C++" {
+template <class F> struct VbHost {
+  static constexpr int FW = F::WORDS, A = F::ARK64;
+  std::vector<uint4> chain, table;
+  std::vector<uint8_t> tinf;
+  size_t n;
+  uint32_t H;
+  VbHost(const uint64_t* xy, const uint8_t* inf, size_t n_, int c) : n(n_), H(1u << (c - 1)) {
+    chain.resize((size_t)H * FW * n); table.resize((size_t)H * (2 * FW / 4) * n); tinf.resize((size_t)H * n);
+    for (size_t i = 0; i < n; i++) {
+      const Affine<F> p = {F::norm(F::from_ark(xy + i * 2 * A)), F::norm(F::from_ark(xy + i * 2 * A + A))};
+      vb_build_table<F>(p, inf && inf[i], H, chain.data(), table.data(), tinf.data(), n, (uint32_t)i);
+    }
+  }
+  static void row(const Xyzz<F>& a, uint64_t* o, uint8_t* inf) {
+    Affine<F> r;
+    if (fb_to_affine(a, r)) { r.x.to_ark(o); r.y.to_ark(o + A); *inf = 0; }
+    else { for (int k = 0; k < 2 * A; k++) o[k] = 0; *inf = 1; }
+  }
+};
+template <class F> static void vb_table_host(const uint64_t* xy, int inf, int c, uint64_t* out, uint8_t* oinf) {
+  const uint8_t f = inf ? 1 : 0;
+  VbHost<F> t(xy, &f, 1, c);
+  for (uint32_t e = 0; e < t.H; e++) {
+    oinf[e] = t.tinf[e];
+    const Affine<F> p = vb_load_entry<F>(t.table.data(), 1, 0, e);
+    uint64_t* o = out + (size_t)e * 2 * VbHost<F>::A;
+    if (oinf[e]) for (int k = 0; k < 2 * VbHost<F>::A; k++) o[k] = 0;
+    else { p.x.to_ark(o); p.y.to_ark(o + VbHost<F>::A); }
+  }
+}
+template <class F, int N64> static void vb_mul_host(const uint64_t* xy, const uint8_t* inf, const uint64_t* sc, size_t n_sc, size_t n, int c, int bits, int glv,
+                                                    uint64_t* out, uint8_t* oinf) {
+  VbHost<F> t(xy, inf, n, c);
+  for (size_t i = 0; i < n; i++) {
+    const uint64_t* s = sc + (n_sc == 1 ? 0 : i) * N64;
+    Xyzz<F> a;
+    if constexpr (N64 == 4 && sizeof(F) <= 64) a = glv ? vb_ladder_glv<F>(s, c, t.table.data(), t.tinf.data(), n, (uint32_t)i)
+                                                        : vb_ladder<F, N64>(s, bits, c, t.table.data(), t.tinf.data(), n, (uint32_t)i);
+    else a = vb_ladder<F, N64>(s, bits, c, t.table.data(), t.tinf.data(), n, (uint32_t)i);
+    VbHost<F>::row(a, out + i * 2 * VbHost<F>::A, oinf + i);
+  }
+}
+}  // extern "C++"
+// the table of ONE point: out 2^(c-1) rows [e + 1]P (affine arkworks limbs, zero rows for identities), oinf their flags
+void ht_var_base_table(int group, const uint64_t* xy, int inf, int c, uint64_t* out, uint8_t* oinf) {
+  if (group == 0) vb_table_host<Fp<P377>>(xy, inf, c, out, oinf);
+  else if (group == 1) vb_table_host<Fp2<P377>>(xy, inf, c, out, oinf);
+  else vb_table_host<Fp<P761>>(xy, inf, c, out, oinf);
+}
+// out[i] = [k_i] P_i by the plain ladder (glv = 0) or, group 0 only, the subgroup ladder (glv = 1)
+void ht_var_base_mul(int group, int glv, const uint64_t* xy, const uint8_t* inf, const uint64_t* sc, size_t n_sc, size_t n, int c, uint64_t* out, uint8_t* oinf) {
+  if (group == 0) vb_mul_host<Fp<P377>, 4>(xy, inf, sc, n_sc, n, c, 253, glv, out, oinf);
+  else if (group == 1) vb_mul_host<Fp2<P377>, 4>(xy, inf, sc, n_sc, n, c, 253, 0, out, oinf);
+  else vb_mul_host<Fp<P761>, 6>(xy, inf, sc, n_sc, n, c, 377, 0, out, oinf);
 }
 // ---- groth16_verify.h: the lane routines of groth16_verify_unit.h's kernels in host loops, one template over the curve description; the
 // exported twins are its two instantiations (BW6-761: rows of 24 u64, inputs of 6; BLS12-377: G1 rows of 12 u64, inputs of 4).

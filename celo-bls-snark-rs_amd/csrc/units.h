@@ -132,6 +132,15 @@ int groth16_setup(int curve, const uint64_t* qa, const uint64_t* qb, const uint6
 int groth16_setup_r1cs(int curve, const R1cs* r, unsigned log_n, const uint64_t* omega, const uint64_t* tau, const uint64_t* toxic, const uint64_t* g1_xy,
                        const uint64_t* g2_xy, int window_bits, uint64_t* out_vk, uint64_t* out_rows, ProvingKey** out_key);
 
+// ---- batched variable-base scalar multiplication and batched signing (unit_varbase.hip).  group 0 / 1: BLS12-377 G1 / G2, 2: BW6-761
+int scalar_mul_batch(int group, int subgroup, const void* xy, const void* inf, const void* scalars, size_t n_scalars, size_t n, void* out_xy, void* out_inf, int dev,
+                     void* stream);
+int scalar_mul_set_window(int c);
+int scalar_mul_set_chunk_rows(uint32_t rows);
+void scalar_mul_last_ms(float ms[4]);
+int sign_batch_377(const uint64_t* sk, size_t n_sk, const uint8_t* domain, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off,
+                   size_t n, int mode, uint8_t* out_sig48, uint8_t* attempts);
+
 // ---- constraint matrices (unit_r1cs.hip)
 int r1cs_load(int curve, size_t m, size_t n_vars, size_t n_inputs, const uint64_t* const row_ptr[3], const uint32_t* const col[3], const uint64_t* const val[3],
               const uint64_t nnz[3], R1cs** out, uint64_t* first_bad);

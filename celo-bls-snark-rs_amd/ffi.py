@@ -66,6 +66,10 @@ EXPORTS = [
     "groth16_verify_batch_bw6_761_serialized", "celo_amd_groth16_draw_exponents", "celo_amd_groth16_verify_last",
     "groth16_vk_load_bls12_377", "groth16_vk_load_bls12_377_serialized", "groth16_verify_batch_bls12_377", "groth16_verify_batch_bls12_377_serialized",
     "groth16_serialize_proof_bls12_377",
+    "scalar_mul_batch_bls12_377_g1", "scalar_mul_batch_bls12_377_g1_subgroup", "scalar_mul_batch_bls12_377_g2", "scalar_mul_batch_bw6_761_g1",
+    "scalar_mul_batch_bw6_761_g2", "scalar_mul_batch_bls12_377_g1_dev", "scalar_mul_batch_bls12_377_g1_subgroup_dev", "scalar_mul_batch_bls12_377_g2_dev",
+    "scalar_mul_batch_bw6_761_g1_dev", "scalar_mul_batch_bw6_761_g2_dev", "sign_batch_bls12_377",
+    "celo_amd_scalar_mul_set_window", "celo_amd_scalar_mul_set_chunk_rows", "celo_amd_scalar_mul_last_ms",
 ]
 
 _lib = None
@@ -1215,6 +1219,94 @@ def setup_timings():
     ms = (C.c_float * 8)()
     lib().celo_amd_setup_last_timings(ms)
     return dict(zip(("table", "fr_prep", "g1_rows", "g2_rows", "normalize", "key_tables", "wall"), list(ms)[:7]))
+
+
+# ---- batched variable-base scalar multiplication and batched signing (include/celo_bls_amd.h: scalar_mul_batch_*, sign_batch_bls12_377)
+SCALAR_MUL_BLOCK = 64                    # lanes per workgroup of the table and ladder kernels (csrc/unit_varbase.hip VB_BLOCK)
+SCALAR_MUL_WINDOWS = tuple(range(2, 9))  # the window bits celo_amd_scalar_mul_set_window accepts besides 0 (csrc/var_base.h VB_MIN_C .. VB_MAX_C)
+SIG_DOMAIN, POP_DOMAIN = b"ULforxof", b"ULforpop"
+
+
+def _scalar_mul_name(group, subgroup):
+    if subgroup and group != "bls12_377_g1":
+        raise ValueError("the subgroup path exists for bls12_377_g1 only")
+    return "scalar_mul_batch_" + group + ("_subgroup" if subgroup else "")
+
+
+def scalar_mul_batch(group, xy, inf, scalars, subgroup=False):
+    """out_i = [k_i] P_i: xy (n, 12 | 24) affine arkworks limbs, inf (n,) uint8 or None, scalars (n, 4 | 6) canonical uint64 limbs - or ONE row,
+    shared by every point.  subgroup (bls12_377_g1 only): the caller vouches for points of the prime-order subgroup (the GLV ladder).
+    Returns (xy, inf) in the row format of fixed_base_mul.  Raises ValueError on code 2 (a scalar >= r, a scalar count that is neither 1 nor n)."""
+    aw, sw, _ = GROUP_SHAPE[group]
+    name = _scalar_mul_name(group, subgroup)
+    pts = _rows(xy, aw)
+    n = pts.shape[0]
+    sc = _rows(scalars, sw)
+    fl = None if inf is None else np.ascontiguousarray(inf, dtype=np.uint8)
+    assert fl is None or fl.shape == (n,)
+    out = np.zeros((n, aw), dtype=np.uint64)
+    oinf = np.zeros(n, dtype=np.uint8)
+    rc = getattr(lib(), name)(_p(pts), _p(fl), _p(sc), C.c_size_t(sc.shape[0]), C.c_size_t(n), _p(out), _p(oinf))
+    if rc == 2:
+        raise ValueError("%s: bad arguments (code 2)" % name)
+    if rc != 0:
+        raise RuntimeError("%s failed with code %d" % (name, rc))
+    return out, oinf
+
+
+def scalar_mul_batch_dev(group, d_xy, d_inf, d_scalars, n_scalars, n, d_out, d_out_inf, subgroup=False, stream=0):
+    """The same on device buffers (data pointers; d_inf may be 0 / None); returns the code (0, or 2: nothing written)."""
+    return getattr(lib(), _scalar_mul_name(group, subgroup) + "_dev")(C.c_void_p(d_xy), C.c_void_p(d_inf or None), C.c_void_p(d_scalars), C.c_size_t(n_scalars),
+                                                                     C.c_size_t(n), C.c_void_p(d_out), C.c_void_p(d_out_inf), C.c_void_p(stream))
+
+
+def set_scalar_mul_window(c):
+    """the ladder's window bits (0 = the default, else one of SCALAR_MUL_WINDOWS)"""
+    rc = lib().celo_amd_scalar_mul_set_window(C.c_int(c))
+    if rc != 0:
+        raise ValueError("celo_amd_scalar_mul_set_window(%d) failed with code %d" % (c, rc))
+
+
+def set_scalar_mul_chunk_rows(rows):
+    """rows per chunk of the per-call workspace (0 = the default)"""
+    rc = lib().celo_amd_scalar_mul_set_chunk_rows(C.c_uint32(rows))
+    if rc != 0:
+        raise ValueError("celo_amd_scalar_mul_set_chunk_rows(%d) failed with code %d" % (rows, rc))
+
+
+def scalar_mul_last_ms():
+    """the last scalar_mul_batch_* / sign_batch call: {table, ladder, normalize, wall} in ms"""
+    ms = (C.c_float * 4)()
+    assert lib().celo_amd_scalar_mul_last_ms(ms) == 0
+    return dict(zip(("table", "ladder", "normalize", "wall"), list(ms)))
+
+
+def sign_batch(sk, domain, messages, extras=None, mode=0):
+    """sig_i = [sk_i] H(msg_i) (include/celo_bls_amd.h: sign_batch_bls12_377).  sk: (1 | n, 4) canonical uint64 limbs (one key for every message,
+    or one per message); domain: SIG_DOMAIN | POP_DOMAIN; messages / extras: lists of bytes (extras None = no extra data); mode 0 direct,
+    2 composite, 3 composite CIP22.  Returns (sigs (n, 48) uint8 as serialize_signature writes them, attempts (n,) uint8; 255 = no point and a
+    zero signature).  Raises ValueError on code 2."""
+    n = len(messages)
+    assert len(domain) == 8 and (extras is None or len(extras) == n)
+
+    def pack(items):
+        off = np.zeros(n + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(b) for b in items], dtype=np.uint64) if n else []
+        data = np.frombuffer(b"".join(items) or b"\0", dtype=np.uint8)
+        return data, off
+    mdat, moff = pack(messages)
+    edat, eoff = pack(extras) if extras is not None else (None, None)
+    dom = np.frombuffer(bytes(domain), dtype=np.uint8)
+    keys = _rows(sk, 4)
+    sig = np.zeros((n, 48), dtype=np.uint8)
+    att = np.zeros(n, dtype=np.uint8)
+    rc = lib().sign_batch_bls12_377(_p(keys), C.c_size_t(keys.shape[0]), _p(dom), _p(mdat), _p(moff), _p(edat), _p(eoff), C.c_size_t(n), C.c_int(mode), _p(sig),
+                                    _p(att))
+    if rc == 2:
+        raise ValueError("sign_batch_bls12_377: bad arguments (code 2)")
+    if rc != 0:
+        raise RuntimeError("sign_batch_bls12_377 failed with code %d" % rc)
+    return sig, att
 
 
 class SetupError(RuntimeError):

@@ -696,6 +696,57 @@ int groth16_setup_bls12_377(const uint64_t* qap_a, const uint64_t* qap_b, const 
 int celo_amd_fixed_base_set_window(int window_bits);
 int celo_amd_setup_last_timings(float ms[8]);
 
+/* ---- Batched variable-base scalar multiplication out_i = [k_i] P_i: n points, each with its own scalar (PrivateKey::sign = hash * sk,
+ * crates/bls-crypto/src/bls/secret.rs:65; the sign_batch / keygen_mul helpers of crates/bls-crypto/src/test_helpers.rs:20,54; re-randomising
+ * points, blinding a list of keys).  csrc/var_base.h, csrc/unit_varbase.hip, DESIGN.md section 6i.
+ * xy: n affine points in arkworks Montgomery limbs (12 u64 for BLS12-377 G1, 24 for the other groups); inf: n identity flags, or NULL for none.
+ * P_i is ANY point of the curve, not only the prime-order subgroup (points off the curve are not validated, as elsewhere).
+ * scalars: n_scalars x (4 | 6) u64, canonical and below the group order r; n_scalars is n, or 1: every row then uses scalars[0] (one key, many
+ * messages) and the scalar is not copied.
+ * out_xy / out_inf: the row format of fixed_base_mul_*: affine arkworks limbs, and a zero row with inf = 1 for the identity.
+ * _subgroup (BLS12-377 G1 only): the CALLER vouches that every P_i lies in the prime-order subgroup - the contract of
+ * msm_bls12_377_g1_subgroup.  The scalar is split k = k0 + k1 x^2 and [k]P = [k0]P + [k1](beta x, -y), the halves sharing ~127 doublings
+ * instead of 253; the result is the same group element, so the same row bit for bit.  With a point outside the subgroup the result is
+ * unspecified.  G2 and BW6-761 have the plain path only (their endomorphism forms are not implemented here).
+ * _dev: every pointer is a DEVICE pointer, the work is enqueued on hip_stream and the call returns after it has drained.
+ * Returns 0 (also for n = 0); 2 with NOTHING written: a NULL xy / scalars / output, n_scalars not in {1, n}, a scalar >= r; 1 / 10: HIP errors. */
+int scalar_mul_batch_bls12_377_g1(const uint64_t* xy /* n x 12 */, const uint8_t* inf /* n or NULL */, const uint64_t* scalars /* n_scalars x 4 */,
+                                  size_t n_scalars, size_t n, uint64_t* out_xy, uint8_t* out_inf);
+int scalar_mul_batch_bls12_377_g1_subgroup(const uint64_t* xy /* n x 12 */, const uint8_t* inf, const uint64_t* scalars /* n_scalars x 4 */,
+                                           size_t n_scalars, size_t n, uint64_t* out_xy, uint8_t* out_inf);
+int scalar_mul_batch_bls12_377_g2(const uint64_t* xy /* n x 24 */, const uint8_t* inf, const uint64_t* scalars /* n_scalars x 4 */, size_t n_scalars,
+                                  size_t n, uint64_t* out_xy, uint8_t* out_inf);
+int scalar_mul_batch_bw6_761_g1(const uint64_t* xy /* n x 24 */, const uint8_t* inf, const uint64_t* scalars /* n_scalars x 6 */, size_t n_scalars,
+                                size_t n, uint64_t* out_xy, uint8_t* out_inf);
+int scalar_mul_batch_bw6_761_g2(const uint64_t* xy /* n x 24 */, const uint8_t* inf, const uint64_t* scalars /* n_scalars x 6 */, size_t n_scalars,
+                                size_t n, uint64_t* out_xy, uint8_t* out_inf);
+int scalar_mul_batch_bls12_377_g1_dev(const void* d_xy, const void* d_inf, const void* d_scalars, size_t n_scalars, size_t n, void* d_out_xy,
+                                      void* d_out_inf, void* hip_stream);
+int scalar_mul_batch_bls12_377_g1_subgroup_dev(const void* d_xy, const void* d_inf, const void* d_scalars, size_t n_scalars, size_t n, void* d_out_xy,
+                                               void* d_out_inf, void* hip_stream);
+int scalar_mul_batch_bls12_377_g2_dev(const void* d_xy, const void* d_inf, const void* d_scalars, size_t n_scalars, size_t n, void* d_out_xy,
+                                      void* d_out_inf, void* hip_stream);
+int scalar_mul_batch_bw6_761_g1_dev(const void* d_xy, const void* d_inf, const void* d_scalars, size_t n_scalars, size_t n, void* d_out_xy,
+                                    void* d_out_inf, void* hip_stream);
+int scalar_mul_batch_bw6_761_g2_dev(const void* d_xy, const void* d_inf, const void* d_scalars, size_t n_scalars, size_t n, void* d_out_xy,
+                                    void* d_out_inf, void* hip_stream);
+/* Batched signing, sig_i = [sk_i] H(msg_i): the hash of hash_to_g1_* (mode 0 direct, 2 composite, 3 composite CIP22 - the numbering of
+ * hash_to_g2_one_bls12_377; 1 is not a mode here), the subgroup path above (a hash is cofactor-cleared) and compress_bls12_377_g1.
+ * sk: n_sk x 4 u64 canonical, the 32 bytes of serialize_private_key; n_sk is 1 (one key signs every message) or n.  domain: SIG_DOMAIN for
+ * signatures, POP_DOMAIN for proofs of possession, as sign_message / sign_pop pass them.  msgs / msg_off / extras / extra_off: as
+ * hash_to_g1_direct_bls12_377 (extras and extra_off may be NULL).  out_sig48: n x 48 bytes as serialize_signature writes them; attempts: n
+ * counters.  A message whose hash found no counter (attempts[i] == 255) gets 48 zero bytes; the call still returns 0.
+ * Returns 0 (also for n = 0); 2 with nothing written: a NULL argument, n_sk not in {1, n}, a key >= r, an unknown mode. */
+int sign_batch_bls12_377(const uint64_t* sk /* n_sk x 4 */, size_t n_sk /* 1 or n */, const uint8_t domain[8], const uint8_t* msgs, const uint64_t* msg_off,
+                         const uint8_t* extras, const uint64_t* extra_off, size_t n, int mode, uint8_t* out_sig48 /* n x 48 */, uint8_t* attempts /* n */);
+/* test and A/B hooks: the ladder's window bits c (0 = the default of DESIGN.md 6i, else 2 .. 8: a table of 2^(c-1) entries per row); the rows
+ * per chunk of the per-call workspace (0 = the default, which keeps the workspace below 256 MiB; at most 2^24); and the last
+ * scalar_mul_batch_* / sign_batch_* call's times in ms: [0] table build, [1] ladder, [2] normalisation, [3] the whole call (wall; for
+ * sign_batch_* the hash included, whose kernel time celo_amd_hash_last_ms reports).  The setters return 2 for a value outside the range. */
+int celo_amd_scalar_mul_set_window(int c);
+int celo_amd_scalar_mul_set_chunk_rows(uint32_t rows);
+int celo_amd_scalar_mul_last_ms(float ms[4]);
+
 /* ---- R1CS matrices on the device: the step of ark-groth16 0.1 between cs.to_matrices() and the entry points above - the constraint evaluation
  * of R1CStoQAP::witness_map (prover) and R1CStoQAP::instance_map_with_evaluation (setup).  Synthesis (running the gadgets) stays with the caller;
  * its result is data: three sparse matrices of n_constraints rows and the full assignment.

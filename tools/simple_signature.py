@@ -6,7 +6,9 @@ COMPOSITE_HASH_TO_G1), the keys and signatures are aggregated (in the example's 
 signature count twice), ONE verify_signature of the aggregate.  Signing is host code; the pairing check runs
 on the GPU.
 
-usage: python tools/simple_signature.py -m MESSAGE [-k KEYS (default 64; 3 = the reference example's shape)] [--direct] [--cip22]"""
+--gpu-sign: the N signatures by ONE sign_batch_bls12_377 call on the device instead of the host loop over sign_message (the same bytes).
+
+usage: python tools/simple_signature.py -m MESSAGE [-k KEYS (default 64; 3 = the reference example's shape)] [--direct] [--cip22] [--gpu-sign]"""
 import argparse
 import ctypes as C
 import os
@@ -24,10 +26,11 @@ def main():
     ap.add_argument("-k", dest="keys", type=int, default=64)
     ap.add_argument("--direct", action="store_true", help="direct (Blake2Xs) hasher instead of the composite one")
     ap.add_argument("--cip22", action="store_true")
+    ap.add_argument("--gpu-sign", action="store_true", help="sign with one sign_batch_bls12_377 call instead of the host loop over sign_message")
     a = ap.parse_args()
     lib = C.CDLL(ffi.LIB_PATH)
     for f in ("init", "generate_private_key", "private_key_to_public_key", "sign_message", "aggregate_public_keys", "aggregate_signatures",
-              "verify_signature", "serialize_private_key", "serialize_signature", "serialize_public_key", "free_vec"):
+              "verify_signature", "serialize_private_key", "serialize_signature", "serialize_public_key", "deserialize_signature", "free_vec"):
         getattr(lib, f).restype = C.c_bool
     if not lib.init():
         sys.exit("no gfx950 device: the verification path has no CPU fallback")
@@ -45,8 +48,18 @@ def main():
     for i in range(a.keys):
         sk, pk, sg = C.c_void_p(), C.c_void_p(), C.c_void_p()
         assert lib.generate_private_key(C.byref(sk)) and lib.private_key_to_public_key(sk, C.byref(pk))
-        assert lib.sign_message(sk, msg, C.c_int(len(msg)), b"", C.c_int(0), comp, cip, C.byref(sg))
+        if not a.gpu_sign:
+            assert lib.sign_message(sk, msg, C.c_int(len(msg)), b"", C.c_int(0), comp, cip, C.byref(sg))
         sks.append(sk); pks.append(pk); sigs.append(sg)
+    if a.gpu_sign:
+        import numpy as np
+        keys = np.frombuffer(b"".join(bytes.fromhex(hexof("serialize_private_key", sk)) for sk in sks), dtype=np.uint64).reshape(a.keys, 4)
+        t0 = time.perf_counter()
+        raw, att = ffi.sign_batch(keys, ffi.SIG_DOMAIN, [msg] * a.keys, None, 0 if a.direct else 3 if a.cip22 else 2)
+        print("sign_batch: %d signatures in %.1f ms" % (a.keys, (time.perf_counter() - t0) * 1e3))
+        for i in range(a.keys):
+            assert att[i] != 255 and lib.deserialize_signature(raw[i].tobytes(), C.c_int(48), C.byref(sigs[i]))
+    for i, (sk, sg) in enumerate(zip(sks, sigs)):
         if a.keys <= 4:
             print("sk%d: %s" % (i + 1, hexof("serialize_private_key", sk)))
             print("sig%d: %s" % (i + 1, hexof("serialize_signature", sg)))
