@@ -66,6 +66,26 @@ def sign_batch(secret_keys, messages, extras=None, pop=False, composite=False, c
     return [sig[i].tobytes() for i in range(len(messages))]
 
 
+def verify_seals(public_keys, bitmaps, messages, signatures, extras=None, min_signers=None, composite=False, cip22=False, combined=False, key=None):
+    """Aggregated seals to verdicts in one call (include/celo_bls_amd.h: verify_aggregated_seals_bls12_377): the keys a bitmap selects are summed,
+    enough of them must have signed, and e(sig, -g2) e(H(m), apk) == 1.  public_keys: one list of affine G2 points shared by every seal, or a
+    list of such lists, one per seal; bitmaps: one sequence of 0 / 1 per seal; signatures: 48-byte compressed signatures; min_signers: one
+    int for every seal, a list, or None.  combined: one random linear combination first (mode 1; key: its 8 uint32 words, None = OS randomness).
+    Returns (list of bool, list of status codes 0 .. 4)."""
+    m = len(messages)
+    shared = m == 0 or not isinstance(public_keys[0], list)
+    sets = [list(public_keys)] if shared else [list(s) for s in public_keys]
+    pk_xy, pk_inf = codec.pack_affine([P for s in sets for P in s], codec.Q377, ext=2)
+    offsets = np.cumsum([0] + [len(s) for s in sets]).astype(np.uint32)
+    bits = np.array([list(b) for b in bitmaps], dtype=np.uint8).reshape(m, len(sets[0])) if shared else np.concatenate([np.asarray(list(b), dtype=np.uint8) for b in bitmaps])
+    mins = None if min_signers is None else np.full(m, min_signers, dtype=np.uint32) if isinstance(min_signers, int) else np.asarray(min_signers, dtype=np.uint32)
+    ng2, _ = codec.pack_affine([_neg_g2(G2_GENERATOR)], codec.Q377, ext=2)
+    sigs = np.frombuffer(b"".join(signatures) or b"\0" * 48, dtype=np.uint8)[:48 * m].reshape(m, 48)
+    ok, st = ffi.verify_aggregated_seals(pk_xy, pk_inf, offsets, bits, mins, ffi.SIG_DOMAIN, list(messages), extras, sigs, ng2[0],
+                                         hash_mode=3 if cip22 else 2 if composite else 0, mode=1 if combined else 0, key=key)
+    return [bool(x) for x in ok], [int(x) for x in st]
+
+
 def verify_hash(public_key, message_hash, signature):
     """PublicKey::verify_sig with the hash already computed (public.rs:94-120): e(sig,-g2) * e(H(m),pk) == 1."""
     g1, i1 = codec.pack_affine([signature, message_hash], codec.Q377)

@@ -551,6 +551,28 @@ int sign_batch_bls12_377(const uint64_t* sk, size_t n_sk, const uint8_t domain[8
 int celo_amd_scalar_mul_set_window(int c) { return scalar_mul_set_window(c); }
 int celo_amd_scalar_mul_set_chunk_rows(uint32_t rows) { return scalar_mul_set_chunk_rows(rows); }
 int celo_amd_scalar_mul_last_ms(float ms[4]) { if (!ms) return 2; scalar_mul_last_ms(ms); return 0; }
+// ---- masked segmented point sums and aggregated seals (unit_seals.hip)
+#define AGG_BITMAP(NAME, GROUP)                                                                                                                            \
+  int aggregate_by_bitmap_##NAME(const uint64_t* pk_xy, const uint8_t* pk_inf, const uint32_t* offsets, size_t n_sets, const uint8_t* bits, size_t m,      \
+                                 uint64_t* out_xy, uint8_t* out_inf, uint32_t* out_count) {                                                                \
+    return aggregate_by_bitmap(GROUP, pk_xy, pk_inf, offsets, n_sets, bits, m, out_xy, out_inf, out_count, 0, nullptr);                                    \
+  }                                                                                                                                                        \
+  int aggregate_by_bitmap_##NAME##_dev(const void* d_pk_xy, const void* d_pk_inf, const uint32_t* offsets, size_t n_sets, const void* d_bits, size_t m,    \
+                                       void* d_out_xy, void* d_out_inf, void* d_out_count, void* hip_stream) {                                             \
+    return aggregate_by_bitmap(GROUP, d_pk_xy, d_pk_inf, offsets, n_sets, d_bits, m, d_out_xy, d_out_inf, d_out_count, 1, hip_stream);                     \
+  }
+AGG_BITMAP(bls12_377_g1, 0)
+AGG_BITMAP(bls12_377_g2, 1)
+#undef AGG_BITMAP
+int verify_aggregated_seals_bls12_377(const uint64_t* pk_xy, const uint8_t* pk_inf, const uint32_t* offsets, size_t n_sets, const uint8_t* bits, const uint32_t* min_signers,
+                                      const uint8_t domain[8], const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off, int hash_mode,
+                                      const uint8_t* sig48, const uint64_t neg_g2_xy[24], size_t m, int mode, const uint32_t* key, uint8_t* out_ok, uint8_t* out_status) {
+  return verify_aggregated_seals_377(pk_xy, pk_inf, offsets, n_sets, bits, min_signers, domain, msgs, msg_off, extras, extra_off, hash_mode, sig48, neg_g2_xy, m, mode, key,
+                                     out_ok, out_status);
+}
+int celo_amd_aggregate_set_lanes(int lanes) { return aggregate_set_lanes(lanes); }
+int celo_amd_aggregate_set_complement(int mode) { return aggregate_set_complement(mode); }
+int celo_amd_seals_last(int* path, int* lanes, float ms[8]) { if (!path || !lanes || !ms) return 2; seals_last(path, lanes, ms); return 0; }
 // ---- R1CS matrices on the device (unit_r1cs.hip)
 #define R1CS_LOAD(NAME, CURVE)                                                                                                                              \
   int NAME(size_t n_constraints, size_t n_vars, size_t n_inputs, const uint64_t* a_row_ptr, const uint32_t* a_col, const uint64_t* a_val, size_t a_nnz,     \

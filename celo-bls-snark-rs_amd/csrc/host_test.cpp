@@ -11,6 +11,7 @@
 #include "wire761.h"
 #include "fixed_base.h"
 #include "var_base.h"
+#include "aggregate.h"
 #include "groth16_verify.h"
 #include "r1cs.h"
 #include "hash_direct.h"
@@ -674,6 +675,56 @@ void ht_var_base_mul(int group, int glv, const uint64_t* xy, const uint8_t* inf,
   else if (group == 1) vb_mul_host<Fp2<P377>, 4>(xy, inf, sc, n_sc, n, c, 253, 0, out, oinf);
   else vb_mul_host<Fp<P761>, 6>(xy, inf, sc, n_sc, n, c, 377, 0, out, oinf);
 }
+// ---- aggregate.h: k_seal_count and k_masked_sum of unit_seals.hip in host loops - the L lanes of a sum one after the other, their partials
+// folded through a buffer of L slots in the kernel's rounds, the complement by the kernel's rule - and each row's affine form by its own
+// inversion.  group 0 / 1: BLS12-377 G1 / G2.  offsets, n_sets, bits, m: as aggregate_by_bitmap_*; complement: -1 / 0 / 1.
+extern "C++" {
+template <class F>
+static Xyzz<F> agg_sum_host(const uint64_t* xy, const uint8_t* inf, const uint8_t* bits, uint32_t n, uint32_t L, bool neg, const uint32_t* total) {
+  const size_t SW = agg_slot_words<F>();
+  std::vector<Xyzz<F>> acc(L);
+  std::vector<uint4> slots(L * SW / 4);
+  uint32_t* sl = reinterpret_cast<uint32_t*>(slots.data());
+  for (uint32_t l = 0; l < L; l++) {
+    acc[l] = agg_lane_sum<F>(xy, inf, bits, n, l, L, neg);
+    agg_store<F>(sl + l * SW, acc[l]);
+  }
+  for (uint32_t s = L >> 1; s; s >>= 1) {
+    for (uint32_t l = 0; l < s; l++) agg_fold_step<F>(acc[l], sl, l, s);
+    if (s > 1) for (uint32_t l = 0; l < s; l++) agg_store<F>(sl + l * SW, acc[l]);
+  }
+  agg_finish<F>(acc[0], neg, total);
+  return acc[0];
+}
+template <class F>
+static void agg_host(const uint64_t* xy, const uint8_t* inf, const uint32_t* off, size_t n_sets, const uint8_t* bits, size_t m, int L, int complement, uint64_t* out,
+                     uint8_t* oinf, uint32_t* count) {
+  constexpr int A = F::ARK64;
+  const bool shared = n_sets == 1;
+  std::vector<uint4> total(F::WORDS);
+  uint32_t* tw = reinterpret_cast<uint32_t*>(total.data());
+  if (shared) agg_store<F>(tw, agg_sum_host<F>(xy + (size_t)off[0] * 2 * A, inf ? inf + off[0] : nullptr, nullptr, off[1] - off[0], AGG_MAX_LANES, false, nullptr));
+  for (size_t i = 0; i < m; i++) {
+    const uint32_t row0 = shared ? off[0] : off[i], n = shared ? off[1] - off[0] : off[i + 1] - off[i];
+    const uint8_t* b = bits + (shared ? i * (size_t)n : (size_t)off[i]);
+    const uint32_t c = agg_count(b, n);
+    const bool neg = agg_side(c, n, complement, shared);
+    const uint32_t lanes = L ? (uint32_t)L : agg_pick_lanes(neg ? n - c : c, m);
+    const Xyzz<F> a = agg_sum_host<F>(xy + (size_t)row0 * 2 * A, inf ? inf + row0 : nullptr, b, n, lanes, neg, tw);
+    count[i] = c;
+    Affine<F> r;
+    uint64_t* o = out + i * 2 * A;
+    if (fb_to_affine(a, r)) { r.x.to_ark(o); r.y.to_ark(o + A); oinf[i] = 0; }
+    else { for (int k = 0; k < 2 * A; k++) o[k] = 0; oinf[i] = 1; }
+  }
+}
+}  // extern "C++"
+void ht_aggregate_by_bitmap(int group, const uint64_t* xy, const uint8_t* inf, const uint32_t* off, size_t n_sets, const uint8_t* bits, size_t m, int lanes, int complement,
+                            uint64_t* out, uint8_t* oinf, uint32_t* count) {
+  if (group == 0) agg_host<Fp<P377>>(xy, inf, off, n_sets, bits, m, lanes, complement, out, oinf, count);
+  else agg_host<Fp2<P377>>(xy, inf, off, n_sets, bits, m, lanes, complement, out, oinf, count);
+}
+uint32_t ht_aggregate_pick_lanes(uint32_t max_adds, size_t m) { return agg_pick_lanes(max_adds, m); }
 // ---- groth16_verify.h: the lane routines of groth16_verify_unit.h's kernels in host loops, one template over the curve description; the
 // exported twins are its two instantiations (BW6-761: rows of 24 u64, inputs of 6; BLS12-377: G1 rows of 12 u64, inputs of 4).
 // g16_input_row_host: abc n_abc G1 rows (affine arkworks limbs, none the identity), inputs n x (n_abc - 1) canonical scalars, window bits c ->

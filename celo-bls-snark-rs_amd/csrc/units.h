@@ -141,6 +141,17 @@ void scalar_mul_last_ms(float ms[4]);
 int sign_batch_377(const uint64_t* sk, size_t n_sk, const uint8_t* domain, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off,
                    size_t n, int mode, uint8_t* out_sig48, uint8_t* attempts);
 
+// ---- masked segmented point sums: the aggregated key of every seal from its signer bitmap (unit_seals.hip).  group 0 / 1: BLS12-377 G1 / G2
+int aggregate_by_bitmap(int group, const void* xy, const void* inf, const uint32_t* offsets, size_t n_sets, const void* bits, size_t m, void* out_xy, void* out_inf,
+                        void* out_count, int dev, void* stream);
+int aggregate_set_lanes(int lanes);
+int aggregate_set_complement(int mode);
+// the last aggregate_by_bitmap / verify_aggregated_seals call: path (-1 for a bare sum), the lane width used, the stage times
+void seals_last(int* path, int* lanes, float ms[8]);
+int verify_aggregated_seals_377(const uint64_t* pk_xy, const uint8_t* pk_inf, const uint32_t* offsets, size_t n_sets, const uint8_t* bits, const uint32_t* min_signers,
+                                const uint8_t* domain, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off, int hash_mode,
+                                const uint8_t* sig48, const uint64_t neg_g2_xy[24], size_t m, int mode, const uint32_t* key, uint8_t* out_ok, uint8_t* out_status);
+
 // ---- constraint matrices (unit_r1cs.hip)
 int r1cs_load(int curve, size_t m, size_t n_vars, size_t n_inputs, const uint64_t* const row_ptr[3], const uint32_t* const col[3], const uint64_t* const val[3],
               const uint64_t nnz[3], R1cs** out, uint64_t* first_bad);

@@ -70,6 +70,8 @@ EXPORTS = [
     "scalar_mul_batch_bw6_761_g2", "scalar_mul_batch_bls12_377_g1_dev", "scalar_mul_batch_bls12_377_g1_subgroup_dev", "scalar_mul_batch_bls12_377_g2_dev",
     "scalar_mul_batch_bw6_761_g1_dev", "scalar_mul_batch_bw6_761_g2_dev", "sign_batch_bls12_377",
     "celo_amd_scalar_mul_set_window", "celo_amd_scalar_mul_set_chunk_rows", "celo_amd_scalar_mul_last_ms",
+    "aggregate_by_bitmap_bls12_377_g1", "aggregate_by_bitmap_bls12_377_g2", "aggregate_by_bitmap_bls12_377_g1_dev", "aggregate_by_bitmap_bls12_377_g2_dev",
+    "verify_aggregated_seals_bls12_377", "celo_amd_aggregate_set_lanes", "celo_amd_aggregate_set_complement", "celo_amd_seals_last",
 ]
 
 _lib = None
@@ -1307,6 +1309,117 @@ def sign_batch(sk, domain, messages, extras=None, mode=0):
     if rc != 0:
         raise RuntimeError("sign_batch_bls12_377 failed with code %d" % rc)
     return sig, att
+
+
+# ---- masked segmented point sums (include/celo_bls_amd.h: aggregate_by_bitmap_*)
+AGGREGATE_LANES = (1, 2, 4, 8, 16, 32, 64)   # the lane widths celo_amd_aggregate_set_lanes accepts besides 0 (csrc/aggregate.h)
+AGGREGATE_GROUPS = ("bls12_377_g1", "bls12_377_g2")
+
+
+def aggregate_by_bitmap(group, pk_xy, pk_inf, offsets, bits):
+    """out_i = sum of the rows of pk_xy that bits_i selects.  offsets: (m + 1,) uint32 with bits (rows,) parallel to the rows - per-seal sets -
+    or (2,) with bits (m, n) - one shared set of n = offsets[1] - offsets[0] rows.  pk_inf: (rows,) uint8 or None.  Returns (xy (m, 12 | 24), inf (m,),
+    count (m,) uint32) in the row format of fixed_base_mul.  Raises ValueError on code 2."""
+    if group not in AGGREGATE_GROUPS:
+        raise ValueError("aggregate_by_bitmap: group is one of %s" % (AGGREGATE_GROUPS,))
+    aw = GROUP_SHAPE[group][0]
+    pts = _rows(pk_xy, aw)
+    off = np.ascontiguousarray(offsets, dtype=np.uint32).reshape(-1)
+    b = np.ascontiguousarray(bits, dtype=np.uint8)
+    n_sets = off.shape[0] - 1
+    m = b.shape[0] if (b.ndim == 2 and n_sets == 1) else n_sets
+    fl = None if pk_inf is None else np.ascontiguousarray(pk_inf, dtype=np.uint8)
+    o = [int(v) for v in off]
+    if n_sets < 1 or any(hi < lo for lo, hi in zip(o, o[1:])) or pts.shape[0] < o[-1] or (fl is not None and fl.shape != (pts.shape[0],)) or \
+            b.size != (m * (o[1] - o[0]) if n_sets == 1 else o[-1]):
+        raise ValueError("aggregate_by_bitmap_%s: offsets, rows and bits do not match" % group)
+    if pts.shape[0] == 0:
+        pts = np.zeros((1, aw), dtype=np.uint64)      # (a pointer to pass: no row is read)
+    if b.size == 0:
+        b = np.zeros(1, dtype=np.uint8)
+    out = np.zeros((m, aw), dtype=np.uint64)
+    oinf = np.zeros(m, dtype=np.uint8)
+    cnt = np.zeros(m, dtype=np.uint32)
+    rc = getattr(lib(), "aggregate_by_bitmap_" + group)(_p(pts), _p(fl), _p(off), C.c_size_t(n_sets), _p(b), C.c_size_t(m), _p(out), _p(oinf), _p(cnt))
+    if rc == 2:
+        raise ValueError("aggregate_by_bitmap_%s: bad arguments (code 2)" % group)
+    if rc != 0:
+        raise RuntimeError("aggregate_by_bitmap_%s failed with code %d" % (group, rc))
+    return out, oinf, cnt
+
+
+def aggregate_by_bitmap_dev(group, d_pk_xy, d_pk_inf, offsets, d_bits, m, d_out_xy, d_out_inf, d_out_count=0, stream=0):
+    """The same on device buffers (data pointers; d_pk_inf and d_out_count may be 0 / None); offsets stays a host array.  Returns the code
+    (0, or 2: nothing written)."""
+    off = np.ascontiguousarray(offsets, dtype=np.uint32).reshape(-1)
+    return getattr(lib(), "aggregate_by_bitmap_" + group + "_dev")(C.c_void_p(d_pk_xy), C.c_void_p(d_pk_inf or None), _p(off), C.c_size_t(off.shape[0] - 1),
+                                                                  C.c_void_p(d_bits), C.c_size_t(m), C.c_void_p(d_out_xy), C.c_void_p(d_out_inf),
+                                                                  C.c_void_p(d_out_count or None), C.c_void_p(stream))
+
+
+def set_aggregate_lanes(lanes):
+    """lanes per sum (0 = the rule of csrc/aggregate.h, else one of AGGREGATE_LANES)"""
+    rc = lib().celo_amd_aggregate_set_lanes(C.c_int(lanes))
+    if rc != 0:
+        raise ValueError("celo_amd_aggregate_set_lanes(%d) failed with code %d" % (lanes, rc))
+
+
+def set_aggregate_complement(mode):
+    """-1 = the side rule, 0 = always sum the ones, 1 = the complement for every seal of a shared-set call"""
+    rc = lib().celo_amd_aggregate_set_complement(C.c_int(mode))
+    if rc != 0:
+        raise ValueError("celo_amd_aggregate_set_complement(%d) failed with code %d" % (mode, rc))
+
+
+def seals_last():
+    """the last aggregate_by_bitmap / verify_aggregated_seals call: {path (-1: a bare sum; 0 each, 1 combined accepted, 2 combined rejected then
+    each), lanes, ms: sums, decode, hash, combine, products, transfers, wall, count}"""
+    path, lanes, ms = C.c_int(0), C.c_int(0), (C.c_float * 8)()
+    assert lib().celo_amd_seals_last(C.byref(path), C.byref(lanes), ms) == 0
+    return {"path": path.value, "lanes": lanes.value, "ms": dict(zip(("sums", "decode", "hash", "combine", "products", "transfers", "wall", "count"), list(ms)))}
+
+
+def verify_aggregated_seals(pk_xy, pk_inf, offsets, bits, min_signers, domain, messages, extras, sigs, neg_g2_xy, hash_mode=0, mode=0, key=None):
+    """m aggregated seals to verdicts (include/celo_bls_amd.h: verify_aggregated_seals_bls12_377).  pk_xy / pk_inf / offsets / bits as
+    aggregate_by_bitmap (G2 keys); min_signers (m,) uint32 or None; messages / extras: lists of bytes (extras None = no extra data); sigs (m, 48)
+    uint8 as serialize_signature writes them; hash_mode 0 direct, 2 composite, 3 composite CIP22; mode 0 each, 1 combined; key (8,) uint32 or
+    None = OS randomness.  Returns (ok (m,) uint8, status (m,) uint8).  Raises ValueError on code 2."""
+    m = len(messages)
+    assert len(domain) == 8 and (extras is None or len(extras) == m)
+
+    def pack(items):
+        off = np.zeros(m + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(b) for b in items], dtype=np.uint64) if m else []
+        return np.frombuffer(b"".join(items) or b"\0", dtype=np.uint8), off
+    mdat, moff = pack(messages)
+    edat, eoff = pack(extras) if extras is not None else (None, None)
+    pts = _rows(pk_xy, 24)
+    off = np.ascontiguousarray(offsets, dtype=np.uint32).reshape(-1)
+    b = np.ascontiguousarray(bits, dtype=np.uint8)
+    fl = None if pk_inf is None else np.ascontiguousarray(pk_inf, dtype=np.uint8)
+    mins = None if min_signers is None else np.ascontiguousarray(min_signers, dtype=np.uint32)
+    sg = np.ascontiguousarray(sigs, dtype=np.uint8).reshape(-1, 48)
+    o = [int(v) for v in off]
+    n_sets = off.shape[0] - 1
+    if n_sets < 1 or any(hi < lo for lo, hi in zip(o, o[1:])) or pts.shape[0] < o[-1] or (fl is not None and fl.shape != (pts.shape[0],)) or \
+            b.size != (m * (o[1] - o[0]) if n_sets == 1 else o[-1]) or sg.shape[0] != m or (mins is not None and mins.shape != (m,)):
+        raise ValueError("verify_aggregated_seals_bls12_377: offsets, rows, bits, signatures and thresholds do not match")
+    if pts.shape[0] == 0:
+        pts = np.zeros((1, 24), dtype=np.uint64)
+    if b.size == 0:
+        b = np.zeros(1, dtype=np.uint8)
+    k = None if key is None else np.ascontiguousarray(key, dtype=np.uint32).reshape(8)
+    ng2 = np.ascontiguousarray(neg_g2_xy, dtype=np.uint64).reshape(24)
+    dom = np.frombuffer(bytes(domain), dtype=np.uint8)
+    ok = np.zeros(m, dtype=np.uint8)
+    st = np.zeros(m, dtype=np.uint8)
+    rc = lib().verify_aggregated_seals_bls12_377(_p(pts), _p(fl), _p(off), C.c_size_t(n_sets), _p(b), _p(mins), _p(dom), _p(mdat), _p(moff), _p(edat), _p(eoff),
+                                                 C.c_int(hash_mode), _p(sg), _p(ng2), C.c_size_t(m), C.c_int(mode), _p(k), _p(ok), _p(st))
+    if rc == 2:
+        raise ValueError("verify_aggregated_seals_bls12_377: bad arguments (code 2)")
+    if rc != 0:
+        raise RuntimeError("verify_aggregated_seals_bls12_377 failed with code %d" % rc)
+    return ok, st
 
 
 class SetupError(RuntimeError):

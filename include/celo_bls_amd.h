@@ -747,6 +747,68 @@ int celo_amd_scalar_mul_set_window(int c);
 int celo_amd_scalar_mul_set_chunk_rows(uint32_t rows);
 int celo_amd_scalar_mul_last_ms(float ms[4]);
 
+/* ---- Masked segmented point sums: the aggregated key of every seal of a batch from its signer bitmap (PublicKeyCache::aggregate,
+ * crates/bls-crypto/src/bls/cache.rs:65-87; the native twin of BlsGadget::enforce_bitmap, crates/epoch-snark/src/gadgets/single_update.rs:71-117;
+ * the G1 form is Signature::aggregate over a bitmap).  csrc/aggregate.h, csrc/unit_seals.hip, DESIGN.md section 6j.
+ *   out_i = sum { P_j : bits_i[j] != 0 }        out_count[i] = the number of non-zero bytes of bits_i
+ * Rows are those of fixed_base_mul_* / scalar_mul_batch_*: affine arkworks Montgomery limbs (12 u64 for G1, 24 for G2), a zero row with
+ * inf = 1 for the identity.  P_j is ANY point of the curve (not validated, as elsewhere): duplicate keys, a key and its negative and sums
+ * that are the identity are legal.  A selected row flagged in pk_inf adds nothing but still counts.
+ * Two forms.  n_sets == m, per-seal sets: seal i owns rows [offsets[i], offsets[i+1]) of pk_xy / pk_inf and the bytes of `bits` at the same
+ * indices (one byte per row; offsets[n_sets] rows and bytes in all).  n_sets == 1, the shared set: every seal reads rows
+ * [offsets[0], offsets[1]), n of them, and bits is m x n bytes, row-major - one validator set, one bitmap per block.
+ * The shared-set form computes the set's total T once per call, and a seal with strictly fewer zeros than ones is summed as T plus the
+ * NEGATED keys at its zero bytes (the reference's cache: "the previous total minus the few who are absent"); a tie sums the ones.  The
+ * result is the same group element, so the same row bit for bit.
+ * L lanes cooperate on one sum (L a power of two, 1 .. 64): each adds the selected rows j = lane (mod L) by mixed additions, then the L
+ * partials are folded pairwise through LDS by full additions.  L per call, from a = the largest number of rows a seal adds after the side
+ * choice and m:  L = min(smallest power of two >= a / 4, largest power of two <= 2^16 / m), at least 1 (csrc/aggregate.h agg_pick_lanes).
+ * _dev: every pointer but offsets is a DEVICE pointer (d_out_count may be NULL); the work is enqueued on hip_stream and the call returns
+ * after it has drained.
+ * Returns 0 (also for m = 0, which touches nothing); 2 with NOTHING written and before any use of the device: a NULL pk_xy / offsets / bits /
+ * out_xy / out_inf, n_sets not in {1, m}, decreasing offsets, m > 2^24; 100: no device; 1 / 10: HIP errors. */
+int aggregate_by_bitmap_bls12_377_g2(const uint64_t* pk_xy /* rows x 24 */, const uint8_t* pk_inf /* rows or NULL */, const uint32_t* offsets /* n_sets + 1 */,
+                                     size_t n_sets /* 1 or m */, const uint8_t* bits, size_t m, uint64_t* out_xy /* m x 24 */, uint8_t* out_inf /* m */,
+                                     uint32_t* out_count /* m, may be NULL */);
+int aggregate_by_bitmap_bls12_377_g1(const uint64_t* pk_xy /* rows x 12 */, const uint8_t* pk_inf, const uint32_t* offsets, size_t n_sets, const uint8_t* bits, size_t m,
+                                     uint64_t* out_xy /* m x 12 */, uint8_t* out_inf, uint32_t* out_count);
+int aggregate_by_bitmap_bls12_377_g2_dev(const void* d_pk_xy, const void* d_pk_inf, const uint32_t* offsets, size_t n_sets, const void* d_bits, size_t m,
+                                         void* d_out_xy, void* d_out_inf, void* d_out_count, void* hip_stream);
+int aggregate_by_bitmap_bls12_377_g1_dev(const void* d_pk_xy, const void* d_pk_inf, const uint32_t* offsets, size_t n_sets, const void* d_bits, size_t m,
+                                         void* d_out_xy, void* d_out_inf, void* d_out_count, void* hip_stream);
+/* Aggregated seals to verdicts, chained on the device: the check a node makes once per block and the epoch prover once per transition
+ * (EpochTransition { block, aggregate_signature, bitmap }, crates/epoch-snark/src/epoch_block.rs:19-30; the minimum-signers rule of
+ * gadgets/single_update.rs:71-117):  apk_i = the masked sum above, count_i >= min_signers[i], e(sig_i, -g2) e(H(m_i), apk_i) == 1.
+ * One call: count + sums; the m signatures (serialize_signature form, 48 B) decoded and subgroup-checked on the device; the message hashes of
+ * hash_to_g1_* (hash_mode 0 direct, 2 composite, 3 composite CIP22: sign_batch's numbering; messages and extras packed as there; the hash
+ * rows pass through the host, as in sign_batch); a pack kernel writes the pairs into the pairing engine's slots; the engine's products.
+ * Nothing but verdicts and statuses returns.  out_status[i], the first that applies, out_ok[i] = 1 iff it is 0:
+ *   0 clean and the product is one      1 count < min_signers[i], or count == 0 (a seal by nobody is not a seal)
+ *   2 the signature does not decode or lies outside G1      3 the hash found no counter      4 the product is not one
+ * A seal with status 1 - 3 takes no part in any product.  An apk that is the identity with count > 0 follows the pairing engine: that pair
+ * contributes 1.  Precondition as for batch_verify_bls12_377: the keys are elements of G2.
+ * mode 0 "each": m products of two pairs.  mode 1 "combined", contract and fallback of groth16_verify_batch_*: with the exponents r_i of
+ * celo_amd_groth16_draw_exponents under `key` (8 words; NULL = 32 bytes from the OS), e(sum r_i sig_i, -g2) prod e([r_i] H(m_i), apk_i) == 1
+ * over the clean seals - one m-term G1 MSM, one scalar_mul_batch on the subgroup path, one product of m + 1 pairs; if it holds every clean
+ * seal is accepted, if not the call runs mode 0 and returns its verdicts.  Measured: a product of two pairs is cheap next to
+ * the ladder and the MSM, so combined never won - 1.05 x the time of each at 17 280 seals, 1.23 x at 4 096, 1.45 x at 64: call mode 0 unless a
+ * caller wants the single combined product for its own sake.
+ * Returns 0 (also for m = 0); 2 with nothing written and before any use of the device: a NULL required pointer (pk_inf, min_signers, extras,
+ * extra_off, key and out_status may be NULL), hash_mode not in {0, 2, 3}, mode not in {0, 1}, n_sets not in {1, m}, decreasing offsets, m > 2^24. */
+int verify_aggregated_seals_bls12_377(const uint64_t* pk_xy, const uint8_t* pk_inf, const uint32_t* offsets, size_t n_sets, const uint8_t* bits,
+                                      const uint32_t* min_signers /* m, or NULL: no threshold */, const uint8_t domain[8], const uint8_t* msgs,
+                                      const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off, int hash_mode, const uint8_t* sig48 /* m x 48 */,
+                                      const uint64_t neg_g2_xy[24], size_t m, int mode /* 0 each, 1 combined */, const uint32_t* key /* 8, or NULL */,
+                                      uint8_t* out_ok /* m */, uint8_t* out_status /* m, may be NULL */);
+/* test and A/B hooks: the lane width (0 = the rule above, else 1, 2, 4, .. 64) and the complement (-1 = the rule above, 0 = never, 1 = for
+ * every seal of a shared-set call); anything else returns 2.  celo_amd_seals_last: the last call's record - path (-1 a bare sum; 0 each,
+ * 1 combined accepted, 2 combined rejected then each), the lane width used, and times in ms: [0] count + sums + normalisation (kernel time),
+ * [1] signature decoding, [2] hash kernels, [3] exponents + ladder + MSM (wall), [4] products, [5] transfers, [6] the whole call (wall),
+ * [7] the count kernel alone (its share of [0]). */
+int celo_amd_aggregate_set_lanes(int lanes);
+int celo_amd_aggregate_set_complement(int mode);
+int celo_amd_seals_last(int* path, int* lanes, float ms[8]);
+
 /* ---- R1CS matrices on the device: the step of ark-groth16 0.1 between cs.to_matrices() and the entry points above - the constraint evaluation
  * of R1CStoQAP::witness_map (prover) and R1CStoQAP::instance_map_with_evaluation (setup).  Synthesis (running the gadgets) stays with the caller;
  * its result is data: three sparse matrices of n_constraints rows and the full assignment.
