@@ -458,14 +458,7 @@ int hash_to_g1_cip22_tail_bls12_377(const uint8_t domain[8], const uint8_t* inne
 }
 int hash_to_g1_composite_bls12_377(const uint8_t domain[8], const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off,
                                    size_t n, int cip22, uint64_t* out_xy, uint8_t* attempts) {
-  if (!cip22) return hash_to_g1_direct_run(domain, msgs, msg_off, extras, extra_off, n, out_xy, attempts, 2);
-  if (n == 0) return 0;
-  if (!msg_off) return 2;
-  std::vector<uint8_t> inner(n * 48);                        // CIP22: one CRH per message, then the loops over xof(c || extra || inner)
-  std::vector<uint64_t> ioff(n + 1);
-  for (size_t i = 0; i <= n; i++) ioff[i] = 48 * i;
-  if (int rc = pedersen_crh_run(msgs, msg_off, n, inner.data())) return rc;
-  return hash_to_g1_direct_run(domain, inner.data(), ioff.data(), extras, extra_off, n, out_xy, attempts, 1);
+  return hash_to_g1_direct_run(domain, msgs, msg_off, extras, extra_off, n, out_xy, attempts, cip22 ? 3 : 2);
 }
 int hash_to_g2_direct_bls12_377(const uint8_t domain[8], const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off,
                                 size_t n, int compat, uint64_t* out_xy, uint8_t* attempts) {
@@ -477,15 +470,7 @@ int hash_to_g2_cip22_tail_bls12_377(const uint8_t domain[8], const uint8_t* inne
 }
 int hash_to_g2_composite_bls12_377(const uint8_t domain[8], const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off,
                                    size_t n, int cip22, int compat, uint64_t* out_xy, uint8_t* attempts) {
-  if (compat != 0 && compat != 1) return 2;
-  if (!cip22) return hash_to_g2_run(domain, msgs, msg_off, extras, extra_off, n, compat, out_xy, attempts, 2);
-  if (n == 0) return 0;
-  if (!msg_off) return 2;
-  std::vector<uint8_t> inner(n * 48);                        // CIP22: one CRH per message, then the loops over xof(c || extra || inner)
-  std::vector<uint64_t> ioff(n + 1);
-  for (size_t i = 0; i <= n; i++) ioff[i] = 48 * i;
-  if (int rc = pedersen_crh_run(msgs, msg_off, n, inner.data())) return rc;
-  return hash_to_g2_run(domain, inner.data(), ioff.data(), extras, extra_off, n, compat, out_xy, attempts, 1);
+  return hash_to_g2_run(domain, msgs, msg_off, extras, extra_off, n, compat, out_xy, attempts, cip22 ? 3 : 2);
 }
 int hash_to_g2_one_bls12_377(const uint8_t domain[8], const uint8_t* msg, size_t mlen, const uint8_t* extra, size_t elen, int mode, int compat, uint64_t out_xy[24],
                              int* attempt) {

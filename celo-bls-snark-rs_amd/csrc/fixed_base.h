@@ -9,6 +9,9 @@
 #pragma once
 #include "curve.h"
 #include "fp2.h"
+#if defined(__HIPCC__)
+#include "runtime.h"
+#endif
 
 namespace celo {
 
@@ -41,6 +44,36 @@ template <int N64> HD bool fb_below(const uint64_t* s, const uint64_t* m) {
   }
   return false;
 }
+
+#if defined(__HIPCC__)
+// N u64 handed to a kernel by value (a group order, a generator's limbs)
+template <int N> struct ArkWords { uint64_t v[N]; };
+// flag |= 1 for a scalar >= the group order
+template <int N64>
+__global__ void __launch_bounds__(256) k_scalars_below(const uint64_t* __restrict__ sc, uint32_t n, ArkWords<N64> r, uint32_t* flag) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint64_t s[N64];
+#pragma unroll
+  for (int k = 0; k < N64; k++) s[k] = sc[(size_t)i * N64 + k];
+  if (!fb_below<N64>(s, r.v)) atomicOr(flag, 1u);
+}
+// The range check of the device-pointer entries: n scalars on the device (N64 u64 each) against `order`, on cs's stream, which it
+// synchronises.  0: all below; 2: one is not; else 10 (a HIP call failed).
+template <int N64> int scalars_below_order(const uint64_t* d_sc, size_t n, const uint64_t* order, CallScope& cs) {
+  ArkWords<N64> r;
+  for (int k = 0; k < N64; k++) r.v[k] = order[k];
+  uint32_t flag = 0;
+  uint32_t* d_flag;
+  HIP_TRY(cs.alloc(&d_flag, 4), 10);
+  HIP_TRY(hipMemsetAsync(d_flag, 0, 4, cs.stream()), 10);
+  hipLaunchKernelGGL((k_scalars_below<N64>), dim3(((uint32_t)n + 255) / 256), dim3(256), 0, cs.stream(), d_sc, (uint32_t)n, r, d_flag);
+  HIP_TRY(hipGetLastError(), 10);
+  HIP_TRY(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, cs.stream()), 10);
+  HIP_TRY(hipStreamSynchronize(cs.stream()), 10);
+  return flag ? 2 : 0;
+}
+#endif
 
 // XYZZ -> affine with one inversion (x = X / ZZ, y = Y / ZZZ); false for the identity
 template <class F> HD bool fb_to_affine(const Xyzz<F>& a, Affine<F>& out) {

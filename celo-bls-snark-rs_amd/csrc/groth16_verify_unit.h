@@ -16,8 +16,6 @@
 #include "groth16_verify.h"
 #include "normalize.h"
 #include <hip/hip_runtime.h>
-#include <sys/random.h>
-#include <chrono>
 #include <cstring>
 #include <memory>
 #include <vector>
@@ -47,20 +45,14 @@ struct VerifyingKey {
 // per SIMD for the 28-limb field, as the other 28-limb lane kernels (unit_wire761.hip: the XYZZ accumulator, the point and the addition's
 // temporaries); two for the 14-limb field, as unit_wire.hip's
 template <class C> struct G16Dev;
-template <> struct G16Dev<G16Bw6> {
+template <> struct G16Dev<G16Bw6> : Pairing761 {
   typedef G_761 Group;
   static constexpr int WAVES = 1;
-  static int stage(uint32_t k, size_t m, PairingStage* st) { return pairing_stage_761(k, m, st); }
-  static int run_staged(PairingStage* st, const uint32_t* off, size_t m, uint8_t* is_one) { return pairing_run_staged_761(st, off, m, is_one); }
-  static int timings(float ms[4]) { return pairing_timings_761(ms); }
   static int decode(int g2, const uint8_t* in, size_t n, uint64_t* out, uint8_t* status, void* stream) { return wire761_decode(g2, 1, in, n, 1, out, status, 1, stream); }
 };
-template <> struct G16Dev<G16Bls> {
+template <> struct G16Dev<G16Bls> : Pairing377 {
   typedef G1_377 Group;
   static constexpr int WAVES = 2;
-  static int stage(uint32_t k, size_t m, PairingStage* st) { return pairing_stage_377(k, m, st); }
-  static int run_staged(PairingStage* st, const uint32_t* off, size_t m, uint8_t* is_one) { return pairing_run_staged_377(st, off, m, is_one); }
-  static int timings(float ms[4]) { return pairing_timings_377(ms); }
   static int decode(int g2, const uint8_t* in, size_t n, uint64_t* out, uint8_t* status, void* stream) { return wire_decompress(g2, in, n, 1, out, status, 1, stream); }
 };
 
@@ -189,7 +181,6 @@ template <class C> struct G16Impl {
   static constexpr int FW = F::WORDS, A = F::ARK64, W1 = C::G1W, W2 = C::G2W, KW = G16_KW, N64 = C::N64;
   static constexpr int WL = W1 > W2 ? W1 : W2;
   static constexpr size_t PROOF_BYTES = 2 * C::G1_BYTES + C::G2_BYTES;
-  static constexpr int K = sizeof(F) <= 64 ? 8 : 4;      // rows per lane of the normalisation (unit_setup.hip's choice per field)
 
   // ---- key load
   static int vk_build(const uint64_t* rows /* alpha, beta, gamma, delta, abc[n_abc]: KW u64 each */, const uint8_t* inf /* or NULL */, size_t n_abc, VerifyingKey** out) {
@@ -222,8 +213,8 @@ template <class C> struct G16Impl {
     HIP_TRY(hipMalloc(&vk->d_table, (vk->n_in ? vk->n_in : 1) * E * 2 * FW * 4), 10);
     HIP_TRY(hipMalloc(&vk->d_tinf, (vk->n_in ? vk->n_in : 1) * E), 10);
     {
-      CallScope cs(nullptr);
-      HIP_TRY(cs.create_stream(), 10);
+      CallScope cs;
+      HIP_TRY(cs.open(0, nullptr), 10);
       HIP_TRY(hipMemcpyAsync(vk->d_key, key, sizeof key, hipMemcpyHostToDevice, cs.stream()), 10);
       HIP_TRY(hipMemcpyAsync(vk->d_abc0, abc0, sizeof abc0, hipMemcpyHostToDevice, cs.stream()), 10);
       std::vector<uint64_t> bases((size_t)vk->n_in * W1);                      // the input bases as rows of their own width
@@ -260,37 +251,25 @@ template <class C> struct G16Impl {
     if (!*inf) { r.x.to_ark(row); r.y.to_ark(row + A); }
   }
 
-  struct StageGuard {      // an engine that was staged and not run goes back to its pool
-    PairingStage ps;
-    ~StageGuard() { if (ps.lease) (void)D::run_staged(&ps, nullptr, 0, nullptr); }
-  };
   struct DevProofs { uint64_t *a, *b, *c, *inputs, *acc; uint8_t *ainf, *binf, *cinf, *accinf, *status; };
 
   // m products of four pairs; is_one: m host bytes.  The producer stream s is chained in front of the engine's by an event.
   static int run_each(const VerifyingKey* vk, const DevProofs& d, size_t m, CallScope& cs, uint8_t* is_one, float* ms_pair) {
-    StageGuard g;
-    if (int rc = D::stage((uint32_t)(4 * m), m, &g.ps)) return rc;
-    hipEvent_t ready;
-    HIP_TRY(cs.event(&ready), 10);
-    HIP_TRY(hipEventRecord(ready, cs.stream()), 10);
-    HIP_TRY(hipStreamWaitEvent(g.ps.stream, ready, 0), 10);
+    StagedProduct<D> g;
+    if (int rc = g.stage((uint32_t)(4 * m), m)) return rc;
+    if (int rc = g.after(cs)) return rc;
     hipLaunchKernelGGL((k_g16_pack_each<C>), dim3((unsigned)((m * WL + 255) / 256)), dim3(256), 0, g.ps.stream, d.a, d.ainf, d.b, d.binf, d.c, d.cinf, d.acc, d.accinf,
                        d.status, vk->d_key, vk->kinf, (uint32_t)m, g.ps.d_g1, g.ps.d_g2, g.ps.d_i1, g.ps.d_i2);
     HIP_TRY(hipGetLastError(), 10);
     std::vector<uint32_t> off(m + 1);
     for (size_t p = 0; p <= m; p++) off[p] = (uint32_t)(4 * p);
-    if (int rc = D::run_staged(&g.ps, off.data(), m, is_one)) return rc;      // synchronises the engine's stream, and s through the event
-    float pm[4];
-    D::timings(pm);
-    *ms_pair += pm[3];
-    return 0;
+    return g.run(off.data(), m, is_one, ms_pair);
   }
 
   // Everything after the proofs' rows, identity flags, statuses and inputs are on the device (stream cs.stream()).
   static int verify_core(const VerifyingKey* vk, DevProofs& d, size_t m, int mode, const uint32_t* key, uint8_t* out_ok, CallScope& cs, EvLog& log, float* ms, int* path) {
     const hipStream_t s = cs.stream();
     const uint32_t m32 = (uint32_t)m, wblocks = (m32 + 63) / 64;
-    const unsigned nblocks = ((m32 + K - 1) / K + 63) / 64;
     uint32_t* d_xyzz;
     std::vector<uint8_t> h_status(m), is_one(m);
     HIP_TRY(cs.alloc(&d_xyzz, m * 4 * FW * 4), 10);
@@ -299,7 +278,7 @@ template <class C> struct G16Impl {
     hipEvent_t e0 = log.open();
     hipLaunchKernelGGL((k_g16_inputs<C>), dim3(wblocks), dim3(64), 0, s, d.inputs, m32, vk->n_in, vk->d_abc0, vk->abc0_inf ? 1 : 0, vk->d_table, vk->d_tinf, vk->c, vk->W,
                        d_xyzz, d.status);
-    hipLaunchKernelGGL((k_normalize<F, K, false, 0, true>), dim3(nblocks), dim3(64), 0, s, (const void*)d_xyzz, d.acc, d.accinf, m32, 0);
+    normalize_xyzz<F, true>(d_xyzz, d.acc, d.accinf, m32, 0, s);
     log.close(1, e0);
     HIP_TRY(hipGetLastError(), 10);
     HIP_TRY(hipMemcpyAsync(h_status.data(), d.status, m, hipMemcpyDeviceToHost, s), 10);
@@ -307,14 +286,7 @@ template <class C> struct G16Impl {
     if (mode == 1) {
       uint32_t k8[8];
       if (key) memcpy(k8, key, sizeof k8);
-      else {                                               // 32 bytes from the operating system per call, as batch_verify_strict's exponent stream
-        size_t got = 0;
-        while (got < sizeof k8) {
-          const ssize_t r = getrandom((uint8_t*)k8 + got, sizeof k8 - got, 0);
-          if (r <= 0) return 1;
-          got += (size_t)r;
-        }
-      }
+      else if (!os_random(k8, sizeof k8)) return 1;         // 32 bytes from the operating system per call, as batch_verify_strict's exponent stream
       uint64_t *d_r4, *d_sc, *d_ra;
       uint32_t* d_off;
       uint8_t* d_rainf;
@@ -331,12 +303,12 @@ template <class C> struct G16Impl {
       if (int rc = bv_draw_exponents(k8, d_off, 1, m, d_r4, s)) return rc;
       hipLaunchKernelGGL((k_g16_exponents<N64>), dim3((m32 + 255) / 256), dim3(256), 0, s, d_r4, d.status, m32, d_sc);
       hipLaunchKernelGGL((k_g16_scale<C>), dim3(wblocks), dim3(64), 0, s, d.a, d.ainf, d.status, d_sc, m32, d_xyzz);
-      hipLaunchKernelGGL((k_normalize<F, K, false, 0, true>), dim3(nblocks), dim3(64), 0, s, (const void*)d_xyzz, d_ra, d_rainf, m32, 0);
+      normalize_xyzz<F, true>(d_xyzz, d_ra, d_rainf, m32, 0, s);
       log.close(2, e0);
       HIP_TRY(hipGetLastError(), 10);
       HIP_TRY(hipMemcpyAsync(h_r4.data(), d_r4, m * 32, hipMemcpyDeviceToHost, s), 10);
       // sum r_i acc_i, sum r_i C_i: the variable-base MSM over the rows where they lie, the same scalars (zero for a proof whose status is set)
-      const auto t0 = std::chrono::steady_clock::now();
+      const WallMs wall_msm;
       uint64_t jac[2][3 * 12], tail[3 * W1];
       uint8_t tinf[3];
       if (int rc = MsmApi<typename D::Group>::dev(d.acc, d.accinf, d_sc, m, 0, jac[0], s)) return rc;
@@ -355,11 +327,11 @@ template <class C> struct G16Impl {
       }
       if (vk->kinf & 1u) { memset(tail + 2 * W1, 0, W1 * 8); tinf[2] = 1; }
       else mul_row(vk->neg_alpha, sum, tail + 2 * W1, &tinf[2]);
-      ms[3] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      ms[3] = wall_msm.ms();
       int one = 0;
       {
-        StageGuard g;
-        if (int rc = D::stage(m32 + 3, 1, &g.ps)) return rc;
+        StagedProduct<D> g;
+        if (int rc = g.stage(m32 + 3, 1)) return rc;
         hipLaunchKernelGGL((k_g16_pack_combined<C>), dim3((unsigned)(((m + 3) * WL + 255) / 256)), dim3(256), 0, g.ps.stream, d_ra, d_rainf, d.b, d.binf, d.status,
                            vk->d_key, vk->kinf, m32, g.ps.d_g1, g.ps.d_g2, g.ps.d_i1, g.ps.d_i2);
         HIP_TRY(hipGetLastError(), 10);
@@ -367,10 +339,7 @@ template <class C> struct G16Impl {
         HIP_TRY(hipMemcpyAsync(g.ps.d_i1 + m, tinf, 3, hipMemcpyHostToDevice, g.ps.stream), 10);
         const uint32_t off[2] = {0, m32 + 3};
         uint8_t v = 0;
-        if (int rc = D::run_staged(&g.ps, off, 1, &v)) return rc;
-        float pm[4];
-        D::timings(pm);
-        ms[4] += pm[3];
+        if (int rc = g.run(off, 1, &v, &ms[4])) return rc;
         one = v;
       }
       if (one) {
@@ -424,12 +393,12 @@ int G16Api<C>::verify(const VerifyingKey* vk, const uint64_t* a_xy, const uint8_
   if (vk->n_in && !inputs) return 2;
   if (int rc0 = api_enter()) return rc0;
   if (vk->device != api_device()) return 101;
-  const auto t0 = std::chrono::steady_clock::now();
+  const WallMs wall;
   float ms[8] = {};
   int path = 0;
   const int rc = [&]() -> int {
-    CallScope cs(nullptr);
-    HIP_TRY(cs.create_stream(), 10);
+    CallScope cs;
+    HIP_TRY(cs.open(0, nullptr), 10);
     const hipStream_t s = cs.stream();
     EvLog log(s);
     typename I::DevProofs d = {};
@@ -447,11 +416,10 @@ int G16Api<C>::verify(const VerifyingKey* vk, const uint64_t* a_xy, const uint8_
     if (proofs) {
       uint64_t *d_bytes, *d_g1b, *d_g2b;
       uint8_t* d_st;
-      HIP_TRY(cs.alloc(&d_bytes, m * PB), 10);
       HIP_TRY(cs.alloc(&d_g1b, 2 * m * S1), 10);
       HIP_TRY(cs.alloc(&d_g2b, m * S2), 10);
       HIP_TRY(cs.alloc(&d_st, 3 * m), 10);
-      HIP_TRY(hipMemcpyAsync(d_bytes, proofs, m * PB, hipMemcpyHostToDevice, s), 10);
+      HIP_TRY(cs.in(&d_bytes, proofs, m * PB, 0), 10);
       log.close(6, e0);
       e0 = log.open();
       hipLaunchKernelGGL((k_g16_split<C>), dim3((unsigned)((m * (PB / 8) + 255) / 256)), dim3(256), 0, s, d_bytes, (uint32_t)m, d_g1b, d_g2b);
@@ -475,7 +443,7 @@ int G16Api<C>::verify(const VerifyingKey* vk, const uint64_t* a_xy, const uint8_
     log.sum(ms);
     return rcv;
   }();
-  ms[5] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  ms[5] = wall.ms();
   if (!rc) groth16_verify_note(path, vk->c, ms);
   return rc;
 }

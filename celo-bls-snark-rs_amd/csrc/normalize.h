@@ -88,4 +88,12 @@ k_normalize(const void* __restrict__ in_, uint64_t* __restrict__ out, uint8_t* _
   });
 }
 
+// The XYZZ form's launch: n device rows of 4 F::WORDS words -> n affine rows and flags, enqueued on s.  K rows per lane by the field's size
+// (8 for the 14-limb field, 4 for the wider ones).  ZERO_Y: the instance that can write the identity as (0, 1), when ark_zero_y asks for it.
+template <class F, bool ZERO_Y>
+void normalize_xyzz(const uint32_t* d_xyzz, uint64_t* d_out, uint8_t* d_inf, uint32_t n, int ark_zero_y, hipStream_t s) {
+  constexpr int K = sizeof(F) <= 64 ? 8 : 4;
+  hipLaunchKernelGGL((k_normalize<F, K, false, 0, ZERO_Y>), dim3(((n + K - 1) / K + 63) / 64), dim3(64), 0, s, (const void*)d_xyzz, d_out, d_inf, n, ark_zero_y);
+}
+
 }  // namespace celo

@@ -12,7 +12,9 @@
 // celo_amd_use_device() binds a host thread to a device, the msm_*_multi entry points do that internally (one thread per device).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <sys/random.h>
 #include <atomic>
+#include <chrono>
 #include <condition_variable>
 #include <cstdio>
 #include <memory>
@@ -127,12 +129,36 @@ struct OwnedStream {
   }
 };
 
+// n bytes from the operating system (the seed of an exponent stream); false when it gives none
+inline bool os_random(void* buf, size_t n) {
+  for (size_t got = 0; got < n;) {
+    const ssize_t r = getrandom((uint8_t*)buf + got, n - got, 0);
+    if (r <= 0) return false;
+    got += (size_t)r;
+  }
+  return true;
+}
+
+// Wall-clock ms since construction.  With a slot: written there on destruction - declared in front of a CallScope, the time includes
+// the release of the call's resources on every exit.
+struct WallMs {
+  explicit WallMs(float* slot_ = nullptr) : slot(slot_) {}
+  ~WallMs() { if (slot) *slot = ms(); }
+  float ms() const { return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+  const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  float* const slot;
+};
+
 // The device resources of ONE call: its allocations, its events and, when create_stream() made one, its stream.  The call runs on
 // stream() - the caller's, the null stream, or its own.  Released on every exit, in this order: the stream is synchronised, the
 // allocations freed, the events destroyed, then an owned stream destroyed.
+//
+// The call frame of an entry point that takes host pointers (dev = 0) or device pointers (dev = 1): open() picks the stream, in() / out() /
+// inout() name what crosses the bus - with dev set they hand the caller's pointer through, otherwise they allocate and stage -, the unit
+// enqueues its work on stream(), copy_back() enqueues the way home, and the unit synchronises where it reads the results.
 class CallScope {
  public:
-  explicit CallScope(hipStream_t s) : s_(s) {}
+  explicit CallScope(hipStream_t s = nullptr) : s_(s) {}
   CallScope(const CallScope&) = delete;
   CallScope& operator=(const CallScope&) = delete;
   ~CallScope() {
@@ -162,10 +188,46 @@ class CallScope {
     *out = e;
     return rc;
   }
+  // dev: the call runs on the caller's stream; else on a non-blocking stream of its own
+  hipError_t open(int dev, void* caller_stream) {
+    if (!dev) return create_stream();
+    s_ = (hipStream_t)caller_stream;
+    return hipSuccess;
+  }
+  // an input of `bytes` at p: *d = p (dev, or p == nullptr: an optional input that is absent), else a device copy of bytes + pad, enqueued
+  template <class T> hipError_t in(T** d, const void* p, size_t bytes, int dev, size_t pad = 0) {
+    *d = (T*)p;
+    if (dev || !p) return hipSuccess;
+    const hipError_t e = alloc(d, bytes + pad);
+    return e != hipSuccess ? e : hipMemcpyAsync(*d, p, bytes, hipMemcpyHostToDevice, s_);
+  }
+  // an output of `bytes` at p: *d = p (dev, or p == nullptr), else a device buffer that copy_back() returns to p
+  template <class T> hipError_t out(T** d, void* p, size_t bytes, int dev) {
+    *d = (T*)p;
+    if (dev || !p) return hipSuccess;
+    const hipError_t e = alloc(d, bytes);
+    if (e == hipSuccess) back_.push_back({p, *d, bytes});
+    return e;
+  }
+  // a buffer the call overwrites in place
+  template <class T> hipError_t inout(T** d, void* p, size_t bytes, int dev) {
+    const hipError_t e = in(d, p, bytes, dev);
+    if (e == hipSuccess && !dev && p) back_.push_back({p, *d, bytes});
+    return e;
+  }
+  hipError_t copy_back() {            // every registered output, in registration order; the caller synchronises
+    for (const Back& b : back_) {
+      const hipError_t e = hipMemcpyAsync(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost, s_);
+      if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  }
  private:
+  struct Back { void* host; const void* dev; size_t bytes; };
   hipStream_t s_ = nullptr;
   bool owned_ = false;
   std::vector<void*> mem_;
+  std::vector<Back> back_;
   std::vector<hipEvent_t> ev_;
 };
 
@@ -192,5 +254,27 @@ struct BatchRun { void* lease = nullptr; uint64_t* d_out = nullptr; hipStream_t 
 // A pairing engine whose input slots (k pairs in m products) are handed to a producer kernel; pairing_run_staged_* runs the
 // check on what the slots hold (stream order) and returns the engine.
 struct PairingStage { void* lease = nullptr; uint64_t* d_g1 = nullptr; uint64_t* d_g2 = nullptr; uint8_t* d_i1 = nullptr; uint8_t* d_i2 = nullptr; hipStream_t stream = nullptr; };
+// One staged pairing product over the engine of D (units.h Pairing377 / Pairing761): stage(), optionally after() a producer, the caller's
+// pack kernel and tail uploads into ps's slots on ps.stream, run().  An engine that was staged and not run goes back to its pool.
+template <class D> struct StagedProduct {
+  PairingStage ps;
+  ~StagedProduct() { if (ps.lease) (void)D::run_staged(&ps, nullptr, 0, nullptr); }
+  int stage(uint32_t pairs, size_t products) { return D::stage(pairs, products, &ps); }
+  int after(CallScope& cs) {          // the engine's stream waits for what cs.stream() holds now
+    hipEvent_t ready;
+    HIP_TRY(cs.event(&ready), 10);
+    HIP_TRY(hipEventRecord(ready, cs.stream()), 10);
+    HIP_TRY(hipStreamWaitEvent(ps.stream, ready, 0), 10);
+    return 0;
+  }
+  // m verdicts (host bytes) for the products [off[p], off[p + 1]); synchronises the engine's stream, and a producer's through after()'s event
+  int run(const uint32_t* off, size_t m, uint8_t* is_one, float* ms_pair) {
+    if (int rc = D::run_staged(&ps, off, m, is_one)) return rc;
+    float pm[4];
+    D::timings(pm);
+    *ms_pair += pm[3];
+    return 0;
+  }
+};
 
 }  // namespace celo

@@ -4,7 +4,6 @@
 #include <string>
 #include <unordered_map>
 #include <unordered_set>
-#include <sys/random.h>
 #include "seam.h"
 
 using namespace celo;
@@ -94,16 +93,11 @@ void g2_compress(const Affine<Fq2_>& p, bool inf, uint8_t* out) {
   fq_to_bytes(p.x.c1, out + 48);
   if (wire_lex_largest(p.y)) out[95] |= 0x80;
 }
-// A ChaCha20 stream seeded with 32 bytes from the operating system (getrandom): what rand::thread_rng() is in the reference
+// A ChaCha20 stream seeded with 32 bytes from the operating system (runtime.h os_random): what rand::thread_rng() is in the reference
 // (batch.rs:51 draws the batching exponents from it).  One system call per FFI call instead of one per exponent word.
 bool os_seeded_rng(ChaCha20Rng& rng) {
   uint8_t seed[32];
-  size_t got = 0;
-  while (got < sizeof seed) {
-    ssize_t r = getrandom(seed + got, sizeof seed - got, 0);
-    if (r <= 0) return false;
-    got += (size_t)r;
-  }
+  if (!os_random(seed, sizeof seed)) return false;
   memcpy(rng.key, seed, 32);
   return true;
 }

@@ -293,14 +293,28 @@ static int hash_rounds(const uint8_t* domain, const uint8_t* msgs, const uint64_
   }
   return 0;
 }
+// The hash step of a protocol mode (units.h): the round loop in the caller's mode, or for CIP22 (mode 3) one CRH per message and then the
+// loops over xof(c || extra || inner)
+template <class G>
+static int hash_step(const uint8_t* domain, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off, size_t n, int compat,
+                     uint64_t* out_xy, uint8_t* attempts, int mode, float* split_ms) {
+  if (mode != 3) return hash_rounds<G>(domain, msgs, msg_off, extras, extra_off, n, compat, out_xy, attempts, mode, split_ms);
+  if (n == 0) return 0;
+  if (!msg_off) return 2;
+  std::vector<uint8_t> inner(n * 48);
+  std::vector<uint64_t> ioff(n + 1);
+  for (size_t i = 0; i <= n; i++) ioff[i] = 48 * i;
+  if (int rc = pedersen_crh_run(msgs, msg_off, n, inner.data())) return rc;
+  return hash_rounds<G>(domain, inner.data(), ioff.data(), extras, extra_off, n, compat, out_xy, attempts, 1, split_ms);
+}
 int hash_to_g1_direct_run(const uint8_t* domain, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off,
                           size_t n, uint64_t* out_xy, uint8_t* attempts, int mode) {
-  return hash_rounds<HashG1>(domain, msgs, msg_off, extras, extra_off, n, 0, out_xy, attempts, mode, nullptr);
+  return hash_step<HashG1>(domain, msgs, msg_off, extras, extra_off, n, 0, out_xy, attempts, mode, nullptr);
 }
 int hash_to_g2_run(const uint8_t* domain, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off, size_t n, int compat,
                    uint64_t* out_xy, uint8_t* attempts, int mode) {
   if (compat != 0 && compat != 1) return 2;
-  return hash_rounds<HashG2>(domain, msgs, msg_off, extras, extra_off, n, compat, out_xy, attempts, mode, g_hash_g2_ms);
+  return hash_step<HashG2>(domain, msgs, msg_off, extras, extra_off, n, compat, out_xy, attempts, mode, g_hash_g2_ms);
 }
 // one message on the host, no device touched: mode 0 direct, 1 the CIP22 tail (`msg` is the inner CRH), 2 composite, 3 composite CIP22
 int hash_to_g2_one_run(const uint8_t* domain, const uint8_t* msg, size_t mlen, const uint8_t* extra, size_t elen, int mode, int compat, uint64_t* out_xy, int* attempt) {

@@ -18,7 +18,6 @@
 #include "runtime.h"
 #include "units.h"
 #include <algorithm>
-#include <chrono>
 #include <thread>
 #include <vector>
 #include <cstring>
@@ -43,7 +42,8 @@ __global__ void __launch_bounds__(256) k_to_canonical(uint64_t* __restrict__ a, 
   FR::from_ark(a + (size_t)i * FR::ARK64).to_canonical(a + (size_t)i * FR::ARK64);
 }
 
-// dev = 1: a, b, c are DEVICE pointers (a is overwritten with h; b and c are overwritten with intermediate values).
+// a, b, c: host or device pointers (runtime.h, the call frame; on the caller's stream in both forms).  a is overwritten with h; as device
+// pointers b and c are overwritten with intermediate values.
 template <class FR>
 int witness_map_run(uint64_t* a, uint64_t* b, uint64_t* c, unsigned log_n, const uint64_t* omega, const uint64_t* omega_inv, const uint64_t* coset,
                     const uint64_t* coset_inv, const uint64_t* n_inv, const uint64_t* z_inv, int out_canonical, int dev, void* stream_) {
@@ -52,22 +52,18 @@ int witness_map_run(uint64_t* a, uint64_t* b, uint64_t* c, unsigned log_n, const
   const size_t n = size_t(1) << log_n, bytes = n * FR::ARK64 * 8;
   CallScope cs((hipStream_t)stream_);
   const hipStream_t stream = cs.stream();
-  uint64_t *da = a, *db = b, *dc = c;
+  uint64_t *da, *db, *dc;
   uint32_t zw[FR::WORDS];
   {
     FR v = FR::wred(FR::from_ark(z_inv));
     memset(zw, 0, sizeof zw);
     v.store(zw);
   }
-  if (!dev) {
-    HIP_TRY(cs.alloc(&da, bytes), 10); HIP_TRY(cs.alloc(&db, bytes), 10); HIP_TRY(cs.alloc(&dc, bytes), 10);
-    HIP_TRY(hipMemcpyAsync(da, a, bytes, hipMemcpyHostToDevice, stream), 10);
-    HIP_TRY(hipMemcpyAsync(db, b, bytes, hipMemcpyHostToDevice, stream), 10);
-    HIP_TRY(hipMemcpyAsync(dc, c, bytes, hipMemcpyHostToDevice, stream), 10);
-  }
+  HIP_TRY(cs.inout(&da, a, bytes, dev), 10);
+  HIP_TRY(cs.in(&db, b, bytes, dev), 10);
+  HIP_TRY(cs.in(&dc, c, bytes, dev), 10);
   uint32_t* d_z;
-  HIP_TRY(cs.alloc(&d_z, sizeof zw), 10);
-  HIP_TRY(hipMemcpyAsync(d_z, zw, sizeof zw, hipMemcpyHostToDevice, stream), 10);
+  HIP_TRY(cs.in(&d_z, zw, sizeof zw, 0), 10);
   // an NTT engine keeps the twiddle table of its last (omega, n) and the pool hands the same engine back to a serial caller: the
   // table is rebuilt three times per witness map (inverse, forward, inverse: ~20 us each at 2^20), not seven
   for (uint64_t* p : {da, db, dc}) if (int rc = ntt_run<FR>(p, log_n, omega_inv, nullptr, 0, n_inv, 1, stream)) return rc;        // ifft
@@ -76,7 +72,7 @@ int witness_map_run(uint64_t* a, uint64_t* b, uint64_t* c, unsigned log_n, const
   if (int rc = ntt_run<FR>(da, log_n, omega_inv, coset_inv, 1, n_inv, 1, stream)) return rc;                                          // coset_ifft
   if (out_canonical) hipLaunchKernelGGL((k_to_canonical<FR>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, da, (uint32_t)n);
   HIP_TRY(hipGetLastError(), 10);
-  if (!dev) HIP_TRY(hipMemcpyAsync(a, da, bytes, hipMemcpyDeviceToHost, stream), 10);
+  HIP_TRY(cs.copy_back(), 10);
   HIP_TRY(hipStreamSynchronize(stream), 10);
   return 0;
 }
@@ -285,13 +281,12 @@ static int prove_r1cs_t(const ProvingKey* k, const R1cs* r, size_t n_vars, size_
   typedef typename C::FR FR;
   constexpr int A = C::S;
   const size_t n = size_t(1) << log_n;
-  CallScope cs(nullptr);
-  HIP_TRY(cs.create_stream(), 10);
+  CallScope cs;
+  HIP_TRY(cs.open(0, nullptr), 10);
   const hipStream_t s = cs.stream();
   uint64_t *d_z, *d_a, *d_b, *d_c;
-  HIP_TRY(cs.alloc(&d_z, n_vars * A * 8), 10);
+  HIP_TRY(cs.in(&d_z, z, n_vars * A * 8, 0), 10);
   HIP_TRY(cs.alloc(&d_a, n * A * 8), 10); HIP_TRY(cs.alloc(&d_b, n * A * 8), 10); HIP_TRY(cs.alloc(&d_c, n * A * 8), 10);
-  HIP_TRY(hipMemcpyAsync(d_z, z, n_vars * A * 8, hipMemcpyHostToDevice, s), 10);
   if (int rc = r1cs_rows(r, d_z, log_n, d_a, d_b, d_c, 1, s)) return rc;
   if (int rc = witness_map_run<FR>(d_a, d_b, d_c, log_n, omega, omega_inv, coset, coset_inv, n_inv, z_inv, 1, 1, s)) return rc;
   if (n_vars > 1) hipLaunchKernelGGL((k_to_canonical<FR>), dim3((unsigned)((n_vars - 1 + 255) / 256)), dim3(256), 0, s, d_z + A, (uint32_t)(n_vars - 1));
@@ -309,10 +304,10 @@ int groth16_prove_r1cs(const ProvingKey* k, const R1cs* r, const uint64_t* z, un
   if (curve != k->curve) return 2;
   if (k->device != api_device() || device != api_device()) return 101;
   if (log_n > 28 || (size_t(1) << log_n) < m + n_inputs) return 2;
-  const auto t0 = std::chrono::steady_clock::now();
+  const WallMs wall;
   const int rc = curve ? prove_r1cs_t<Bls12>(k, r, n_vars, n_inputs, z, log_n, omega, omega_inv, coset, coset_inv, n_inv, z_inv, out_a, out_b, out_c)
                        : prove_r1cs_t<Bw6>(k, r, n_vars, n_inputs, z, log_n, omega, omega_inv, coset, coset_inv, n_inv, z_inv, out_a, out_b, out_c);
-  r1cs_note_ms(4, std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  r1cs_note_ms(4, wall.ms());
   return rc;
 }
 }  // namespace celo

@@ -3,7 +3,6 @@
 // R1CStoQAP::instance_map_with_evaluation (their transposes with the Lagrange basis at tau).  DESIGN.md section 6g.
 #include "r1cs.h"
 #include <hip/hip_runtime.h>
-#include <chrono>
 #include <cstring>
 #include <mutex>
 #include <vector>
@@ -141,7 +140,7 @@ static int load_t(int curve, size_t m, size_t n_vars, size_t n_inputs, const R1c
   if (out) *out = nullptr;
   if (int rc0 = api_enter()) return rc0;
   if (!out) return 2;
-  const auto t0 = std::chrono::steady_clock::now();
+  const WallMs wall;
   if (int rc = r1cs_validate<N64>(m, n_vars, n_inputs, mats, P::P64, first_bad)) return rc;
   R1cs* r = new R1cs();
   r->curve = curve; r->device = api_device(); r->m = m; r->n_vars = n_vars; r->n_inputs = n_inputs;
@@ -156,7 +155,7 @@ static int load_t(int curve, size_t m, size_t n_vars, size_t n_inputs, const R1c
   }
   if (rc) { r1cs_free(r); return rc; }
   *out = r;
-  note_ms(0, std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  note_ms(0, wall.ms());
   return 0;
 }
 int r1cs_load(int curve, size_t m, size_t n_vars, size_t n_inputs, const uint64_t* const row_ptr[3], const uint32_t* const col[3], const uint64_t* const val[3],
@@ -175,26 +174,20 @@ void r1cs_shape(const R1cs* r, int* curve, int* device, size_t* m, size_t* n_var
   *curve = r->curve; *device = r->device; *m = r->m; *n_vars = r->n_vars; *n_inputs = r->n_inputs;
 }
 
-// ---- prover side: (A z, B z, C z) over 2^log_n rows.  dev = 0: z and the outputs are host pointers; 1: device pointers, run on stream_.
+// ---- prover side: (A z, B z, C z) over 2^log_n rows.  z and the outputs: host or device pointers (runtime.h, the call frame).
 template <class FR>
 static int rows_t(const R1cs* r, const uint64_t* z, unsigned log_n, uint64_t* oa, uint64_t* ob, uint64_t* oc, int dev, void* stream_) {
   constexpr int A = FR::ARK64;
   if (log_n > 28 || (size_t(1) << log_n) < r->m + r->n_inputs) return 2;
   const size_t n = size_t(1) << log_n, bytes = n * A * 8;
-  CallScope cs(dev ? (hipStream_t)stream_ : nullptr);
-  if (!dev) HIP_TRY(cs.create_stream(), 10);
+  CallScope cs;
+  HIP_TRY(cs.open(dev, stream_), 10);
   const hipStream_t s = cs.stream();
-  const uint64_t* d_z = z;
-  uint64_t* d_o[3] = {oa, ob, oc};
+  uint64_t *d_z, *d_o[3], *h_o[3] = {oa, ob, oc};
   uint32_t* parts;
   HIP_TRY(cs.alloc(&parts, (size_t)max_chunks(r->mat) * FR::WORDS * 4), 10);
-  if (!dev) {
-    uint64_t* zz;
-    HIP_TRY(cs.alloc(&zz, r->n_vars * A * 8), 10);
-    HIP_TRY(hipMemcpyAsync(zz, z, r->n_vars * A * 8, hipMemcpyHostToDevice, s), 10);
-    d_z = zz;
-    for (int k = 0; k < 3; k++) HIP_TRY(cs.alloc(&d_o[k], bytes), 10);
-  }
+  HIP_TRY(cs.in(&d_z, z, r->n_vars * A * 8, dev), 10);
+  for (int k = 0; k < 3; k++) HIP_TRY(cs.out(&d_o[k], h_o[k], bytes, dev), 10);
   EvLog log(s);
   float ms[8] = {};
   if (n > r->m) for (int k = 0; k < 3; k++) HIP_TRY(hipMemsetAsync(d_o[k] + r->m * A, 0, (n - r->m) * A * 8, s), 10);
@@ -204,10 +197,7 @@ static int rows_t(const R1cs* r, const uint64_t* z, unsigned log_n, uint64_t* oa
   HIP_TRY(hipGetLastError(), 10);
   // the input-consistency rows a[m + i] = z_i
   HIP_TRY(hipMemcpyAsync(d_o[0] + r->m * A, d_z, r->n_inputs * A * 8, hipMemcpyDeviceToDevice, s), 10);
-  if (!dev) {
-    uint64_t* h_o[3] = {oa, ob, oc};
-    for (int k = 0; k < 3; k++) HIP_TRY(hipMemcpyAsync(h_o[k], d_o[k], bytes, hipMemcpyDeviceToHost, s), 10);
-  }
+  HIP_TRY(cs.copy_back(), 10);
   HIP_TRY(hipStreamSynchronize(s), 10);
   log.sum(ms);
   note_ms(1, ms[1]);
@@ -225,16 +215,15 @@ static int check_t(const R1cs* r, const uint64_t* z, int64_t* first_unsatisfied)
   constexpr int A = FR::ARK64;
   *first_unsatisfied = -1;
   if (r->m == 0) return 0;
-  CallScope cs(nullptr);
-  HIP_TRY(cs.create_stream(), 10);
+  CallScope cs;
+  HIP_TRY(cs.open(0, nullptr), 10);
   const hipStream_t s = cs.stream();
   uint64_t *d_z, *d_o[3];
   uint32_t *parts, *d_first, first = 0xffffffffu;
-  HIP_TRY(cs.alloc(&d_z, r->n_vars * A * 8), 10);
+  HIP_TRY(cs.in(&d_z, z, r->n_vars * A * 8, 0), 10);
   for (int k = 0; k < 3; k++) HIP_TRY(cs.alloc(&d_o[k], r->m * A * 8), 10);
   HIP_TRY(cs.alloc(&parts, (size_t)max_chunks(r->mat) * FR::WORDS * 4), 10);
   HIP_TRY(cs.alloc(&d_first, 4), 10);
-  HIP_TRY(hipMemcpyAsync(d_z, z, r->n_vars * A * 8, hipMemcpyHostToDevice, s), 10);
   HIP_TRY(hipMemsetAsync(d_first, 0xff, 4, s), 10);
   for (int k = 0; k < 3; k++) matvec<FR>(r->mat[k], d_z, d_o[k], parts, s);
   hipLaunchKernelGGL((k_r1cs_check<FR>), dim3((unsigned)((r->m + 255) / 256)), dim3(256), 0, s, d_o[0], d_o[1], d_o[2], (uint32_t)r->m, d_first);
@@ -252,7 +241,7 @@ int r1cs_check(const R1cs* r, const uint64_t* z, int64_t* first_unsatisfied) {
 }
 
 // ---- setup side: a_i(tau), b_i(tau), c_i(tau) for the n_vars variables and zt = Z(tau) (a host pointer in both forms).
-// dev = 0: oa / ob / oc are host pointers; 1: device pointers, run on stream_.
+// oa / ob / oc: host or device pointers (runtime.h, the call frame).
 template <class FR>
 static int qap_t(const R1cs* r, unsigned log_n, const uint64_t* omega, const uint64_t* tau, uint64_t* oa, uint64_t* ob, uint64_t* oc, uint64_t* ozt, int dev,
                  void* stream_) {
@@ -260,14 +249,14 @@ static int qap_t(const R1cs* r, unsigned log_n, const uint64_t* omega, const uin
   if (log_n > 28 || (size_t(1) << log_n) < r->m + r->n_inputs) return 2;
   const size_t n = size_t(1) << log_n, bytes = r->n_vars * A * 8;
   const R1csLagConsts<FR> k = r1cs_lagrange_consts<FR>(log_n, omega, tau, ozt);
-  CallScope cs(dev ? (hipStream_t)stream_ : nullptr);
-  if (!dev) HIP_TRY(cs.create_stream(), 10);
+  CallScope cs;
+  HIP_TRY(cs.open(dev, stream_), 10);
   const hipStream_t s = cs.stream();
-  uint64_t *d_l, *d_o[3] = {oa, ob, oc};
+  uint64_t *d_l, *d_o[3], *h_o[3] = {oa, ob, oc};
   uint32_t* parts;
   HIP_TRY(cs.alloc(&d_l, n * A * 8), 10);
   HIP_TRY(cs.alloc(&parts, (size_t)max_chunks(r->tr) * FR::WORDS * 4), 10);
-  if (!dev) for (int q = 0; q < 3; q++) HIP_TRY(cs.alloc(&d_o[q], bytes), 10);
+  for (int q = 0; q < 3; q++) HIP_TRY(cs.out(&d_o[q], h_o[q], bytes, dev), 10);
   EvLog log(s);
   float ms[8] = {};
   hipEvent_t e0 = log.open();
@@ -279,10 +268,7 @@ static int qap_t(const R1cs* r, unsigned log_n, const uint64_t* omega, const uin
   hipLaunchKernelGGL((k_r1cs_add_inputs<FR>), dim3((unsigned)((r->n_inputs + 63) / 64)), dim3(64), 0, s, d_o[0], d_l + r->m * A, (uint32_t)r->n_inputs);
   log.close(3, e0);
   HIP_TRY(hipGetLastError(), 10);
-  if (!dev) {
-    uint64_t* h_o[3] = {oa, ob, oc};
-    for (int q = 0; q < 3; q++) HIP_TRY(hipMemcpyAsync(h_o[q], d_o[q], bytes, hipMemcpyDeviceToHost, s), 10);
-  }
+  HIP_TRY(cs.copy_back(), 10);
   HIP_TRY(hipStreamSynchronize(s), 10);
   log.sum(ms);
   note_ms(2, ms[2]);

@@ -6,8 +6,6 @@
 #include "groth16_verify.h"
 #include "normalize.h"
 #include <hip/hip_runtime.h>
-#include <sys/random.h>
-#include <chrono>
 #include <cstring>
 #include <mutex>
 #include <vector>
@@ -87,7 +85,6 @@ template <class F> struct Agg {
   static constexpr int A = F::ARK64, FW = F::WORDS;
   static int run(const uint64_t* d_xy, const uint8_t* d_inf, const uint32_t* offsets, size_t n_sets, const uint8_t* d_bits, size_t m, uint64_t* d_out, uint8_t* d_oinf,
                  uint32_t* d_count, hipStream_t s, EvLog* log, int* lanes_used) {
-    constexpr int K = sizeof(F) <= 64 ? 8 : 4;
     CallScope cs(s);
     const uint32_t shared = n_sets == 1 ? 1u : 0u;        // (m == 1 with one set: the two forms coincide; it runs as the shared form)
     uint32_t *d_off, *d_info, *d_tmp, *d_total;
@@ -113,7 +110,7 @@ template <class F> struct Agg {
       hipLaunchKernelGGL((k_masked_sum<F>), dim3(1), dim3(AGG_BLOCK), AGG_BLOCK * slot_bytes, s, d_xy, d_inf, d_off, 1u, nullptr, nullptr, nullptr, 1u, AGG_MAX_LANES, d_total);
     hipLaunchKernelGGL((k_masked_sum<F>), dim3(((uint32_t)m + AGG_BLOCK / L - 1) / (AGG_BLOCK / L)), dim3(AGG_BLOCK), L > 1 ? AGG_BLOCK * slot_bytes : 0, s, d_xy, d_inf, d_off,
                        shared, d_bits, d_side, d_total, (uint32_t)m, L, d_tmp);
-    hipLaunchKernelGGL((k_normalize<F, K, false, 0, false>), dim3((((uint32_t)m + K - 1) / K + 63) / 64), dim3(64), 0, s, (const void*)d_tmp, d_out, d_oinf, (uint32_t)m, 0);
+    normalize_xyzz<F, false>(d_tmp, d_out, d_oinf, (uint32_t)m, 0, s);
     log->close(0, e0);
     HIP_TRY(hipGetLastError(), 10);
     HIP_TRY(hipStreamSynchronize(s), 10);
@@ -129,7 +126,8 @@ static int agg_refuse(const void* xy, const uint32_t* offsets, size_t n_sets, co
   return 0;
 }
 
-// dev = 0: host pointers; 1: device pointers (offsets stays a host pointer), run on stream_
+// Host or device pointers (runtime.h, the call frame); offsets stays a host pointer in both forms.  The rows, bytes and flags carry 8
+// bytes of slack on the device.
 template <class F>
 static int agg_call(const void* xy, const void* inf, const uint32_t* offsets, size_t n_sets, const void* bits, size_t m, void* out_xy, void* out_inf, void* out_count,
                     int dev, void* stream_) {
@@ -140,42 +138,27 @@ static int agg_call(const void* xy, const void* inf, const uint32_t* offsets, si
   std::lock_guard<std::mutex> lk(agg_mu);
   for (float& t : g_agg_ms) t = 0.f;
   g_agg_last_path = -1;
-  const auto t0 = std::chrono::steady_clock::now();
-  const int rc = [&]() -> int {
-    CallScope cs(dev ? (hipStream_t)stream_ : nullptr);
-    if (!dev) HIP_TRY(cs.create_stream(), 10);
-    const hipStream_t s = cs.stream();
-    EvLog log(s);
-    const size_t rows = offsets[n_sets], n_bits = n_sets == 1 ? m * (size_t)(offsets[1] - offsets[0]) : rows;
-    uint64_t *d_xy = (uint64_t*)xy, *d_out = (uint64_t*)out_xy;
-    uint8_t *d_inf = (uint8_t*)inf, *d_bits = (uint8_t*)bits, *d_oinf = (uint8_t*)out_inf;
-    uint32_t* d_count = (uint32_t*)out_count;
-    if (!dev) {
-      HIP_TRY(cs.alloc(&d_xy, rows * RW * 8 + 8), 10);
-      HIP_TRY(cs.alloc(&d_bits, n_bits + 8), 10);
-      HIP_TRY(cs.alloc(&d_out, m * RW * 8), 10);
-      HIP_TRY(cs.alloc(&d_oinf, m), 10);
-      HIP_TRY(hipMemcpyAsync(d_xy, xy, rows * RW * 8, hipMemcpyHostToDevice, s), 10);
-      HIP_TRY(hipMemcpyAsync(d_bits, bits, n_bits, hipMemcpyHostToDevice, s), 10);
-      if (inf) {
-        HIP_TRY(cs.alloc(&d_inf, rows + 8), 10);
-        HIP_TRY(hipMemcpyAsync(d_inf, inf, rows, hipMemcpyHostToDevice, s), 10);
-      }
-    }
-    if (!dev || !d_count) HIP_TRY(cs.alloc(&d_count, m * 4), 10);
-    if (int rcr = Agg<F>::run(d_xy, d_inf, offsets, n_sets, d_bits, m, d_out, d_oinf, d_count, s, &log, &g_agg_last_lanes)) return rcr;
-    if (!dev) {
-      HIP_TRY(hipMemcpyAsync(out_xy, d_out, m * RW * 8, hipMemcpyDeviceToHost, s), 10);
-      HIP_TRY(hipMemcpyAsync(out_inf, d_oinf, m, hipMemcpyDeviceToHost, s), 10);
-      if (out_count) HIP_TRY(hipMemcpyAsync(out_count, d_count, m * 4, hipMemcpyDeviceToHost, s), 10);
-    }
-    HIP_TRY(hipStreamSynchronize(s), 10);
-    log.sum(g_agg_ms);
-    g_agg_ms[0] += g_agg_ms[7];
-    return 0;
-  }();
-  g_agg_ms[6] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return rc;
+  const WallMs wall(&g_agg_ms[6]);
+  CallScope cs;
+  HIP_TRY(cs.open(dev, stream_), 10);
+  EvLog log(cs.stream());
+  const size_t rows = offsets[n_sets], n_bits = n_sets == 1 ? m * (size_t)(offsets[1] - offsets[0]) : rows;
+  uint64_t *d_xy, *d_out;
+  uint8_t *d_inf, *d_bits, *d_oinf;
+  uint32_t* d_count;
+  HIP_TRY(cs.in(&d_xy, xy, rows * RW * 8, dev, 8), 10);
+  HIP_TRY(cs.in(&d_bits, bits, n_bits, dev, 8), 10);
+  HIP_TRY(cs.in(&d_inf, inf, rows, dev, 8), 10);
+  HIP_TRY(cs.out(&d_out, out_xy, m * RW * 8, dev), 10);
+  HIP_TRY(cs.out(&d_oinf, out_inf, m, dev), 10);
+  HIP_TRY(cs.out(&d_count, out_count, m * 4, dev), 10);
+  if (!d_count) HIP_TRY(cs.alloc(&d_count, m * 4), 10);            // the counts are optional to the caller, not to the sums
+  if (int rcr = Agg<F>::run(d_xy, d_inf, offsets, n_sets, d_bits, m, d_out, d_oinf, d_count, cs.stream(), &log, &g_agg_last_lanes)) return rcr;
+  HIP_TRY(cs.copy_back(), 10);
+  HIP_TRY(hipStreamSynchronize(cs.stream()), 10);
+  log.sum(g_agg_ms);
+  g_agg_ms[0] += g_agg_ms[7];
+  return 0;
 }
 
 // group 0 / 1: BLS12-377 G1 / G2
@@ -249,30 +232,19 @@ __global__ void __launch_bounds__(256) k_pack_seal_combined(const uint64_t* __re
   }
 }
 
-struct SealStageGuard {      // an engine that was staged and not run goes back to its pool
-  PairingStage ps;
-  ~SealStageGuard() { if (ps.lease) (void)pairing_run_staged_377(&ps, nullptr, 0, nullptr); }
-};
 struct SealDev { uint64_t *sig, *hash, *apk; uint8_t *siginf, *apkinf, *status; };
 
 // m products of two pairs behind the producer stream of cs; is_one: m host bytes
 static int seals_run_each(const SealDev& d, const SealNegG2& ng2, size_t m, CallScope& cs, uint8_t* is_one, float* ms_pair) {
-  SealStageGuard g;
-  if (int rc = pairing_stage_377((uint32_t)(2 * m), m, &g.ps)) return rc;
-  hipEvent_t ready;
-  HIP_TRY(cs.event(&ready), 10);
-  HIP_TRY(hipEventRecord(ready, cs.stream()), 10);
-  HIP_TRY(hipStreamWaitEvent(g.ps.stream, ready, 0), 10);
+  StagedProduct<Pairing377> g;
+  if (int rc = g.stage((uint32_t)(2 * m), m)) return rc;
+  if (int rc = g.after(cs)) return rc;
   hipLaunchKernelGGL(k_pack_seal_pairs, dim3((unsigned)((m * 24 + 255) / 256)), dim3(256), 0, g.ps.stream, d.sig, d.siginf, d.hash, d.apk, d.apkinf, d.status, ng2, (uint32_t)m,
                      g.ps.d_g1, g.ps.d_g2, g.ps.d_i1, g.ps.d_i2);
   HIP_TRY(hipGetLastError(), 10);
   std::vector<uint32_t> off(m + 1);
   for (size_t p = 0; p <= m; p++) off[p] = (uint32_t)(2 * p);
-  if (int rc = pairing_run_staged_377(&g.ps, off.data(), m, is_one)) return rc;      // synchronises the engine's stream, and cs's through the event
-  float pm[4];
-  pairing_timings_377(pm);
-  *ms_pair += pm[3];
-  return 0;
+  return g.run(off.data(), m, is_one, ms_pair);
 }
 
 int verify_aggregated_seals_377(const uint64_t* pk_xy, const uint8_t* pk_inf, const uint32_t* offsets, size_t n_sets, const uint8_t* bits, const uint32_t* min_signers,
@@ -282,17 +254,11 @@ int verify_aggregated_seals_377(const uint64_t* pk_xy, const uint8_t* pk_inf, co
   if (!domain || !msgs || !msg_off || !sig48 || !neg_g2_xy || !out_ok || (hash_mode != 0 && hash_mode != 2 && hash_mode != 3) || (mode != 0 && mode != 1)) return 2;
   if (int rc = agg_refuse(pk_xy, offsets, n_sets, bits, m, pk_xy, pk_xy)) return rc;
   if (int rc0 = api_enter()) return rc0;
-  const auto t0 = std::chrono::steady_clock::now();
+  const WallMs wall;
   // the message hashes: the hash unit hands its rows back on the host, as in sign_batch
   std::vector<uint64_t> hxy(m * 12);
   std::vector<uint8_t> att(m);
-  if (hash_mode == 3) {
-    std::vector<uint8_t> inner(m * 48);
-    std::vector<uint64_t> ioff(m + 1);
-    for (size_t i = 0; i <= m; i++) ioff[i] = 48 * i;
-    if (int rc = pedersen_crh_run(msgs, msg_off, m, inner.data())) return rc;
-    if (int rc = hash_to_g1_direct_run(domain, inner.data(), ioff.data(), extras, extra_off, m, hxy.data(), att.data(), 1)) return rc;
-  } else if (int rc = hash_to_g1_direct_run(domain, msgs, msg_off, extras, extra_off, m, hxy.data(), att.data(), hash_mode)) return rc;
+  if (int rc = hash_to_g1_direct_run(domain, msgs, msg_off, extras, extra_off, m, hxy.data(), att.data(), hash_mode)) return rc;
   const float ms_hash = hash_last_ms();
   SealNegG2 ng2;
   for (int q = 0; q < 24; q++) ng2.xy[q] = neg_g2_xy[q];
@@ -302,42 +268,31 @@ int verify_aggregated_seals_377(const uint64_t* pk_xy, const uint8_t* pk_inf, co
   g_agg_ms[2] = ms_hash;
   int path = 0;
   const int rc = [&]() -> int {
-    CallScope cs(nullptr);
-    HIP_TRY(cs.create_stream(), 10);
+    CallScope cs;
+    HIP_TRY(cs.open(0, nullptr), 10);
     const hipStream_t s = cs.stream();
     EvLog log(s);
     const uint32_t m32 = (uint32_t)m;
     const size_t rows = offsets[n_sets], n_bits = n_sets == 1 ? m * (size_t)(offsets[1] - offsets[0]) : rows;
     uint64_t* d_xy;
-    uint8_t *d_inf = nullptr, *d_bits, *d_sig48, *d_wire, *d_att;
-    uint32_t *d_count, *d_min = nullptr;
+    uint8_t *d_inf, *d_bits, *d_sig48, *d_wire, *d_att;
+    uint32_t *d_count, *d_min;
     SealDev d;
-    HIP_TRY(cs.alloc(&d_xy, rows * 192 + 8), 10);
-    HIP_TRY(cs.alloc(&d_bits, n_bits + 8), 10);
-    HIP_TRY(cs.alloc(&d_sig48, m * 48), 10);
     HIP_TRY(cs.alloc(&d_wire, m), 10);
-    HIP_TRY(cs.alloc(&d_att, m), 10);
     HIP_TRY(cs.alloc(&d_count, m * 4), 10);
     HIP_TRY(cs.alloc(&d.sig, m * 96), 10);
-    HIP_TRY(cs.alloc(&d.hash, m * 96), 10);
     HIP_TRY(cs.alloc(&d.apk, m * 192), 10);
     HIP_TRY(cs.alloc(&d.siginf, m), 10);
     HIP_TRY(cs.alloc(&d.apkinf, m), 10);
     HIP_TRY(cs.alloc(&d.status, m), 10);
     hipEvent_t e0 = log.open();
-    HIP_TRY(hipMemcpyAsync(d_xy, pk_xy, rows * 192, hipMemcpyHostToDevice, s), 10);
-    HIP_TRY(hipMemcpyAsync(d_bits, bits, n_bits, hipMemcpyHostToDevice, s), 10);
-    HIP_TRY(hipMemcpyAsync(d_sig48, sig48, m * 48, hipMemcpyHostToDevice, s), 10);
-    HIP_TRY(hipMemcpyAsync(d.hash, hxy.data(), m * 96, hipMemcpyHostToDevice, s), 10);
-    HIP_TRY(hipMemcpyAsync(d_att, att.data(), m, hipMemcpyHostToDevice, s), 10);
-    if (pk_inf) {
-      HIP_TRY(cs.alloc(&d_inf, rows + 8), 10);
-      HIP_TRY(hipMemcpyAsync(d_inf, pk_inf, rows, hipMemcpyHostToDevice, s), 10);
-    }
-    if (min_signers) {
-      HIP_TRY(cs.alloc(&d_min, m * 4), 10);
-      HIP_TRY(hipMemcpyAsync(d_min, min_signers, m * 4, hipMemcpyHostToDevice, s), 10);
-    }
+    HIP_TRY(cs.in(&d_xy, pk_xy, rows * 192, 0, 8), 10);
+    HIP_TRY(cs.in(&d_bits, bits, n_bits, 0, 8), 10);
+    HIP_TRY(cs.in(&d_sig48, sig48, m * 48, 0), 10);
+    HIP_TRY(cs.in(&d.hash, hxy.data(), m * 96, 0), 10);
+    HIP_TRY(cs.in(&d_att, att.data(), m, 0), 10);
+    HIP_TRY(cs.in(&d_inf, pk_inf, rows, 0, 8), 10);
+    HIP_TRY(cs.in(&d_min, min_signers, m * 4, 0), 10);
     log.close(5, e0);
     if (int rcr = Agg<Fp2<P377>>::run(d_xy, d_inf, offsets, n_sets, d_bits, m, d.apk, d.apkinf, d_count, s, &log, &g_agg_last_lanes)) return rcr;
     if (int rcw = wire_decompress(0, d_sig48, m, 1, d.sig, d_wire, 1, s)) return rcw;
@@ -354,15 +309,8 @@ int verify_aggregated_seals_377(const uint64_t* pk_xy, const uint8_t* pk_inf, co
     if (mode == 1) {
       uint32_t k8[8];
       if (key) memcpy(k8, key, sizeof k8);
-      else {                                               // 32 bytes from the operating system per call, as the Groth16 verifier's exponent stream
-        size_t got = 0;
-        while (got < sizeof k8) {
-          const ssize_t r = getrandom((uint8_t*)k8 + got, sizeof k8 - got, 0);
-          if (r <= 0) return 1;
-          got += (size_t)r;
-        }
-      }
-      const auto t1 = std::chrono::steady_clock::now();
+      else if (!os_random(k8, sizeof k8)) return 1;         // 32 bytes from the operating system per call, as the Groth16 verifier's exponent stream
+      const WallMs wall_msm;
       uint64_t *d_r4, *d_sc, *d_rh;
       uint32_t* d_off;
       uint8_t* d_rhinf;
@@ -384,21 +332,18 @@ int verify_aggregated_seals_377(const uint64_t* pk_xy, const uint8_t* pk_inf, co
       if (int rcm = MsmApi<G1_377>::dev(d.sig, d.siginf, d_sc, m, 1, jac, s)) return rcm;
       HIP_TRY(hipStreamSynchronize(s), 10);
       if (int rcn = wire_normalize(0, jac, 1, tail, &tinf)) return rcn;
-      g_agg_ms[3] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t1).count();
+      g_agg_ms[3] = wall_msm.ms();
       uint8_t v = 0;
       {
-        SealStageGuard g;
-        if (int rcs = pairing_stage_377(m32 + 1, 1, &g.ps)) return rcs;
+        StagedProduct<Pairing377> g;
+        if (int rcs = g.stage(m32 + 1, 1)) return rcs;
         hipLaunchKernelGGL(k_pack_seal_combined, dim3((unsigned)(((m + 1) * 24 + 255) / 256)), dim3(256), 0, g.ps.stream, d_rh, d_rhinf, d.apk, d.apkinf, d.status, ng2, m32,
                            g.ps.d_g1, g.ps.d_g2, g.ps.d_i1, g.ps.d_i2);
         HIP_TRY(hipGetLastError(), 10);
         HIP_TRY(hipMemcpyAsync(g.ps.d_g1 + m * 12, tail, sizeof tail, hipMemcpyHostToDevice, g.ps.stream), 10);
         HIP_TRY(hipMemcpyAsync(g.ps.d_i1 + m, &tinf, 1, hipMemcpyHostToDevice, g.ps.stream), 10);
         const uint32_t off[2] = {0, m32 + 1};
-        if (int rcp = pairing_run_staged_377(&g.ps, off, 1, &v)) return rcp;
-        float pm[4];
-        pairing_timings_377(pm);
-        g_agg_ms[4] += pm[3];
+        if (int rcp = g.run(off, 1, &v, &g_agg_ms[4])) return rcp;
       }
       if (v) {
         for (size_t i = 0; i < m; i++) is_one[i] = 1;
@@ -414,7 +359,7 @@ int verify_aggregated_seals_377(const uint64_t* pk_xy, const uint8_t* pk_inf, co
   }();
   g_agg_ms[0] += g_agg_ms[7];
   g_agg_last_path = path;
-  g_agg_ms[6] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  g_agg_ms[6] = wall.ms();
   if (rc) return rc;
   for (size_t i = 0; i < m; i++) {
     const uint8_t st = h_status[i] ? h_status[i] : is_one[i] ? 0 : 4;

@@ -5,7 +5,6 @@
 #include "fixed_base.h"
 #include "normalize.h"
 #include <hip/hip_runtime.h>
-#include <chrono>
 #include <cstring>
 #include <mutex>
 #include <vector>
@@ -24,7 +23,6 @@ static constexpr int FB_DEFAULT_C = 10;   // same-box A/B on 2^20 BW6-761 G1 row
 // the last call's timings in ms: [0] table build, [1] Fr preparation, [2] G1 rows, [3] G2 rows, [4] normalisation, [5] key tables, [6] wall
 static float g_setup_ms[8] = {};
 
-template <int N> struct ArkWords { uint64_t v[N]; };
 template <class FR> struct FrParams;
 template <class P> struct FrParams<Fp<P>> { typedef P type; };
 
@@ -51,16 +49,6 @@ __global__ void __launch_bounds__(64) k_fbm_table(const uint32_t* __restrict__ b
   if (!binf[w]) ok = fb_to_affine(fb_table_entry(fb_load_entry<F>(bases + (size_t)w * 2 * F::WORDS), d), r);
   fb_store_entry(table + (size_t)e * 2 * F::WORDS, r);
   tinf[e] = ok ? 0 : 1;
-}
-// flag |= 1 for a scalar >= the group order
-template <int N64>
-__global__ void __launch_bounds__(256) k_fbm_range(const uint64_t* __restrict__ sc, uint32_t n, ArkWords<N64> r, uint32_t* flag) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  uint64_t s[N64];
-#pragma unroll
-  for (int k = 0; k < N64; k++) s[k] = sc[(size_t)i * N64 + k];
-  if (!fb_below<N64>(s, r.v)) atomicOr(flag, 1u);
 }
 // one lane per scalar: k_i G in XYZZ (device form, 4 FW words per row)
 template <class F, int N64>
@@ -140,7 +128,6 @@ template <class F, int N64, int BITS> struct Fbm {
   // cat: the timing slot of the scalar kernel (2 = G1, 3 = G2); the normalisation goes to slot 4.
   int rows(const uint64_t* d_sc, size_t n, uint64_t* d_out, uint8_t* d_inf, int ark_zero_y, hipStream_t s, EvLog* log, int cat) {
     constexpr size_t CHUNK = size_t(1) << 20;
-    constexpr int K = sizeof(F) <= 64 ? 8 : 4;
     if (n == 0) return 0;
     CallScope cs(s);
     uint32_t* tmp;
@@ -152,8 +139,7 @@ template <class F, int N64, int BITS> struct Fbm {
       hipLaunchKernelGGL((k_fbm_rows<F, N64>), dim3((k + 255) / 256), dim3(256), 0, s, d_sc + lo * N64, k, table, tinf, c, W, tmp);
       log->close(cat, e0);
       e0 = log->open();
-      hipLaunchKernelGGL((k_normalize<F, K, false, 0, true>), dim3(((k + K - 1) / K + 63) / 64), dim3(64), 0, s, (const void*)tmp, d_out + lo * 2 * A, d_inf + lo, k,
-                         ark_zero_y);
+      normalize_xyzz<F, true>(tmp, d_out + lo * 2 * A, d_inf + lo, k, ark_zero_y, s);
       log->close(4, e0);
       HIP_TRY(hipGetLastError(), 10);
     }
@@ -175,7 +161,7 @@ template <class F> static bool gen_is_identity(const uint64_t* xy) {
   return x0 && (y0 || y1);
 }
 
-// out[i] = k_i G.  dev = 0: scalars / out / inf are host pointers; 1: device pointers, run on stream_.  A scalar >= r: 2, nothing written.
+// out[i] = k_i G.  scalars / out / inf: host or device pointers (runtime.h, the call frame).  A scalar >= r: 2, nothing written.
 template <class FB, class FR>
 static int fbm_mul(const uint64_t* gen, const void* scalars, size_t n, void* out_xy, void* inf, int dev, void* stream_) {
   typedef typename FB::Fc F;
@@ -190,45 +176,23 @@ static int fbm_mul(const uint64_t* gen, const void* scalars, size_t n, void* out
     const uint64_t* sc = (const uint64_t*)scalars;
     for (size_t i = 0; i < n; i++) if (!fb_below<N64>(sc + i * N64, FrParams<FR>::type::P64)) return 2;
   }
-  const auto t0 = std::chrono::steady_clock::now();
-  const int rc = [&]() -> int {     // the device work: its resources are released before the wall time is taken
-    CallScope cs(dev ? (hipStream_t)stream_ : nullptr);
-    if (!dev) HIP_TRY(cs.create_stream(), 10);
-    const hipStream_t s = cs.stream();
-    EvLog log(s);
-    FB fb;
-    uint64_t *d_sc = (uint64_t*)scalars, *d_out = (uint64_t*)out_xy;
-    uint8_t* d_inf = (uint8_t*)inf;
-    if (dev) {
-      ArkWords<N64> r;
-      for (int k = 0; k < N64; k++) r.v[k] = FrParams<FR>::type::P64[k];
-      uint32_t flag = 0;
-      uint32_t* d_flag;
-      HIP_TRY(cs.alloc(&d_flag, 4), 10);
-      HIP_TRY(hipMemsetAsync(d_flag, 0, 4, s), 10);
-      hipLaunchKernelGGL((k_fbm_range<N64>), dim3(((uint32_t)n + 255) / 256), dim3(256), 0, s, d_sc, (uint32_t)n, r, d_flag);
-      HIP_TRY(hipGetLastError(), 10);
-      HIP_TRY(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, s), 10);
-      HIP_TRY(hipStreamSynchronize(s), 10);
-      if (flag) return 2;
-    } else {
-      HIP_TRY(cs.alloc(&d_sc, n * N64 * 8), 10);
-      HIP_TRY(cs.alloc(&d_out, n * RW * 8), 10);
-      HIP_TRY(cs.alloc(&d_inf, n), 10);
-      HIP_TRY(hipMemcpyAsync(d_sc, scalars, n * N64 * 8, hipMemcpyHostToDevice, s), 10);
-    }
-    if (int rcb = fb.build(gen, s, &log)) return rcb;
-    if (int rcr = fb.rows(d_sc, n, d_out, d_inf, 0, s, &log, 2)) return rcr;
-    if (!dev) {
-      HIP_TRY(hipMemcpyAsync(out_xy, d_out, n * RW * 8, hipMemcpyDeviceToHost, s), 10);
-      HIP_TRY(hipMemcpyAsync(inf, d_inf, n, hipMemcpyDeviceToHost, s), 10);
-    }
-    HIP_TRY(hipStreamSynchronize(s), 10);
-    log.sum(g_setup_ms);
-    return 0;
-  }();
-  g_setup_ms[6] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return rc;
+  const WallMs wall(&g_setup_ms[6]);
+  CallScope cs;
+  HIP_TRY(cs.open(dev, stream_), 10);
+  EvLog log(cs.stream());
+  FB fb;
+  uint64_t *d_sc, *d_out;
+  uint8_t* d_inf;
+  if (dev) if (int rcs = scalars_below_order<N64>((const uint64_t*)scalars, n, FrParams<FR>::type::P64, cs)) return rcs;
+  HIP_TRY(cs.in(&d_sc, scalars, n * N64 * 8, dev), 10);
+  HIP_TRY(cs.out(&d_out, out_xy, n * RW * 8, dev), 10);
+  HIP_TRY(cs.out(&d_inf, inf, n, dev), 10);
+  if (int rcb = fb.build(gen, cs.stream(), &log)) return rcb;
+  if (int rcr = fb.rows(d_sc, n, d_out, d_inf, 0, cs.stream(), &log, 2)) return rcr;
+  HIP_TRY(cs.copy_back(), 10);
+  HIP_TRY(hipStreamSynchronize(cs.stream()), 10);
+  log.sum(g_setup_ms);
+  return 0;
 }
 
 int fixed_base_mul(int group, const uint64_t* gen, const void* scalars, size_t n, void* out_xy, void* inf, int dev, void* stream) {
@@ -308,83 +272,79 @@ static int setup_run(int curve, int dev_in, const uint64_t* qa, const uint64_t* 
   setup_canon<FR>(toxic + N, head2); setup_canon<FR>(toxic + 2 * N, head2 + N); setup_canon<FR>(toxic + 3 * N, head2 + 2 * N);
   std::lock_guard<std::mutex> lk(setup_mu);
   for (float& t : g_setup_ms) t = 0.f;
-  const auto t0 = std::chrono::steady_clock::now();
-  const int rc = [&]() -> int {     // the device work: its resources are released before the wall time is taken
-    CallScope cs(nullptr);
-    HIP_TRY(cs.create_stream(), 10);
-    const hipStream_t s = cs.stream();
-    EvLog log(s);
-    const size_t qb_bytes = n_vars * N * 8;
-    uint64_t *d_s1, *d_s2, *d_r1, *d_r2;
-    const uint64_t *d_qa = qa, *d_qb = qb, *d_qc = qc;
-    uint8_t *d_i1, *d_i2;
-    HIP_TRY(cs.alloc(&d_s1, n1 * N * 8), 10);
-    HIP_TRY(cs.alloc(&d_s2, n2 * N * 8), 10);
-    HIP_TRY(cs.alloc(&d_r1, n1 * R1 * 8), 10);
-    HIP_TRY(cs.alloc(&d_r2, n2 * R2 * 8), 10);
-    HIP_TRY(cs.alloc(&d_i1, n1), 10);
-    HIP_TRY(cs.alloc(&d_i2, n2), 10);
-    if (!dev_in) {
-      uint64_t* d_q;
-      HIP_TRY(cs.alloc(&d_q, 3 * qb_bytes), 10);
-      HIP_TRY(hipMemcpyAsync(d_q, qa, qb_bytes, hipMemcpyHostToDevice, s), 10);
-      HIP_TRY(hipMemcpyAsync(d_q + n_vars * N, qb, qb_bytes, hipMemcpyHostToDevice, s), 10);
-      HIP_TRY(hipMemcpyAsync(d_q + 2 * n_vars * N, qc, qb_bytes, hipMemcpyHostToDevice, s), 10);
-      d_qa = d_q; d_qb = d_q + n_vars * N; d_qc = d_q + 2 * n_vars * N;
-    }
-    HIP_TRY(hipMemcpyAsync(d_s1, head1, sizeof head1, hipMemcpyHostToDevice, s), 10);
-    HIP_TRY(hipMemcpyAsync(d_s2, head2, sizeof head2, hipMemcpyHostToDevice, s), 10);
-    hipEvent_t e0 = log.open();
-    hipLaunchKernelGGL((k_setup_fr<FR>), dim3((unsigned)((n_vars + 255) / 256)), dim3(256), 0, s, d_qa, d_qb, d_qc, (uint32_t)n_vars, (uint32_t)n_inputs, alpha, beta, ginv, dinv, d_s1, d_s2, (uint32_t)n_h);
-    if (n_h) {
-      const size_t blocks = (n_h + SETUP_H_BLOCK - 1) / SETUP_H_BLOCK;
-      hipLaunchKernelGGL((k_setup_h<FR>), dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, s, zt_dinv, tau_d, (uint32_t)n_h,
-                         d_s1 + (3 + n_inputs + 2 * n_vars) * N);
-    }
-    log.close(1, e0);
-    HIP_TRY(hipGetLastError(), 10);
-    {
-      FB1 t1;
-      if (int rcb = t1.build(g1_xy, s, &log)) return rcb;
-      if (int rcr = t1.rows(d_s1, n1, d_r1, d_i1, 1, s, &log, 2)) return rcr;
-    }
-    {
-      FB2 t2;
-      if (int rcb = t2.build(g2_xy, s, &log)) return rcb;
-      if (int rcr = t2.rows(d_s2, n2, d_r2, d_i2, 1, s, &log, 3)) return rcr;
-    }
-    const size_t r_abc = 3, r_a = r_abc + n_inputs, r_h = r_a + 2 * n_vars, r_l = r_h + n_h;
-    if (out_vk) {
-      uint64_t* o = out_vk;
-      HIP_TRY(hipMemcpyAsync(o, d_r1, R1 * 8, hipMemcpyDeviceToHost, s), 10); o += R1;
-      HIP_TRY(hipMemcpyAsync(o, d_r2, 3 * R2 * 8, hipMemcpyDeviceToHost, s), 10); o += 3 * R2;
-      HIP_TRY(hipMemcpyAsync(o, d_r1 + r_abc * R1, n_inputs * R1 * 8, hipMemcpyDeviceToHost, s), 10);
-    }
-    if (out_rows) {
-      uint64_t* o = out_rows;
-      HIP_TRY(hipMemcpyAsync(o, d_r1 + R1, 2 * R1 * 8, hipMemcpyDeviceToHost, s), 10); o += 2 * R1;
-      HIP_TRY(hipMemcpyAsync(o, d_r1 + r_a * R1, 2 * n_vars * R1 * 8, hipMemcpyDeviceToHost, s), 10); o += 2 * n_vars * R1;
-      HIP_TRY(hipMemcpyAsync(o, d_r2 + 3 * R2, n_vars * R2 * 8, hipMemcpyDeviceToHost, s), 10); o += n_vars * R2;
-      HIP_TRY(hipMemcpyAsync(o, d_r1 + r_h * R1, (n_h + n_vars - n_inputs) * R1 * 8, hipMemcpyDeviceToHost, s), 10);
-    }
-    HIP_TRY(hipStreamSynchronize(s), 10);
-    log.sum(g_setup_ms);
-    if (!out_key) return 0;
-    // the four key elements the composition keeps on the host (query[0] of a and b_g2, alpha_g1, beta_g2): four rows, not a query
-    uint64_t a0[R1], b0[R2], al[R1], be[R2];
-    HIP_TRY(hipMemcpy(a0, d_r1 + r_a * R1, sizeof a0, hipMemcpyDeviceToHost), 10);
-    HIP_TRY(hipMemcpy(b0, d_r2 + 3 * R2, sizeof b0, hipMemcpyDeviceToHost), 10);
-    HIP_TRY(hipMemcpy(al, d_r1, sizeof al, hipMemcpyDeviceToHost), 10);
-    HIP_TRY(hipMemcpy(be, d_r2, sizeof be, hipMemcpyDeviceToHost), 10);
-    const auto k0 = std::chrono::steady_clock::now();
-    // (sets *out_key only on success; the key is the call's last step, so nothing after it can fail)
-    const int rck = groth16_key_load_dev(curve, d_r1 + r_a * R1, d_i1 + r_a, n_vars, d_r2 + 3 * R2, d_i2 + 3, n_vars, d_r1 + r_h * R1, d_i1 + r_h, n_h,
-                                         d_r1 + r_l * R1, d_i1 + r_l, n_vars - n_inputs, a0, b0, al, be, window_bits, out_key);
-    g_setup_ms[5] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - k0).count();
-    return rck;
-  }();
-  g_setup_ms[6] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return rc;
+  const WallMs wall(&g_setup_ms[6]);     // (declared in front of the call's resources: their release is inside the wall time)
+  CallScope cs;
+  HIP_TRY(cs.open(0, nullptr), 10);
+  const hipStream_t s = cs.stream();
+  EvLog log(s);
+  const size_t qb_bytes = n_vars * N * 8;
+  uint64_t *d_s1, *d_s2, *d_r1, *d_r2;
+  const uint64_t *d_qa = qa, *d_qb = qb, *d_qc = qc;
+  uint8_t *d_i1, *d_i2;
+  HIP_TRY(cs.alloc(&d_s1, n1 * N * 8), 10);
+  HIP_TRY(cs.alloc(&d_s2, n2 * N * 8), 10);
+  HIP_TRY(cs.alloc(&d_r1, n1 * R1 * 8), 10);
+  HIP_TRY(cs.alloc(&d_r2, n2 * R2 * 8), 10);
+  HIP_TRY(cs.alloc(&d_i1, n1), 10);
+  HIP_TRY(cs.alloc(&d_i2, n2), 10);
+  if (!dev_in) {
+    uint64_t* d_q;
+    HIP_TRY(cs.alloc(&d_q, 3 * qb_bytes), 10);
+    HIP_TRY(hipMemcpyAsync(d_q, qa, qb_bytes, hipMemcpyHostToDevice, s), 10);
+    HIP_TRY(hipMemcpyAsync(d_q + n_vars * N, qb, qb_bytes, hipMemcpyHostToDevice, s), 10);
+    HIP_TRY(hipMemcpyAsync(d_q + 2 * n_vars * N, qc, qb_bytes, hipMemcpyHostToDevice, s), 10);
+    d_qa = d_q; d_qb = d_q + n_vars * N; d_qc = d_q + 2 * n_vars * N;
+  }
+  HIP_TRY(hipMemcpyAsync(d_s1, head1, sizeof head1, hipMemcpyHostToDevice, s), 10);
+  HIP_TRY(hipMemcpyAsync(d_s2, head2, sizeof head2, hipMemcpyHostToDevice, s), 10);
+  hipEvent_t e0 = log.open();
+  hipLaunchKernelGGL((k_setup_fr<FR>), dim3((unsigned)((n_vars + 255) / 256)), dim3(256), 0, s, d_qa, d_qb, d_qc, (uint32_t)n_vars, (uint32_t)n_inputs, alpha, beta, ginv, dinv, d_s1, d_s2, (uint32_t)n_h);
+  if (n_h) {
+    const size_t blocks = (n_h + SETUP_H_BLOCK - 1) / SETUP_H_BLOCK;
+    hipLaunchKernelGGL((k_setup_h<FR>), dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, s, zt_dinv, tau_d, (uint32_t)n_h,
+                       d_s1 + (3 + n_inputs + 2 * n_vars) * N);
+  }
+  log.close(1, e0);
+  HIP_TRY(hipGetLastError(), 10);
+  {
+    FB1 t1;
+    if (int rcb = t1.build(g1_xy, s, &log)) return rcb;
+    if (int rcr = t1.rows(d_s1, n1, d_r1, d_i1, 1, s, &log, 2)) return rcr;
+  }
+  {
+    FB2 t2;
+    if (int rcb = t2.build(g2_xy, s, &log)) return rcb;
+    if (int rcr = t2.rows(d_s2, n2, d_r2, d_i2, 1, s, &log, 3)) return rcr;
+  }
+  const size_t r_abc = 3, r_a = r_abc + n_inputs, r_h = r_a + 2 * n_vars, r_l = r_h + n_h;
+  if (out_vk) {
+    uint64_t* o = out_vk;
+    HIP_TRY(hipMemcpyAsync(o, d_r1, R1 * 8, hipMemcpyDeviceToHost, s), 10); o += R1;
+    HIP_TRY(hipMemcpyAsync(o, d_r2, 3 * R2 * 8, hipMemcpyDeviceToHost, s), 10); o += 3 * R2;
+    HIP_TRY(hipMemcpyAsync(o, d_r1 + r_abc * R1, n_inputs * R1 * 8, hipMemcpyDeviceToHost, s), 10);
+  }
+  if (out_rows) {
+    uint64_t* o = out_rows;
+    HIP_TRY(hipMemcpyAsync(o, d_r1 + R1, 2 * R1 * 8, hipMemcpyDeviceToHost, s), 10); o += 2 * R1;
+    HIP_TRY(hipMemcpyAsync(o, d_r1 + r_a * R1, 2 * n_vars * R1 * 8, hipMemcpyDeviceToHost, s), 10); o += 2 * n_vars * R1;
+    HIP_TRY(hipMemcpyAsync(o, d_r2 + 3 * R2, n_vars * R2 * 8, hipMemcpyDeviceToHost, s), 10); o += n_vars * R2;
+    HIP_TRY(hipMemcpyAsync(o, d_r1 + r_h * R1, (n_h + n_vars - n_inputs) * R1 * 8, hipMemcpyDeviceToHost, s), 10);
+  }
+  HIP_TRY(hipStreamSynchronize(s), 10);
+  log.sum(g_setup_ms);
+  if (!out_key) return 0;
+  // the four key elements the composition keeps on the host (query[0] of a and b_g2, alpha_g1, beta_g2): four rows, not a query
+  uint64_t a0[R1], b0[R2], al[R1], be[R2];
+  HIP_TRY(hipMemcpy(a0, d_r1 + r_a * R1, sizeof a0, hipMemcpyDeviceToHost), 10);
+  HIP_TRY(hipMemcpy(b0, d_r2 + 3 * R2, sizeof b0, hipMemcpyDeviceToHost), 10);
+  HIP_TRY(hipMemcpy(al, d_r1, sizeof al, hipMemcpyDeviceToHost), 10);
+  HIP_TRY(hipMemcpy(be, d_r2, sizeof be, hipMemcpyDeviceToHost), 10);
+  const WallMs wall_key;
+  // (sets *out_key only on success; the key is the call's last step, so nothing after it can fail)
+  const int rck = groth16_key_load_dev(curve, d_r1 + r_a * R1, d_i1 + r_a, n_vars, d_r2 + 3 * R2, d_i2 + 3, n_vars, d_r1 + r_h * R1, d_i1 + r_h, n_h,
+                                       d_r1 + r_l * R1, d_i1 + r_l, n_vars - n_inputs, a0, b0, al, be, window_bits, out_key);
+  g_setup_ms[5] = wall_key.ms();
+  return rck;
 }
 
 int groth16_setup(int curve, const uint64_t* qa, const uint64_t* qb, const uint64_t* qc, size_t n_vars, size_t n_inputs, const uint64_t* zt, const uint64_t* tau,
@@ -407,7 +367,7 @@ int groth16_setup_r1cs(int curve, const R1cs* r, unsigned log_n, const uint64_t*
   r1cs_shape(r, &r_curve, &device, &m, &n_vars, &n_inputs);
   if (r_curve != curve) return 2;
   if (device != api_device()) return 101;
-  const auto t0 = std::chrono::steady_clock::now();
+  const WallMs wall;
   const int N = curve ? 4 : 6;
   const int rc = [&]() -> int {
     CallScope cs(nullptr);
@@ -421,7 +381,7 @@ int groth16_setup_r1cs(int curve, const R1cs* r, unsigned log_n, const uint64_t*
       return setup_run<Fbm761, Fbm761, FrBw6>(0, 1, qa, qb, qc, n_vars, n_inputs, zt, tau, n_h, toxic, g1_xy, g2_xy, window_bits, out_vk, out_rows, out_key);
     return setup_run<FbmG1_377, FbmG2_377, FrBls>(1, 1, qa, qb, qc, n_vars, n_inputs, zt, tau, n_h, toxic, g1_xy, g2_xy, window_bits, out_vk, out_rows, out_key);
   }();
-  r1cs_note_ms(5, std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  r1cs_note_ms(5, wall.ms());
   return rc;
 }
 

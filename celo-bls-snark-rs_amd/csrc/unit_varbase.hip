@@ -5,7 +5,6 @@
 #include "var_base.h"
 #include "normalize.h"
 #include <hip/hip_runtime.h>
-#include <chrono>
 #include <cstring>
 #include <mutex>
 #include <vector>
@@ -25,8 +24,6 @@ static constexpr size_t VB_WORKSPACE = size_t(1) << 28;   // the default chunk k
 static constexpr int VB_BLOCK = 64;          // one wave per workgroup: the kernels are register-heavy and the batches often small
 // the last call's timings in ms: [0] table build, [1] ladder, [2] normalisation, [3] whole call (wall)
 static float g_vb_ms[4] = {};
-
-template <int N> struct VbWords { uint64_t v[N]; };
 
 // lane i -> the table of P_i (var_base.h vb_build_table).  xy: rows of 2 A arkworks limbs; inf: flags or null.
 template <class F>
@@ -54,16 +51,6 @@ __global__ void __launch_bounds__(VB_BLOCK) k_vb_ladder(const uint64_t* __restri
   uint32_t* o = xyzz + (size_t)i * 4 * F::WORDS;
   a.X.store(o); a.Y.store(o + F::WORDS); a.ZZ.store(o + 2 * F::WORDS); a.ZZZ.store(o + 3 * F::WORDS);
 }
-// flag |= 1 for a scalar >= the group order
-template <int N64>
-__global__ void __launch_bounds__(256) k_vb_range(const uint64_t* __restrict__ sc, uint32_t n, VbWords<N64> r, uint32_t* flag) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  uint64_t s[N64];
-#pragma unroll
-  for (int k = 0; k < N64; k++) s[k] = sc[(size_t)i * N64 + k];
-  if (!fb_below<N64>(s, r.v)) atomicOr(flag, 1u);
-}
 
 // ---- one group: F the coordinate field, N64 u64 per scalar, BITS scalar bits
 template <class F, int N64, int BITS> struct Vbm {
@@ -78,7 +65,6 @@ template <class F, int N64, int BITS> struct Vbm {
   // n rows, everything on the device, enqueued on s in chunks that bound the workspace; returns after the stream has drained
   template <bool GLV>
   static int run(const uint64_t* d_xy, const uint8_t* d_inf, const uint64_t* d_sc, size_t n_sc, size_t n, uint64_t* d_out, uint8_t* d_oinf, hipStream_t s, EvLog* log) {
-    constexpr int K = sizeof(F) <= 64 ? 8 : 4;
     if (n == 0) return 0;
     const int c = g_vb_c ? g_vb_c : vb_default_c<F>();
     const uint32_t H = 1u << (c - 1);
@@ -103,7 +89,7 @@ template <class F, int N64, int BITS> struct Vbm {
                          tmp);
       log->close(1, e0);
       e0 = log->open();
-      hipLaunchKernelGGL((k_normalize<F, K, false, 0, false>), dim3(((k + K - 1) / K + 63) / 64), dim3(64), 0, s, (const void*)tmp, d_out + lo * 2 * A, d_oinf + lo, k, 0);
+      normalize_xyzz<F, false>(tmp, d_out + lo * 2 * A, d_oinf + lo, k, 0, s);
       log->close(2, e0);
       HIP_TRY(hipGetLastError(), 10);
     }
@@ -120,7 +106,7 @@ template <int N64> static const uint64_t* vb_order() {
   else return P377::P64;
 }
 
-// dev = 0: host pointers; 1: device pointers, run on stream_.  Refused arguments: 2, nothing written.
+// Host or device pointers (runtime.h, the call frame).  Refused arguments: 2, nothing written.
 template <class VB, int N64, bool GLV>
 static int vb_mul(const void* xy, const void* inf, const void* scalars, size_t n_sc, size_t n, void* out_xy, void* out_inf, int dev, void* stream_) {
   constexpr int RW = 2 * VB::A;
@@ -133,49 +119,23 @@ static int vb_mul(const void* xy, const void* inf, const void* scalars, size_t n
   }
   std::lock_guard<std::mutex> lk(vb_mu);
   for (float& t : g_vb_ms) t = 0.f;
-  const auto t0 = std::chrono::steady_clock::now();
-  const int rc = [&]() -> int {     // the device work: its resources are released before the wall time is taken
-    CallScope cs(dev ? (hipStream_t)stream_ : nullptr);
-    if (!dev) HIP_TRY(cs.create_stream(), 10);
-    const hipStream_t s = cs.stream();
-    EvLog log(s);
-    uint64_t *d_xy = (uint64_t*)xy, *d_sc = (uint64_t*)scalars, *d_out = (uint64_t*)out_xy;
-    uint8_t *d_inf = (uint8_t*)inf, *d_oinf = (uint8_t*)out_inf;
-    if (dev) {
-      VbWords<N64> r;
-      for (int k = 0; k < N64; k++) r.v[k] = vb_order<N64>()[k];
-      uint32_t flag = 0;
-      uint32_t* d_flag;
-      HIP_TRY(cs.alloc(&d_flag, 4), 10);
-      HIP_TRY(hipMemsetAsync(d_flag, 0, 4, s), 10);
-      hipLaunchKernelGGL((k_vb_range<N64>), dim3(((uint32_t)n_sc + 255) / 256), dim3(256), 0, s, d_sc, (uint32_t)n_sc, r, d_flag);
-      HIP_TRY(hipGetLastError(), 10);
-      HIP_TRY(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, s), 10);
-      HIP_TRY(hipStreamSynchronize(s), 10);
-      if (flag) return 2;
-    } else {
-      HIP_TRY(cs.alloc(&d_xy, n * RW * 8), 10);
-      HIP_TRY(cs.alloc(&d_sc, n_sc * N64 * 8), 10);
-      HIP_TRY(cs.alloc(&d_out, n * RW * 8), 10);
-      HIP_TRY(cs.alloc(&d_oinf, n), 10);
-      HIP_TRY(hipMemcpyAsync(d_xy, xy, n * RW * 8, hipMemcpyHostToDevice, s), 10);
-      HIP_TRY(hipMemcpyAsync(d_sc, scalars, n_sc * N64 * 8, hipMemcpyHostToDevice, s), 10);
-      if (inf) {
-        HIP_TRY(cs.alloc(&d_inf, n), 10);
-        HIP_TRY(hipMemcpyAsync(d_inf, inf, n, hipMemcpyHostToDevice, s), 10);
-      }
-    }
-    if (int rcr = VB::template run<GLV>(d_xy, d_inf, d_sc, n_sc, n, d_out, d_oinf, s, &log)) return rcr;
-    if (!dev) {
-      HIP_TRY(hipMemcpyAsync(out_xy, d_out, n * RW * 8, hipMemcpyDeviceToHost, s), 10);
-      HIP_TRY(hipMemcpyAsync(out_inf, d_oinf, n, hipMemcpyDeviceToHost, s), 10);
-    }
-    HIP_TRY(hipStreamSynchronize(s), 10);
-    log.sum(g_vb_ms);
-    return 0;
-  }();
-  g_vb_ms[3] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return rc;
+  const WallMs wall(&g_vb_ms[3]);
+  CallScope cs;
+  HIP_TRY(cs.open(dev, stream_), 10);
+  EvLog log(cs.stream());
+  uint64_t *d_xy, *d_sc, *d_out;
+  uint8_t *d_inf, *d_oinf;
+  if (dev) if (int rcs = scalars_below_order<N64>((const uint64_t*)scalars, n_sc, vb_order<N64>(), cs)) return rcs;
+  HIP_TRY(cs.in(&d_xy, xy, n * RW * 8, dev), 10);
+  HIP_TRY(cs.in(&d_sc, scalars, n_sc * N64 * 8, dev), 10);
+  HIP_TRY(cs.in(&d_inf, inf, n, dev), 10);
+  HIP_TRY(cs.out(&d_out, out_xy, n * RW * 8, dev), 10);
+  HIP_TRY(cs.out(&d_oinf, out_inf, n, dev), 10);
+  if (int rcr = VB::template run<GLV>(d_xy, d_inf, d_sc, n_sc, n, d_out, d_oinf, cs.stream(), &log)) return rcr;
+  HIP_TRY(cs.copy_back(), 10);
+  HIP_TRY(hipStreamSynchronize(cs.stream()), 10);
+  log.sum(g_vb_ms);
+  return 0;
 }
 
 // group 0 / 1: BLS12-377 G1 / G2, 2: BW6-761 (both groups); subgroup: the GLV ladder (group 0 only)
@@ -217,45 +177,36 @@ int sign_batch_377(const uint64_t* sk, size_t n_sk, const uint8_t* domain, const
   if (!sk || !domain || !msgs || !msg_off || !out_sig48 || !attempts || (n_sk != 1 && n_sk != n) || n > 0x7fffffffu) return 2;
   if (mode != 0 && mode != 2 && mode != 3) return 2;
   for (size_t i = 0; i < n_sk; i++) if (!fb_below<4>(sk + i * 4, P253::P64)) return 2;
-  const auto t0 = std::chrono::steady_clock::now();
+  const WallMs wall;
   std::vector<uint64_t> hxy(n * 12);
   std::vector<uint8_t> att(n), hinf(n);
-  if (mode == 3) {                                             // CIP22: one CRH per message, then the loops over xof(c || extra || inner)
-    std::vector<uint8_t> inner(n * 48);
-    std::vector<uint64_t> ioff(n + 1);
-    for (size_t i = 0; i <= n; i++) ioff[i] = 48 * i;
-    if (int rc = pedersen_crh_run(msgs, msg_off, n, inner.data())) return rc;
-    if (int rc = hash_to_g1_direct_run(domain, inner.data(), ioff.data(), extras, extra_off, n, hxy.data(), att.data(), 1)) return rc;
-  } else if (int rc = hash_to_g1_direct_run(domain, msgs, msg_off, extras, extra_off, n, hxy.data(), att.data(), mode)) return rc;
+  if (int rc = hash_to_g1_direct_run(domain, msgs, msg_off, extras, extra_off, n, hxy.data(), att.data(), mode)) return rc;
   for (size_t i = 0; i < n; i++) hinf[i] = att[i] == 255 ? 1 : 0;
   std::vector<uint8_t> sig(n * 48);
   std::lock_guard<std::mutex> lk(vb_mu);
   for (float& t : g_vb_ms) t = 0.f;
-  const int rc = [&]() -> int {
-    CallScope cs(nullptr);
-    HIP_TRY(cs.create_stream(), 10);
+  const int rc = [&]() -> int {     // the device work: its resources are released before the wall time is taken
+    CallScope cs;
+    HIP_TRY(cs.open(0, nullptr), 10);
     const hipStream_t s = cs.stream();
     EvLog log(s);
     uint64_t *d_xy, *d_sc, *d_out;
     uint8_t *d_inf, *d_oinf, *d_sig, *d_status;
-    HIP_TRY(cs.alloc(&d_xy, n * 96), 10);
-    HIP_TRY(cs.alloc(&d_sc, n_sk * 32), 10);
+    HIP_TRY(cs.in(&d_xy, hxy.data(), n * 96, 0), 10);
+    HIP_TRY(cs.in(&d_sc, sk, n_sk * 32, 0), 10);
+    HIP_TRY(cs.in(&d_inf, hinf.data(), n, 0), 10);
     HIP_TRY(cs.alloc(&d_out, n * 96), 10);
-    HIP_TRY(cs.alloc(&d_inf, n), 10);
     HIP_TRY(cs.alloc(&d_oinf, n), 10);
-    HIP_TRY(cs.alloc(&d_sig, n * 48), 10);
+    HIP_TRY(cs.out(&d_sig, sig.data(), n * 48, 0), 10);
     HIP_TRY(cs.alloc(&d_status, n), 10);
-    HIP_TRY(hipMemcpyAsync(d_xy, hxy.data(), n * 96, hipMemcpyHostToDevice, s), 10);
-    HIP_TRY(hipMemcpyAsync(d_sc, sk, n_sk * 32, hipMemcpyHostToDevice, s), 10);
-    HIP_TRY(hipMemcpyAsync(d_inf, hinf.data(), n, hipMemcpyHostToDevice, s), 10);
     if (int rcr = VbmG1_377::run<true>(d_xy, d_inf, d_sc, n_sk, n, d_out, d_oinf, s, &log)) return rcr;
     if (int rce = wire_encode(0, 1, d_out, d_oinf, n, d_sig, d_status, 1, s)) return rce;
-    HIP_TRY(hipMemcpyAsync(sig.data(), d_sig, n * 48, hipMemcpyDeviceToHost, s), 10);
+    HIP_TRY(cs.copy_back(), 10);
     HIP_TRY(hipStreamSynchronize(s), 10);
     log.sum(g_vb_ms);
     return 0;
   }();
-  g_vb_ms[3] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  g_vb_ms[3] = wall.ms();
   if (rc) return rc;
   for (size_t i = 0; i < n; i++) {
     if (hinf[i]) memset(out_sig48 + i * 48, 0, 48);

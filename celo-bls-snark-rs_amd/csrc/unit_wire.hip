@@ -12,8 +12,8 @@
 #define FROW_OCC __attribute__((amdgpu_waves_per_eu(2, 2)))
 #endif
 namespace celo {
-// decode / normalise calls allocate their buffers per call and run on the caller's stream (or the null stream); calls from
-// several host threads are serialised per process by this lock (they are bulk calls: one fills the GPU)
+// decode / normalise calls stage through the call frame of runtime.h and run on the caller's stream in both forms (the null stream when
+// none is given); calls from several host threads are serialised per process by this lock (they are bulk calls: one fills the GPU)
 static std::mutex wire_mu;
 
 // in: n x 48 (G1) / n x 96 (G2) wire bytes.  out: n x 12 / n x 24 u64, affine (x, y) in arkworks Montgomery limbs (the layout
@@ -66,14 +66,11 @@ int wire_decompress(int g2, const uint8_t* in, size_t n, int check, uint64_t* ou
   const size_t ib = g2 ? 96 : 48, ow = g2 ? 24 : 12;
   CallScope cs((hipStream_t)stream_);
   const hipStream_t stream = cs.stream();
-  uint8_t *d_in = (uint8_t*)in, *d_st = status;
-  uint64_t* d_out = out;
-  if (!dev) {
-    HIP_TRY(cs.alloc(&d_in, n * ib), 10);
-    HIP_TRY(cs.alloc(&d_out, n * ow * 8), 10);
-    HIP_TRY(cs.alloc(&d_st, n), 10);
-    HIP_TRY(hipMemcpyAsync(d_in, in, n * ib, hipMemcpyHostToDevice, stream), 10);
-  }
+  uint8_t *d_in, *d_st;
+  uint64_t* d_out;
+  HIP_TRY(cs.in(&d_in, in, n * ib, dev), 10);
+  HIP_TRY(cs.out(&d_out, out, n * ow * 8, dev), 10);
+  HIP_TRY(cs.out(&d_st, status, n, dev), 10);
   hipEvent_t e0, e1;
   HIP_TRY(cs.event(&e0), 10);
   HIP_TRY(cs.event(&e1), 10);
@@ -82,10 +79,7 @@ int wire_decompress(int g2, const uint8_t* in, size_t n, int check, uint64_t* ou
   else hipLaunchKernelGGL((k_decompress<false>), dim3(((uint32_t)n + 63) / 64), dim3(64), 0, stream, d_in, d_out, d_st, (uint32_t)n, check, k);
   HIP_TRY(hipGetLastError(), 10);
   HIP_TRY(hipEventRecord(e1, stream), 10);
-  if (!dev) {
-    HIP_TRY(hipMemcpyAsync(out, d_out, n * ow * 8, hipMemcpyDeviceToHost, stream), 10);
-    HIP_TRY(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, stream), 10);
-  }
+  HIP_TRY(cs.copy_back(), 10);
   HIP_TRY(hipStreamSynchronize(stream), 10);
   HIP_TRY(hipEventElapsedTime(&g_wire_ms, e0, e1), 10);
   return 0;
@@ -101,10 +95,9 @@ int wire_normalize(int group, const uint64_t* jac, size_t n, uint64_t* out_xy, u
   CallScope cs(nullptr);
   uint64_t *d_in, *d_out;
   uint8_t* d_inf;
-  HIP_TRY(cs.alloc(&d_in, n * 3 * cw * 8), 10);
-  HIP_TRY(cs.alloc(&d_out, n * 2 * cw * 8), 10);
-  HIP_TRY(cs.alloc(&d_inf, n), 10);
-  HIP_TRY(hipMemcpyAsync(d_in, jac, n * 3 * cw * 8, hipMemcpyHostToDevice, 0), 10);
+  HIP_TRY(cs.in(&d_in, jac, n * 3 * cw * 8, 0), 10);
+  HIP_TRY(cs.out(&d_out, out_xy, n * 2 * cw * 8, 0), 10);
+  HIP_TRY(cs.out(&d_inf, inf, n, 0), 10);
   hipEvent_t e0, e1;
   HIP_TRY(cs.event(&e0), 10);
   HIP_TRY(cs.event(&e1), 10);
@@ -115,8 +108,7 @@ int wire_normalize(int group, const uint64_t* jac, size_t n, uint64_t* out_xy, u
   else hipLaunchKernelGGL((k_normalize<Fq, 8, true, 2, false>), grid8, dim3(64), 0, 0, d_in, d_out, d_inf, (uint32_t)n, 0);
   HIP_TRY(hipGetLastError(), 10);
   HIP_TRY(hipEventRecord(e1, 0), 10);
-  HIP_TRY(hipMemcpyAsync(out_xy, d_out, n * 2 * cw * 8, hipMemcpyDeviceToHost, 0), 10);
-  HIP_TRY(hipMemcpyAsync(inf, d_inf, n, hipMemcpyDeviceToHost, 0), 10);
+  HIP_TRY(cs.copy_back(), 10);
   HIP_TRY(hipStreamSynchronize(0), 10);
   HIP_TRY(hipEventElapsedTime(&g_wire_ms, e0, e1), 10);
   return 0;

@@ -2,7 +2,6 @@
 // ark-groth16 0.1 ProvingKey<BW6_761> that decodes its point sections on the device straight into the buffers the fixed-base table build reads.
 #include "wire761.h"
 #include <hip/hip_runtime.h>
-#include <chrono>
 #include <cstdio>
 #include <mutex>
 #include "runtime.h"
@@ -70,17 +69,14 @@ int wire761_decode(int g2, int compressed, const uint8_t* in, size_t n, int chec
   if (n == 0) return 0;
   if (!in || !out || !status || n > 0x7fffffffu) return 2;
   const size_t ib = compressed ? 96 : 192;
-  CallScope cs(dev ? (hipStream_t)stream_ : nullptr);
-  if (!dev) HIP_TRY(cs.create_stream(), 10);
+  CallScope cs;
+  HIP_TRY(cs.open(dev, stream_), 10);
   const hipStream_t stream = cs.stream();
-  uint8_t *d_in = (uint8_t*)in, *d_st = status;
-  uint64_t* d_out = out;
-  if (!dev) {
-    HIP_TRY(cs.alloc(&d_in, n * ib), 10);
-    HIP_TRY(cs.alloc(&d_out, n * 24 * 8), 10);
-    HIP_TRY(cs.alloc(&d_st, n), 10);
-    HIP_TRY(hipMemcpyAsync(d_in, in, n * ib, hipMemcpyHostToDevice, stream), 10);
-  }
+  uint8_t *d_in, *d_st;
+  uint64_t* d_out;
+  HIP_TRY(cs.in(&d_in, in, n * ib, dev), 10);
+  HIP_TRY(cs.out(&d_out, out, n * 24 * 8, dev), 10);
+  HIP_TRY(cs.out(&d_st, status, n, dev), 10);
   hipEvent_t e0, e1;
   HIP_TRY(cs.event(&e0), 10);
   HIP_TRY(cs.event(&e1), 10);
@@ -88,10 +84,7 @@ int wire761_decode(int g2, int compressed, const uint8_t* in, size_t n, int chec
   launch_decode761(g2, compressed, d_in, n, check, d_out, d_st, stream);
   HIP_TRY(hipGetLastError(), 10);
   HIP_TRY(hipEventRecord(e1, stream), 10);
-  if (!dev) {
-    HIP_TRY(hipMemcpyAsync(out, d_out, n * 24 * 8, hipMemcpyDeviceToHost, stream), 10);
-    HIP_TRY(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, stream), 10);
-  }
+  HIP_TRY(cs.copy_back(), 10);
   HIP_TRY(hipStreamSynchronize(stream), 10);
   HIP_TRY(hipEventElapsedTime(&g_w761_ms[0], e0, e1), 10);
   return 0;
@@ -166,12 +159,12 @@ int wire761_key_load(const uint8_t* bytes, size_t len, int form, int window_bits
     if (st == WIRE_INFINITY) Fw761::one().to_ark(host_rows[q] + 12);
     else if (st != WIRE_OK) return 10;                                // not reached: the same function accepted these bytes on the device
   }
-  const auto t0 = std::chrono::steady_clock::now();
+  const WallMs wall;
   // (frees the key itself when it fails, and sets *out_key only on success: the call's last step)
   const int rc = groth16_key_load_dev(0, d_xy + base[4] * 24, d_st + base[4], L[W761_A], d_xy + base[6] * 24, d_st + base[6], L[W761_BG2],
                                       d_xy + base[7] * 24, d_st + base[7], L[W761_H], d_xy + base[8] * 24, d_st + base[8], L[W761_L],
                                       host_rows[0], host_rows[1], host_rows[2], host_rows[3], window_bits, out_key);
-  g_w761_ms[3] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  g_w761_ms[3] = wall.ms();
   return rc;
 }
 void wire761_last_timings(float ms[4]) { for (int i = 0; i < 4; i++) ms[i] = g_w761_ms[i]; }

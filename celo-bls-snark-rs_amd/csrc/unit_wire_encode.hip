@@ -66,21 +66,15 @@ int wire_encode(int group, int compressed, const uint64_t* rows, const uint8_t* 
   if (int rc0 = api_enter()) return rc0;
   std::lock_guard<std::mutex> lk(wenc_mu);
   const size_t rw = group == 0 ? 12 : 24, ob = (group == 0 ? 48 : 96) * (compressed ? 1 : 2);
-  CallScope cs(dev ? (hipStream_t)stream_ : nullptr);
-  if (!dev) HIP_TRY(cs.create_stream(), 10);
+  CallScope cs;
+  HIP_TRY(cs.open(dev, stream_), 10);
   const hipStream_t stream = cs.stream();
-  uint64_t *d_in = (uint64_t*)rows, *d_out = (uint64_t*)out;
-  uint8_t *d_inf = (uint8_t*)inf, *d_st = status;
-  if (!dev) {
-    HIP_TRY(cs.alloc(&d_in, n * rw * 8), 10);
-    HIP_TRY(cs.alloc(&d_out, n * ob), 10);
-    HIP_TRY(cs.alloc(&d_st, n), 10);
-    HIP_TRY(hipMemcpyAsync(d_in, rows, n * rw * 8, hipMemcpyHostToDevice, stream), 10);
-    if (inf) {
-      HIP_TRY(cs.alloc(&d_inf, n), 10);
-      HIP_TRY(hipMemcpyAsync(d_inf, inf, n, hipMemcpyHostToDevice, stream), 10);
-    }
-  }
+  uint64_t *d_in, *d_out;
+  uint8_t *d_inf, *d_st;
+  HIP_TRY(cs.in(&d_in, rows, n * rw * 8, dev), 10);
+  HIP_TRY(cs.in(&d_inf, inf, n, dev), 10);
+  HIP_TRY(cs.out(&d_out, out, n * ob, dev), 10);
+  HIP_TRY(cs.out(&d_st, status, n, dev), 10);
   hipEvent_t e0, e1;
   HIP_TRY(cs.event(&e0), 10);
   HIP_TRY(cs.event(&e1), 10);
@@ -88,10 +82,7 @@ int wire_encode(int group, int compressed, const uint64_t* rows, const uint8_t* 
   launch_encode(group, compressed, d_in, d_inf, d_out, d_st, n, 0, stream);
   HIP_TRY(hipGetLastError(), 10);
   HIP_TRY(hipEventRecord(e1, stream), 10);
-  if (!dev) {
-    HIP_TRY(hipMemcpyAsync(out, d_out, n * ob, hipMemcpyDeviceToHost, stream), 10);
-    HIP_TRY(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, stream), 10);
-  }
+  HIP_TRY(cs.copy_back(), 10);
   HIP_TRY(hipStreamSynchronize(stream), 10);
   float ms = 0.f;
   HIP_TRY(hipEventElapsedTime(&ms, e0, e1), 10);

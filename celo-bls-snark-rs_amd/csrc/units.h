@@ -75,6 +75,17 @@ int pairing_timings_377(float ms[4]);
 int pairing_stage_761(uint32_t k, size_t m, PairingStage* st);
 int pairing_run_staged_761(PairingStage* st, const uint32_t* offsets, size_t m, uint8_t* is_one);
 int pairing_timings_761(float ms[4]);
+// the staged entry points of a curve's engine as one type (runtime.h StagedProduct, groth16_verify_unit.h G16Dev)
+struct Pairing377 {
+  static int stage(uint32_t k, size_t m, PairingStage* st) { return pairing_stage_377(k, m, st); }
+  static int run_staged(PairingStage* st, const uint32_t* off, size_t m, uint8_t* is_one) { return pairing_run_staged_377(st, off, m, is_one); }
+  static int timings(float ms[4]) { return pairing_timings_377(ms); }
+};
+struct Pairing761 {
+  static int stage(uint32_t k, size_t m, PairingStage* st) { return pairing_stage_761(k, m, st); }
+  static int run_staged(PairingStage* st, const uint32_t* off, size_t m, uint8_t* is_one) { return pairing_run_staged_761(st, off, m, is_one); }
+  static int timings(float ms[4]) { return pairing_timings_761(ms); }
+};
 void final_exp_w3_377(const uint32_t* prod, uint8_t* is_one, uint64_t* gt, uint32_t m, hipStream_t s);
 void final_exp_w2_377(const uint32_t* prod, uint8_t* is_one, uint64_t* gt, uint32_t m, hipStream_t s);
 
@@ -107,7 +118,8 @@ int wire761_key_serialize(const uint64_t* vk, size_t n_inputs, const uint64_t* r
                           uint64_t* first_bad);
 int wire761_proof_serialize(const uint64_t* a_xyz, const uint64_t* b_xyz, const uint64_t* c_xyz, uint8_t* out);
 
-// ---- hash to G1 (unit_hash.hip; the composite hasher's generator table is seam_hash.hip's)
+// ---- hash to G1 (unit_hash.hip; the composite hasher's generator table is seam_hash.hip's).  mode, for both groups: 0 direct, 1 the CIP22
+// tail (msgs are the inner CRHs), 2 composite, 3 composite CIP22: one CRH per message (pedersen_crh_run), then the tail over the 48-byte inners
 int hash_to_g1_direct_run(const uint8_t* domain, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off, size_t n, uint64_t* out_xy,
                           uint8_t* attempts, int mode);
 int pedersen_crh_run(const uint8_t* msgs, const uint64_t* msg_off, size_t n, uint8_t* out48);

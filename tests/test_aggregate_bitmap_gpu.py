@@ -205,3 +205,30 @@ def test_last_call_record_and_the_lane_rule(gpu):
     gpu.set_aggregate_complement(0)
     _shared(gpu, name, pts, [all_but_one])                          # 99 rows: 32 lanes of 4
     assert gpu.seals_last()["lanes"] == 32
+
+
+@pytest.mark.parametrize("m", [1, 65])
+@pytest.mark.parametrize("name", ac.GROUPS)
+def test_host_and_device_forms_with_and_without_flags(gpu, name, m):
+    """m = 1 and one seal past a 64-lane workgroup over 9 keys without an identity: flags of zero and no flags at all, host and device
+    forms - four times the same rows, flags and counts"""
+    g = ac.group(name)
+    n = 9
+    xy, inf = ac.pack_keys(name, ac.keys(name, n))
+    assert not inf.any()
+    bits = _seeded_bitmaps(m, n, 300 + m)
+    want = gpu.aggregate_by_bitmap(name, xy, inf, [0, n], bits)
+    none = gpu.aggregate_by_bitmap(name, xy, None, [0, n], bits)
+    assert all(np.array_equal(a, b) for a, b in zip(none, want))
+    d_xy = torch.from_numpy(xy.view(np.int64).copy()).cuda()
+    d_inf = torch.from_numpy(inf.copy()).cuda()
+    d_bits = torch.from_numpy(bits.copy()).cuda()
+    for flags in (d_inf.data_ptr(), 0):
+        d_out = torch.full((m * g.aw,), SENTINEL, dtype=torch.int64, device="cuda")
+        d_oinf = torch.full((m,), 9, dtype=torch.uint8, device="cuda")
+        d_cnt = torch.full((m,), 9, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        assert gpu.aggregate_by_bitmap_dev(name, d_xy.data_ptr(), flags, [0, n], d_bits.data_ptr(), m, d_out.data_ptr(), d_oinf.data_ptr(), d_cnt.data_ptr()) == 0
+        torch.cuda.synchronize()
+        got = (d_out.cpu().numpy().view(np.uint64).reshape(m, g.aw), d_oinf.cpu().numpy(), d_cnt.cpu().numpy().view(np.uint32))
+        assert all(np.array_equal(a, b) for a, b in zip(got, want))

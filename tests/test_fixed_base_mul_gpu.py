@@ -99,3 +99,41 @@ def test_normalize_bw6_761(gpu, group):
     xy, inf = gpu.normalize(group, jac)
     want, winf = co.pack_761(pts)
     assert np.array_equal(xy, want) and np.array_equal(inf, winf)
+
+
+def _dev_mul(gpu, group, gen, limbs):
+    n, aw = limbs.shape[0], gs.GROUPS[group][4]
+    d_sc = torch.from_numpy(limbs.view(np.int64).copy()).cuda()
+    d_out = torch.full((n * aw,), 7, dtype=torch.int64, device="cuda")
+    d_inf = torch.full((n,), 9, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    rc = gpu.fixed_base_mul_dev(group, gen, d_sc.data_ptr(), n, d_out.data_ptr(), d_inf.data_ptr())
+    torch.cuda.synchronize()
+    return rc, d_out.cpu().numpy().view(np.uint64).reshape(n, aw), d_inf.cpu().numpy()
+
+
+@pytest.mark.parametrize("group", sorted(gs.GROUPS))
+def test_host_and_device_forms_and_the_device_range_check(gpu, group):
+    """n = 1 and 65: the two forms return the same bytes.  n = 257 (the range check runs 256 lanes per block: row 256 sits alone in the
+    second): all r - 1 passes; r in row 256 and all-ones in row 0 are refused with nothing written; the next call is a normal one."""
+    _, curve, g, sw, aw = gs.GROUPS[group]
+    curve, g, E, G, r, sc = _case(group, 65, 91)
+    gen = gs.pack(curve, g, [G])[0][0]
+    limbs = co.ints_to_limbs(sc, sw)
+    for n in (1, 65):
+        want, winf = gpu.fixed_base_mul(group, gen, limbs[:n])
+        rc, out, inf = _dev_mul(gpu, group, gen, limbs[:n])
+        assert rc == 0 and np.array_equal(out, want) and np.array_equal(inf, winf)
+    top = np.repeat(co.ints_to_limbs([r - 1], sw), 257, axis=0)
+    want, winf = gpu.fixed_base_mul(group, gen, top)
+    assert np.array_equal(want[0], gs.pack(curve, g, [E.neg(G)])[0][0]) and not winf.any()
+    rc, out, inf = _dev_mul(gpu, group, gen, top)
+    assert rc == 0 and np.array_equal(out, want) and np.array_equal(inf, winf)
+    last, first = top.copy(), top.copy()
+    last[256] = co.ints_to_limbs([r], sw)[0]
+    first[0] = 0xFFFFFFFFFFFFFFFF
+    for bad in (last, first):
+        rc, out, inf = _dev_mul(gpu, group, gen, bad)
+        assert rc == 2 and (out.view(np.int64) == 7).all() and (inf == 9).all()
+    rc, out, inf = _dev_mul(gpu, group, gen, top)
+    assert rc == 0 and np.array_equal(out, want)

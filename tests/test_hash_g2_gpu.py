@@ -301,3 +301,13 @@ def test_two_threads_one_group_each(gpu, refs):
     for t in threads:
         t.join()
     assert errors == []
+
+
+@pytest.mark.parametrize("compat", [0, 1])
+def test_composite_cip22_is_the_crh_followed_by_the_tail(gpu, compat):
+    """three messages: hash_to_g2_composite(cip22) == composite_crh -> hash_to_g2_cip22_tail, rows and attempts byte for byte"""
+    msgs, extras = [b"", b"a", b"hash step " * 20], [b"x", b"", b"extra data"]
+    for ex in (extras, None):
+        xy, att = gpu.hash_to_g2_composite(SIG, msgs, ex, cip22=True, compat=compat)
+        txy, tatt = gpu.hash_to_g2_direct(SIG, gpu.composite_crh(msgs), ex, cip22_tail=True, compat=compat)
+        assert (att != 255).all() and np.array_equal(att, tatt) and np.array_equal(xy, txy)

@@ -344,3 +344,31 @@ def test_two_threads_share_a_key_and_a_circuit(gpu, curve):
             key.release()
     finally:
         r.release()
+
+
+@pytest.mark.parametrize("curve", CURVES)
+def test_host_and_device_forms_of_rows_and_qap_at_tau(gpu, curve):
+    """the smallest case and a chain of 65 constraints (one row past a 64-lane wave): groth16_r1cs_rows / _qap_at_tau and their _dev forms
+    return the same bytes, every byte of the device buffers written"""
+    for case in (rc.toy(curve), rc.chain(curve, 65)):
+        p, log_n, N = case.p, case.log_n(), 6 if curve == "bw6_761" else 4
+        n = 1 << log_n
+        z = rc.mont(rc.random_assignment(case, 9), p)
+        omega, tau = rc.mont([gs.root_of_unity(curve, log_n)], p)[0], rc.mont([random.Random(10).randrange(2, p)], p)[0]
+        r = load(gpu, case)
+        try:
+            rows = r.rows(z, log_n)
+            a, b, c, zt = r.qap_at_tau(log_n, omega, tau)
+            d_z = torch.from_numpy(np.ascontiguousarray(z, dtype=np.uint64).view(np.int64).copy()).cuda()
+            d_rows = [torch.full((n * N,), 0x5A5A5A5A, dtype=torch.int64, device="cuda") for _ in range(3)]
+            d_qap = [torch.full((case.n_vars * N,), 0x5A5A5A5A, dtype=torch.int64, device="cuda") for _ in range(3)]
+            torch.cuda.synchronize()
+            r.rows_dev(d_z.data_ptr(), log_n, *[t.data_ptr() for t in d_rows])
+            zt_dev = r.qap_at_tau_dev(log_n, omega, tau, *[t.data_ptr() for t in d_qap])
+            torch.cuda.synchronize()
+        finally:
+            r.release()
+        for k in range(3):
+            assert np.array_equal(d_rows[k].cpu().numpy().view(np.uint64).reshape(n, N), rows[k]), (case.name, "rows", k)
+            assert np.array_equal(d_qap[k].cpu().numpy().view(np.uint64).reshape(case.n_vars, N), (a, b, c)[k]), (case.name, "qap", k)
+        assert np.array_equal(zt_dev, zt)

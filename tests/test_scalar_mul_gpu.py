@@ -202,3 +202,49 @@ def test_timings_of_the_last_call(gpu):
     gpu.scalar_mul_batch("bls12_377_g1", b.xy, b.inf, b.sc)
     ms = gpu.scalar_mul_last_ms()
     assert ms["table"] > 0 and ms["ladder"] > 0 and ms["normalize"] > 0 and ms["wall"] >= ms["table"] + ms["ladder"] + ms["normalize"]
+
+
+@pytest.mark.parametrize("n", [1, 65])
+@pytest.mark.parametrize("name,subgroup", ENTRIES, ids=IDS)
+def test_host_and_device_forms_agree_with_and_without_flags(gpu, name, subgroup, n):
+    """rows without an identity among them: the host form with flags of zero and with none, the device form with flags of zero and with a
+    null pointer - four times the same bytes"""
+    g = sc.group(name)
+    b, want = _big(name)
+    keep = [i for i in range(BIG) if not b.inf[i]][:n]
+    s, want = b.take(keep), (want[0][keep], want[1][keep])
+    assert not s.inf.any()
+    _same(gpu.scalar_mul_batch(name, s.xy, s.inf, s.sc, subgroup=subgroup), want)
+    _same(gpu.scalar_mul_batch(name, s.xy, None, s.sc, subgroup=subgroup), want)
+    rc, out, oinf = _dev_call(gpu, name, subgroup, s)
+    assert rc == 0
+    _same((out, oinf), want)
+    d_xy = torch.from_numpy(s.xy.view(np.int64).copy()).cuda()
+    d_sc = torch.from_numpy(s.sc.view(np.int64).copy()).cuda()
+    d_out = torch.full((n * g.aw,), SENTINEL, dtype=torch.int64, device="cuda")
+    d_oinf = torch.full((n,), 9, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    assert gpu.scalar_mul_batch_dev(name, d_xy.data_ptr(), 0, d_sc.data_ptr(), n, n, d_out.data_ptr(), d_oinf.data_ptr(), subgroup=subgroup) == 0
+    torch.cuda.synchronize()
+    _same((d_out.cpu().numpy().view(np.uint64).reshape(n, g.aw), d_oinf.cpu().numpy()), want)
+
+
+@pytest.mark.parametrize("name,subgroup", ENTRIES, ids=IDS)
+def test_device_range_check_over_two_blocks(gpu, name, subgroup):
+    """257 device scalars: the check runs 256 lanes per block, so row 256 sits alone in the second.  All r - 1 passes; r in row 256 and
+    all-ones in row 0 are refused with nothing written; the call after a refusal is a normal one."""
+    g = sc.group(name)
+    b, _ = _big(name)
+    top = np.repeat(co.ints_to_limbs([g.r - 1], g.sw), BIG, axis=0)
+    rc, out, oinf = _dev_call(gpu, name, subgroup, b, sc_rows=top)
+    assert rc == 0
+    _same((out, oinf), gpu.scalar_mul_batch(name, b.xy, b.inf, top, subgroup=subgroup))
+    last, first = top.copy(), top.copy()
+    last[256] = co.ints_to_limbs([g.r], g.sw)[0]
+    first[0] = 0xFFFFFFFFFFFFFFFF
+    for bad in (last, first):
+        rc, out, oinf = _dev_call(gpu, name, subgroup, b, sc_rows=bad)
+        assert rc == 2 and (out == SENTINEL).all() and (oinf == 9).all()
+    rc, out, oinf = _dev_call(gpu, name, subgroup, b)
+    assert rc == 0
+    _same((out, oinf), sc.seeded_expected(name, BIG, SEED))

@@ -153,3 +153,16 @@ def test_sign_then_verify_end_to_end(gpu):
     bxy, st = gpu.decompress("g1", bad.tobytes())
     assert not st.any()
     assert gpu.batch_verify(pk, bxy, exps, offsets, hxy, neg_g2).tolist() == [1, 1, 0, 1, 1]
+
+
+def test_cip22_signatures_are_the_three_steps_of_the_public_entries(gpu):
+    """three messages in CIP22 mode: sign_batch == hash_to_g1_composite(cip22) -> scalar_mul_batch (subgroup entry) -> encode_points, byte for byte"""
+    keys = _keys(3, 41)
+    msgs, extras = _messages(3, 42)
+    sk = co.ints_to_limbs(keys, 4)
+    sig, att = gpu.sign_batch(sk, gpu.SIG_DOMAIN, msgs, extras, 3)
+    hxy, hatt = gpu.hash_to_g1_composite(gpu.SIG_DOMAIN, msgs, extras, cip22=True)
+    assert np.array_equal(att, hatt) and (hatt != 255).all()
+    rows, inf = gpu.scalar_mul_batch("bls12_377_g1", hxy, None, sk, subgroup=True)
+    enc, st = gpu.encode_points("g1", rows, inf, True)
+    assert not st.any() and [sig[i].tobytes() for i in range(3)] == [enc[i].tobytes() for i in range(3)]

@@ -125,3 +125,32 @@ def test_batch_2_18_with_spoiled_rows(gpu, curve):
     torch.cuda.synchronize()
     assert np.array_equal(d_st.cpu().numpy(), want_st)
     assert np.array_equal(d_out.cpu().numpy().view(np.uint64).reshape(n, 24), want_xy)
+
+
+@pytest.mark.parametrize("n", [1, 65])
+@pytest.mark.parametrize("curve", [ecc.E1_761, ecc.E2_761], ids=["g1", "g2"])
+def test_host_and_device_forms_return_the_same_bytes(gpu, curve, n):
+    """n = 1 and one row past a 64-lane workgroup over the reference's points, the last encoding spoiled: decompress_bw6_761_* and its _dev
+    form agree on rows and statuses; a refused device call (no output pointer) writes nothing, and the call after it is a normal one"""
+    import ctypes as C
+    group = "bw6_761_g2" if curve is ecc.E2_761 else "bw6_761_g1"
+    ref = [d for c, d in bs.reference_points() if c is curve]
+    enc = [ref[i % len(ref)] for i in range(n)]
+    enc[-1] = (Q + 7).to_bytes(96, "little")
+    data = b"".join(enc)
+    xy, st = gpu.decompress(group, data, check_subgroup=True)
+    assert st.tolist() == [0] * (n - 1) + [2] and xy[:-1].any(axis=1).all() and not xy[-1].any()
+
+    def dev_call(with_out):
+        d_in = torch.from_numpy(np.frombuffer(data, dtype=np.uint8).copy()).cuda()
+        d_out = torch.full((n * 24,), 0x5A5A5A5A, dtype=torch.int64, device="cuda")
+        d_st = torch.full((n,), 0xEE, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        rc = getattr(gpu.lib(), "decompress_%s_dev" % group)(C.c_void_p(d_in.data_ptr()), C.c_size_t(n), C.c_int(1), C.c_void_p(d_out.data_ptr() if with_out else 0),
+                                                            C.c_void_p(d_st.data_ptr()), C.c_void_p(0))
+        torch.cuda.synchronize()
+        return rc, d_out.cpu().numpy().view(np.uint64).reshape(n, 24), d_st.cpu().numpy()
+    rc, out, dst = dev_call(False)
+    assert rc == 2 and (out == 0x5A5A5A5A).all() and (dst == 0xEE).all()
+    rc, out, dst = dev_call(True)
+    assert rc == 0 and np.array_equal(out, xy) and np.array_equal(dst, st)

@@ -198,3 +198,32 @@ def test_flag_byte_0xc0_is_no_encoding(gpu):
         wxy, wst = co.decompress(group, data, True)
         assert st.tolist() == [2, 2, 0] and wst.tolist() == [2, 2, 0]
         assert np.array_equal(xy, wxy) and not xy[:2].any()
+
+
+@pytest.mark.parametrize("n", [1, 65])
+@pytest.mark.parametrize("group", ["g1", "g2"])
+def test_host_and_device_forms_return_the_same_bytes(gpu, group, n):
+    """n = 1 and one row past a 64-lane workgroup, the last encoding spoiled: decompress_* and decompress_*_dev agree on rows and statuses; a
+    refused device call (no output pointer) writes nothing, and the call after it is a normal one"""
+    import ctypes as C
+    curve, gen, size, words = (ecc.E1_377, ecc.G1_377, 48, 12) if group == "g1" else (ecc.E2_377, ecc.G2_377, 96, 24)
+    enc = [ecc.ser_point(curve, P) for P in seeded_points(curve, gen, min(n, 5), 900 + n)]
+    enc = [enc[i % len(enc)] for i in range(n)]
+    enc[-1] = bytes([enc[-1][0] ^ 1]) + enc[-1][1:]
+    data = b"".join(enc)
+    xy, st = gpu.decompress(group, data)
+    assert st[:-1].tolist() == [0] * (n - 1) and xy[:-1].any(axis=1).all()
+
+    def dev_call(with_out):
+        d_in = torch.from_numpy(np.frombuffer(data, dtype=np.uint8).copy()).cuda()
+        d_out = torch.full((n * words,), 0x5A5A5A5A, dtype=torch.int64, device="cuda")
+        d_st = torch.full((n,), 0xEE, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        rc = getattr(gpu.lib(), "decompress_bls12_377_%s_dev" % group)(C.c_void_p(d_in.data_ptr()), C.c_size_t(n), C.c_int(1),
+                                                                      C.c_void_p(d_out.data_ptr() if with_out else 0), C.c_void_p(d_st.data_ptr()), C.c_void_p(0))
+        torch.cuda.synchronize()
+        return rc, d_out.cpu().numpy().view(np.uint64).reshape(n, words), d_st.cpu().numpy()
+    rc, out, dst = dev_call(False)
+    assert rc == 2 and (out == 0x5A5A5A5A).all() and (dst == 0xEE).all()
+    rc, out, dst = dev_call(True)
+    assert rc == 0 and np.array_equal(out, xy) and np.array_equal(dst, st)
