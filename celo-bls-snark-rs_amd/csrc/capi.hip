@@ -558,6 +558,27 @@ int verify_aggregated_seals_bls12_377(const uint64_t* pk_xy, const uint8_t* pk_i
 int celo_amd_aggregate_set_lanes(int lanes) { return aggregate_set_lanes(lanes); }
 int celo_amd_aggregate_set_complement(int mode) { return aggregate_set_complement(mode); }
 int celo_amd_seals_last(int* path, int* lanes, float ms[8]) { if (!path || !lanes || !ms) return 2; seals_last(path, lanes, ms); return 0; }
+// ---- epoch blocks to bytes, public inputs and verdicts (unit_epoch.hip); celo_epoch_blocks is EpochBlocks field for field
+static_assert(sizeof(celo_epoch_blocks) == sizeof(celo::EpochBlocks), "celo_epoch_blocks and EpochBlocks are one layout");
+int epoch_encoded_size(int kind, uint64_t n_keys, uint64_t max_validators, uint64_t* bytes) { return celo::epoch_encoded_size(kind, n_keys, max_validators, bytes); }
+int epoch_encode_blocks_bls12_377(const celo_epoch_blocks* blocks, size_t nb, int kind, const uint64_t* out_off, uint8_t* out, uint8_t* extras, uint8_t* status) {
+  return epoch_encode_blocks((const EpochBlocks*)blocks, nb, kind, out_off, out, extras, status, 0, nullptr);
+}
+int epoch_encode_blocks_bls12_377_dev(const celo_epoch_blocks* blocks, size_t nb, int kind, const uint64_t* out_off, void* d_out, void* d_extras, void* d_status,
+                                      void* hip_stream) {
+  return epoch_encode_blocks((const EpochBlocks*)blocks, nb, kind, out_off, d_out, d_extras, d_status, 1, hip_stream);
+}
+int epoch_public_inputs_bw6_761(const celo_epoch_blocks* first, const celo_epoch_blocks* last, size_t m, uint64_t* out_inputs, uint8_t* out_status) {
+  return epoch_public_inputs((const EpochBlocks*)first, (const EpochBlocks*)last, m, out_inputs, out_status, 0, nullptr);
+}
+int epoch_public_inputs_bw6_761_dev(const celo_epoch_blocks* first, const celo_epoch_blocks* last, size_t m, void* d_out_inputs, void* d_out_status, void* hip_stream) {
+  return epoch_public_inputs((const EpochBlocks*)first, (const EpochBlocks*)last, m, d_out_inputs, d_out_status, 1, hip_stream);
+}
+int verify_epoch_proofs_bw6_761(const void* vk, const uint8_t* proofs, const celo_epoch_blocks* first, const celo_epoch_blocks* last, size_t m, int mode,
+                                const uint32_t* key, uint8_t* out_ok, uint8_t* out_status) {
+  return verify_epoch_proofs((const VerifyingKey*)vk, proofs, (const EpochBlocks*)first, (const EpochBlocks*)last, m, mode, key, out_ok, out_status);
+}
+int celo_amd_epoch_last(float ms[8]) { if (!ms) return 2; epoch_last(ms); return 0; }
 // ---- R1CS matrices on the device (unit_r1cs.hip)
 #define R1CS_LOAD(NAME, CURVE)                                                                                                                              \
   int NAME(size_t n_constraints, size_t n_vars, size_t n_inputs, const uint64_t* a_row_ptr, const uint32_t* a_col, const uint64_t* a_val, size_t a_nnz,     \

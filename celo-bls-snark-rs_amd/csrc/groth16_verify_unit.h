@@ -174,6 +174,12 @@ __global__ void __launch_bounds__(256) k_g16_fold(const uint8_t* __restrict__ st
   status[i] = (sa >= WIRE_INVALID || sb >= WIRE_INVALID || sc >= WIRE_INVALID) ? 1 : 0;
 }
 
+// a status per proof that the caller brings (the epoch unit's: a block that does not decode) joins the decoder's
+template <class C> __global__ void __launch_bounds__(256) k_g16_merge_status(const uint8_t* __restrict__ pre, uint32_t m, uint8_t* __restrict__ status) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < m && pre[i]) status[i] = 1;
+}
+
 template <class C> struct G16Impl {
   typedef typename C::F F;
   typedef typename C::F2 F2;
@@ -267,7 +273,8 @@ template <class C> struct G16Impl {
   }
 
   // Everything after the proofs' rows, identity flags, statuses and inputs are on the device (stream cs.stream()).
-  static int verify_core(const VerifyingKey* vk, DevProofs& d, size_t m, int mode, const uint32_t* key, uint8_t* out_ok, CallScope& cs, EvLog& log, float* ms, int* path) {
+  static int verify_core(const VerifyingKey* vk, DevProofs& d, size_t m, int mode, const uint32_t* key, uint8_t* out_ok, CallScope& cs, EvLog& log, float* ms, int* path,
+                         uint8_t* out_refused = nullptr /* m host bytes: the statuses the verdicts were masked with */) {
     const hipStream_t s = cs.stream();
     const uint32_t m32 = (uint32_t)m, wblocks = (m32 + 63) / 64;
     uint32_t* d_xyzz;
@@ -344,6 +351,7 @@ template <class C> struct G16Impl {
       }
       if (one) {
         for (size_t i = 0; i < m; i++) out_ok[i] = h_status[i] ? 0 : 1;
+        if (out_refused) memcpy(out_refused, h_status.data(), m);
         *path = 1;
         return 0;
       }
@@ -351,6 +359,7 @@ template <class C> struct G16Impl {
     }
     if (int rc = run_each(vk, d, m, cs, is_one.data(), &ms[4])) return rc;
     for (size_t i = 0; i < m; i++) out_ok[i] = (is_one[i] && !h_status[i]) ? 1 : 0;
+    if (out_refused) memcpy(out_refused, h_status.data(), m);
     return 0;
   }
 };
@@ -378,10 +387,13 @@ template <class C> int G16Api<C>::vk_load_serialized(const uint8_t* bytes, size_
   return G16Impl<C>::vk_build(rows.data(), inf.data(), inf.size() - 4, out);
 }
 
-// proofs != NULL: the serialized entry (m x PROOF_BYTES, a_xy .. c_inf unused); else the limb entry
+// proofs != NULL: the serialized entry (m x PROOF_BYTES, a_xy .. c_inf unused); else the limb entry.  d_inputs != NULL (verify_staged): the
+// inputs are on the device already, complete in stream order for a new stream (the caller has synchronised); d_pre: m device bytes, a proof
+// whose byte is set is treated as one that did not decode; out_refused: m host bytes, the statuses the verdicts were masked with
 template <class C>
-int G16Api<C>::verify(const VerifyingKey* vk, const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf, const uint64_t* c_xy,
-                      const uint8_t* c_inf, const uint8_t* proofs, const uint64_t* inputs, size_t m, int mode, const uint32_t* key, uint8_t* out_ok) {
+static int g16_verify_call(const VerifyingKey* vk, const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf, const uint64_t* c_xy,
+                           const uint8_t* c_inf, const uint8_t* proofs, const uint64_t* inputs, const uint64_t* d_inputs, const uint8_t* d_pre, size_t m, int mode,
+                           const uint32_t* key, uint8_t* out_ok, uint8_t* out_refused) {
   typedef G16Impl<C> I;
   typedef G16Dev<C> D;
   constexpr int W1 = C::G1W, W2 = C::G2W, S1 = C::G1_BYTES, S2 = C::G2_BYTES;
@@ -390,7 +402,7 @@ int G16Api<C>::verify(const VerifyingKey* vk, const uint64_t* a_xy, const uint8_
   if (!vk || !out_ok || (mode != 0 && mode != 1) || m > (size_t(1) << 24)) return 2;
   if (!proofs && (!a_xy || !b_xy || !c_xy)) return 2;
   if (!groth16_vk_is_live(vk, C::ID)) return 2;
-  if (vk->n_in && !inputs) return 2;
+  if (vk->n_in && !inputs && !d_inputs) return 2;
   if (int rc0 = api_enter()) return rc0;
   if (vk->device != api_device()) return 101;
   const WallMs wall;
@@ -407,12 +419,13 @@ int G16Api<C>::verify(const VerifyingKey* vk, const uint64_t* a_xy, const uint8_
     const size_t in_bytes = m * vk->n_in * C::N64 * 8;
     HIP_TRY(cs.alloc(&d_rows, m * (2 * W1 + W2) * 8), 10);
     HIP_TRY(cs.alloc(&d_flags, 4 * m), 10);
-    HIP_TRY(cs.alloc(&d.inputs, in_bytes ? in_bytes : 8), 10);
+    if (d_inputs) d.inputs = const_cast<uint64_t*>(d_inputs);
+    else HIP_TRY(cs.alloc(&d.inputs, in_bytes ? in_bytes : 8), 10);
     d.a = d_rows; d.c = d_rows + m * W1; d.b = d_rows + 2 * m * W1;          // (A and C adjacent: one decoder call serves both)
     d.ainf = d_flags; d.cinf = d_flags + m; d.binf = d_flags + 2 * m; d.status = d_flags + 3 * m;
     hipEvent_t e0 = log.open();
     HIP_TRY(hipMemsetAsync(d_flags, 0, 4 * m, s), 10);
-    if (in_bytes) HIP_TRY(hipMemcpyAsync(d.inputs, inputs, in_bytes, hipMemcpyHostToDevice, s), 10);
+    if (in_bytes && !d_inputs) HIP_TRY(hipMemcpyAsync(d.inputs, inputs, in_bytes, hipMemcpyHostToDevice, s), 10);
     if (proofs) {
       uint64_t *d_bytes, *d_g1b, *d_g2b;
       uint8_t* d_st;
@@ -438,7 +451,11 @@ int G16Api<C>::verify(const VerifyingKey* vk, const uint64_t* a_xy, const uint8_
       if (c_inf) HIP_TRY(hipMemcpyAsync(d.cinf, c_inf, m, hipMemcpyHostToDevice, s), 10);
       log.close(6, e0);
     }
-    const int rcv = I::verify_core(vk, d, m, mode, key, out_ok, cs, log, ms, &path);
+    if (d_pre) {
+      hipLaunchKernelGGL((k_g16_merge_status<C>), dim3(((uint32_t)m + 255) / 256), dim3(256), 0, s, d_pre, (uint32_t)m, d.status);
+      HIP_TRY(hipGetLastError(), 10);
+    }
+    const int rcv = I::verify_core(vk, d, m, mode, key, out_ok, cs, log, ms, &path, out_refused);
     HIP_TRY(hipStreamSynchronize(s), 10);
     log.sum(ms);
     return rcv;
@@ -446,6 +463,17 @@ int G16Api<C>::verify(const VerifyingKey* vk, const uint64_t* a_xy, const uint8_
   ms[5] = wall.ms();
   if (!rc) groth16_verify_note(path, vk->c, ms);
   return rc;
+}
+template <class C>
+int G16Api<C>::verify(const VerifyingKey* vk, const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf, const uint64_t* c_xy,
+                      const uint8_t* c_inf, const uint8_t* proofs, const uint64_t* inputs, size_t m, int mode, const uint32_t* key, uint8_t* out_ok) {
+  return g16_verify_call<C>(vk, a_xy, a_inf, b_xy, b_inf, c_xy, c_inf, proofs, inputs, nullptr, nullptr, m, mode, key, out_ok, nullptr);
+}
+template <class C>
+int G16Api<C>::verify_staged(const VerifyingKey* vk, const uint8_t* proofs, const uint64_t* d_inputs, const uint8_t* d_pre, size_t m, int mode, const uint32_t* key,
+                             uint8_t* out_ok, uint8_t* out_refused) {
+  if (m && (!proofs || !d_inputs)) return 2;
+  return g16_verify_call<C>(vk, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, proofs, nullptr, d_inputs, d_pre, m, mode, key, out_ok, out_refused);
 }
 
 }  // namespace celo

@@ -27,8 +27,9 @@ struct B2sTab {
 };
 
 HD uint32_t b2s_rotr(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }
-// RFC 7693 compression F(h, m, t, last)
-WIRE_FN void b2s_compress(uint32_t h[8], const uint32_t m[16], uint64_t t, bool last) {
+// RFC 7693 compression F(h, m, t, last).  The inlined form is for a kernel that keeps h and m in registers (epoch.h: one message per lane,
+// many blocks); behind the out-of-line b2s_compress both arrays are stack objects of the caller.
+HD void b2s_compress_inline(uint32_t h[8], const uint32_t m[16], uint64_t t, bool last) {
   uint32_t v[16];
   for (int i = 0; i < 8; i++) { v[i] = h[i]; v[i + 8] = B2sTab::IV[i]; }
   v[12] ^= (uint32_t)t;
@@ -53,6 +54,7 @@ WIRE_FN void b2s_compress(uint32_t h[8], const uint32_t m[16], uint64_t t, bool 
 #undef CELO_B2S_G
   for (int i = 0; i < 8; i++) h[i] ^= v[i] ^ v[i + 8];
 }
+WIRE_FN void b2s_compress(uint32_t h[8], const uint32_t m[16], uint64_t t, bool last) { b2s_compress_inline(h, m, t, last); }
 // h = IV ^ parameter block (no key, no salt); node_offset is the 48-bit field
 HD void b2s_init(uint32_t h[8], uint8_t digest_length, uint8_t fanout, uint8_t depth, uint32_t leaf_length, uint64_t node_offset,
                  uint8_t node_depth, uint8_t inner_length, const uint8_t personal[8]) {

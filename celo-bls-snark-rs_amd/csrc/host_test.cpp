@@ -15,6 +15,7 @@
 #include "groth16_verify.h"
 #include "r1cs.h"
 #include "hash_direct.h"
+#include "epoch.h"
 #include "host64.h"
 #include <cstring>
 using namespace celo;
@@ -892,5 +893,49 @@ int64_t ht_r1cs_check_rows(int curve, const uint64_t* a, const uint64_t* b, cons
     if (!ok) return (int64_t)j;
   }
   return -1;
+}
+// ---- epoch.h under bounds tracking: the twins of k_epoch_key_record, k_epoch_pack, k_epoch_blake2s and k_epoch_inputs (the same templates).
+// One block of `kind` from affine rows (24 u64, inf or NULL) to its bytes (out: epoch_encoded_size of them, every word through
+// epoch_pack_word) and, for kind 2, its 7 bytes of extra data.  sum_row / sum_inf: the aggregated key of the last-epoch form, from the caller.
+int64_t ht_epoch_encode(int kind, uint32_t index, uint32_t round, uint32_t max_non_signers, uint32_t max_validators, const uint8_t* epoch_entropy,
+                        const uint8_t* parent_entropy, const uint64_t* rows, const uint8_t* inf, uint32_t n_keys, const uint64_t* sum_row, int sum_inf, uint8_t* out,
+                        uint64_t cap, uint8_t* extra) {
+  if (kind < 0 || kind >= EPOCH_KINDS || !epoch_block_ok(n_keys, max_validators)) return -2;
+  const uint64_t bytes = (epoch_encoded_bits(kind, n_keys, max_validators) + 7) / 8;
+  if (bytes > cap) return -1;
+  std::vector<uint32_t> recs((size_t)(n_keys + 1) * EPOCH_REC_WORDS);
+  for (uint32_t i = 0; i < n_keys; i++) epoch_key_record(rows + (size_t)i * 24, inf && inf[i], recs.data() + (size_t)i * EPOCH_REC_WORDS);
+  uint64_t gen[24];
+  Fq::from_limbs(T377::G2_GEN_X0).to_ark(gen); Fq::from_limbs(T377::G2_GEN_X1).to_ark(gen + 6);
+  Fq::from_limbs(T377::G2_GEN_Y0).to_ark(gen + 12); Fq::from_limbs(T377::G2_GEN_Y1).to_ark(gen + 18);
+  epoch_key_record(gen, false, recs.data() + (size_t)n_keys * EPOCH_REC_WORDS);
+  uint32_t sum[EPOCH_REC_WORDS] = {}, hd[EPOCH_HDR_WORDS];
+  if (kind == 1) epoch_key_record(sum_row, sum_inf != 0, sum);
+  epoch_header(kind, index, max_non_signers, epoch_entropy, parent_entropy, hd);
+  const uint32_t nk = epoch_key_slots(kind, n_keys, max_validators);
+  const uint64_t words = (bytes + 63) / 64 * 16;           // the slot of k_epoch_pack: the padding must come out zero
+  for (uint64_t w = 0; w < words; w++) {
+    const uint32_t v = epoch_pack_word(kind, w, n_keys, nk, hd, recs.data(), recs.data() + (size_t)n_keys * EPOCH_REC_WORDS, sum);
+    for (int b = 0; b < 4; b++) {
+      const uint64_t j = 4 * w + b;
+      if (j < bytes) out[j] = (uint8_t)(v >> (8 * b));
+      else if ((uint8_t)(v >> (8 * b))) return -3;
+    }
+  }
+  if (kind == 2 && extra) epoch_extra(index, round, max_non_signers, extra);
+  return (int64_t)bytes;
+}
+void ht_epoch_key_record(const uint64_t* row, int inf, uint32_t* rec24) { epoch_key_record(row, inf != 0, rec24); }
+void ht_epoch_blake2s(const uint8_t* msg, uint64_t len, uint8_t* out32) {
+  std::vector<uint32_t> slot((len + 63) / 64 * 16 + 16, 0);
+  for (uint64_t j = 0; j < len; j++) slot[j / 4] |= (uint32_t)msg[j] << (8 * (j % 4));
+  uint32_t h[8];
+  epoch_blake2s(slot.data(), len, h);
+  for (int i = 0; i < 32; i++) out32[i] = (uint8_t)(h[i / 4] >> (8 * (i % 4)));
+}
+void ht_epoch_inputs(const uint8_t* h_first32, const uint8_t* h_last32, uint64_t* out12) {
+  uint32_t a[8] = {}, b[8] = {};
+  for (int i = 0; i < 32; i++) { a[i / 4] |= (uint32_t)h_first32[i] << (8 * (i % 4)); b[i / 4] |= (uint32_t)h_last32[i] << (8 * (i % 4)); }
+  epoch_inputs(a, b, out12);
 }
 }

@@ -16,6 +16,10 @@ bool groth16_vk_is_live(const VerifyingKey* vk, int curve) {
   std::lock_guard<std::mutex> lk(g_vk_mu);
   return vk_live().count(vk) != 0 && vk->curve == curve;
 }
+int groth16_vk_inputs(const VerifyingKey* vk, int curve) {
+  std::lock_guard<std::mutex> lk(g_vk_mu);
+  return vk_live().count(vk) != 0 && vk->curve == curve ? (int)vk->n_in : -1;
+}
 int groth16_vk_release(VerifyingKey* vk) {
   if (!vk) return 2;
   {

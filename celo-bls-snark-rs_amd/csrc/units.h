@@ -164,6 +164,20 @@ int verify_aggregated_seals_377(const uint64_t* pk_xy, const uint8_t* pk_inf, co
                                 const uint8_t* domain, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off, int hash_mode,
                                 const uint8_t* sig48, const uint64_t neg_g2_xy[24], size_t m, int mode, const uint32_t* key, uint8_t* out_ok, uint8_t* out_status);
 
+// ---- epoch blocks to bytes, public inputs and verdicts (unit_epoch.hip; epoch.h).  nb blocks: the per-block fields and the offsets are
+// host arrays in both forms; keys (keys_form 0: 96-byte compressed G2 keys, 1: affine rows of 24 u64 with keys_inf or NULL) and the entropies
+// (nb x 16 bytes or NULL) are device pointers with dev = 1.  The layout of celo_epoch_blocks (include/celo_bls_amd.h)
+struct EpochBlocks {
+  const uint16_t* index; const uint8_t* round; const uint32_t* max_non_signers; const uint32_t* max_validators;
+  const uint8_t* epoch_entropy; const uint8_t* parent_entropy; const void* keys; const uint8_t* keys_inf; const uint32_t* key_off; int keys_form;
+};
+int epoch_encoded_size(int kind, uint64_t n_keys, uint64_t max_validators, uint64_t* bytes);
+int epoch_encode_blocks(const EpochBlocks* b, size_t nb, int kind, const uint64_t* out_off, void* out, void* extras, void* status, int dev, void* stream);
+int epoch_public_inputs(const EpochBlocks* first, const EpochBlocks* last, size_t m, void* out_inputs, void* out_status, int dev, void* stream);
+int verify_epoch_proofs(const VerifyingKey* vk, const uint8_t* proofs, const EpochBlocks* first, const EpochBlocks* last, size_t m, int mode, const uint32_t* key,
+                        uint8_t* out_ok, uint8_t* out_status);
+void epoch_last(float ms[8]);
+
 // ---- constraint matrices (unit_r1cs.hip)
 int r1cs_load(int curve, size_t m, size_t n_vars, size_t n_inputs, const uint64_t* const row_ptr[3], const uint32_t* const col[3], const uint64_t* const val[3],
               const uint64_t nnz[3], R1cs** out, uint64_t* first_bad);
@@ -202,11 +216,17 @@ template <class C> struct G16Api {
   static int vk_load_serialized(const uint8_t* bytes, size_t len, VerifyingKey** out);
   static int verify(const VerifyingKey* vk, const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf, const uint64_t* c_xy,
                     const uint8_t* c_inf, const uint8_t* proofs, const uint64_t* inputs, size_t m, int mode, const uint32_t* key, uint8_t* out_ok);
+  // the serialized entry with the inputs (m x n_in x N64 u64, canonical) and one status byte per proof already on the DEVICE (unit_epoch.hip): a
+  // proof whose byte is set is handled as one that does not decode.  out_refused (m host bytes, may be NULL): 1 where the proof took part in
+  // no product - the caller's byte, a point that does not decode or lies outside its subgroup, an input out of range
+  static int verify_staged(const VerifyingKey* vk, const uint8_t* proofs, const uint64_t* d_inputs, const uint8_t* d_pre_status, size_t m, int mode, const uint32_t* key,
+                           uint8_t* out_ok, uint8_t* out_refused);
 };
 extern template struct G16Api<G16Bw6>; extern template struct G16Api<G16Bls>;
 // what the two curves share (unit_groth16_verify.hip): the handles that are alive, the last call's record, the exponent draw
 void groth16_vk_adopt(VerifyingKey* vk);
 bool groth16_vk_is_live(const VerifyingKey* vk, int curve);
+int groth16_vk_inputs(const VerifyingKey* vk, int curve);        // the number of public inputs of a live handle of `curve`, or -1
 int groth16_vk_release(VerifyingKey* vk);
 void groth16_verify_note(int path, int window_bits, const float ms[8]);
 int groth16_draw_exponents_run(const uint32_t key[8], size_t m, uint64_t* out);

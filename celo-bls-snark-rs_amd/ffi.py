@@ -72,6 +72,8 @@ EXPORTS = [
     "celo_amd_scalar_mul_set_window", "celo_amd_scalar_mul_set_chunk_rows", "celo_amd_scalar_mul_last_ms",
     "aggregate_by_bitmap_bls12_377_g1", "aggregate_by_bitmap_bls12_377_g2", "aggregate_by_bitmap_bls12_377_g1_dev", "aggregate_by_bitmap_bls12_377_g2_dev",
     "verify_aggregated_seals_bls12_377", "celo_amd_aggregate_set_lanes", "celo_amd_aggregate_set_complement", "celo_amd_seals_last",
+    "epoch_encoded_size", "epoch_encode_blocks_bls12_377", "epoch_encode_blocks_bls12_377_dev", "epoch_public_inputs_bw6_761", "epoch_public_inputs_bw6_761_dev",
+    "verify_epoch_proofs_bw6_761", "celo_amd_epoch_last",
 ]
 
 _lib = None
@@ -1420,6 +1422,126 @@ def verify_aggregated_seals(pk_xy, pk_inf, offsets, bits, min_signers, domain, m
     if rc != 0:
         raise RuntimeError("verify_aggregated_seals_bls12_377 failed with code %d" % rc)
     return ok, st
+
+
+# ---- epoch blocks to bytes, public inputs and verdicts (include/celo_bls_amd.h: epoch_*; csrc/epoch.h)
+EPOCH_KINDS = {"first": 0, "last": 1, "inner": 2, "legacy": 3}
+EPOCH_MAX_KEYS = 1 << 16
+
+
+class EpochBlocksC(C.Structure):
+    """celo_epoch_blocks"""
+    _fields_ = [("index", C.c_void_p), ("round", C.c_void_p), ("max_non_signers", C.c_void_p), ("max_validators", C.c_void_p), ("epoch_entropy", C.c_void_p),
+                ("parent_entropy", C.c_void_p), ("keys", C.c_void_p), ("keys_inf", C.c_void_p), ("key_off", C.c_void_p), ("keys_form", C.c_int)]
+
+
+class EpochBlocks:
+    """nb epoch blocks in the layout of celo_epoch_blocks.  index / round / max_non_signers / max_validators: (nb,) integers; epoch_entropy /
+    parent_entropy: (nb, 16) uint8 or None (every entropy absent); key_off: (nb + 1,) uint32; keys: (key_off[nb], 96) uint8 compressed G2 keys
+    (keys_form 0) or (key_off[nb], 24) uint64 affine rows with keys_inf (key_off[nb],) uint8 or None (keys_form 1).  Keeps the arrays alive."""
+    def __init__(self, index, round_, max_non_signers, max_validators, epoch_entropy, parent_entropy, keys, key_off, keys_form=0, keys_inf=None):
+        self.index = np.ascontiguousarray(index, dtype=np.uint16).reshape(-1)
+        self.nb = self.index.shape[0]
+        self.round = np.ascontiguousarray(round_, dtype=np.uint8).reshape(-1)
+        self.mns = np.ascontiguousarray(max_non_signers, dtype=np.uint32).reshape(-1)
+        self.maxv = np.ascontiguousarray(max_validators, dtype=np.uint32).reshape(-1)
+        self.ee = None if epoch_entropy is None else np.ascontiguousarray(epoch_entropy, dtype=np.uint8).reshape(self.nb, 16)
+        self.pe = None if parent_entropy is None else np.ascontiguousarray(parent_entropy, dtype=np.uint8).reshape(self.nb, 16)
+        self.key_off = np.ascontiguousarray(key_off, dtype=np.uint32).reshape(-1)
+        self.keys_form = int(keys_form)
+        n = int(self.key_off[-1]) if self.key_off.size else 0
+        if self.keys_form == 0:
+            self.keys = np.ascontiguousarray(keys, dtype=np.uint8).reshape(-1, 96)
+        else:
+            self.keys = _rows(keys, 24)
+        self.inf = None if keys_inf is None else np.ascontiguousarray(keys_inf, dtype=np.uint8).reshape(-1)
+        if not (self.round.shape[0] == self.mns.shape[0] == self.maxv.shape[0] == self.nb and self.key_off.shape[0] == self.nb + 1 and self.keys.shape[0] >= n and
+                (self.inf is None or self.inf.shape[0] >= n)):
+            raise ValueError("EpochBlocks: the arrays do not match")
+        if self.keys.shape[0] == 0:
+            self.keys = np.zeros((1, self.keys.shape[1]), dtype=self.keys.dtype)      # (a pointer to pass: no key is read)
+        self.c = EpochBlocksC(*[_p(a).value if a is not None else None for a in (self.index, self.round, self.mns, self.maxv, self.ee, self.pe, self.keys, self.inf,
+                                                                                  self.key_off)], self.keys_form)
+
+    def n_keys(self):
+        return (self.key_off[1:].astype(np.int64) - self.key_off[:-1].astype(np.int64))
+
+
+def epoch_encoded_size(kind, n_keys, max_validators):
+    """bytes of one block of `kind` (0 .. 3 or a name of EPOCH_KINDS).  Raises ValueError on code 2."""
+    out = C.c_uint64(0)
+    rc = lib().epoch_encoded_size(C.c_int(EPOCH_KINDS.get(kind, kind)), C.c_uint64(n_keys), C.c_uint64(max_validators), C.byref(out))
+    if rc != 0:
+        raise ValueError("epoch_encoded_size: bad arguments (code %d)" % rc)
+    return out.value
+
+
+def _epoch_rc(name, rc):
+    if rc == 2:
+        raise ValueError("%s: bad arguments (code 2)" % name)
+    if rc != 0:
+        raise RuntimeError("%s failed with code %d" % (name, rc))
+
+
+def epoch_encode_blocks(blocks, kind):
+    """Every block of an EpochBlocks in the form `kind` -> (list of bytes, extras (nb, 7) uint8 or None, status (nb,) uint8, (msgs, msg_off) as the
+    hash entry points take them).  A block whose status is 1 comes out as zero bytes."""
+    kind = EPOCH_KINDS.get(kind, kind)
+    nb = blocks.nb
+    if kind not in (0, 1, 2, 3):
+        raise ValueError("epoch_encode_blocks: kind is 0 .. 3")
+    sizes = [epoch_encoded_size(kind, int(n), int(v)) for n, v in zip(blocks.n_keys(), blocks.maxv)]
+    off = np.zeros(nb + 1, dtype=np.uint64)
+    off[1:] = np.cumsum(sizes, dtype=np.uint64) if nb else []
+    out = np.zeros(max(1, int(off[-1])), dtype=np.uint8)
+    extras = np.zeros((nb, 7), dtype=np.uint8) if kind == 2 else None
+    status = np.zeros(nb, dtype=np.uint8)
+    _epoch_rc("epoch_encode_blocks_bls12_377", lib().epoch_encode_blocks_bls12_377(C.byref(blocks.c), C.c_size_t(nb), C.c_int(kind), _p(off), _p(out), _p(extras), _p(status)))
+    return [out[int(off[i]):int(off[i + 1])].tobytes() for i in range(nb)], extras, status, (out, off)
+
+
+def epoch_encode_blocks_dev(blocks_c, nb, kind, out_off, d_out, d_extras, d_status, stream=0):
+    """The same with device keys / entropies (an EpochBlocksC whose keys, keys_inf and entropies are device addresses) and device outputs; returns the code."""
+    off = np.ascontiguousarray(out_off, dtype=np.uint64)
+    return lib().epoch_encode_blocks_bls12_377_dev(C.byref(blocks_c), C.c_size_t(nb), C.c_int(kind), _p(off), C.c_void_p(d_out), C.c_void_p(d_extras or None),
+                                                   C.c_void_p(d_status), C.c_void_p(stream))
+
+
+def epoch_public_inputs(first, last):
+    """m (first, last) block pairs -> (inputs (m, 2, 6) uint64 canonical, status (m,) uint8: 0, 1 bad first block, 2 bad last block)"""
+    m = first.nb
+    if last.nb != m:
+        raise ValueError("epoch_public_inputs: as many last blocks as first blocks")
+    out = np.zeros((m, 2, 6), dtype=np.uint64)
+    st = np.zeros(m, dtype=np.uint8)
+    _epoch_rc("epoch_public_inputs_bw6_761", lib().epoch_public_inputs_bw6_761(C.byref(first.c), C.byref(last.c), C.c_size_t(m), _p(out), _p(st)))
+    return out, st
+
+
+def epoch_public_inputs_dev(first_c, last_c, m, d_out_inputs, d_out_status, stream=0):
+    return lib().epoch_public_inputs_bw6_761_dev(C.byref(first_c), C.byref(last_c), C.c_size_t(m), C.c_void_p(d_out_inputs), C.c_void_p(d_out_status), C.c_void_p(stream))
+
+
+def verify_epoch_proofs(vk, proofs, first, last, mode=0, key=None):
+    """m serialized proofs (m x 288 bytes) of the epoch circuit under a VerifyingKey (BW6-761, two inputs) with their first and last blocks ->
+    (ok (m,) uint8, status (m,) uint8: 0 accepted, 1 / 2 bad first / last block, 3 bad proof point, 4 product not one)"""
+    m = first.nb
+    buf = np.frombuffer(bytes(proofs) or b"\0", dtype=np.uint8)
+    if last.nb != m or len(bytes(proofs)) != 288 * m:
+        raise ValueError("verify_epoch_proofs: m first blocks, m last blocks, m x 288 proof bytes")
+    k = None if key is None else np.ascontiguousarray(key, dtype=np.uint32).reshape(8)
+    ok = np.zeros(m, dtype=np.uint8)
+    st = np.zeros(m, dtype=np.uint8)
+    _epoch_rc("verify_epoch_proofs_bw6_761", lib().verify_epoch_proofs_bw6_761(vk.h, _p(buf), C.byref(first.c), C.byref(last.c), C.c_size_t(m), C.c_int(mode), _p(k), _p(ok),
+                                                                                _p(st)))
+    return ok, st
+
+
+def epoch_last():
+    """the last epoch_* / verify_epoch_proofs call's times in ms (celo_amd_epoch_last)"""
+    ms = (C.c_float * 8)()
+    assert lib().celo_amd_epoch_last(ms) == 0
+    return dict(zip(("decode", "sums", "pack", "hash", "transfers", "verify", "wall"), list(ms)[:7]))
 
 
 class SetupError(RuntimeError):

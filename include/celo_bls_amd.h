@@ -809,6 +809,66 @@ int celo_amd_aggregate_set_lanes(int lanes);
 int celo_amd_aggregate_set_complement(int mode);
 int celo_amd_seals_last(int* path, int* lanes, float ms[8]);
 
+/* ---- Epoch blocks to bytes, to the Groth16 public inputs of the epoch proof and to verdicts: what epoch_snark::verify
+ * (crates/epoch-snark/src/api/verifier.rs:23-40) does per proof on the host, for many proofs on the device.  A light client holds a first and a
+ * last EpochBlock per proof (EpochBlockFFI: index, entropies, maximum_non_signers, maximum_validators, compressed keys), not Fr elements; the
+ * steps from one to the other - decode and subgroup-check every key, sum the last block's keys, bit-encode both blocks (epoch_block.rs:117-140,
+ * 174-181, encoding.rs:23-47), Blake2s under "ULforout", pack the 512 bits as 376 | 136 - run here as kernels.  csrc/epoch.h,
+ * csrc/unit_epoch.hip, DESIGN.md section 6k.
+ *
+ * celo_epoch_blocks: nb blocks.  index, round, max_non_signers, max_validators and key_off (nb + 1 offsets into keys: block i owns keys
+ * [key_off[i], key_off[i+1])) are HOST arrays in every form - they size the call.  round is read by kind 2 only and may be NULL otherwise.
+ * epoch_entropy / parent_entropy: nb x 16 bytes, or NULL.  A NULL array, an absent entropy and sixteen zero bytes encode to the same 128 zero
+ * bits (encode_entropy_cip22), so there is no per-block flag.  keys_form 0: keys = 96-byte compressed G2 keys as in EpochBlockFFI.pubkeys,
+ * decoded and subgroup-checked on the device; keys_form 1: affine rows of 24 u64 (arkworks Montgomery limbs) with keys_inf flags or NULL,
+ * TRUSTED as the MSM entries trust theirs (neither the curve nor the subgroup is looked at).  An identity key is accepted: it encodes as
+ * arkworks' zero() = (0, 1) and adds nothing to the sum, as Seam A `verify` treats it.  In the _dev forms keys, keys_inf and the entropies
+ * are DEVICE pointers, like the outputs.
+ *
+ * epoch_encoded_size (host code): kind 0 first-epoch form, 176 + 755 K bits; 1 last-epoch form with the aggregated key appended,
+ * 176 + 755 (K + 1); 2 inner CIP22 (the message validators sign), 256 + 755 K with 7 bytes of extra data; 3 pre-CIP22 encode_to_bytes,
+ * 48 + 755 n_keys.  K = max(n_keys, max_validators); bytes = ceil(bits / 8).
+ * epoch_encode_blocks_bls12_377: block i's bytes at out + out_off[i]; out_off (nb + 1, a host array, out_off[0] = 0) must be the running sum
+ * of epoch_encoded_size.  Kind 2 also writes extras (nb x 7 bytes): out / out_off / extras are the msgs / msg_off / extras of hash_to_g1_* and
+ * verify_aggregated_seals_bls12_377 (extra_off[i] = 7 i).  status[i]: 0 clean; 1 a key does not decode or lies outside G2 - that block's
+ * bytes are zero.
+ * epoch_public_inputs_bw6_761: out_inputs = m x 2 x 6 u64, canonical (what groth16_verify_batch_bw6_761 takes); out_status[i] 0, 1 a bad first
+ * block, 2 a bad last block (the inputs of such a proof are not meaningful).
+ * verify_epoch_proofs_bw6_761: the inputs above, then groth16_verify_batch_bw6_761_serialized on proofs (m x 288 bytes, A | B | C) under vk - the
+ * inputs and block statuses are read by the verifier where they lie.  out_status[i] (may be NULL), the first that applies; out_ok[i] = 1 iff 0:
+ *   0 accepted    1 / 2 as above    3 a proof point does not decode or is outside its subgroup    4 the product is not one
+ * A proof with status 1 - 3 takes part in no product and no combination, like a malformed serialized proof of the batch verifier.  mode, key,
+ * limits and the precondition handling are groth16_verify_batch_bw6_761_serialized's; celo_amd_groth16_verify_last describes the verifier's part.
+ *
+ * Returns 0 (also for nb / m = 0); 2 with NOTHING written and before any use of the device: a NULL required pointer, decreasing offsets, out_off
+ * not the sizes' running sum, nb or m above 2^24, kind or keys_form out of range, mode not in {0, 1}, a block with n_keys or max_validators above
+ * 65 536 (a limit the reference does not have: no single maximum_validators sizes a buffer here), more than 2^31 - 1 keys, vk not a live BW6-761
+ * handle with exactly two inputs; 100: no device; 1 / 10: HIP errors.
+ * celo_amd_epoch_last: the last call's times in ms: [0] key decoding, [1] key sums + normalisation, [2] records + pack, [3] Blake2s + input
+ * packing, [4] transfers, [5] the verifier (wall), [6] the whole call (wall), [7] unused. */
+typedef struct celo_epoch_blocks {
+  const uint16_t* index;           /* nb */
+  const uint8_t* round;            /* nb, or NULL unless kind 2 */
+  const uint32_t* max_non_signers; /* nb */
+  const uint32_t* max_validators;  /* nb */
+  const uint8_t* epoch_entropy;    /* nb x 16, or NULL */
+  const uint8_t* parent_entropy;   /* nb x 16, or NULL */
+  const void* keys;                /* key_off[nb] x 96 bytes (keys_form 0) or x 24 u64 (keys_form 1) */
+  const uint8_t* keys_inf;         /* keys_form 1: key_off[nb] flags, or NULL */
+  const uint32_t* key_off;         /* nb + 1 */
+  int keys_form;
+} celo_epoch_blocks;
+int epoch_encoded_size(int kind, uint64_t n_keys, uint64_t max_validators, uint64_t* bytes);
+int epoch_encode_blocks_bls12_377(const celo_epoch_blocks* blocks, size_t nb, int kind, const uint64_t* out_off /* nb + 1 */, uint8_t* out, uint8_t* extras /* nb x 7, kind 2 */,
+                                  uint8_t* status /* nb */);
+int epoch_encode_blocks_bls12_377_dev(const celo_epoch_blocks* blocks, size_t nb, int kind, const uint64_t* out_off, void* d_out, void* d_extras, void* d_status,
+                                      void* hip_stream);
+int epoch_public_inputs_bw6_761(const celo_epoch_blocks* first, const celo_epoch_blocks* last, size_t m, uint64_t* out_inputs /* m x 12 */, uint8_t* out_status /* m */);
+int epoch_public_inputs_bw6_761_dev(const celo_epoch_blocks* first, const celo_epoch_blocks* last, size_t m, void* d_out_inputs, void* d_out_status, void* hip_stream);
+int verify_epoch_proofs_bw6_761(const void* vk, const uint8_t* proofs /* m x 288 */, const celo_epoch_blocks* first, const celo_epoch_blocks* last, size_t m,
+                                int mode /* 0 each, 1 combined */, const uint32_t* key /* 8, or NULL */, uint8_t* out_ok /* m */, uint8_t* out_status /* m, may be NULL */);
+int celo_amd_epoch_last(float ms[8]);
+
 /* ---- R1CS matrices on the device: the step of ark-groth16 0.1 between cs.to_matrices() and the entry points above - the constraint evaluation
  * of R1CStoQAP::witness_map (prover) and R1CStoQAP::instance_map_with_evaluation (setup).  Synthesis (running the gadgets) stays with the caller;
  * its result is data: three sparse matrices of n_constraints rows and the full assignment.
