@@ -369,11 +369,29 @@ int decode_uncompressed_bw6_761_g1(const uint8_t* in, size_t n, int check, uint6
 int decode_uncompressed_bw6_761_g2(const uint8_t* in, size_t n, int check, uint64_t* out_xy, uint8_t* status) {
   return wire761_decode(1, 0, in, n, check, out_xy, status, 0, nullptr);
 }
-int groth16_key_layout_bw6_761(const uint8_t* bytes, size_t len, int form, uint64_t out[16]) { return wire761_key_layout(bytes, len, form, out); }
+int decode_uncompressed_bls12_377_g1(const uint8_t* in, size_t n, int check, uint64_t* out_xy, uint8_t* status) {
+  return wire377_decode(0, 0, in, n, check, out_xy, status, 0, nullptr);
+}
+int decode_uncompressed_bls12_377_g2(const uint8_t* in, size_t n, int check, uint64_t* out_xy, uint8_t* status) {
+  return wire377_decode(1, 0, in, n, check, out_xy, status, 0, nullptr);
+}
+int decode_uncompressed_bls12_377_g1_dev(const uint8_t* d_in, size_t n, int check, uint64_t* d_out_xy, uint8_t* d_status, void* hip_stream) {
+  return wire377_decode(0, 0, d_in, n, check, d_out_xy, d_status, 1, hip_stream);
+}
+int decode_uncompressed_bls12_377_g2_dev(const uint8_t* d_in, size_t n, int check, uint64_t* d_out_xy, uint8_t* d_status, void* hip_stream) {
+  return wire377_decode(1, 0, d_in, n, check, d_out_xy, d_status, 1, hip_stream);
+}
+int groth16_key_layout_bw6_761(const uint8_t* bytes, size_t len, int form, uint64_t out[16]) { return wire_key_layout(0, bytes, len, form, out); }
+int groth16_key_layout_bls12_377(const uint8_t* bytes, size_t len, int form, uint64_t out[16]) { return wire_key_layout(1, bytes, len, form, out); }
 int groth16_load_key_bw6_761_serialized(const uint8_t* bytes, size_t len, int form, int window_bits, void** out_key, uint64_t* first_bad_point) {
   if (!out_key) return 2;
   *out_key = nullptr;
-  return wire761_key_load(bytes, len, form, window_bits, (ProvingKey**)out_key, first_bad_point);
+  return wire_key_load(0, bytes, len, form, window_bits, (ProvingKey**)out_key, first_bad_point);
+}
+int groth16_load_key_bls12_377_serialized(const uint8_t* bytes, size_t len, int form, int window_bits, void** out_key, uint64_t* first_bad_point) {
+  if (!out_key) return 2;
+  *out_key = nullptr;
+  return wire_key_load(1, bytes, len, form, window_bits, (ProvingKey**)out_key, first_bad_point);
 }
 // ---- Groth16 verification of many proofs under one key (unit_groth16_verify.hip, unit_groth16_verify377.hip)
 int groth16_vk_load_bw6_761(const uint64_t alpha_g1[24], const uint64_t beta_g2[24], const uint64_t gamma_g2[24], const uint64_t delta_g2[24], const uint64_t* gamma_abc_g1,
@@ -434,11 +452,18 @@ int encode_uncompressed_bw6_761_dev(const uint64_t* d_rows, const uint8_t* d_inf
   return wire_encode(2, 0, d_rows, d_inf, n, d_out, d_status, 1, hip_stream);
 }
 int groth16_serialized_key_size_bw6_761(size_t n_inputs, size_t n_vars, size_t n_h, int form, int vk_only, uint64_t* len) {
-  return wire761_key_size(n_inputs, n_vars, n_h, form, vk_only, len);
+  return wire_key_size(0, n_inputs, n_vars, n_h, form, vk_only, len);
+}
+int groth16_serialized_key_size_bls12_377(size_t n_inputs, size_t n_vars, size_t n_h, int form, int vk_only, uint64_t* len) {
+  return wire_key_size(1, n_inputs, n_vars, n_h, form, vk_only, len);
 }
 int groth16_serialize_key_bw6_761(const uint64_t* vk, size_t n_inputs, const uint64_t* rows, size_t n_vars, size_t n_h, int form, uint8_t* out, size_t cap, uint64_t* out_len,
                                   uint64_t* first_bad_point) {
-  return wire761_key_serialize(vk, n_inputs, rows, n_vars, n_h, form, out, cap, out_len, first_bad_point);
+  return wire_key_serialize(0, vk, n_inputs, rows, n_vars, n_h, form, out, cap, out_len, first_bad_point);
+}
+int groth16_serialize_key_bls12_377(const uint64_t* vk, size_t n_inputs, const uint64_t* rows, size_t n_vars, size_t n_h, int form, uint8_t* out, size_t cap, uint64_t* out_len,
+                                    uint64_t* first_bad_point) {
+  return wire_key_serialize(1, vk, n_inputs, rows, n_vars, n_h, form, out, cap, out_len, first_bad_point);
 }
 int groth16_serialize_proof_bw6_761(const uint64_t a_xyz[36], const uint64_t b_xyz[36], const uint64_t c_xyz[36], uint8_t out[288]) {
   return wire761_proof_serialize(a_xyz, b_xyz, c_xyz, out);

@@ -342,6 +342,14 @@ void ht_wire_decode(int g2, const uint8_t* in, size_t n, int check, uint64_t* ou
     }
   }
 }
+// the uncompressed forms of wire.h under bounds tracking: n x 96 B (G1) / n x 192 B (G2) -> 12 / 24 u64 rows + status (k_decode377u runs the same templates)
+void ht_wire377_decode_uncompressed(int g2, int check, const uint8_t* in, size_t n, uint64_t* out, uint8_t* status) {
+  const WireConsts& k = wire_consts();
+  for (size_t i = 0; i < n; i++) {
+    if (g2) status[i] = wire_decode_row_g2<false>(in + i * 192, k, check != 0, out + i * 24);
+    else status[i] = wire_decode_row_g1<false>(in + i * 96, k, check != 0, out + i * 12);
+  }
+}
 // wire761.h under bounds tracking: n BW6-761 points (compressed 96 B / uncompressed 192 B) -> 24 u64 rows + status (k_decode761 runs the same template)
 void ht_wire761_decode(int g2, int compressed, int check, const uint8_t* in, size_t n, uint64_t* out, uint8_t* status) {
   const size_t ib = compressed ? 96 : 192;
@@ -382,7 +390,7 @@ int ht_wire761_encode_jacobian(const uint64_t* xyz, uint8_t* out96) {
   memcpy(out96, w, 96);
   return st;
 }
-int ht_wire761_key_size(size_t n_inputs, size_t n_vars, size_t n_h, int form, int vk_only, uint64_t* len) { return w761_key_size(n_inputs, n_vars, n_h, form, vk_only, len); }
+int ht_wire761_key_size(size_t n_inputs, size_t n_vars, size_t n_h, int form, int vk_only, uint64_t* len) { return wkey_size(0, n_inputs, n_vars, n_h, form, vk_only, len); }
 // the two forms of the subgroup test on one affine on-curve point (ark limbs): bit 0 = endomorphism form (what the decoders run),
 // bit 1 = the r * P ladder (the reference's definition)
 int ht_wire_subgroup_both(int g2, const uint64_t* xy) {

@@ -246,7 +246,7 @@ int groth16_key_load(int curve, const uint64_t* a_query, size_t na, const uint64
   return (curve ? key_load<Bls12> : key_load<Bw6>)(0, a_query, nullptr, na, b_g2_query, nullptr, nb, h_query, nullptr, nh, l_query, nullptr, nl, a_query, b_g2_query,
                                                    alpha_g1, beta_g2, window_bits, out);
 }
-// The same key from DEVICE rows (wire761_key_load, unit_wire761.hip; groth16_setup, unit_setup.hip)
+// The same key from DEVICE rows (wire_key_load, unit_wire761.hip; groth16_setup, unit_setup.hip)
 int groth16_key_load_dev(int curve, const uint64_t* d_a, const uint8_t* d_ainf, size_t na, const uint64_t* d_b, const uint8_t* d_binf, size_t nb,
                          const uint64_t* d_h, const uint8_t* d_hinf, size_t nh, const uint64_t* d_l, const uint8_t* d_linf, size_t nl,
                          const uint64_t* a0, const uint64_t* b0, const uint64_t* alpha_g1, const uint64_t* beta_g2, int window_bits, ProvingKey** out) {

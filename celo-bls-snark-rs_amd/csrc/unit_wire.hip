@@ -1,5 +1,5 @@
-// Translation unit: bulk decoding of compressed BLS12-377 points (see wire.h), one point per lane, and the batch normalisation of
-// Jacobian points of both curves (normalize.h).
+// Translation unit: bulk decoding of BLS12-377 points, compressed and uncompressed (see wire.h), one point per lane, and the batch
+// normalisation of Jacobian points of both curves (normalize.h).
 #include "wire.h"
 #include "normalize.h"
 #include <hip/hip_runtime.h>
@@ -40,6 +40,17 @@ template <bool G2> __global__ void __launch_bounds__(64) FROW_OCC k_decompress(c
   }
 }
 
+// The uncompressed forms (wire.h wire_decode_row_*<false>): in n x 96 (G1) / n x 192 (G2) bytes, x then y; out and status as above.  check:
+// the curve equation and the same subgroup test; 0: the canonical range alone.  No square root, so no table and no run-time-indexed array;
+// one kernel per group (a split into parse and subgroup passes, as unit_wire761.hip has it, would buy nothing here: DESIGN.md section 6c''').
+template <bool G2> __global__ void __launch_bounds__(64) FROW_OCC k_decode377u(const uint8_t* __restrict__ in, uint64_t* __restrict__ out,
+                                                                      uint8_t* __restrict__ status, uint32_t n, int check, WireConsts k) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if constexpr (G2) status[i] = wire_decode_row_g2<false>(in + (size_t)i * 192, k, check != 0, out + (size_t)i * 24);
+  else status[i] = wire_decode_row_g1<false>(in + (size_t)i * 96, k, check != 0, out + (size_t)i * 12);
+}
+
 // the constants with the discrete-log tables in device memory: one copy per device, uploaded on first use there
 int wire_consts_device(WireConsts& out) {
   static std::mutex mu;
@@ -56,14 +67,37 @@ int wire_consts_device(WireConsts& out) {
 }
 static float g_wire_ms = 0.f;
 
+// one decode launch on device buffers (the entry points below; the serialized-key loader of unit_wire761.hip, one per section)
+int wire377_launch_decode(int g2, int compressed, const uint8_t* d_in, size_t n, int check, uint64_t* d_out, uint8_t* d_st, hipStream_t stream) {
+  WireConsts k = wire_consts();
+  if (compressed) { if (int rck = wire_consts_device(k)) return rck; }
+  else k.tab = nullptr;                                               // the uncompressed forms take no root
+  const dim3 grid(((uint32_t)n + 63) / 64), block(64);
+  if (compressed) {
+    if (g2) hipLaunchKernelGGL((k_decompress<true>), grid, block, 0, stream, d_in, d_out, d_st, (uint32_t)n, check, k);
+    else hipLaunchKernelGGL((k_decompress<false>), grid, block, 0, stream, d_in, d_out, d_st, (uint32_t)n, check, k);
+  } else {
+    if (g2) hipLaunchKernelGGL((k_decode377u<true>), grid, block, 0, stream, d_in, d_out, d_st, (uint32_t)n, check, k);
+    else hipLaunchKernelGGL((k_decode377u<false>), grid, block, 0, stream, d_in, d_out, d_st, (uint32_t)n, check, k);
+  }
+  return hipGetLastError() == hipSuccess ? 0 : 10;
+}
+
 int wire_decompress(int g2, const uint8_t* in, size_t n, int check, uint64_t* out, uint8_t* status, int dev, void* stream_) {
+  return wire377_decode(g2, 1, in, n, check, out, status, dev, stream_);
+}
+// compressed: 1 = 48 / 96 B points (k_decompress), 0 = 96 / 192 B (k_decode377u)
+int wire377_decode(int g2, int compressed, const uint8_t* in, size_t n, int check, uint64_t* out, uint8_t* status, int dev, void* stream_) {
   if (int rc0 = api_enter()) return rc0;
   std::lock_guard<std::mutex> lk(wire_mu);
   if (n == 0) return 0;
   if (!in || !out || !status || n > 0x7fffffffu) return 2;
-  WireConsts k;
-  if (int rck = wire_consts_device(k)) return rck;
-  const size_t ib = g2 ? 96 : 48, ow = g2 ? 24 : 12;
+  if (!compressed && dev && ((uintptr_t)out & 7)) return 2;           // the rows are stored as 64-bit words
+  if (compressed) {                                                   // first use on this device: the tables' upload stays outside the events
+    WireConsts k;
+    if (int rck = wire_consts_device(k)) return rck;
+  }
+  const size_t ib = (g2 ? 96 : 48) * (compressed ? 1 : 2), ow = g2 ? 24 : 12;
   CallScope cs((hipStream_t)stream_);
   const hipStream_t stream = cs.stream();
   uint8_t *d_in, *d_st;
@@ -75,9 +109,7 @@ int wire_decompress(int g2, const uint8_t* in, size_t n, int check, uint64_t* ou
   HIP_TRY(cs.event(&e0), 10);
   HIP_TRY(cs.event(&e1), 10);
   HIP_TRY(hipEventRecord(e0, stream), 10);
-  if (g2) hipLaunchKernelGGL((k_decompress<true>), dim3(((uint32_t)n + 63) / 64), dim3(64), 0, stream, d_in, d_out, d_st, (uint32_t)n, check, k);
-  else hipLaunchKernelGGL((k_decompress<false>), dim3(((uint32_t)n + 63) / 64), dim3(64), 0, stream, d_in, d_out, d_st, (uint32_t)n, check, k);
-  HIP_TRY(hipGetLastError(), 10);
+  if (int rcl = wire377_launch_decode(g2, compressed, d_in, n, check, d_out, d_st, stream)) return rcl;
   HIP_TRY(hipEventRecord(e1, stream), 10);
   HIP_TRY(cs.copy_back(), 10);
   HIP_TRY(hipStreamSynchronize(stream), 10);

@@ -1,5 +1,6 @@
 // Translation unit: bulk decoding of serialized BW6-761 points (see wire761.h), one point per lane, and the loader of a serialized
-// ark-groth16 0.1 ProvingKey<BW6_761> that decodes its point sections on the device straight into the buffers the fixed-base table build reads.
+// ark-groth16 0.1 ProvingKey<BW6_761> or ProvingKey<Bls12_377> (the latter's points through unit_wire.hip's kernels) that decodes its point
+// sections on the device straight into the buffers the fixed-base table build reads.
 #include "wire761.h"
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -90,51 +91,72 @@ int wire761_decode(int g2, int compressed, const uint8_t* in, size_t n, int chec
   return 0;
 }
 
-int wire761_key_layout(const uint8_t* bytes, size_t len, int form, uint64_t out[16]) { return w761_key_layout(bytes, len, form, out); }
+int wire_key_layout(int curve, const uint8_t* bytes, size_t len, int form, uint64_t out[16]) { return wkey_layout(curve, bytes, len, form, out); }
 
-// ProvingKey::<BW6_761>::deserialize (form 0) / deserialize_uncompressed (1) / deserialize_unchecked (2), then groth16_load_key_bw6_761.
-// The whole byte string crosses to the device once; every point of every section is decoded there (one launch per section, all into one
-// row buffer indexed by the point's position in serialization order), the first rejected index is found by an atomic minimum, and the four
-// queries' rows and statuses are handed to the table build where they lie (a status-1 row - the point at infinity - is that query's identity
-// through the build's `inf` bytes: after the check every status is 0 or 1).  a_query[0], b_g2_query[0], alpha_g1 and beta_g2, which the key
-// keeps on the host, are decoded again on the host from their bytes (unchecked: the device has checked them).
-int wire761_key_load(const uint8_t* bytes, size_t len, int form, int window_bits, ProvingKey** out_key, uint64_t* first_bad) {
+// one point of a key, decoded again on the host (unchecked: the device has checked it) into the row the key keeps there
+static WireStatus key_host_row(int curve, int g2, int compressed, const uint8_t* src, uint64_t* row) {
+  if (curve == 0) {
+    if (g2) return compressed ? w761_decode_row<4, true>(src, false, row) : w761_decode_row<4, false>(src, false, row);
+    return compressed ? w761_decode_row<-1, true>(src, false, row) : w761_decode_row<-1, false>(src, false, row);
+  }
+  const WireConsts& k = wire_consts();
+  if (g2) return compressed ? wire_decode_row_g2<true>(src, k, false, row) : wire_decode_row_g2<false>(src, k, false, row);
+  return compressed ? wire_decode_row_g1<true>(src, k, false, row) : wire_decode_row_g1<false>(src, k, false, row);
+}
+
+// ProvingKey::<E>::deserialize (form 0) / deserialize_uncompressed (1) / deserialize_unchecked (2), then groth16_load_key_<curve>; curve 0 =
+// BW6-761, 1 = BLS12-377.  The whole byte string crosses to the device once; every point of every section is decoded there (one launch per
+// section: k_decode761 + k_subgroup761, or unit_wire.hip's k_decompress / k_decode377u) into a G1 row buffer and a G2 row buffer (24 u64 per
+// row; BLS12-377 G1: 12), each in serialization order, with one status array indexed by the point's position in serialization order.  The first
+// rejected index is found by an atomic minimum, and the four queries' rows and statuses are handed to the table build where they lie (a status-1
+// row - the point at infinity - is that query's identity through the build's `inf` bytes: after the check every status is 0 or 1).
+// a_query[0], b_g2_query[0], alpha_g1 and beta_g2, which the key keeps on the host, are decoded again on the host from their bytes.
+int wire_key_load(int curve, const uint8_t* bytes, size_t len, int form, int window_bits, ProvingKey** out_key, uint64_t* first_bad) {
   if (!out_key) return 2;
   *out_key = nullptr;
   uint64_t L[16];
-  if (int rcl = w761_key_layout(bytes, len, form, L)) return rcl;
+  if (int rcl = wkey_layout(curve, bytes, len, form, L)) return rcl;
   if (L[W761_A] == 0 || L[W761_BG2] == 0) return 2;                 // the proof needs a_query[0] and b_g2_query[0]
   if (L[W761_NPOINTS] > 0x7fffffffu) return 2;
   if (int rc0 = api_enter()) return rc0;
   std::lock_guard<std::mutex> lk(w761_mu);
   const int compressed = form == 0, check = form != 2;
-  const uint64_t P = L[W761_PT], N = L[W761_NPOINTS];
+  const uint64_t P = L[W761_PT], N = L[W761_NPOINTS], w1 = curve ? 12 : 24, w2 = 24;    // u64 per G1 / G2 row
   struct Sec { uint64_t off, n; int g2; };
   const Sec secs[9] = {{0, 1, 0},     {P, 3, 1},           {L[W761_ABC + 1], L[W761_ABC], 0}, {L[W761_BETA_G1], 2, 0}, {L[W761_A + 1], L[W761_A], 0},
                        {L[W761_BG1 + 1], L[W761_BG1], 0}, {L[W761_BG2 + 1], L[W761_BG2], 1}, {L[W761_H + 1], L[W761_H], 0}, {L[W761_L + 1], L[W761_L], 0}};
-  uint64_t base[9];
-  for (uint64_t s = 0, acc = 0; s < 9; s++) { base[s] = acc; acc += secs[s].n; }
+  uint64_t base[9], row[9], n_grp[2] = {0, 0};                       // a section's first point: in serialization order, among its group's rows
+  for (uint64_t s = 0, acc = 0; s < 9; s++) {
+    base[s] = acc;
+    acc += secs[s].n;
+    row[s] = n_grp[secs[s].g2];
+    n_grp[secs[s].g2] += secs[s].n;
+  }
   CallScope cs(nullptr);
   HIP_TRY(cs.create_stream(), 10);
   const hipStream_t stream = cs.stream();
   hipEvent_t ev[3];
   for (auto& e : ev) HIP_TRY(cs.event(&e), 10);
   uint8_t *d_bytes, *d_st;
-  uint64_t* d_xy;
+  uint64_t* d_xy[2];
   unsigned long long* d_first;
   unsigned long long first = ~0ull;
   HIP_TRY(cs.alloc(&d_bytes, len), 10);
-  HIP_TRY(cs.alloc(&d_xy, N * 24 * 8), 10);
+  HIP_TRY(cs.alloc(&d_xy[0], n_grp[0] * w1 * 8), 10);
+  HIP_TRY(cs.alloc(&d_xy[1], n_grp[1] * w2 * 8), 10);
   HIP_TRY(cs.alloc(&d_st, N), 10);
   HIP_TRY(cs.alloc(&d_first, sizeof(unsigned long long)), 10);
+  auto rows_of = [&](int s) { return d_xy[secs[s].g2] + row[s] * (secs[s].g2 ? w2 : w1); };
   HIP_TRY(hipEventRecord(ev[0], stream), 10);
   HIP_TRY(hipMemcpyAsync(d_bytes, bytes, len, hipMemcpyHostToDevice, stream), 10);
   HIP_TRY(hipMemcpyAsync(d_first, &first, sizeof first, hipMemcpyHostToDevice, stream), 10);
   HIP_TRY(hipEventRecord(ev[1], stream), 10);
   for (int s = 0; s < 9; s++) {
     if (!secs[s].n) continue;
-    launch_decode761(secs[s].g2, compressed, d_bytes + secs[s].off, secs[s].n, check, d_xy + base[s] * 24, d_st + base[s], stream);
-    HIP_TRY(hipGetLastError(), 10);
+    if (curve == 0) {
+      launch_decode761(secs[s].g2, compressed, d_bytes + secs[s].off, secs[s].n, check, rows_of(s), d_st + base[s], stream);
+      HIP_TRY(hipGetLastError(), 10);
+    } else if (int rcd = wire377_launch_decode(secs[s].g2, compressed, d_bytes + secs[s].off, secs[s].n, check, rows_of(s), d_st + base[s], stream)) return rcd;
   }
   hipLaunchKernelGGL(k_first_bad761, dim3(((uint32_t)N + 255) / 256), dim3(256), 0, stream, d_st, (uint32_t)N, d_first);
   HIP_TRY(hipGetLastError(), 10);
@@ -152,18 +174,15 @@ int wire761_key_load(const uint8_t* bytes, size_t len, int form, int window_bits
   const uint64_t where[4] = {secs[4].off, secs[6].off, 0, P};      // a_query[0], b_g2_query[0], alpha_g1, beta_g2
   const int grp[4] = {0, 1, 0, 1};
   for (int q = 0; q < 4; q++) {
-    const uint8_t* src = bytes + where[q];
-    WireStatus st;
-    if (grp[q]) st = compressed ? w761_decode_row<4, true>(src, false, host_rows[q]) : w761_decode_row<4, false>(src, false, host_rows[q]);
-    else st = compressed ? w761_decode_row<-1, true>(src, false, host_rows[q]) : w761_decode_row<-1, false>(src, false, host_rows[q]);
-    if (st == WIRE_INFINITY) Fw761::one().to_ark(host_rows[q] + 12);
+    const WireStatus st = key_host_row(curve, grp[q], compressed, bytes + where[q], host_rows[q]);
+    const uint64_t y_at = (grp[q] ? w2 : w1) / 2;                     // y (an Fq2 y: its c0) in the row
+    if (st == WIRE_INFINITY) { if (curve) Fq::one().to_ark(host_rows[q] + y_at); else Fw761::one().to_ark(host_rows[q] + y_at); }
     else if (st != WIRE_OK) return 10;                                // not reached: the same function accepted these bytes on the device
   }
   const WallMs wall;
   // (frees the key itself when it fails, and sets *out_key only on success: the call's last step)
-  const int rc = groth16_key_load_dev(0, d_xy + base[4] * 24, d_st + base[4], L[W761_A], d_xy + base[6] * 24, d_st + base[6], L[W761_BG2],
-                                      d_xy + base[7] * 24, d_st + base[7], L[W761_H], d_xy + base[8] * 24, d_st + base[8], L[W761_L],
-                                      host_rows[0], host_rows[1], host_rows[2], host_rows[3], window_bits, out_key);
+  const int rc = groth16_key_load_dev(curve, rows_of(4), d_st + base[4], L[W761_A], rows_of(6), d_st + base[6], L[W761_BG2], rows_of(7), d_st + base[7], L[W761_H],
+                                      rows_of(8), d_st + base[8], L[W761_L], host_rows[0], host_rows[1], host_rows[2], host_rows[3], window_bits, out_key);
   g_w761_ms[3] = wall.ms();
   return rc;
 }

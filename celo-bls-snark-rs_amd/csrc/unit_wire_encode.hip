@@ -1,6 +1,6 @@
 // Translation unit: bulk ENCODING of points into arkworks' wire form (wire.h WireEnc, wire761.h), one point per lane - the twin of
-// unit_wire.hip's and unit_wire761.hip's decoders - and, on top of it, the writers of a serialized ark-groth16 0.1 ProvingKey<BW6_761> /
-// VerifyingKey (what groth16_load_key_bw6_761_serialized reads) and of a Proof.
+// unit_wire.hip's and unit_wire761.hip's decoders - and, on top of it, the writers of a serialized ark-groth16 0.1 ProvingKey / VerifyingKey
+// of either curve (what groth16_load_key_<curve>_serialized reads) and of a Proof.
 #include "wire761.h"
 #include <hip/hip_runtime.h>
 #include <atomic>
@@ -92,46 +92,51 @@ int wire_encode(int group, int compressed, const uint64_t* rows, const uint8_t* 
 float wire_encode_last_ms() { return g_wenc_ms.load(); }
 void wire_encode_key_timings(float ms[3]) { for (int i = 0; i < 3; i++) ms[i] = g_wenc_key_ms[i].load(); }
 
-int wire761_key_size(size_t n_inputs, size_t n_vars, size_t n_h, int form, int vk_only, uint64_t* len) { return w761_key_size(n_inputs, n_vars, n_h, form, vk_only, len); }
+int wire_key_size(int curve, size_t n_inputs, size_t n_vars, size_t n_h, int form, int vk_only, uint64_t* len) { return wkey_size(curve, n_inputs, n_vars, n_h, form, vk_only, len); }
 
-// ProvingKey::<BW6_761>::serialize (form 0) / serialize_uncompressed (1), or VerifyingKey's when rows == NULL, from the out_vk / out_rows
-// buffers of groth16_setup_bw6_761.  Both buffers are rows of 24 u64 in serialization order, so a point's row number is its index in the
-// loader's index space.  The rows cross to the device once; each contiguous run of rows (broken only by the Vec length fields) is one launch
-// that writes straight to its byte offset - every offset is a multiple of 8 -; the bytes cross back once and the six length fields are filled
-// in on the host.  A row (0, 1 in Montgomery form) is the identity here, as groth16_setup_* emits it and groth16_load_key_* reads it.
-int wire761_key_serialize(const uint64_t* vk, size_t n_inputs, const uint64_t* rows, size_t n_vars, size_t n_h, int form, uint8_t* out, size_t cap, uint64_t* out_len,
-                          uint64_t* first_bad) {
+// ProvingKey::<E>::serialize (form 0) / serialize_uncompressed (1), or VerifyingKey's when rows == NULL, from the out_vk / out_rows buffers of
+// groth16_setup_<curve> (curve 0 = BW6-761: every row 24 u64; 1 = BLS12-377: G1 rows 12 u64, G2 rows - beta_g2, gamma_g2, delta_g2 and
+// b_g2_query - 24).  Both buffers hold their rows in serialization order, so a point's position there is its index in the loader's index
+// space.  The rows cross to the device once; each contiguous run of rows of one group (broken otherwise only by the Vec length fields) is one
+// launch that writes straight to its byte offset - every offset is a multiple of 8 -; the bytes cross back once and the six length fields are
+// filled in on the host.  A row (0, 1 in Montgomery form) is the identity here, as groth16_setup_* emits it and groth16_load_key_* reads it.
+int wire_key_serialize(int curve, const uint64_t* vk, size_t n_inputs, const uint64_t* rows, size_t n_vars, size_t n_h, int form, uint8_t* out, size_t cap,
+                       uint64_t* out_len, uint64_t* first_bad) {
   if (!vk || !out_len) return 2;
   uint64_t need = 0;
-  if (int rcs = w761_key_size(n_inputs, n_vars, n_h, form, rows == nullptr, &need)) return rcs;
+  if (int rcs = wkey_size(curve, n_inputs, n_vars, n_h, form, rows == nullptr, &need)) return rcs;
   *out_len = need;
   if (cap < need) return W761_ERR_CAPACITY;
   if (!out) return 2;
-  const uint64_t P = form == 0 ? 96 : 192, n_vk = 4 + (uint64_t)n_inputs, n_l = rows ? n_vars - n_inputs : 0;
+  const uint64_t P = wkey_g1_bytes(curve, form), P2 = wkey_g2_bytes(curve, form), w1 = curve ? 12 : 24, w2 = 24;   // bytes and u64 per G1 / G2 point
+  const uint64_t n_vk = 4 + (uint64_t)n_inputs, n_l = rows ? n_vars - n_inputs : 0;
   const uint64_t n_rows = rows ? 2 + 3 * (uint64_t)n_vars + n_h + n_l : 0, N = n_vk + n_rows;
   if (N > 0x7fffffffu) return 2;
   if (int rc0 = api_enter()) return rc0;
   std::lock_guard<std::mutex> lk(wenc_mu);
-  // the runs: {first row, rows, byte offset}; a Vec's length field sits in the 8 bytes before its run
-  struct Run { uint64_t row, n, off; bool vec; };
-  Run runs[8];
+  // the runs: {first point, its first word in the row buffer, points, byte offset}; a Vec's length field sits in the 8 bytes before its run
+  struct Run { uint64_t pt, word, n, off; bool vec, g2; };
+  Run runs[9];
   int nr = 0;
-  uint64_t pos = 0, row = 0;
-  auto add = [&](uint64_t cnt, bool vec) {
+  uint64_t pos = 0, pt = 0, word = 0;
+  auto add = [&](uint64_t cnt, bool vec, bool g2) {
     if (vec) pos += 8;
-    runs[nr++] = {row, cnt, pos, vec};
-    row += cnt;
-    pos += cnt * P;
+    runs[nr++] = {pt, word, cnt, pos, vec, g2};
+    pt += cnt;
+    word += cnt * (g2 ? w2 : w1);
+    pos += cnt * (g2 ? P2 : P);
   };
-  add(4, false);                 // alpha_g1, beta_g2, gamma_g2, delta_g2
-  add(n_inputs, true);           // gamma_abc_g1
+  add(1, false, false);          // alpha_g1
+  add(3, false, true);           // beta_g2, gamma_g2, delta_g2
+  add(n_inputs, true, false);    // gamma_abc_g1
+  const uint64_t vk_words = word;
   if (rows) {
-    add(2, false);               // beta_g1, delta_g1
-    add(n_vars, true);           // a_query
-    add(n_vars, true);           // b_g1_query
-    add(n_vars, true);           // b_g2_query
-    add(n_h, true);              // h_query
-    add(n_l, true);              // l_query
+    add(2, false, false);        // beta_g1, delta_g1
+    add(n_vars, true, false);    // a_query
+    add(n_vars, true, false);    // b_g1_query
+    add(n_vars, true, true);     // b_g2_query
+    add(n_h, true, false);       // h_query
+    add(n_l, true, false);       // l_query
   }
   CallScope cs(nullptr);
   HIP_TRY(cs.create_stream(), 10);
@@ -142,18 +147,18 @@ int wire761_key_serialize(const uint64_t* vk, size_t n_inputs, const uint64_t* r
   uint8_t *d_out, *d_st;
   unsigned long long* d_first;
   unsigned long long first = ~0ull;
-  HIP_TRY(cs.alloc(&d_rows, N * 24 * 8), 10);
+  HIP_TRY(cs.alloc(&d_rows, word * 8), 10);
   HIP_TRY(cs.alloc(&d_out, need), 10);
   HIP_TRY(cs.alloc(&d_st, N), 10);
   HIP_TRY(cs.alloc(&d_first, sizeof first), 10);
   HIP_TRY(hipEventRecord(ev[0], stream), 10);
-  HIP_TRY(hipMemcpyAsync(d_rows, vk, n_vk * 24 * 8, hipMemcpyHostToDevice, stream), 10);
-  if (rows) HIP_TRY(hipMemcpyAsync(d_rows + n_vk * 24, rows, n_rows * 24 * 8, hipMemcpyHostToDevice, stream), 10);
+  HIP_TRY(hipMemcpyAsync(d_rows, vk, vk_words * 8, hipMemcpyHostToDevice, stream), 10);
+  if (rows) HIP_TRY(hipMemcpyAsync(d_rows + vk_words, rows, (word - vk_words) * 8, hipMemcpyHostToDevice, stream), 10);
   HIP_TRY(hipMemcpyAsync(d_first, &first, sizeof first, hipMemcpyHostToDevice, stream), 10);
   HIP_TRY(hipEventRecord(ev[1], stream), 10);
   for (int r = 0; r < nr; r++) {
     if (!runs[r].n) continue;
-    launch_encode(2, form == 0, d_rows + runs[r].row * 24, nullptr, (uint64_t*)(d_out + runs[r].off), d_st + runs[r].row, runs[r].n, 1, stream);
+    launch_encode(curve ? (runs[r].g2 ? 1 : 0) : 2, form == 0, d_rows + runs[r].word, nullptr, (uint64_t*)(d_out + runs[r].off), d_st + runs[r].pt, runs[r].n, 1, stream);
     HIP_TRY(hipGetLastError(), 10);
   }
   hipLaunchKernelGGL(k_first_bad_encode, dim3(((uint32_t)N + 255) / 256), dim3(256), 0, stream, d_st, (uint32_t)N, d_first);

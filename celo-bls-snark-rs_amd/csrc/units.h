@@ -102,20 +102,23 @@ int bv_draw_exponents(const uint32_t key[8], const uint32_t* d_offsets, size_t m
 
 // ---- point decoding and normalisation (unit_wire.hip, unit_wire761.hip).  group 0 / 1: BLS12-377 G1 / G2, 2: BW6-761
 int wire_decompress(int g2, const uint8_t* in, size_t n, int check, uint64_t* out, uint8_t* status, int dev, void* stream);
+int wire377_decode(int g2, int compressed, const uint8_t* in, size_t n, int check, uint64_t* out, uint8_t* status, int dev, void* stream);
+int wire377_launch_decode(int g2, int compressed, const uint8_t* d_in, size_t n, int check, uint64_t* d_out, uint8_t* d_st, hipStream_t stream);
 int wire_normalize(int group, const uint64_t* jac, size_t n, uint64_t* out_xy, uint8_t* inf);
 int wire_consts_device(WireConsts& out);
 float wire_last_ms();
 int wire761_decode(int g2, int compressed, const uint8_t* in, size_t n, int check, uint64_t* out, uint8_t* status, int dev, void* stream);
-int wire761_key_layout(const uint8_t* bytes, size_t len, int form, uint64_t out[16]);
-int wire761_key_load(const uint8_t* bytes, size_t len, int form, int window_bits, ProvingKey** out_key, uint64_t* first_bad);
+// the serialized Groth16 proving key of curve 0 = BW6-761 / 1 = BLS12-377: the layout walk and the loader
+int wire_key_layout(int curve, const uint8_t* bytes, size_t len, int form, uint64_t out[16]);
+int wire_key_load(int curve, const uint8_t* bytes, size_t len, int form, int window_bits, ProvingKey** out_key, uint64_t* first_bad);
 void wire761_last_timings(float ms[4]);
 // ---- point encoding and the key / proof writers (unit_wire_encode.hip).  group as above; compressed: 1 = x with the sign flag, 0 = x || y
 int wire_encode(int group, int compressed, const uint64_t* rows, const uint8_t* inf, size_t n, uint8_t* out, uint8_t* status, int dev, void* stream);
 float wire_encode_last_ms();
 void wire_encode_key_timings(float ms[3]);
-int wire761_key_size(size_t n_inputs, size_t n_vars, size_t n_h, int form, int vk_only, uint64_t* len);
-int wire761_key_serialize(const uint64_t* vk, size_t n_inputs, const uint64_t* rows, size_t n_vars, size_t n_h, int form, uint8_t* out, size_t cap, uint64_t* out_len,
-                          uint64_t* first_bad);
+int wire_key_size(int curve, size_t n_inputs, size_t n_vars, size_t n_h, int form, int vk_only, uint64_t* len);
+int wire_key_serialize(int curve, const uint64_t* vk, size_t n_inputs, const uint64_t* rows, size_t n_vars, size_t n_h, int form, uint8_t* out, size_t cap,
+                       uint64_t* out_len, uint64_t* first_bad);
 int wire761_proof_serialize(const uint64_t* a_xyz, const uint64_t* b_xyz, const uint64_t* c_xyz, uint8_t* out);
 
 // ---- hash to G1 (unit_hash.hip; the composite hasher's generator table is seam_hash.hip's).  mode, for both groups: 0 direct, 1 the CIP22

@@ -50,14 +50,16 @@ HD int wire_cmp(const uint64_t* a, const uint64_t* b, int n) {
   }
   return 0;
 }
-// canonical little-endian bytes -> field element; false when the integer is not below q (Fp::read's from_repr failure)
-HD bool wire_fq_from_bytes(const uint8_t* in, Fq& out) {
+// canonical little-endian bytes -> field element; false when the integer is not below q (Fp::read's from_repr failure).
+// flags: the last byte carries the two flag bits, which are not part of the integer (read in place, as wire761.h's w761_from_bytes)
+HD bool wire_fq_from_bytes(const uint8_t* in, Fq& out, bool flags = false) {
   uint64_t w[6];
   for (int i = 0; i < 6; i++) {
     uint64_t v = 0;
     for (int b = 7; b >= 0; b--) v = (v << 8) | in[8 * i + b];
     w[i] = v;
   }
+  if (flags) w[5] &= ~(0xC0ull << 56);
   if (wire_cmp(w, P377::P64, 6) >= 0) return false;
   out = Fq::from_canonical(w);
   return true;
@@ -303,6 +305,65 @@ HD WireStatus wire_decode_g2(const uint8_t* in, const WireConsts& k, bool check_
   p = {Fq2::norm(x), Fq2::norm(y)};
   if (check_subgroup && !wire_in_subgroup(p, k)) return WIRE_NOT_IN_SUBGROUP;
   return WIRE_OK;
+}
+
+// ---- uncompressed points (GroupAffine::deserialize_uncompressed, checked; deserialize_unchecked, range only): x then y, an Fq2 coordinate
+// as c0 || c1, the flags on the last byte of y.  Status and order as wire761.h's w761_parse states them: flags 0xC0 -> 2; the infinity flag
+// -> 1, before any range check; a component >= q -> 2 (only y's last component is read without the flag bits: a set 0x80 alone is ignored,
+// a high bit anywhere else makes that component >= q); checked: off the curve -> 2 (stricter than ark 0.1, as for BW6-761), outside the
+// subgroup -> 3.  No square root: nothing here touches WireTables, and nothing is indexed at run time.
+// the point up to the subgroup test; p is set when WIRE_OK
+HD WireStatus wire_parse_uncompressed_g1(const uint8_t* in, bool check, Affine<Fq>& p) {
+  const uint8_t flags = in[95] & 0xC0;
+  if (flags == 0xC0) return WIRE_INVALID;
+  if (flags & 0x40) return WIRE_INFINITY;
+  Fq x, y;
+  if (!wire_fq_from_bytes(in, x) || !wire_fq_from_bytes(in + 48, y, true)) return WIRE_INVALID;
+  if (check && !wire_eq(Fq::sqr(y), Fq::norm(Fq::add(Fq::mul(Fq::sqr(x), x), Fq::one())))) return WIRE_INVALID;
+  p = {Fq::norm(x), Fq::norm(y)};
+  return WIRE_OK;
+}
+HD WireStatus wire_parse_uncompressed_g2(const uint8_t* in, const WireConsts& k, bool check, Affine<Fq2>& p) {
+  const uint8_t flags = in[191] & 0xC0;
+  if (flags == 0xC0) return WIRE_INVALID;
+  if (flags & 0x40) return WIRE_INFINITY;
+  Fq2 x, y;
+  if (!wire_fq_from_bytes(in, x.c0) || !wire_fq_from_bytes(in + 48, x.c1) || !wire_fq_from_bytes(in + 96, y.c0) || !wire_fq_from_bytes(in + 144, y.c1, true))
+    return WIRE_INVALID;
+  if (check) {
+    const Fq2 tb = {Fq::zero(), wire_neg(k.inv5)};                    // B' = 1/u = -u/5, as in wire_decode_g2
+    const Fq2 rhs = Fq2::norm(Fq2::add(Fq2::mul(Fq2::sqr(x), x), tb)), yy = Fq2::sqr(y);
+    if (!wire_eq(yy.c0, rhs.c0) || !wire_eq(yy.c1, rhs.c1)) return WIRE_INVALID;
+  }
+  p = {Fq2::norm(x), Fq2::norm(y)};
+  return WIRE_OK;
+}
+// the row forms the MSM, pairing and key entry points take: affine (x, y) as arkworks Montgomery limbs, 12 u64 (G1) / 24 u64 (G2: c0 then
+// c1 per coordinate); zeros unless WIRE_OK.  COMPRESSED: 48 / 96 B through wire_decode_g1 / _g2; else 96 / 192 B, parsed above, then the
+// same subgroup test when checked
+template <bool COMPRESSED> HD WireStatus wire_decode_row_g1(const uint8_t* in, const WireConsts& k, bool check, uint64_t* out) {
+  Affine<Fq> p = {Fq::zero(), Fq::zero()};
+  WireStatus st;
+  if constexpr (COMPRESSED) st = wire_decode_g1(in, k, check, p);
+  else {
+    st = wire_parse_uncompressed_g1(in, check, p);
+    if (st == WIRE_OK && check && !wire_in_subgroup(p, k)) st = WIRE_NOT_IN_SUBGROUP;
+  }
+  if (st == WIRE_OK) { p.x.to_ark(out); p.y.to_ark(out + 6); }
+  else for (int j = 0; j < 12; j++) out[j] = 0;
+  return st;
+}
+template <bool COMPRESSED> HD WireStatus wire_decode_row_g2(const uint8_t* in, const WireConsts& k, bool check, uint64_t* out) {
+  Affine<Fq2> p = {Fq2::zero(), Fq2::zero()};
+  WireStatus st;
+  if constexpr (COMPRESSED) st = wire_decode_g2(in, k, check, p);
+  else {
+    st = wire_parse_uncompressed_g2(in, k, check, p);
+    if (st == WIRE_OK && check && !wire_in_subgroup(p, k)) st = WIRE_NOT_IN_SUBGROUP;
+  }
+  if (st == WIRE_OK) { p.x.c0.to_ark(out); p.x.c1.to_ark(out + 6); p.y.c0.to_ark(out + 12); p.y.c1.to_ark(out + 18); }
+  else for (int j = 0; j < 24; j++) out[j] = 0;
+  return st;
 }
 
 // ---- encoding (arkworks 0.1 CanonicalSerialize for GroupAffine: serialize / serialize_uncompressed), the twin of the decoders above and of

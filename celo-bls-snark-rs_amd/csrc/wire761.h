@@ -191,42 +191,48 @@ HD WireStatus w761_encode_jacobian(const uint64_t* xyz, uint64_t* out12) {
   return W761EncC::row(row, inf, false, out12);
 }
 
-// ---- host: the layout of a serialized ark-groth16 0.1 ProvingKey<BW6_761> (its derive order; Vec = u64 LE length, then the elements):
+// ---- host: the layout of a serialized ark-groth16 0.1 ProvingKey<E> (its derive order; Vec = u64 LE length, then the elements):
 //   vk { alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1: Vec<G1> }, beta_g1, delta_g1,
 //   a_query: Vec<G1>, b_g1_query: Vec<G1>, b_g2_query: Vec<G2>, h_query: Vec<G1>, l_query: Vec<G1>
+// One walk for both curves (curve 0 = BW6-761, 1 = BLS12-377); they differ in the two point sizes alone.  A G1 point is P bytes and a G2
+// point P2: BW6-761 P = P2 = 96 compressed / 192 uncompressed (both groups over Fq); BLS12-377 P = 48 / 96 and P2 = 2 P (G2 over Fq2), so
+// there only the three G2 elements of the vk and b_g2_query have the double stride.
 // The length fields are input: no count * size is formed before count is known to fit what is left.
 enum W761Layout { W761_PT = 0, W761_LEN = 1, W761_ABC = 2, W761_A = 4, W761_BG1 = 6, W761_BG2 = 8, W761_H = 10, W761_L = 12, W761_BETA_G1 = 14, W761_NPOINTS = 15 };
 constexpr int W761_ERR_TRUNCATED = 30, W761_ERR_TRAILING = 31, W761_ERR_LENGTH = 32, W761_ERR_POINT = 33;
 constexpr int W761_ERR_CAPACITY = 35;             // the key writer: the output buffer is smaller than the serialization (34 is the R1CS loader's)
-inline int w761_key_layout(const uint8_t* bytes, size_t len, int form, uint64_t out[16]) {
-  if (!out || (!bytes && len) || form < 0 || form > 2) return 2;
+constexpr uint64_t wkey_g1_bytes(int curve, int form) { return (curve ? 48 : 96) * (form == 0 ? 1 : 2); }
+constexpr uint64_t wkey_g2_bytes(int curve, int form) { return 96 * (form == 0 ? 1 : 2); }
+inline int wkey_layout(int curve, const uint8_t* bytes, size_t len, int form, uint64_t out[16]) {
+  if (!out || (!bytes && len) || form < 0 || form > 2 || curve < 0 || curve > 1) return 2;
   for (int i = 0; i < 16; i++) out[i] = 0;
-  const uint64_t P = form == 0 ? 96 : 192;
+  const uint64_t P = wkey_g1_bytes(curve, form), P2 = wkey_g2_bytes(curve, form);
   uint64_t pos = 0, points = 0;
-  auto take = [&](uint64_t count) -> int {          // count points at pos
-    if (count > UINT64_MAX / P) return W761_ERR_LENGTH;
-    if (count * P > len - pos) return W761_ERR_TRUNCATED;
-    pos += count * P;
+  auto take = [&](uint64_t count, uint64_t size) -> int {   // count points of `size` bytes at pos
+    if (count > UINT64_MAX / size) return W761_ERR_LENGTH;
+    if (count * size > len - pos) return W761_ERR_TRUNCATED;
+    pos += count * size;
     points += count;
     return 0;
   };
-  auto vec = [&](int slot) -> int {                 // u64 length, then the points
+  auto vec = [&](int slot, uint64_t size) -> int {  // u64 length, then the points
     if (len - pos < 8) return W761_ERR_TRUNCATED;
     uint64_t n = 0;
     for (int b = 7; b >= 0; b--) n = (n << 8) | bytes[pos + b];
     pos += 8;
     out[slot] = n;
     out[slot + 1] = pos;
-    return take(n);
+    return take(n, size);
   };
-  int rc = take(4);                                 // alpha_g1, beta_g2, gamma_g2, delta_g2
-  if (!rc) rc = vec(W761_ABC);
-  if (!rc) { out[W761_BETA_G1] = pos; rc = take(2); }   // beta_g1, delta_g1
-  if (!rc) rc = vec(W761_A);
-  if (!rc) rc = vec(W761_BG1);
-  if (!rc) rc = vec(W761_BG2);
-  if (!rc) rc = vec(W761_H);
-  if (!rc) rc = vec(W761_L);
+  int rc = take(1, P);                              // alpha_g1
+  if (!rc) rc = take(3, P2);                        // beta_g2, gamma_g2, delta_g2
+  if (!rc) rc = vec(W761_ABC, P);
+  if (!rc) { out[W761_BETA_G1] = pos; rc = take(2, P); }   // beta_g1, delta_g1
+  if (!rc) rc = vec(W761_A, P);
+  if (!rc) rc = vec(W761_BG1, P);
+  if (!rc) rc = vec(W761_BG2, P2);
+  if (!rc) rc = vec(W761_H, P);
+  if (!rc) rc = vec(W761_L, P);
   if (rc) return rc;
   if (pos != len) return W761_ERR_TRAILING;
   out[W761_PT] = P;
@@ -235,13 +241,13 @@ inline int w761_key_layout(const uint8_t* bytes, size_t len, int form, uint64_t 
   return 0;
 }
 
-// The byte length of what w761_key_layout parses, from the counts (the key writer's side): form 0 = 96 B points, 1 = 192 B; vk_only: the
-// VerifyingKey prefix alone (n_vars and n_h are not looked at).  l_query has n_vars - n_inputs rows.  2: no such key, or a length past 64 bits.
-inline int w761_key_size(uint64_t n_inputs, uint64_t n_vars, uint64_t n_h, int form, int vk_only, uint64_t* len) {
-  if (!len || form < 0 || form > 1 || n_inputs == 0 || (!vk_only && n_inputs > n_vars)) return 2;
-  const unsigned __int128 P = form == 0 ? 96 : 192;
-  unsigned __int128 t = (4 + (unsigned __int128)n_inputs) * P + 8;
-  if (!vk_only) t += (2 + 3 * (unsigned __int128)n_vars + n_h + (n_vars - n_inputs)) * P + 5 * 8;
+// The byte length of what wkey_layout parses, from the counts (the key writer's side): form 0 = compressed points, 1 = uncompressed; vk_only:
+// the VerifyingKey prefix alone (n_vars and n_h are not looked at).  l_query has n_vars - n_inputs rows.  2: no such key, or a length past 64 bits.
+inline int wkey_size(int curve, uint64_t n_inputs, uint64_t n_vars, uint64_t n_h, int form, int vk_only, uint64_t* len) {
+  if (!len || form < 0 || form > 1 || curve < 0 || curve > 1 || n_inputs == 0 || (!vk_only && n_inputs > n_vars)) return 2;
+  const unsigned __int128 P = wkey_g1_bytes(curve, form), P2 = wkey_g2_bytes(curve, form);
+  unsigned __int128 t = (1 + (unsigned __int128)n_inputs) * P + 3 * P2 + 8;
+  if (!vk_only) t += (2 + 2 * (unsigned __int128)n_vars + n_h + (n_vars - n_inputs)) * P + (unsigned __int128)n_vars * P2 + 5 * 8;
   if (t > UINT64_MAX) return 2;
   *len = (uint64_t)t;
   return 0;

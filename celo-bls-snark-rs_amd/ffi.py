@@ -45,6 +45,8 @@ EXPORTS = [
     "decompress_bw6_761_g1", "decompress_bw6_761_g2", "decompress_bw6_761_g1_dev", "decompress_bw6_761_g2_dev",
     "decode_uncompressed_bw6_761_g1", "decode_uncompressed_bw6_761_g2", "groth16_key_layout_bw6_761", "groth16_load_key_bw6_761_serialized",
     "celo_amd_wire761_last_timings",
+    "decode_uncompressed_bls12_377_g1", "decode_uncompressed_bls12_377_g2", "decode_uncompressed_bls12_377_g1_dev", "decode_uncompressed_bls12_377_g2_dev",
+    "groth16_key_layout_bls12_377", "groth16_load_key_bls12_377_serialized", "groth16_serialized_key_size_bls12_377", "groth16_serialize_key_bls12_377",
     "compress_bls12_377_g1", "compress_bls12_377_g2", "compress_bw6_761", "compress_bls12_377_g1_dev", "compress_bls12_377_g2_dev", "compress_bw6_761_dev",
     "encode_uncompressed_bls12_377_g1", "encode_uncompressed_bls12_377_g2", "encode_uncompressed_bw6_761",
     "encode_uncompressed_bls12_377_g1_dev", "encode_uncompressed_bls12_377_g2_dev", "encode_uncompressed_bw6_761_dev",
@@ -559,25 +561,26 @@ def groth16_prove(a_query, b_g2_query, h_query, l_query, alpha_g1, beta_g2, assi
     return out
 
 
-# groth16_key_layout_bw6_761 / groth16_load_key_bw6_761_serialized (include/celo_bls_amd.h)
+# groth16_key_layout_<curve> / groth16_load_key_<curve>_serialized (include/celo_bls_amd.h)
 KEY_ERR_TRUNCATED, KEY_ERR_TRAILING, KEY_ERR_LENGTH, KEY_ERR_POINT = 30, 31, 32, 33
 KEY_LAYOUT_SLOTS = {"point_bytes": 0, "len": 1, "gamma_abc_g1": 2, "a_query": 4, "b_g1_query": 6, "b_g2_query": 8, "h_query": 10, "l_query": 12}
 
 
 class KeyLoadError(RuntimeError):
-    def __init__(self, code, first_bad_point=None):
-        super().__init__("groth16_load_key_bw6_761_serialized failed with code %d%s"
-                         % (code, "" if first_bad_point is None else " (first rejected point: %d)" % first_bad_point))
+    def __init__(self, code, first_bad_point=None, curve="bw6_761"):
+        super().__init__("groth16_load_key_%s_serialized failed with code %d%s"
+                         % (curve, code, "" if first_bad_point is None else " (first rejected point: %d)" % first_bad_point))
         self.code = code
         self.first_bad_point = first_bad_point
 
 
-def groth16_key_layout(data, form=0):
-    """Host walk of a serialized ProvingKey<BW6_761> (groth16_key_layout_bw6_761): returns (rc, out) with out the 16 u64 of the header
-    ({section: (count, byte offset)} via KEY_LAYOUT_SLOTS; out[14] the offset of beta_g1, out[15] the number of points)."""
+def groth16_key_layout(data, form=0, curve="bw6_761"):
+    """Host walk of a serialized ProvingKey of `curve` ("bw6_761" / "bls12_377": groth16_key_layout_<curve>): returns (rc, out) with out the
+    16 u64 of the header ({section: (count, byte offset)} via KEY_LAYOUT_SLOTS; out[0] the bytes of a G1 point - a BLS12-377 G2 point has
+    twice as many -, out[14] the offset of beta_g1, out[15] the number of points)."""
     buf = np.frombuffer(bytes(data), dtype=np.uint8)
     out = np.zeros(16, dtype=np.uint64)
-    rc = lib().groth16_key_layout_bw6_761(_p(buf), C.c_size_t(buf.size), C.c_int(form), _p(out))
+    rc = getattr(lib(), "groth16_key_layout_" + curve)(_p(buf), C.c_size_t(buf.size), C.c_int(form), _p(out))
     return rc, out
 
 
@@ -602,16 +605,16 @@ class ProvingKey:
             raise RuntimeError("groth16_load_key_%s failed with code %d" % (curve, rc))
 
     @classmethod
-    def from_serialized(cls, data, form=0, window_bits=0):
-        """A BW6-761 key from the bytes of a serialized ark-groth16 0.1 ProvingKey<BW6_761> (groth16_load_key_bw6_761_serialized): form 0 =
-        compressed, checked; 1 = uncompressed, checked; 2 = uncompressed, unchecked.  Raises KeyLoadError (.code, .first_bad_point)."""
-        k = cls("bw6_761", None, None, None, None, None, None)
+    def from_serialized(cls, data, form=0, window_bits=0, curve="bw6_761"):
+        """A key of `curve` ("bw6_761" / "bls12_377") from the bytes of a serialized ark-groth16 0.1 ProvingKey (groth16_load_key_<curve>_serialized):
+        form 0 = compressed, checked; 1 = uncompressed, checked; 2 = uncompressed, unchecked.  Raises KeyLoadError (.code, .first_bad_point)."""
+        k = cls(curve, None, None, None, None, None, None)
         buf = np.frombuffer(bytes(data), dtype=np.uint8)
         bad = C.c_uint64(0)
-        rc = lib().groth16_load_key_bw6_761_serialized(_p(buf), C.c_size_t(buf.size), C.c_int(form), C.c_int(window_bits), C.byref(k.h), C.byref(bad))
+        rc = getattr(lib(), "groth16_load_key_%s_serialized" % curve)(_p(buf), C.c_size_t(buf.size), C.c_int(form), C.c_int(window_bits), C.byref(k.h), C.byref(bad))
         if rc != 0:
             k.h = C.c_void_p()
-            raise KeyLoadError(rc, bad.value if rc == KEY_ERR_POINT else None)
+            raise KeyLoadError(rc, bad.value if rc == KEY_ERR_POINT else None, curve)
         return k
 
     def prove_r1cs(self, r1cs, z, log_n, consts):
@@ -911,20 +914,30 @@ def decompress_dev(group, d_in, n, d_out, d_status, check_subgroup=True, stream=
         raise RuntimeError("%s failed with code %d" % (fn, rc))
 
 
+_UNCOMPRESSED = {"g1": (96, 12, "decode_uncompressed_bls12_377_g1"), "g2": (192, 24, "decode_uncompressed_bls12_377_g2"),
+                 "bw6_761_g1": (192, 24, "decode_uncompressed_bw6_761_g1"), "bw6_761_g2": (192, 24, "decode_uncompressed_bw6_761_g2")}
+
+
 def decode_uncompressed(group, data, check=True):
-    """Bulk decoding of uncompressed BW6-761 points (decode_uncompressed_bw6_761_g1/_g2): group "bw6_761_g1" / "bw6_761_g2", 192 B each
-    (x, then y with the flags).  check: on the curve and in the subgroup (deserialize_uncompressed); False: range only
-    (deserialize_unchecked).  Returns (xy (n, 24) uint64, status (n,) uint8) as decompress()."""
-    fn = {"bw6_761_g1": "decode_uncompressed_bw6_761_g1", "bw6_761_g2": "decode_uncompressed_bw6_761_g2"}[group]
+    """Bulk decoding of uncompressed points (decode_uncompressed_<curve>_g1/_g2): group "g1" / "g2" (BLS12-377, 96 / 192 B each) or
+    "bw6_761_g1" / "bw6_761_g2" (192 B each); x, then y with the flags.  check: on the curve and in the subgroup
+    (deserialize_uncompressed); False: range only (deserialize_unchecked).  Returns (xy (n, 12 | 24) uint64, status (n,) uint8) as decompress()."""
+    size, words, fn = _UNCOMPRESSED[group]
     buf = np.frombuffer(bytes(data), dtype=np.uint8)
-    assert buf.size % 192 == 0
-    n = buf.size // 192
-    xy = np.zeros((n, 24), dtype=np.uint64)
+    assert buf.size % size == 0
+    n = buf.size // size
+    xy = np.zeros((n, words), dtype=np.uint64)
     st = np.zeros(n, dtype=np.uint8)
     rc = getattr(lib(), fn)(_p(buf), C.c_size_t(n), C.c_int(1 if check else 0), _p(xy), _p(st))
     if rc != 0:
         raise RuntimeError("%s failed with code %d" % (fn, rc))
     return xy, st
+
+
+def decode_uncompressed_dev(group, d_in, n, d_out, d_status, check=True, stream=0):
+    """The same on device buffers (integer device addresses), on `stream`: BLS12-377 only ("g1" / "g2"); returns the entry point's code."""
+    fn = _UNCOMPRESSED[group][2] + "_dev"
+    return getattr(lib(), fn)(C.c_void_p(d_in), C.c_size_t(n), C.c_int(1 if check else 0), C.c_void_p(d_out), C.c_void_p(d_status), C.c_void_p(stream))
 
 
 # ---- encoding into the wire form (include/celo_bls_amd.h: compress_*, encode_uncompressed_*, groth16_serialize_*)
@@ -969,45 +982,49 @@ def encode_points_dev(group, d_rows, d_inf, n, d_out, d_status, compressed=True,
 
 
 class KeySerializeError(RuntimeError):
-    def __init__(self, code, out_len=None, first_bad_point=None):
-        super().__init__("groth16_serialize_key_bw6_761 failed with code %d%s" % (code, "" if first_bad_point is None else " (first bad point: %d)" % first_bad_point))
+    def __init__(self, code, out_len=None, first_bad_point=None, curve="bw6_761"):
+        super().__init__("groth16_serialize_key_%s failed with code %d%s" % (curve, code, "" if first_bad_point is None else " (first bad point: %d)" % first_bad_point))
         self.code = code
         self.out_len = out_len
         self.first_bad_point = first_bad_point
 
 
-def groth16_serialized_key_size(n_inputs, n_vars, n_h, form=0, vk_only=False):
-    """Byte length of the serialized ProvingKey<BW6_761> (or VerifyingKey) with these counts (groth16_serialized_key_size_bw6_761); no device call."""
+def groth16_serialized_key_size(n_inputs, n_vars, n_h, form=0, vk_only=False, curve="bw6_761"):
+    """Byte length of the serialized ProvingKey (or VerifyingKey) of `curve` with these counts (groth16_serialized_key_size_<curve>); no device call."""
     ln = C.c_uint64(0)
-    rc = lib().groth16_serialized_key_size_bw6_761(C.c_size_t(n_inputs), C.c_size_t(n_vars), C.c_size_t(n_h), C.c_int(form), C.c_int(1 if vk_only else 0), C.byref(ln))
+    rc = getattr(lib(), "groth16_serialized_key_size_" + curve)(C.c_size_t(n_inputs), C.c_size_t(n_vars), C.c_size_t(n_h), C.c_int(form), C.c_int(1 if vk_only else 0),
+                                                                C.byref(ln))
     if rc != 0:
-        raise KeySerializeError(rc)
+        raise KeySerializeError(rc, curve=curve)
     return ln.value
 
 
 def _key_rows(x, names):
-    """a flat buffer of 24-u64 rows, or the dict groth16_setup returns for it (sections concatenated in serialization order)"""
+    """a flat uint64 buffer of rows, or the dict groth16_setup returns for it (sections concatenated in serialization order)"""
     if isinstance(x, dict):
         x = np.concatenate([np.ascontiguousarray(x[k], dtype=np.uint64).reshape(-1) for k in names])
-    return _rows(x, 24)
+    return np.ascontiguousarray(x, dtype=np.uint64).reshape(-1)
 
 
-def groth16_serialize_key(vk, rows=None, n_vars=0, n_h=0, form=0, cap=None):
-    """ProvingKey::<BW6_761>::serialize (form 0) / serialize_uncompressed (1) of groth16_setup's "vk" and "rows" (dicts or flat buffers), or
-    VerifyingKey::serialize when rows is None (groth16_serialize_key_bw6_761).  cap: the output buffer's size (default: what is needed).
+def groth16_serialize_key(vk, rows=None, n_vars=0, n_h=0, form=0, cap=None, curve="bw6_761"):
+    """ProvingKey::serialize (form 0) / serialize_uncompressed (1) of groth16_setup's "vk" and "rows" (dicts or flat buffers), or
+    VerifyingKey::serialize when rows is None (groth16_serialize_key_<curve>; "bw6_761": every row 24 u64; "bls12_377": G1 rows 12 u64, G2
+    rows 24).  cap: the output buffer's size (default: what is needed).
     Returns bytes; raises KeySerializeError (.code 35 with .out_len, 33 with .first_bad_point)."""
+    w1 = 24 if curve == "bw6_761" else 12
     v = _key_rows(vk, ("alpha_g1", "beta_g2", "gamma_g2", "delta_g2", "gamma_abc_g1"))
-    n_inputs = v.shape[0] - 4
+    assert v.size >= w1 + 72 and (v.size - w1 - 72) % w1 == 0, "vk: alpha_g1, three G2 rows, then the rows of gamma_abc_g1"
+    n_inputs = (v.size - w1 - 72) // w1
     r = None if rows is None else _key_rows(rows, ("beta_g1", "delta_g1", "a_query", "b_g1_query", "b_g2_query", "h_query", "l_query"))
     if r is not None:
-        assert r.shape[0] == 2 + 3 * n_vars + n_h + (n_vars - n_inputs), "rows do not match n_vars / n_h"
-    need = groth16_serialized_key_size(n_inputs, n_vars, n_h, form, rows is None)
+        assert r.size == (2 + 2 * n_vars + n_h + (n_vars - n_inputs)) * w1 + n_vars * 24, "rows do not match n_vars / n_h"
+    need = groth16_serialized_key_size(n_inputs, n_vars, n_h, form, rows is None, curve)
     out = np.zeros(need if cap is None else cap, dtype=np.uint8)
     ln, bad = C.c_uint64(0), C.c_uint64(0)
-    rc = lib().groth16_serialize_key_bw6_761(_p(v), C.c_size_t(n_inputs), _p(r), C.c_size_t(n_vars), C.c_size_t(n_h), C.c_int(form), _p(out), C.c_size_t(out.size),
-                                             C.byref(ln), C.byref(bad))
+    rc = getattr(lib(), "groth16_serialize_key_" + curve)(_p(v), C.c_size_t(n_inputs), _p(r), C.c_size_t(n_vars), C.c_size_t(n_h), C.c_int(form), _p(out),
+                                                          C.c_size_t(out.size), C.byref(ln), C.byref(bad))
     if rc != 0:
-        raise KeySerializeError(rc, ln.value, bad.value if rc == KEY_ERR_POINT else None)
+        raise KeySerializeError(rc, ln.value, bad.value if rc == KEY_ERR_POINT else None, curve)
     return out[:ln.value].tobytes()
 
 

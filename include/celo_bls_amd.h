@@ -371,6 +371,21 @@ int decompress_bw6_761_g1_dev(const uint8_t* d_in, size_t n, int check_subgroup,
 int decompress_bw6_761_g2_dev(const uint8_t* d_in, size_t n, int check_subgroup, uint64_t* d_out_xy, uint8_t* d_status, void* hip_stream);
 int decode_uncompressed_bw6_761_g1(const uint8_t* in /* n x 192 */, size_t n, int check, uint64_t* out_xy /* n x 24 */, uint8_t* status /* n */);
 int decode_uncompressed_bw6_761_g2(const uint8_t* in /* n x 192 */, size_t n, int check, uint64_t* out_xy /* n x 24 */, uint8_t* status /* n */);
+/* ---- the same uncompressed forms for BLS12-377 (csrc/wire.h wire_decode_row_*, csrc/unit_wire.hip k_decode377u): what
+ * GroupAffine::deserialize_uncompressed / deserialize_unchecked run per point of a large ProvingKey<Bls12_377> - no square root per point.
+ * in: n x 96 B (G1: x, then y) / n x 192 B (G2: x.c0, x.c1, y.c0, y.c1); the flags sit on the last byte of y (G2: of y.c1).  out_xy and
+ * status as decompress_bls12_377_* write them.  check != 0: the canonical range, the curve equation (y^2 = x^3 + 1; y^2 = x^3 + B' over Fq2,
+ * the twist constant of decompress_bls12_377_g2) and the subgroup tests of decompress_bls12_377_*; check == 0: the canonical range only.
+ * status[i], meaning and order as for decode_uncompressed_bw6_761_*: flags 0xC0 -> 2; infinity flag -> 1 (before any range check); a
+ * component >= q -> 2; off the curve (checked) -> 2; outside the subgroup (checked) -> 3; else 0.  A set 0x80 bit alone is ignored (the
+ * y that is written is the y that is read); a high bit on any other component makes it >= q.  Rows are all zero unless status[i] == 0.
+ * Returns 0; 2: n > 2^31 - 1, a NULL pointer, or a _dev out_xy that is not 8-byte aligned (the rows are stored as 64-bit words); 10;
+ * 100.  n == 0 returns 0.  The _dev forms take device pointers and run on hip_stream (0: the null stream); calls are serialised per
+ * process with decompress_bls12_377_*. */
+int decode_uncompressed_bls12_377_g1(const uint8_t* in /* n x 96 */, size_t n, int check, uint64_t* out_xy /* n x 12 */, uint8_t* status /* n */);
+int decode_uncompressed_bls12_377_g2(const uint8_t* in /* n x 192 */, size_t n, int check, uint64_t* out_xy /* n x 24 */, uint8_t* status /* n */);
+int decode_uncompressed_bls12_377_g1_dev(const uint8_t* d_in, size_t n, int check, uint64_t* d_out_xy, uint8_t* d_status, void* hip_stream);
+int decode_uncompressed_bls12_377_g2_dev(const uint8_t* d_in, size_t n, int check, uint64_t* d_out_xy, uint8_t* d_status, void* hip_stream);
 /* ---- a serialized ark-groth16 0.1 ProvingKey<BW6_761> (the reference's Groth16Parameters, crates/epoch-snark/src/api/setup.rs:12,17-20),
  * in the derive order of the struct; a Vec is a u64 little-endian length followed by its elements:
  *   vk { alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1: Vec<G1> }, beta_g1, delta_g1,
@@ -397,8 +412,19 @@ int decode_uncompressed_bw6_761_g2(const uint8_t* in /* n x 192 */, size_t n, in
  * freed and *out_key stays NULL; first_bad_point (may be NULL) is written only with 33. */
 int groth16_key_layout_bw6_761(const uint8_t* bytes, size_t len, int form, uint64_t out[16]);
 int groth16_load_key_bw6_761_serialized(const uint8_t* bytes, size_t len, int form, int window_bits, void** out_key, uint64_t* first_bad_point);
-/* ms[0]: kernel time of the last decompress_bw6_761_* / decode_uncompressed_bw6_761_* call; ms[1..3]: the last serialized key load's
- * transfer of the bytes, decoding (all sections and the rejection scan) and fixed-base table build */
+/* ---- the same for a serialized ProvingKey<Bls12_377> - the reference's hash-helper parameters (Parameters.hash_to_bits,
+ * crates/epoch-snark/src/api/setup.rs:17-20, consumed at prover.rs:112).  One walk and one loader with the BW6-761 entries above: the struct
+ * order, the forms, the return codes, the index space of first_bad_point and the cleanup are theirs word for word.  What differs is that
+ * points have two sizes: a G1 point is P bytes (48 compressed, 96 uncompressed) and a G2 point 2 P.  out[0] = P; alpha_g1, beta_g2, gamma_g2
+ * and delta_g2 sit at offsets 0, P, 3 P, 5 P and the length field of gamma_abc_g1 at 7 P; among the vectors only b_g2_query has the double
+ * stride.  A compressed VerifyingKey with k gamma_abc_g1 entries is 7 x 48 + 8 + 48 k bytes: what groth16_vk_load_bls12_377_serialized reads.
+ * The loader decodes form 0 with the kernels of decompress_bls12_377_* and forms 1 / 2 with those of decode_uncompressed_bls12_377_*, one
+ * launch per section, G1 rows of 12 u64 and G2 rows of 24; the handle is the one groth16_load_key_bls12_377 would build, proves with
+ * groth16_prove_with_key / groth16_prove_r1cs_with_key and is released with groth16_free_key. */
+int groth16_key_layout_bls12_377(const uint8_t* bytes, size_t len, int form, uint64_t out[16]);
+int groth16_load_key_bls12_377_serialized(const uint8_t* bytes, size_t len, int form, int window_bits, void** out_key, uint64_t* first_bad_point);
+/* ms[0]: kernel time of the last decompress_bw6_761_* / decode_uncompressed_bw6_761_* call; ms[1..3]: the last serialized key load's (either
+ * curve) transfer of the bytes, decoding (all sections and the rejection scan) and fixed-base table build */
 int celo_amd_wire761_last_timings(float ms[4]);
 
 /* ---- Groth16 verification over BW6-761 for m proofs under ONE verifying key (BLS12-377: the next block): ark_groth16::prepare_verifying_key + verify_proof
@@ -536,6 +562,13 @@ int groth16_serialized_key_size_bw6_761(size_t n_inputs, size_t n_vars, size_t n
 int groth16_serialize_key_bw6_761(const uint64_t* vk, size_t n_inputs, const uint64_t* rows /* NULL: the VerifyingKey alone */, size_t n_vars, size_t n_h,
                                   int form /* 0 compressed, 1 uncompressed */, uint8_t* out, size_t cap, uint64_t* out_len, uint64_t* first_bad_point /* NULL allowed */);
 int groth16_serialize_proof_bw6_761(const uint64_t a_xyz[36], const uint64_t b_xyz[36], const uint64_t c_xyz[36], uint8_t out[288]);
+/* The same writer and size function for ProvingKey<Bls12_377> / VerifyingKey<Bls12_377>, from the out_vk / out_rows buffers of
+ * groth16_setup_bls12_377 and groth16_setup_r1cs_bls12_377 in their documented order: G1 rows are 12 u64, the G2 rows (beta_g2, gamma_g2,
+ * delta_g2 and those of b_g2_query) 24 u64.  The layout is the one groth16_key_layout_bls12_377 parses; with rows == NULL the output is what
+ * groth16_vk_load_bls12_377_serialized reads.  Forms, return codes, the (0, 1) identity rule and first_bad_point as above. */
+int groth16_serialized_key_size_bls12_377(size_t n_inputs, size_t n_vars, size_t n_h, int form, int vk_only, uint64_t* len);
+int groth16_serialize_key_bls12_377(const uint64_t* vk, size_t n_inputs, const uint64_t* rows /* NULL: the VerifyingKey alone */, size_t n_vars, size_t n_h,
+                                    int form /* 0 compressed, 1 uncompressed */, uint8_t* out, size_t cap, uint64_t* out_len, uint64_t* first_bad_point /* NULL allowed */);
 /* kernel time in ms of the last compress_* / encode_uncompressed_* call (or of the last key writer's launches); the last
  * groth16_serialize_key_bw6_761 call's three phases: rows to the device, encoding, bytes back (what tools/bench_wire_encode.py reports). */
 int celo_amd_wire_encode_last_ms(float* ms);
