@@ -26,7 +26,7 @@
 
 namespace celo {
 
-constexpr int BA_K_MAX = 4;    // tree levels before the XYZZ chain: a launch parameter (MsmTuning::ba_levels), at most this
+constexpr int BA_K_MAX = 4;    // tree levels before the XYZZ chain: a launch parameter (BA_LEVELS, msm_engine.h), at most this
 constexpr uint32_t BA_LANES_OCC1 = 1024u * 64u;      // lanes in flight with one wave per SIMD; the grid is ONE round of them (x occupancy)
 
 template <class G> struct BaCfg { static constexpr bool enabled = false; };

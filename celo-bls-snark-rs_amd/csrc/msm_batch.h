@@ -151,32 +151,9 @@ __global__ void __launch_bounds__(128) k_batch_reduce(const uint32_t* __restrict
   IO::store_xyzz(wsum + (size_t)vw * IO::XYZZ_WORDS, acc);
 }
 
-template <class G>
-__global__ void __launch_bounds__(128) k_batch_horner(const uint32_t* __restrict__ wsum, uint64_t* __restrict__ out, uint32_t nw,
-                                                      uint32_t c, uint32_t m) {
-  typedef typename G::F F;
-  typedef PointIO<F> IO;
-  uint32_t inst = blockIdx.x * blockDim.x + threadIdx.x;
-  if (inst >= m) return;
-  Xyzz<F> acc = Xyzz<F>::identity();
-  for (int w = (int)nw - 1; w >= 0; w--) {
-    for (uint32_t k = 0; k < c; k++) acc = xyzz_dbl(acc);      // inlined: this chain is pure latency (c * nw dependent doublings)
-    Xyzz<F> v = IO::load_xyzz(wsum + ((size_t)inst * nw + w) * IO::XYZZ_WORDS);
-    xyzz_add(acc, v);
-  }
-  uint64_t* o = out + (size_t)inst * 3 * IO::ARK64;
-  if (acc.is_identity() || acc.ZZ.is_zero_mod_p()) {
-    F::zero().to_ark(o); F::one().to_ark(o + IO::ARK64); F::zero().to_ark(o + 2 * IO::ARK64);
-  } else {
-    F::mul(acc.X, acc.ZZ).to_ark(o);
-    F::mul(acc.Y, acc.ZZZ).to_ark(o + IO::ARK64);
-    acc.ZZ.to_ark(o + 2 * IO::ARK64);
-  }
-}
-
-// The same Horner pass with THREE LANES PER INSTANCE (curve_lanes.h): the chain of c * nw dependent doublings is pure latency
-// (136 of them per Batch::verify instance), one lane per instance leaves all but 64 waves of the chip idle, and spreading each
-// doubling's independent products over a lane group more than halves its latency.  21 instances per 64-lane block.
+// The Horner pass over an instance's window sums with THREE LANES PER INSTANCE (curve_lanes.h): the chain of c * nw dependent doublings
+// is pure latency (136 of them per Batch::verify instance), one lane per instance would leave all but 64 waves of the chip idle, and spreading
+// each doubling's independent products over a lane group more than halves its latency.  21 instances per 64-lane block.
 template <class G>
 __global__ void __launch_bounds__(64) k_batch_horner_lanes(const uint32_t* __restrict__ wsum, uint64_t* __restrict__ out, uint32_t nw,
                                                            uint32_t c, uint32_t m) {

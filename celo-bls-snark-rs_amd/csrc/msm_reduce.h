@@ -1,32 +1,14 @@
-// MSM stage 5: folding multi-piece buckets (k_combine_mid / _big), the bit-sliced bucket reduction (k_bitsum, k_bitsum_lanes), results to arkworks form.
+// MSM stage 5: folding multi-piece buckets (k_combine_mid_lanes / k_combine_big), the bit-sliced bucket reduction (k_bitsum, k_bitsum_lanes), results to arkworks form.
 // (part of the MSM pipeline: csrc/msm.h includes the pieces in order and carries the overview)
 #pragma once
 
 namespace celo {
 
-// ---- 5a. buckets cut into 2..16 pieces (e.g. every bucket of a short top window): one lane folds the pieces
+// ---- 5a. buckets cut into 2..16 pieces (e.g. every bucket of a short top window): the pieces are folded into the first
 // (`first` = 1, chunked pipeline: the first piece is the bucket's carrier and stays out of the fold - the pieces from the second on are
-// folded into the second)
-template <class G>
-__global__ void __launch_bounds__(128) k_combine_mid(const uint32_t* __restrict__ mid, const uint32_t* __restrict__ nmid,
-                                                     const uint32_t* __restrict__ counts, const uint32_t* __restrict__ pfirst,
-                                                     uint32_t* __restrict__ partials, uint32_t* __restrict__ pieces_of, uint32_t SEG, uint32_t first = 0) {
-  typedef typename G::F F;
-  typedef PointIO<F> IO;
-  for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < *nmid; q += gridDim.x * blockDim.x) {
-    uint32_t t = mid[q];
-    uint32_t pc = (counts[t] + SEG - 1) / SEG - first, pf = pfirst[t] + first;
-    Xyzz<F> acc = IO::load_xyzz(partials + (size_t)pf * IO::XYZZ_WORDS);
-    for (uint32_t k = 1; k < pc; k++) {
-      Xyzz<F> v = IO::load_xyzz(partials + (size_t)(pf + k) * IO::XYZZ_WORDS);
-      xyzz_add_fn(acc, v);
-    }
-    IO::store_xyzz(partials + (size_t)pf * IO::XYZZ_WORDS, acc);
-    pieces_of[t] = 1;
-  }
-}
-// the same fold with three lanes per bucket (curve_lanes.h): the folds are a handful of dependent additions on lone waves (the
-// 4096 buckets of a short top window, four pieces each), i.e. latency - see k_bitsum_lanes
+// folded into the second).  Three lanes per bucket (curve_lanes.h): the folds are a handful of dependent additions on lone waves (the
+// 4096 buckets of a short top window, four pieces each), i.e. latency - see k_bitsum_lanes.  (The one-lane form, k_combine_mid, went with
+// the A/B switch that could select it.)
 template <class G>
 __global__ void __launch_bounds__(64) k_combine_mid_lanes(const uint32_t* __restrict__ mid, const uint32_t* __restrict__ nmid,
                                                           const uint32_t* __restrict__ counts, const uint32_t* __restrict__ pfirst,
@@ -94,7 +76,7 @@ template <class G> HD Xyzz<typename G::F> load_bucket(const uint32_t* partials, 
   if (!counts) return IO::load_xyzz(partials + (size_t)t * IO::XYZZ_WORDS);    // chunked pipeline: `partials` is the carrier table, one slot per bucket
   uint32_t c = counts[t];
   if (c == 0) return Xyzz<F>::identity();
-  (void)pieces_of; (void)SEG;  // k_combine_mid / k_combine_big have folded multi-piece buckets into their first piece
+  (void)pieces_of; (void)SEG;  // k_combine_mid_lanes / k_combine_big have folded multi-piece buckets into their first piece
   return IO::load_xyzz(partials + (size_t)pfirst[t] * IO::XYZZ_WORDS);
 }
 

@@ -143,8 +143,8 @@ def test_accumulate_kernels_are_out_of_the_sgpr_spill_regime():
 
 
 def test_horner_kernels_of_the_28_limb_field_left_the_spill_regime():
-    """k_batch_horner / k_batch_horner_lanes <G_761> parked 585 / 595 SGPRs in VGPR lanes while the K p tables sat behind
-    pointers; with immediates what remains are exec masks of nested divergent regions."""
+    """the batched Horner kernels of G_761 (the one-lane form, removed since, and k_batch_horner_lanes) parked 585 / 595 SGPRs
+    in VGPR lanes while the K p tables sat behind pointers; with immediates what remains are exec masks of nested divergent regions."""
     import glob
     build = os.path.join(ROOT, "celo-bls-snark-rs_amd", "build")
     seen = 0

@@ -97,7 +97,7 @@ def test_g1_bucket_runs_of_equal_and_opposite_points(gpu):
 
 @pytest.mark.parametrize("logn", [16, 20])
 def test_g1_heavy_skew_large(gpu, logn):
-    """Skew at sizes where runs are cut into many pieces (k_combine_mid / k_combine_big) and one region of the two-level sort
+    """Skew at sizes where runs are cut into many pieces (k_combine_mid_lanes / k_combine_big) and one region of the two-level sort
     spans many tiles (k_tile_count / k_tile_sort; 2^20 is the 16-bit-window, 128-bin configuration of the headline): (a) every
     scalar equal -> one bucket per window holds all points, (b) witness-like: 40% zero, 30% one, rest uniform."""
     n = 1 << logn

@@ -1,4 +1,6 @@
 #!/bin/bash
+# ARCHIVED: the record of how profiles/r6_ba_ab.txt was taken.  Its CELO_BA_OCC, CELO_BA_LEVELS and CELO_BA_ROUNDS variants no longer select anything -
+# the library reads none of them (BA_OCC / BA_LEVELS / BA_ROUNDS are constants in csrc/msm_engine.h) - so every "variant" below runs the same code.
 # batched-affine pre-levels (BW6-761): parity tests, then config 4's bench line over the variants (same box), then a kernel trace
 O=gpurun_out/r6_ba; mkdir -p $O
 export TMPDIR=/tmp
