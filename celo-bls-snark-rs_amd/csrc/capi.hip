@@ -504,6 +504,22 @@ int hash_to_g2_one_bls12_377(const uint8_t domain[8], const uint8_t* msg, size_t
 int celo_amd_hash_g2_set_lane_budget_log(int log) { return hash_g2_set_lane_budget_log(log); }
 int celo_amd_hash_g2_last_split(float ms[2]) { if (!ms) return 2; hash_g2_last_split(ms); return 0; }
 int composite_crh_bls12_377(const uint8_t* msgs, const uint64_t* msg_off, size_t n, uint8_t* out48) { return pedersen_crh_run(msgs, msg_off, n, out48); }
+int composite_crh_bls12_377_dev(const void* d_msgs, const uint64_t* msg_off, size_t n, void* d_out48, void* hip_stream) {
+  return pedersen_crh_run((const uint8_t*)d_msgs, msg_off, n, (uint8_t*)d_out48, 1, hip_stream);
+}
+int hash_to_g1_direct_bls12_377_dev(const uint8_t domain[8], const void* d_msgs, const uint64_t* msg_off, const void* d_extras, const uint64_t* extra_off, size_t n,
+                                    void* d_out_xy, void* d_attempts, void* hip_stream) {
+  return hash_to_g1_direct_run(domain, (const uint8_t*)d_msgs, msg_off, (const uint8_t*)d_extras, extra_off, n, (uint64_t*)d_out_xy, (uint8_t*)d_attempts, 0, 1, hip_stream);
+}
+int hash_to_g1_cip22_tail_bls12_377_dev(const uint8_t domain[8], const void* d_inner, const uint64_t* inner_off, const void* d_extras, const uint64_t* extra_off, size_t n,
+                                        void* d_out_xy, void* d_attempts, void* hip_stream) {
+  return hash_to_g1_direct_run(domain, (const uint8_t*)d_inner, inner_off, (const uint8_t*)d_extras, extra_off, n, (uint64_t*)d_out_xy, (uint8_t*)d_attempts, 1, 1, hip_stream);
+}
+int hash_to_g1_composite_bls12_377_dev(const uint8_t domain[8], const void* d_msgs, const uint64_t* msg_off, const void* d_extras, const uint64_t* extra_off, size_t n,
+                                       int cip22, void* d_out_xy, void* d_attempts, void* hip_stream) {
+  return hash_to_g1_direct_run(domain, (const uint8_t*)d_msgs, msg_off, (const uint8_t*)d_extras, extra_off, n, (uint64_t*)d_out_xy, (uint8_t*)d_attempts, cip22 ? 3 : 2, 1,
+                               hip_stream);
+}
 int celo_amd_hash_last_ms(float* ms) { if (!ms) return 2; *ms = hash_last_ms(); return 0; }
 int celo_amd_hash_last_rounds(int* rounds) { if (!rounds) return 2; *rounds = hash_last_rounds(); return 0; }
 int normalize_bls12_377_g1(const uint64_t* jac, size_t n, uint64_t* out_xy, uint8_t* inf) { return wire_normalize(0, jac, n, out_xy, inf); }
@@ -604,6 +620,14 @@ int verify_epoch_proofs_bw6_761(const void* vk, const uint8_t* proofs, const cel
   return verify_epoch_proofs((const VerifyingKey*)vk, proofs, (const EpochBlocks*)first, (const EpochBlocks*)last, m, mode, key, out_ok, out_status);
 }
 int celo_amd_epoch_last(float ms[8]) { if (!ms) return 2; epoch_last(ms); return 0; }
+// ---- chains of epoch transitions (unit_transitions.hip)
+int verify_epoch_transitions_bls12_377(const celo_epoch_blocks* blocks, size_t nb, const uint32_t* chain_off, size_t n_chains, const uint8_t* bits, const uint8_t* sig48,
+                                       const uint8_t domain[8], const uint64_t neg_g2_xy[24], int mode, uint8_t* out_ok, uint8_t* out_status, uint8_t* out_chain_ok,
+                                       uint8_t* out_crh, uint8_t* out_attempts, uint64_t* out_asig_xy, uint8_t* out_asig_inf) {
+  return verify_epoch_transitions((const EpochBlocks*)blocks, nb, chain_off, n_chains, bits, sig48, domain, neg_g2_xy, mode, out_ok, out_status, out_chain_ok, out_crh,
+                                  out_attempts, out_asig_xy, out_asig_inf);
+}
+int celo_amd_transitions_last(int* path, float ms[8]) { if (!path || !ms) return 2; transitions_last(path, ms); return 0; }
 // ---- R1CS matrices on the device (unit_r1cs.hip)
 #define R1CS_LOAD(NAME, CURVE)                                                                                                                              \
   int NAME(size_t n_constraints, size_t n_vars, size_t n_inputs, const uint64_t* a_row_ptr, const uint32_t* a_col, const uint64_t* a_val, size_t a_nnz,     \

@@ -16,6 +16,7 @@
 #include "r1cs.h"
 #include "hash_direct.h"
 #include "epoch.h"
+#include "transitions.h"
 #include "host64.h"
 #include <cstring>
 using namespace celo;
@@ -932,6 +933,22 @@ int64_t ht_epoch_encode(int kind, uint32_t index, uint32_t round, uint32_t max_n
   }
   if (kind == 2 && extra) epoch_extra(index, round, max_non_signers, extra);
   return (int64_t)bytes;
+}
+// transitions.h: the rule k_transition_status runs, one block from its facts.  f: initial, bad_key, pred_bad_key, index, pred_index, n_keys,
+// pred_n_keys, entropy_live, entropy_equal, signers, pred_max_non_signers, padding_selected, sig_wire, attempt
+int ht_transition_status(const uint32_t f[14]) {
+  TransitionFacts t = {};
+  t.initial = f[0] != 0; t.bad_key = f[1] != 0; t.pred_bad_key = f[2] != 0; t.index = f[3]; t.pred_index = f[4]; t.n_keys = f[5]; t.pred_n_keys = f[6];
+  t.entropy_live = f[7] != 0; t.entropy_equal = f[8] != 0; t.signers = f[9]; t.pred_max_non_signers = f[10]; t.padding_selected = f[11] != 0;
+  t.sig_wire = (uint8_t)f[12]; t.attempt = (uint8_t)f[13];
+  return transition_status(t);
+}
+// the helpers that gather the facts: entropy rows (NULL = all zero) and the padding-key scan over rows of 24 u64
+int ht_transition_entropy(const uint8_t* a, uint64_t i, const uint8_t* b, uint64_t j) {
+  return (transition_entropy_equal(a, i, b, j) ? 1 : 0) | (transition_entropy_nonzero(a, i) ? 2 : 0);
+}
+int ht_transition_padding(const uint64_t* rows, const uint8_t* inf, const uint8_t* bits, uint32_t k0, uint32_t k1, const uint64_t* gen) {
+  return transition_padding_selected(rows, inf, bits, k0, k1, gen) ? 1 : 0;
 }
 void ht_epoch_key_record(const uint64_t* row, int inf, uint32_t* rec24) { epoch_key_record(row, inf != 0, rec24); }
 void ht_epoch_blake2s(const uint8_t* msg, uint64_t len, uint8_t* out32) {

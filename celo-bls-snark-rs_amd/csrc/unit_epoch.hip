@@ -140,6 +140,8 @@ template <class T> static hipError_t epoch_in(CallScope& cs, const T** d, const 
 // one set of nb blocks on the device, up to its records
 struct EpochDev {
   EpochFields f = {};
+  const uint64_t* rows = nullptr;   // key_off[nb] decoded keys
+  const uint8_t* inf = nullptr;     // ... and their flags: the identity, or a key that did not decode
   uint32_t* recs = nullptr;     // key_off[nb] key records, then the generator's
   uint32_t* sums = nullptr;     // nb records: the aggregated keys (with_sums)
   uint8_t* status = nullptr;    // nb
@@ -187,6 +189,8 @@ static int epoch_stage(CallScope& cs, EvLog& log, const EpochBlocks& b, size_t n
   HIP_TRY(hipMemcpyAsync(d.recs + (size_t)nkeys * EPOCH_REC_WORDS, grec.w, sizeof grec.w, hipMemcpyHostToDevice, s), 10);
   hipLaunchKernelGGL(k_epoch_block_status, dim3((nb32 + 255) / 256), dim3(256), 0, s, d.f.key_off, d_kst, d_inf_in, nb32, d_inf, d.status);
   HIP_TRY(hipGetLastError(), 10);
+  d.rows = d_rows;
+  d.inf = d_inf;
   uint64_t* d_sum = nullptr;
   uint8_t* d_suminf = nullptr;
   if (with_sums) {
@@ -230,6 +234,24 @@ static int epoch_pack(CallScope& cs, EvLog& log, const EpochBlocks& b, size_t nb
   hipLaunchKernelGGL(k_epoch_pack, dim3((unsigned)((d.slot_words + 255) / 256)), dim3(256), 0, s, d.f, kind, (uint32_t)nb, d.slot_off, d.recs, d.sums, d.status, d.slots);
   log.close(EP_PACK, e0);
   HIP_TRY(hipGetLastError(), 10);
+  return 0;
+}
+
+int epoch_refuse_blocks(const EpochBlocks& b, size_t nb, bool need_round) { return epoch_refuse(b, nb, need_round); }
+// host pointers throughout (the caller's frame stages what it adds); no record of its own: the times go to the caller's log
+int epoch_stage_bytes(CallScope& cs, EvLog& log, const EpochBlocks& b, size_t nb, int kind, const uint64_t* out_off, EpochStaged* out) {
+  EpochDev d;
+  if (int rc = epoch_stage(cs, log, b, nb, 0, kind == 1, d)) return rc;
+  if (int rc = epoch_pack(cs, log, b, nb, kind, d)) return rc;
+  uint64_t* d_out_off;
+  uint8_t* d_bytes;
+  HIP_TRY(cs.in(&d_out_off, out_off, (nb + 1) * 8, 0), 10);
+  HIP_TRY(cs.alloc(&d_bytes, out_off[nb] + 8), 10);
+  hipEvent_t e0 = log.open();
+  if (out_off[nb]) hipLaunchKernelGGL(k_epoch_compact, dim3((unsigned)((out_off[nb] + 255) / 256)), dim3(256), 0, cs.stream(), d.slots, d.slot_off, d_out_off, (uint32_t)nb, d_bytes);
+  log.close(EP_PACK, e0);
+  HIP_TRY(hipGetLastError(), 10);
+  *out = {d.f.index, d.f.round, d.f.mns, d.f.key_off, d.f.ee, d.f.pe, d.rows, d.inf, d.status, d_bytes};
   return 0;
 }
 

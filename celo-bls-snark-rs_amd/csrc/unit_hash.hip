@@ -146,18 +146,31 @@ static int ensure_device_gens(const EdPoint* h_gens, size_t ngens) {
 // under the G2 accumulation.
 struct HashScratch { hipStream_t stream = nullptr; uint8_t* buf = nullptr; size_t cap = 0; };
 static HashScratch g_hash_scratch[MAX_DEVICES];
-static int hash_scratch(size_t need, HashScratch** out) {
+// keep: bytes at the head of the scratch that outlive a growth (the CRH rows of a CIP22 call, between its two steps; the step that wrote
+// them has drained)
+static int hash_scratch(size_t need, HashScratch** out, size_t keep = 0) {
   HashScratch& h = g_hash_scratch[api_device()];
   if (!h.stream && hipStreamCreateWithFlags(&h.stream, hipStreamNonBlocking) != hipSuccess) { h.stream = nullptr; return 10; }
   if (need > h.cap) {
-    if (h.buf) (void)hipFree(h.buf);
+    uint8_t* old = keep ? h.buf : nullptr;
+    if (h.buf && !old) (void)hipFree(h.buf);
     h.buf = nullptr; h.cap = 0;
-    if (hipMalloc((void**)&h.buf, need + need / 4) != hipSuccess) { h.buf = nullptr; return 10; }
+    if (hipMalloc((void**)&h.buf, need + need / 4) != hipSuccess) { h.buf = nullptr; if (old) (void)hipFree(old); return 10; }
     h.cap = need + need / 4;
+    if (old) {
+      const hipError_t e = hipMemcpy(h.buf, old, keep, hipMemcpyDeviceToDevice);
+      (void)hipFree(old);
+      if (e != hipSuccess) return 10;
+    }
   }
   *out = &h;
   return 0;
 }
+// Where a call's operands live.  msgs / rest: the message bytes / the extras, rows and attempts are DEVICE pointers (the _dev entries set both; the
+// second step of a CIP22 call reads its messages, the CRH rows, at the head of the scratch in either form).  stream: the caller's, with rest.
+// head: bytes at the start of the scratch that the call leaves alone.
+// at_head: the messages ARE the head of the scratch (the `msgs` argument is not used).
+struct HashWhere { bool msgs = false, rest = false, at_head = false; hipStream_t stream = nullptr; size_t head = 0; };
 static float g_hash_ms = 0.f;
 static int g_hash_rounds = 0;
 
@@ -202,15 +215,11 @@ struct HashG2 {
   }
 };
 
-// The round loop of both groups.  split_ms (optional): kernel time of the candidate rounds and of the finish kernel.
+// The round loop of both groups, under hash_mu.  split_ms (optional): kernel time of the candidate rounds and of the finish kernel.
 template <class G>
-static int hash_rounds(const uint8_t* domain, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off, size_t n, int compat,
-                       uint64_t* out_xy, uint8_t* attempts, int mode, float* split_ms) {
+static int hash_rounds_locked(const uint8_t* domain, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off, size_t n, int compat,
+                              uint64_t* out_xy, uint8_t* attempts, int mode, float* split_ms, const EdPoint* h_gens, size_t ngens, const HashWhere& w) {
   constexpr int ROW = G::ROW;
-  size_t ngens = 0;
-  const EdPoint* h_gens = mode == TAI_COMPOSITE ? celo_composite_gens(&ngens) : nullptr;   // before the lock: 0.5 s on first use
-  if (int rc0 = api_enter()) return rc0;
-  std::lock_guard<std::mutex> lk(hash_mu);
   if (n == 0) return 0;
   if (mode == TAI_COMPOSITE) {
     if (int rcg = ensure_device_gens(h_gens, ngens)) return rcg;
@@ -223,26 +232,29 @@ static int hash_rounds(const uint8_t* domain, const uint8_t* msgs, const uint64_
     if (msg_off[i + 1] < msg_off[i] || (extra_off && extra_off[i + 1] < extra_off[i])) return 2;
   }
   const size_t mb = msg_off[n], eb = extra_off ? extra_off[n] : 0;
-  if ((mb && !msgs) || (eb && !extras)) return 2;
+  if ((mb && !msgs && !w.at_head) || (eb && !extras)) return 2;
+  const bool dev_msgs = w.msgs || w.at_head;
   const WireConsts& kh = wire_consts();   // host tables (the serial fallback below)
   WireConsts k;
   if (int rck = wire_consts_device(k)) return rck;
   HashDom dom;
   memcpy(dom.b, domain, 8);
   std::vector<uint8_t> redo(n);
-  size_t off = 0;
+  // what the caller holds on the device is used where it lies; the rest takes a slice of the scratch
+  size_t off = w.head;
   auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~size_t(255); return o; };
-  const size_t o_off = take((n + 1) * 2 * 8), o_out = take(n * ROW * 8), o_cand = take(n * ROW * 8), o_list = take(2 * n * 4), o_cnt = take(256 * 4),
-               o_att = take(n), o_redo = take(n), o_bytes = take(mb + eb + 8);
+  const size_t o_off = take((n + 1) * 2 * 8), o_out = take(w.rest ? 0 : n * ROW * 8), o_cand = take(n * ROW * 8), o_list = take(2 * n * 4), o_cnt = take(256 * 4),
+               o_att = take(w.rest ? 0 : n), o_redo = take(n), o_msgs = take(dev_msgs ? 0 : mb + 8), o_extras = take(w.rest ? 0 : eb + 8);
   HashScratch* hs = nullptr;
-  if (hash_scratch(off, &hs)) return 10;
-  CallScope cs(hs->stream);               // the scratch and its stream stay with the device; the call owns its events
+  if (hash_scratch(off, &hs, w.head)) return 10;
+  CallScope cs(w.rest ? w.stream : hs->stream);   // the scratch and its stream stay with the device; the call owns its events
   const hipStream_t st = cs.stream();
-  uint64_t *d_off = (uint64_t*)(hs->buf + o_off), *d_out = (uint64_t*)(hs->buf + o_out), *d_cand = (uint64_t*)(hs->buf + o_cand);
+  uint64_t *d_off = (uint64_t*)(hs->buf + o_off), *d_out = w.rest ? out_xy : (uint64_t*)(hs->buf + o_out), *d_cand = (uint64_t*)(hs->buf + o_cand);
   uint32_t *d_list = (uint32_t*)(hs->buf + o_list), *d_cnt = (uint32_t*)(hs->buf + o_cnt);
-  uint8_t *d_att = hs->buf + o_att, *d_redo = hs->buf + o_redo, *d_bytes = hs->buf + o_bytes;
-  if (mb) HIP_TRY(hipMemcpyAsync(d_bytes, msgs, mb, hipMemcpyHostToDevice, st), 10);
-  if (eb) HIP_TRY(hipMemcpyAsync(d_bytes + mb, extras, eb, hipMemcpyHostToDevice, st), 10);
+  uint8_t *d_att = w.rest ? attempts : hs->buf + o_att, *d_redo = hs->buf + o_redo;
+  const uint8_t *d_msgs = w.at_head ? hs->buf : w.msgs ? msgs : hs->buf + o_msgs, *d_extras = w.rest ? extras : hs->buf + o_extras;
+  if (mb && !dev_msgs) HIP_TRY(hipMemcpyAsync(hs->buf + o_msgs, msgs, mb, hipMemcpyHostToDevice, st), 10);
+  if (eb && !w.rest) HIP_TRY(hipMemcpyAsync(hs->buf + o_extras, extras, eb, hipMemcpyHostToDevice, st), 10);
   HIP_TRY(hipMemcpyAsync(d_off, msg_off, (n + 1) * 8, hipMemcpyHostToDevice, st), 10);
   if (extra_off) HIP_TRY(hipMemcpyAsync(d_off + n + 1, extra_off, (n + 1) * 8, hipMemcpyHostToDevice, st), 10);
   HIP_TRY(hipMemsetAsync(d_cnt, 0, 256 * 4, st), 10);
@@ -251,7 +263,7 @@ static int hash_rounds(const uint8_t* domain, const uint8_t* msgs, const uint64_
   HIP_TRY(cs.event(&e1), 10);
   if (split_ms) HIP_TRY(cs.event(&em), 10);
   HIP_TRY(hipEventRecord(e0, st), 10);
-  const HashIn in = {d_bytes, d_off, d_bytes + mb, extra_off ? d_off + n + 1 : nullptr};
+  const HashIn in = {d_msgs, d_off, d_extras, extra_off ? d_off + n + 1 : nullptr};
   const size_t budget = size_t(1) << G::budget_log();
   uint32_t count = (uint32_t)n, base = 0;
   int round = 0;
@@ -273,8 +285,10 @@ static int hash_rounds(const uint8_t* domain, const uint8_t* msgs, const uint64_
   G::finish(dim3(((uint32_t)n + 63) / 64), st, d_cand, d_att, d_out, d_redo, (uint32_t)n);
   HIP_TRY(hipGetLastError(), 10);
   HIP_TRY(hipEventRecord(e1, st), 10);
-  HIP_TRY(hipMemcpyAsync(out_xy, d_out, n * ROW * 8, hipMemcpyDeviceToHost, st), 10);
-  HIP_TRY(hipMemcpyAsync(attempts, d_att, n, hipMemcpyDeviceToHost, st), 10);
+  if (!w.rest) {
+    HIP_TRY(hipMemcpyAsync(out_xy, d_out, n * ROW * 8, hipMemcpyDeviceToHost, st), 10);
+    HIP_TRY(hipMemcpyAsync(attempts, d_att, n, hipMemcpyDeviceToHost, st), 10);
+  }
   HIP_TRY(hipMemcpyAsync(redo.data(), d_redo, n, hipMemcpyDeviceToHost, st), 10);
   HIP_TRY(hipStreamSynchronize(st), 10);
   HIP_TRY(hipEventElapsedTime(&g_hash_ms, e0, e1), 10);
@@ -282,34 +296,66 @@ static int hash_rounds(const uint8_t* domain, const uint8_t* msgs, const uint64_
     HIP_TRY(hipEventElapsedTime(&split_ms[0], e0, em), 10);
     HIP_TRY(hipEventElapsedTime(&split_ms[1], em, e1), 10);
   }
-  // the counter whose cofactor multiple was the identity is skipped like the reference's loop does: continue serially after it
+  // the counter whose cofactor multiple was the identity is skipped like the reference's loop does: continue serially after it.  What lies on
+  // the device is fetched for the flagged row alone, and the row and its counter go back where the caller reads them.
   for (size_t i = 0; i < n; i++) {
     if (!redo[i]) continue;
+    const size_t mlen = msg_off[i + 1] - msg_off[i], elen = extra_off ? extra_off[i + 1] - extra_off[i] : 0;
+    std::vector<uint8_t> hm, he;
+    const uint8_t *m = (dev_msgs ? d_msgs : msgs) + msg_off[i], *e = extra_off ? extras + extra_off[i] : nullptr;
+    if (dev_msgs && mlen) { hm.resize(mlen); HIP_TRY(hipMemcpy(hm.data(), m, mlen, hipMemcpyDeviceToHost), 10); m = hm.data(); }
+    if (w.rest && elen) { he.resize(elen); HIP_TRY(hipMemcpy(he.data(), e, elen, hipMemcpyDeviceToHost), 10); e = he.data(); }
+    uint64_t row[ROW];
+    uint8_t att = 255;
+    if (w.rest) HIP_TRY(hipMemcpy(&att, attempts + i, 1, hipMemcpyDeviceToHost), 10);
+    else att = attempts[i];
     int c = 255;
-    uint64_t* o = out_xy + i * ROW;
-    if (G::serial(domain, msgs + msg_off[i], msg_off[i + 1] - msg_off[i], extra_off ? extras + extra_off[i] : nullptr, extra_off ? extra_off[i + 1] - extra_off[i] : 0,
-                  compat, kh, o, c, attempts[i] + 1, mode, h_gens)) attempts[i] = (uint8_t)c;
-    else { attempts[i] = 255; memset(o, 0, ROW * 8); }
+    if (G::serial(domain, m, mlen, e, elen, compat, kh, row, c, att + 1, mode, h_gens)) att = (uint8_t)c;
+    else { att = 255; memset(row, 0, sizeof row); }
+    if (w.rest) {
+      HIP_TRY(hipMemcpy(out_xy + i * ROW, row, sizeof row, hipMemcpyHostToDevice), 10);
+      HIP_TRY(hipMemcpy(attempts + i, &att, 1, hipMemcpyHostToDevice), 10);
+    } else {
+      memcpy(out_xy + i * ROW, row, sizeof row);
+      attempts[i] = att;
+    }
   }
   return 0;
 }
+static int pedersen_crh_locked(const uint8_t* msgs, const uint64_t* msg_off, size_t n, uint8_t* out48, const EdPoint* gens, size_t ngens, const HashWhere& w, bool out_at_head);
 // The hash step of a protocol mode (units.h): the round loop in the caller's mode, or for CIP22 (mode 3) one CRH per message and then the
 // loops over xof(c || extra || inner)
 template <class G>
 static int hash_step(const uint8_t* domain, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off, size_t n, int compat,
-                     uint64_t* out_xy, uint8_t* attempts, int mode, float* split_ms) {
-  if (mode != 3) return hash_rounds<G>(domain, msgs, msg_off, extras, extra_off, n, compat, out_xy, attempts, mode, split_ms);
+                     uint64_t* out_xy, uint8_t* attempts, int mode, float* split_ms, int dev = 0, void* stream = nullptr) {
+  HashWhere w;
+  w.msgs = w.rest = dev != 0;
+  w.stream = (hipStream_t)stream;
+  if (mode != 3) {
+    size_t ngens = 0;
+    const EdPoint* h_gens = mode == TAI_COMPOSITE ? celo_composite_gens(&ngens) : nullptr;   // before the lock: 0.5 s on first use
+    if (int rc0 = api_enter()) return rc0;
+    std::lock_guard<std::mutex> lk(hash_mu);
+    return hash_rounds_locked<G>(domain, msgs, msg_off, extras, extra_off, n, compat, out_xy, attempts, mode, split_ms, h_gens, ngens, w);
+  }
   if (n == 0) return 0;
   if (!msg_off) return 2;
-  std::vector<uint8_t> inner(n * 48);
+  size_t ngens = 0;
+  const EdPoint* h_gens = celo_composite_gens(&ngens);
+  if (int rc0 = api_enter()) return rc0;
+  std::lock_guard<std::mutex> lk(hash_mu);
+  // the CRH rows stay on the device: the CRH kernel writes them at the head of the scratch, where the round loop reads them as its messages
   std::vector<uint64_t> ioff(n + 1);
   for (size_t i = 0; i <= n; i++) ioff[i] = 48 * i;
-  if (int rc = pedersen_crh_run(msgs, msg_off, n, inner.data())) return rc;
-  return hash_rounds<G>(domain, inner.data(), ioff.data(), extras, extra_off, n, compat, out_xy, attempts, 1, split_ms);
+  HashWhere wc = w;
+  wc.head = (n * 48 + 255) & ~size_t(255);
+  if (int rc = pedersen_crh_locked(msgs, msg_off, n, nullptr, h_gens, ngens, wc, true)) return rc;
+  wc.at_head = true;
+  return hash_rounds_locked<G>(domain, nullptr, ioff.data(), extras, extra_off, n, compat, out_xy, attempts, 1, split_ms, nullptr, 0, wc);
 }
 int hash_to_g1_direct_run(const uint8_t* domain, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off,
-                          size_t n, uint64_t* out_xy, uint8_t* attempts, int mode) {
-  return hash_step<HashG1>(domain, msgs, msg_off, extras, extra_off, n, 0, out_xy, attempts, mode, nullptr);
+                          size_t n, uint64_t* out_xy, uint8_t* attempts, int mode, int dev, void* stream) {
+  return hash_step<HashG1>(domain, msgs, msg_off, extras, extra_off, n, 0, out_xy, attempts, mode, nullptr, dev, stream);
 }
 int hash_to_g2_run(const uint8_t* domain, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off, size_t n, int compat,
                    uint64_t* out_xy, uint8_t* attempts, int mode) {
@@ -351,13 +397,10 @@ k_pedersen_crh(const EdPoint* __restrict__ gens, const uint8_t* __restrict__ msg
   for (int j = 0; j < 48; j++) out[(size_t)i * 48 + j] = h[j];
 }
 
-int pedersen_crh_run(const uint8_t* msgs, const uint64_t* msg_off, size_t n, uint8_t* out48) {
-  size_t ngens = 0;
-  const EdPoint* gens = celo_composite_gens(&ngens);      // before the lock: building the table takes 0.5 s on first use
-  if (int rc0 = api_enter()) return rc0;
-  std::lock_guard<std::mutex> lk(hash_mu);
+// under hash_mu.  out_at_head: the rows stay at the head of the scratch (w.head bytes; out48 is not used)
+static int pedersen_crh_locked(const uint8_t* msgs, const uint64_t* msg_off, size_t n, uint8_t* out48, const EdPoint* gens, size_t ngens, const HashWhere& w, bool out_at_head) {
   if (n == 0) return 0;
-  if (!msg_off || !out48 || n > 0x7fffffffu) return 2;
+  if (!msg_off || (!out48 && !out_at_head) || n > 0x7fffffffu) return 2;
   for (size_t i = 0; i < n; i++) {
     if (msg_off[i + 1] < msg_off[i] || (msg_off[i + 1] - msg_off[i]) * 8 > PEDERSEN_MAX_BITS) return 2;   // the reference panics on longer messages
   }
@@ -365,14 +408,16 @@ int pedersen_crh_run(const uint8_t* msgs, const uint64_t* msg_off, size_t n, uin
   if (mb && !msgs) return 2;
   if (int rcg = ensure_device_gens(gens, ngens)) return rcg;
   EdPoint* d_gens = g_d_gens;
-  const size_t o_off = 0, o_out = ((n + 1) * 8 + 255) & ~size_t(255), o_bytes = o_out + ((n * 48 + 255) & ~size_t(255));
+  const bool to_dev = out_at_head || w.rest;
+  const size_t o_off = w.head, o_out = o_off + (((n + 1) * 8 + 255) & ~size_t(255)), o_bytes = o_out + (to_dev ? 0 : (n * 48 + 255) & ~size_t(255));
   HashScratch* hs = nullptr;
-  if (hash_scratch(o_bytes + mb + 8, &hs)) return 10;
-  CallScope cs(hs->stream);
+  if (hash_scratch(o_bytes + (w.msgs ? 0 : mb + 8), &hs)) return 10;
+  CallScope cs(w.rest ? w.stream : hs->stream);
   const hipStream_t st = cs.stream();
   uint64_t* d_off = (uint64_t*)(hs->buf + o_off);
-  uint8_t *d_out = hs->buf + o_out, *d_bytes = hs->buf + o_bytes;
-  if (mb) HIP_TRY(hipMemcpyAsync(d_bytes, msgs, mb, hipMemcpyHostToDevice, st), 10);
+  uint8_t* d_out = out_at_head ? hs->buf : w.rest ? out48 : hs->buf + o_out;
+  const uint8_t* d_bytes = w.msgs ? msgs : hs->buf + o_bytes;
+  if (mb && !w.msgs) HIP_TRY(hipMemcpyAsync(hs->buf + o_bytes, msgs, mb, hipMemcpyHostToDevice, st), 10);
   HIP_TRY(hipMemcpyAsync(d_off, msg_off, (n + 1) * 8, hipMemcpyHostToDevice, st), 10);
   hipEvent_t e0, e1;
   HIP_TRY(cs.event(&e0), 10);
@@ -381,10 +426,20 @@ int pedersen_crh_run(const uint8_t* msgs, const uint64_t* msg_off, size_t n, uin
   hipLaunchKernelGGL(k_pedersen_crh, dim3(((uint32_t)n + 63) / 64), dim3(64), 0, st, d_gens, d_bytes, d_off, d_out, (uint32_t)n);
   HIP_TRY(hipGetLastError(), 10);
   HIP_TRY(hipEventRecord(e1, st), 10);
-  HIP_TRY(hipMemcpyAsync(out48, d_out, n * 48, hipMemcpyDeviceToHost, st), 10);
+  if (!to_dev) HIP_TRY(hipMemcpyAsync(out48, d_out, n * 48, hipMemcpyDeviceToHost, st), 10);
   HIP_TRY(hipStreamSynchronize(st), 10);
   HIP_TRY(hipEventElapsedTime(&g_hash_ms, e0, e1), 10);
   return 0;
+}
+int pedersen_crh_run(const uint8_t* msgs, const uint64_t* msg_off, size_t n, uint8_t* out48, int dev, void* stream) {
+  size_t ngens = 0;
+  const EdPoint* gens = celo_composite_gens(&ngens);      // before the lock: building the table takes 0.5 s on first use
+  if (int rc0 = api_enter()) return rc0;
+  std::lock_guard<std::mutex> lk(hash_mu);
+  HashWhere w;
+  w.msgs = w.rest = dev != 0;
+  w.stream = (hipStream_t)stream;
+  return pedersen_crh_locked(msgs, msg_off, n, out48, gens, ngens, w, false);
 }
 float hash_last_ms() { return g_hash_ms; }
 int hash_last_rounds() { return g_hash_rounds; }

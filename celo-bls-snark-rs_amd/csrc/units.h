@@ -123,9 +123,11 @@ int wire761_proof_serialize(const uint64_t* a_xyz, const uint64_t* b_xyz, const 
 
 // ---- hash to G1 (unit_hash.hip; the composite hasher's generator table is seam_hash.hip's).  mode, for both groups: 0 direct, 1 the CIP22
 // tail (msgs are the inner CRHs), 2 composite, 3 composite CIP22: one CRH per message (pedersen_crh_run), then the tail over the 48-byte inners
+// dev = 1 (G1 and the CRH): the bytes, rows and attempts are DEVICE pointers and the work is enqueued on the caller's stream; the offsets are host
+// arrays in both forms, and both return after the work has drained
 int hash_to_g1_direct_run(const uint8_t* domain, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off, size_t n, uint64_t* out_xy,
-                          uint8_t* attempts, int mode);
-int pedersen_crh_run(const uint8_t* msgs, const uint64_t* msg_off, size_t n, uint8_t* out48);
+                          uint8_t* attempts, int mode, int dev = 0, void* stream = nullptr);
+int pedersen_crh_run(const uint8_t* msgs, const uint64_t* msg_off, size_t n, uint8_t* out48, int dev = 0, void* stream = nullptr);
 // ---- hash to G2 (unit_hash.hip): the same round loop, rows of 24 limbs; compat 0 / 1: the flags as the XOF gives them / the deployed remap
 int hash_to_g2_run(const uint8_t* domain, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off, size_t n, int compat,
                    uint64_t* out_xy, uint8_t* attempts, int mode);
@@ -180,6 +182,22 @@ int epoch_public_inputs(const EpochBlocks* first, const EpochBlocks* last, size_
 int verify_epoch_proofs(const VerifyingKey* vk, const uint8_t* proofs, const EpochBlocks* first, const EpochBlocks* last, size_t m, int mode, const uint32_t* key,
                         uint8_t* out_ok, uint8_t* out_status);
 void epoch_last(float ms[8]);
+// for unit_transitions.hip: the refusals of a set of blocks (2, no device touched), and the blocks on the device up to their packed bytes of
+// kind `kind` (block b at out_off[b]; a block of length 0 is left out), enqueued on cs.stream(); times into log in the order of epoch_last
+struct EpochStaged {
+  const uint16_t* index; const uint8_t* round; const uint32_t* mns; const uint32_t* key_off; const uint8_t* ee; const uint8_t* pe;   // the fields, nb each
+  const uint64_t* rows; const uint8_t* inf;      // key_off[nb] decoded keys (24 u64 each) and their identity flags
+  const uint8_t* status;                         // nb: 1 = a key of the block does not decode or lies outside G2
+  uint8_t* bytes;                                // out_off[nb] bytes
+};
+int epoch_refuse_blocks(const EpochBlocks& b, size_t nb, bool need_round);
+int epoch_stage_bytes(CallScope& cs, EvLog& log, const EpochBlocks& b, size_t nb, int kind, const uint64_t* out_off, EpochStaged* out);
+
+// ---- chains of epoch transitions to verdicts (unit_transitions.hip; transitions.h)
+int verify_epoch_transitions(const EpochBlocks* blocks, size_t nb, const uint32_t* chain_off, size_t n_chains, const uint8_t* bits, const uint8_t* sig48,
+                             const uint8_t* domain, const uint64_t neg_g2_xy[24], int mode, uint8_t* out_ok, uint8_t* out_status, uint8_t* out_chain_ok, uint8_t* out_crh,
+                             uint8_t* out_attempts, uint64_t* out_asig_xy, uint8_t* out_asig_inf);
+void transitions_last(int* path, float ms[8]);
 
 // ---- constraint matrices (unit_r1cs.hip)
 int r1cs_load(int curve, size_t m, size_t n_vars, size_t n_inputs, const uint64_t* const row_ptr[3], const uint32_t* const col[3], const uint64_t* const val[3],

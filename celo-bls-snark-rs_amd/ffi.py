@@ -61,6 +61,7 @@ EXPORTS = [
     "groth16_r1cs_check", "groth16_r1cs_qap_at_tau", "groth16_r1cs_qap_at_tau_dev", "groth16_prove_r1cs_with_key", "groth16_setup_r1cs_bw6_761",
     "groth16_setup_r1cs_bls12_377", "celo_amd_r1cs_last_timings",
     "hash_to_g1_direct_bls12_377", "hash_to_g1_composite_bls12_377", "hash_to_g1_cip22_tail_bls12_377", "composite_crh_bls12_377",
+    "hash_to_g1_direct_bls12_377_dev", "hash_to_g1_composite_bls12_377_dev", "hash_to_g1_cip22_tail_bls12_377_dev", "composite_crh_bls12_377_dev",
     "celo_amd_hash_last_ms", "celo_amd_hash_last_rounds",
     "hash_to_g2_direct_bls12_377", "hash_to_g2_cip22_tail_bls12_377", "hash_to_g2_composite_bls12_377", "hash_to_g2_one_bls12_377",
     "celo_amd_hash_g2_set_lane_budget_log", "celo_amd_hash_g2_last_split",
@@ -75,7 +76,7 @@ EXPORTS = [
     "aggregate_by_bitmap_bls12_377_g1", "aggregate_by_bitmap_bls12_377_g2", "aggregate_by_bitmap_bls12_377_g1_dev", "aggregate_by_bitmap_bls12_377_g2_dev",
     "verify_aggregated_seals_bls12_377", "celo_amd_aggregate_set_lanes", "celo_amd_aggregate_set_complement", "celo_amd_seals_last",
     "epoch_encoded_size", "epoch_encode_blocks_bls12_377", "epoch_encode_blocks_bls12_377_dev", "epoch_public_inputs_bw6_761", "epoch_public_inputs_bw6_761_dev",
-    "verify_epoch_proofs_bw6_761", "celo_amd_epoch_last",
+    "verify_epoch_proofs_bw6_761", "celo_amd_epoch_last", "verify_epoch_transitions_bls12_377", "celo_amd_transitions_last",
 ]
 
 _lib = None
@@ -1187,6 +1188,28 @@ def composite_crh(messages):
     return [out[i].tobytes() for i in range(n)]
 
 
+def composite_crh_dev(d_msgs, msg_off, n, d_out48, stream=0):
+    """composite_crh_bls12_377_dev: message bytes and the n x 48 output on the device (data pointers), msg_off a host array.  Returns the code."""
+    off = None if msg_off is None else np.ascontiguousarray(msg_off, dtype=np.uint64).reshape(-1)
+    return lib().composite_crh_bls12_377_dev(C.c_void_p(d_msgs or None), _p(off), C.c_size_t(n), C.c_void_p(d_out48 or None), C.c_void_p(stream))
+
+
+def hash_to_g1_dev(domain, d_msgs, msg_off, d_extras, extra_off, n, d_out_xy, d_attempts, mode=0, stream=0):
+    """The hash_to_g1_*_bls12_377_dev entries: bytes, rows (n x 12 u64) and attempts (n) on the device (data pointers; d_extras 0 / None with
+    extra_off None = no extra data), the offsets host arrays.  mode 0 direct, 1 the CIP22 tail (d_msgs are the inner CRHs), 2 composite, 3 composite
+    CIP22.  Returns the code (0, or 2: nothing written)."""
+    moff = None if msg_off is None else np.ascontiguousarray(msg_off, dtype=np.uint64).reshape(-1)
+    eoff = None if extra_off is None else np.ascontiguousarray(extra_off, dtype=np.uint64).reshape(-1)
+    dom = None if domain is None else np.frombuffer(bytes(domain), dtype=np.uint8)
+    args = (_p(dom), C.c_void_p(d_msgs or None), _p(moff), C.c_void_p(d_extras or None), _p(eoff), C.c_size_t(n))
+    outs = (C.c_void_p(d_out_xy or None), C.c_void_p(d_attempts or None), C.c_void_p(stream))
+    if mode in (2, 3):
+        return lib().hash_to_g1_composite_bls12_377_dev(*args, C.c_int(mode - 2), *outs)
+    if mode not in (0, 1):
+        raise ValueError("hash_to_g1_dev: mode is 0 .. 3")
+    return (lib().hash_to_g1_cip22_tail_bls12_377_dev if mode == 1 else lib().hash_to_g1_direct_bls12_377_dev)(*args, *outs)
+
+
 def normalize(group, jac):
     """Jacobian -> affine for n points in one GPU launch (include/celo_bls_amd.h: normalize_bls12_377_g1/_g2, normalize_bw6_761_g1/_g2).
     group: "g1" | "g2" (BLS12-377) | "bw6_761_g1" | "bw6_761_g2".  jac: (n, 18 | 36) uint64; returns (xy (n, 12 | 24) uint64, inf (n,) uint8)."""
@@ -1559,6 +1582,50 @@ def epoch_last():
     ms = (C.c_float * 8)()
     assert lib().celo_amd_epoch_last(ms) == 0
     return dict(zip(("decode", "sums", "pack", "hash", "transfers", "verify", "wall"), list(ms)[:7]))
+
+
+TRANSITION_STATUS = ("accepted", "bad key", "bad signing set", "index", "key count", "parent entropy", "threshold", "padding key selected", "bad signature",
+                     "no counter", "product")
+
+
+def verify_epoch_transitions(blocks, chain_off, bits, sigs, domain, neg_g2_xy, mode=0, want=("status", "chain_ok", "crh", "attempts", "asig")):
+    """Chains of epoch transitions to verdicts (include/celo_bls_amd.h: verify_epoch_transitions_bls12_377).  blocks: an EpochBlocks (round
+    required); chain_off (n_chains + 1,) uint32; bits (key_off[nb],) uint8, the bytes under block p selecting the signers of block p + 1; sigs
+    (nb, 48) uint8; mode 0 each, 1 chain product; want: the optional outputs to ask for.  Returns {ok (nb,), status (nb,), chain_ok (n_chains,),
+    crh (nb, 48), attempts (nb,), asig_xy (n_chains, 12) uint64, asig_inf (n_chains,)}, the entries not asked for None.  Raises ValueError on code 2."""
+    nb = blocks.nb
+    co = np.ascontiguousarray(chain_off, dtype=np.uint32).reshape(-1)
+    nc = co.shape[0] - 1
+    b = np.ascontiguousarray(bits, dtype=np.uint8).reshape(-1)
+    sg = np.ascontiguousarray(sigs, dtype=np.uint8).reshape(-1, 48)
+    if nc < 0 or sg.shape[0] != nb or b.size != (int(blocks.key_off[-1]) if nb else 0):
+        raise ValueError("verify_epoch_transitions_bls12_377: chain_off, bits and signatures do not match the blocks")
+    if b.size == 0:
+        b = np.zeros(1, dtype=np.uint8)
+    if sg.shape[0] == 0:
+        sg = np.zeros((1, 48), dtype=np.uint8)
+    ng2 = np.ascontiguousarray(neg_g2_xy, dtype=np.uint64).reshape(24)
+    dom = np.frombuffer(bytes(domain), dtype=np.uint8)
+    assert dom.size == 8
+    ok = np.zeros(nb, dtype=np.uint8)
+    st = np.zeros(nb, dtype=np.uint8) if "status" in want else None
+    cok = np.zeros(max(nc, 0), dtype=np.uint8) if "chain_ok" in want else None
+    crh = np.zeros((nb, 48), dtype=np.uint8) if "crh" in want else None
+    att = np.zeros(nb, dtype=np.uint8) if "attempts" in want else None
+    axy = np.zeros((max(nc, 0), 12), dtype=np.uint64) if "asig" in want else None
+    ainf = np.zeros(max(nc, 0), dtype=np.uint8) if "asig" in want else None
+    _epoch_rc("verify_epoch_transitions_bls12_377", lib().verify_epoch_transitions_bls12_377(
+        C.byref(blocks.c), C.c_size_t(nb), _p(co), C.c_size_t(max(nc, 0)), _p(b), _p(sg), _p(dom), _p(ng2), C.c_int(mode), _p(ok), _p(st), _p(cok), _p(crh), _p(att),
+        _p(axy), _p(ainf)))
+    return {"ok": ok, "status": st, "chain_ok": cok, "crh": crh, "attempts": att, "asig_xy": axy, "asig_inf": ainf}
+
+
+def transitions_last():
+    """the last verify_epoch_transitions call: {path (0 each, 1 every chain product held, 2 a chain fell back), ms: decode, sums, pack, hash, transfers,
+    products, wall, signatures}"""
+    path, ms = C.c_int(0), (C.c_float * 8)()
+    assert lib().celo_amd_transitions_last(C.byref(path), ms) == 0
+    return {"path": path.value, "ms": dict(zip(("decode", "sums", "pack", "hash", "transfers", "products", "wall", "signatures"), list(ms)))}
 
 
 class SetupError(RuntimeError):

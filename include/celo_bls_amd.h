@@ -603,6 +603,24 @@ int hash_to_g1_composite_bls12_377(const uint8_t domain[8], const uint8_t* msgs,
  * signatures.rs:169, is the one-message form).  out48: n x 48 bytes, the affine x coordinate little-endian.  A message longer
  * than 93 * 560 * 3 bits is an error for the whole call (the reference panics). */
 int composite_crh_bls12_377(const uint8_t* msgs, const uint64_t* msg_off /* n+1 */, size_t n, uint8_t* out48 /* n x 48 */);
+/* The device-resident forms of the four entries above, for a caller whose messages are made on the GPU and whose rows are read there (the
+ * chain check below is one): d_msgs / d_inner, d_extras, d_out48, d_out_xy and d_attempts are DEVICE pointers; the offsets stay HOST arrays,
+ * because they size the call and are checked before the device is used.  The work is enqueued on hip_stream (NULL: the null stream), behind
+ * whatever the caller has enqueued there, and the call returns after it has drained.  Results, refusals and return codes are those of the
+ * host forms, byte for byte; a CIP22 call (cip22 != 0) keeps its 48-byte CRH rows on the device between its two steps, and
+ * d_out48 of composite_crh_bls12_377_dev can be handed to hash_to_g1_cip22_tail_bls12_377_dev as d_inner with inner_off[i] = 48 i.
+ * A message whose cofactor multiple is the identity (probability 2^-125) is finished by the host's serial loop: that message alone is
+ * fetched, and its row and counter are written back. */
+int composite_crh_bls12_377_dev(const void* d_msgs, const uint64_t* msg_off /* n+1, host */, size_t n, void* d_out48 /* n x 48 */, void* hip_stream);
+int hash_to_g1_direct_bls12_377_dev(const uint8_t domain[8], const void* d_msgs, const uint64_t* msg_off /* n+1, host */, const void* d_extras,
+                                    const uint64_t* extra_off /* n+1 or NULL, host */, size_t n, void* d_out_xy /* n x 12 u64 */, void* d_attempts /* n */,
+                                    void* hip_stream);
+int hash_to_g1_cip22_tail_bls12_377_dev(const uint8_t domain[8], const void* d_inner, const uint64_t* inner_off /* n+1, host */, const void* d_extras,
+                                        const uint64_t* extra_off /* n+1 or NULL, host */, size_t n, void* d_out_xy /* n x 12 u64 */, void* d_attempts /* n */,
+                                        void* hip_stream);
+int hash_to_g1_composite_bls12_377_dev(const uint8_t domain[8], const void* d_msgs, const uint64_t* msg_off /* n+1, host */, const void* d_extras,
+                                       const uint64_t* extra_off /* n+1 or NULL, host */, size_t n, int cip22, void* d_out_xy /* n x 12 u64 */,
+                                       void* d_attempts /* n */, void* hip_stream);
 /* ---- batched hash-to-G2: the same hashers and loops onto the twist over Fq2 - TryAndIncrement<H, G2> / TryAndIncrementCIP22<H, G2>
  * (try_and_increment.rs:63-140, try_and_increment_cip22.rs:75-135; the reference pins ten outputs, hash_to_curve/mod.rs:490-513).  A candidate
  * is 96 XOF bytes (hash_length(96) = 96: every node offset carries 96); the winning point is multiplied by the 502-bit cofactor of the twist.
@@ -901,6 +919,63 @@ int epoch_public_inputs_bw6_761_dev(const celo_epoch_blocks* first, const celo_e
 int verify_epoch_proofs_bw6_761(const void* vk, const uint8_t* proofs /* m x 288 */, const celo_epoch_blocks* first, const celo_epoch_blocks* last, size_t m,
                                 int mode /* 0 each, 1 combined */, const uint32_t* key /* 8, or NULL */, uint8_t* out_ok /* m */, uint8_t* out_status /* m, may be NULL */);
 int celo_amd_epoch_last(float ms[8]);
+
+/* ---- chains of epoch transitions to verdicts: what epoch_snark::prove holds (crates/epoch-snark/src/api/prover.rs:22-82: an initial EpochBlock
+ * and a list of EpochTransition { block, aggregate_signature, bitmap }), checked against what the circuit ValidatorSetUpdate enforces
+ * (gadgets/epochs.rs:97-283, single_update.rs:79-135, epoch_data.rs:223-233, bls-gadgets/src/bls.rs:138-191) BEFORE a proof is made -
+ * create_proof_no_zk does not check satisfaction, and a full node runs the same check over every epoch header it syncs.  One call: keys
+ * decoded once, blocks encoded in the inner CIP22 form, CRH, CIP22 tail, masked key sums, signatures and products all stay on the device.
+ *
+ * Layout: everything is indexed by block.  Chain c owns blocks [chain_off[c], chain_off[c+1]); the first is its initial epoch, every other
+ * block b is a transition with predecessor p = b - 1.  bits[key_off[p] + j] != 0: key j of block p signed block p + 1 (any non-zero byte; the
+ * bytes under the last block of a chain are ignored).  sig48[b]: the aggregate signature over block b, compressed (rows of initial blocks are
+ * ignored).  blocks: celo_epoch_blocks as above, either keys_form, `round` required.  domain: the 8 bytes of the hasher's personalisation;
+ * neg_g2_xy: -g2 as for verify_aggregated_seals_bls12_377.
+ *
+ * out_status[b], the first that applies (out_ok[b] = 1 iff it is 0; an initial block can only get 0 or 1):
+ *    0  accepted
+ *    1  a key of block b does not decode or lies outside G2 (epoch_encode_blocks status 1)
+ *    2  block p has status 1: the signing set is unknown
+ *    3  index[b] != index[p] + 1, compared as integers, no wrap; a transition with index 0 always lands here (the circuit's dummy padding is
+ *       the prover's business, not an input)                                                     epoch_data.rs:223-233
+ *    4  n_keys(b) != n_keys(p): the circuit's num_validators is fixed                            single_update.rs:92
+ *    5  the chain's INITIAL block has a non-zero epoch_entropy and parent_entropy[b] != epoch_entropy[p] (16 bytes; a NULL array is all zero)
+ *                                                                                                epochs.rs:193, single_update.rs:104-107
+ *    6  signers < n_keys(p) - max_non_signers[p] (saturating at 0), or no signer at all          bls.rs:187
+ *    7  a SELECTED key of block p equals the padding key, the G2 generator (an unselected one is legal)    bls.rs:147-148, epoch_block.rs:94-96
+ *    8  the signature does not decode or lies outside G1
+ *    9  the hash found no counter
+ *   10  the product is not one
+ *
+ * mode 0, "is every seal genuine": one two-pair product per clean transition, e(sig_b, -g2) e(H_b, apk_b); out_chain_ok[c] is the AND over
+ * the chain's blocks.
+ * mode 1, "will the proof verify": the circuit's own statement (epochs.rs verify_signature, unweighted aggregation).  Every chain whose
+ * blocks are all free of statuses 1 to 9 is ONE product, e(sum_b sig_b, -g2) prod_b e(H_b, apk_b), all chains in one ragged call of the
+ * pairing engine.  A chain whose product holds has status 0 throughout and out_chain_ok[c] = 1; one whose product fails has its transitions
+ * run as in mode 0 to place status 10.  A chain with a status in 1 to 9 is not multiplied: its clean blocks are checked as in mode 0.
+ * THE CONSEQUENCE: mode 1 accepts a chain whose signatures are individually wrong but sum correctly (sig_a + D and sig_b - D), because the
+ * circuit does too.  It does not say that every seal is genuine; mode 0 does.
+ *
+ * Optional outputs (NULL to skip), what the prover takes away: out_crh[b] the 48-byte CRH of block b's inner encoding (the message_bits of
+ * the hash helper, prover.rs:92-106); out_attempts[b] the hash counter (the hash-to-group gadget's witness); out_asig_xy[c] / out_asig_inf[c]
+ * the sum of the chain's signatures that decoded into G1 (prover.rs:62), an affine row of 12 u64 and an identity flag (the row is zero when
+ * the flag is set).  Rows of initial blocks are zero.
+ *
+ * Returns 0, also for nb == 0; 2, with nothing written and before any use of the device, for a NULL required pointer, chain_off not
+ * increasing from 0 to nb (an empty chain included), mode not in {0, 1}, the refusals of epoch_encode_blocks (key counts, nb > 2^24), or a
+ * block whose inner encoding + 8 bytes exceeds the Pedersen table of 93 * 560 * 3 bits (max(n_keys, max_validators) <= 206 fits; the reference
+ * panics); 100 / 1 / 10 as elsewhere.  Calls from several threads are serialised.  Not covered by tests: more than one device; a hash that
+ * exhausts its counters (no such input is known). */
+int verify_epoch_transitions_bls12_377(const celo_epoch_blocks* blocks, size_t nb, const uint32_t* chain_off /* n_chains + 1 */, size_t n_chains,
+                                       const uint8_t* bits /* key_off[nb] bytes */, const uint8_t* sig48 /* nb x 48 */, const uint8_t domain[8],
+                                       const uint64_t neg_g2_xy[24], int mode /* 0 each, 1 chain product */, uint8_t* out_ok /* nb */,
+                                       uint8_t* out_status /* nb or NULL */, uint8_t* out_chain_ok /* n_chains or NULL */, uint8_t* out_crh /* nb x 48 or NULL */,
+                                       uint8_t* out_attempts /* nb or NULL */, uint64_t* out_asig_xy /* n_chains x 12 or NULL */,
+                                       uint8_t* out_asig_inf /* n_chains or NULL */);
+/* the last verify_epoch_transitions call: *path 0 = each, 1 = chain products and every one held, 2 = at least one chain fell back to its
+ * transitions (-1 before any call); ms in the slots of celo_amd_epoch_last: [0] key decoding, [1] masked sums (keys, then signatures), [2]
+ * packing, [3] CRH + CIP22 tail, [4] transfers, [5] the products, [6] wall time of the call, [7] signature decoding and the status kernel */
+int celo_amd_transitions_last(int* path, float ms[8]);
 
 /* ---- R1CS matrices on the device: the step of ark-groth16 0.1 between cs.to_matrices() and the entry points above - the constraint evaluation
  * of R1CStoQAP::witness_map (prover) and R1CStoQAP::instance_map_with_evaluation (setup).  Synthesis (running the gadgets) stays with the caller;
