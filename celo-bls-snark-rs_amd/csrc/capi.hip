@@ -522,6 +522,8 @@ int hash_to_g1_composite_bls12_377_dev(const uint8_t domain[8], const void* d_ms
 }
 int celo_amd_hash_last_ms(float* ms) { if (!ms) return 2; *ms = hash_last_ms(); return 0; }
 int celo_amd_hash_last_rounds(int* rounds) { if (!rounds) return 2; *rounds = hash_last_rounds(); return 0; }
+int celo_amd_crh_set_lanes(int lanes) { return crh_set_lanes(lanes); }
+int celo_amd_crh_last_lanes(int* lanes) { if (!lanes) return 2; *lanes = crh_last_lanes(); return 0; }
 int normalize_bls12_377_g1(const uint64_t* jac, size_t n, uint64_t* out_xy, uint8_t* inf) { return wire_normalize(0, jac, n, out_xy, inf); }
 int normalize_bls12_377_g2(const uint64_t* jac, size_t n, uint64_t* out_xy, uint8_t* inf) { return wire_normalize(1, jac, n, out_xy, inf); }
 // ---- batched fixed-base scalar multiplication and Groth16 setup (unit_setup.hip)

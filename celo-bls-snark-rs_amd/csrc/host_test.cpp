@@ -446,6 +446,26 @@ int ht_pedersen_crh(const uint64_t* gens_ark, size_t nchunks, const uint8_t* msg
   pedersen_crh(gens.data(), msg, len, out48);
   return 0;
 }
+// k_pedersen_crh_lanes of unit_hash_lanes.hip in host loops: the L lane sums one after the other, their partials folded through a buffer of L slots
+// in the kernel's rounds, lane 0 finishing.  L: a power of two from 1 to 256 (-2 otherwise)
+int ht_pedersen_crh_lanes(const uint64_t* gens_ark, size_t nchunks, const uint8_t* msg, size_t len, int L, uint8_t* out48) {
+  if ((len * 8 + 2) / 3 > nchunks || !crh_lanes_ok(L)) return -2;
+  const std::vector<EdPoint> gens = ht_load_gens(gens_ark, nchunks);
+  std::vector<EdPoint> acc(L, ed_zero());
+  std::vector<uint4> slots((size_t)L * CRH_SLOT_WORDS / 4);
+  uint32_t* sl = reinterpret_cast<uint32_t*>(slots.data());
+  for (int l = 0; l < L; l++) {
+    acc[l] = pedersen_crh_lane_sum(gens.data(), PtrBytes{msg, len}, (uint32_t)l, (uint32_t)L);
+    ed_store(sl + (size_t)l * CRH_SLOT_WORDS, acc[l]);
+  }
+  for (int s = L >> 1; s; s >>= 1) {
+    for (int l = 0; l < s; l++) acc[l] = ed_add(acc[l], ed_load(sl + (size_t)(l + s) * CRH_SLOT_WORDS));
+    if (s > 1) for (int l = 0; l < s; l++) ed_store(sl + (size_t)l * CRH_SLOT_WORDS, acc[l]);
+  }
+  pedersen_crh_finish(acc[0], out48);
+  return 0;
+}
+uint32_t ht_crh_pick_lanes(uint32_t request, size_t max_chunks, size_t n) { return crh_pick_lanes(request, max_chunks, n); }
 // scale_by_cofactor of one affine curve point (ark limbs): 1 and the affine multiple, 0 when the multiple is the identity (points of the
 // cofactor subgroup: what k_hash_finish flags for the serial loop)
 int ht_tai_finish(const uint64_t* xy, uint64_t* out_xy) {

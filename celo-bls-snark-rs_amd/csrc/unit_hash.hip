@@ -173,6 +173,8 @@ static int hash_scratch(size_t need, HashScratch** out, size_t keep = 0) {
 struct HashWhere { bool msgs = false, rest = false, at_head = false; hipStream_t stream = nullptr; size_t head = 0; };
 static float g_hash_ms = 0.f;
 static int g_hash_rounds = 0;
+static int g_crh_last_lanes = 0;                // the width of the last CRH kernel (under hash_mu; celo_amd_crh_last_lanes)
+static std::atomic<int> g_crh_lanes{0};         // 0 = the rule (crh_pick_lanes), else 1, 2, 4, .. 256 (celo_amd_crh_set_lanes)
 
 static float g_hash_g2_ms[2] = {0.f, 0.f};      // the last G2 call's candidate rounds / finish kernel
 static std::atomic<int> g_g2_budget_log{17};    // celo_amd_hash_g2_set_lane_budget_log
@@ -396,14 +398,19 @@ k_pedersen_crh(const EdPoint* __restrict__ gens, const uint8_t* __restrict__ msg
   pedersen_crh(gens, msgs + off[i], (size_t)(off[i + 1] - off[i]), h);
   for (int j = 0; j < 48; j++) out[(size_t)i * 48 + j] = h[j];
 }
+// (the many-lane form, k_pedersen_crh_lanes, is a unit of its own, unit_hash_lanes.hip: in this unit's code object it cost k_pedersen_crh 4 % at
+// 65 536 x 127 B)
 
 // under hash_mu.  out_at_head: the rows stay at the head of the scratch (w.head bytes; out48 is not used)
 static int pedersen_crh_locked(const uint8_t* msgs, const uint64_t* msg_off, size_t n, uint8_t* out48, const EdPoint* gens, size_t ngens, const HashWhere& w, bool out_at_head) {
   if (n == 0) return 0;
   if (!msg_off || (!out48 && !out_at_head) || n > 0x7fffffffu) return 2;
+  size_t max_len = 0;
   for (size_t i = 0; i < n; i++) {
     if (msg_off[i + 1] < msg_off[i] || (msg_off[i + 1] - msg_off[i]) * 8 > PEDERSEN_MAX_BITS) return 2;   // the reference panics on longer messages
+    if (msg_off[i + 1] - msg_off[i] > max_len) max_len = msg_off[i + 1] - msg_off[i];
   }
+  const uint32_t L = crh_pick_lanes((uint32_t)g_crh_lanes.load(), (max_len * 8 + 2) / 3, n);   // one width per call, from the longest message
   const size_t mb = msg_off[n];
   if (mb && !msgs) return 2;
   if (int rcg = ensure_device_gens(gens, ngens)) return rcg;
@@ -423,12 +430,17 @@ static int pedersen_crh_locked(const uint8_t* msgs, const uint64_t* msg_off, siz
   HIP_TRY(cs.event(&e0), 10);
   HIP_TRY(cs.event(&e1), 10);
   HIP_TRY(hipEventRecord(e0, st), 10);
-  hipLaunchKernelGGL(k_pedersen_crh, dim3(((uint32_t)n + 63) / 64), dim3(64), 0, st, d_gens, d_bytes, d_off, d_out, (uint32_t)n);
+  if (L == 1) hipLaunchKernelGGL(k_pedersen_crh, dim3(((uint32_t)n + 63) / 64), dim3(64), 0, st, d_gens, d_bytes, d_off, d_out, (uint32_t)n);
+  else {
+    const uint32_t per = CRH_BLOCK / L;         // messages per workgroup
+    crh_lanes_launch((uint32_t)((n + per - 1) / per), st, d_gens, d_bytes, d_off, d_out, (uint32_t)n, L);
+  }
   HIP_TRY(hipGetLastError(), 10);
   HIP_TRY(hipEventRecord(e1, st), 10);
   if (!to_dev) HIP_TRY(hipMemcpyAsync(out48, d_out, n * 48, hipMemcpyDeviceToHost, st), 10);
   HIP_TRY(hipStreamSynchronize(st), 10);
   HIP_TRY(hipEventElapsedTime(&g_hash_ms, e0, e1), 10);
+  g_crh_last_lanes = (int)L;
   return 0;
 }
 int pedersen_crh_run(const uint8_t* msgs, const uint64_t* msg_off, size_t n, uint8_t* out48, int dev, void* stream) {
@@ -440,6 +452,15 @@ int pedersen_crh_run(const uint8_t* msgs, const uint64_t* msg_off, size_t n, uin
   w.msgs = w.rest = dev != 0;
   w.stream = (hipStream_t)stream;
   return pedersen_crh_locked(msgs, msg_off, n, out48, gens, ngens, w, false);
+}
+int crh_set_lanes(int lanes) {
+  if (lanes != 0 && !crh_lanes_ok(lanes)) return 2;
+  g_crh_lanes.store(lanes);
+  return 0;
+}
+int crh_last_lanes() {
+  std::lock_guard<std::mutex> lk(hash_mu);
+  return g_crh_last_lanes;
 }
 float hash_last_ms() { return g_hash_ms; }
 int hash_last_rounds() { return g_hash_rounds; }

@@ -136,6 +136,10 @@ int hash_g2_set_lane_budget_log(int log);
 void hash_g2_last_split(float ms[2]);
 float hash_last_ms();
 int hash_last_rounds();
+// unit_hash_lanes.hip: k_pedersen_crh_lanes on st, `grid` workgroups of CRH_BLOCK lanes with L lanes per message (L = 2 .. 256; 64 KB of dynamic LDS)
+void crh_lanes_launch(uint32_t grid, hipStream_t st, const EdPoint* gens, const uint8_t* msgs, const uint64_t* off, uint8_t* out, uint32_t n, uint32_t L);
+int crh_set_lanes(int lanes);                    // lanes per message of the CRH kernel: 0 = the rule (pedersen.h crh_pick_lanes), else 1, 2, 4 .. 256
+int crh_last_lanes();                            // the width the last CRH kernel ran with
 const EdPoint* celo_composite_gens(size_t* count);
 
 // ---- batched fixed-base scalar multiplication and Groth16 setup (unit_setup.hip)

@@ -62,7 +62,7 @@ EXPORTS = [
     "groth16_setup_r1cs_bls12_377", "celo_amd_r1cs_last_timings",
     "hash_to_g1_direct_bls12_377", "hash_to_g1_composite_bls12_377", "hash_to_g1_cip22_tail_bls12_377", "composite_crh_bls12_377",
     "hash_to_g1_direct_bls12_377_dev", "hash_to_g1_composite_bls12_377_dev", "hash_to_g1_cip22_tail_bls12_377_dev", "composite_crh_bls12_377_dev",
-    "celo_amd_hash_last_ms", "celo_amd_hash_last_rounds",
+    "celo_amd_hash_last_ms", "celo_amd_hash_last_rounds", "celo_amd_crh_set_lanes", "celo_amd_crh_last_lanes",
     "hash_to_g2_direct_bls12_377", "hash_to_g2_cip22_tail_bls12_377", "hash_to_g2_composite_bls12_377", "hash_to_g2_one_bls12_377",
     "celo_amd_hash_g2_set_lane_budget_log", "celo_amd_hash_g2_last_split",
     "groth16_vk_load_bw6_761", "groth16_vk_load_bw6_761_serialized", "groth16_vk_free", "groth16_verify_batch_bw6_761",
@@ -1171,6 +1171,23 @@ def hash_last_rounds():
     r = C.c_int(0)
     assert lib().celo_amd_hash_last_rounds(C.byref(r)) == 0
     return r.value
+
+
+CRH_LANES = (1, 2, 4, 8, 16, 32, 64, 128, 256)   # the widths celo_amd_crh_set_lanes accepts besides 0 (csrc/pedersen.h)
+
+
+def crh_set_lanes(lanes):
+    """lanes per message of the CRH kernel (0 = the rule of csrc/pedersen.h, else one of CRH_LANES); needs no device"""
+    rc = lib().celo_amd_crh_set_lanes(C.c_int(lanes))
+    if rc != 0:
+        raise ValueError("celo_amd_crh_set_lanes(%d) failed with code %d" % (lanes, rc))
+
+
+def crh_last_lanes():
+    """the width the last CRH kernel of this process ran with (0 before the first)"""
+    lanes = C.c_int(0)
+    assert lib().celo_amd_crh_last_lanes(C.byref(lanes)) == 0
+    return lanes.value
 
 
 def composite_crh(messages):

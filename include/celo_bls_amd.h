@@ -651,6 +651,16 @@ int celo_amd_hash_last_ms(float* ms);
 /* candidate rounds (launches of the try-and-increment kernel) of the last hash_to_g1_* or hash_to_g2_* call that hashed at least one
  * message: each round gives every message still open 1, 2, 4, 8 or 16 adjacent counters, the width chosen from how many are open */
 int celo_amd_hash_last_rounds(int* rounds);
+/* Lanes per message of the CRH kernel behind composite_crh_bls12_377[_dev], the CIP22 composite entries of both groups and every pipeline
+ * that hashes through them (signing, aggregated seals, chains of epoch transitions): lane l of L sums the chunks l (mod L) of its message
+ * and the L partial sums are folded in the workgroup; the hash is the x of a sum in a group, so every width gives the same 48 bytes.
+ * 0 (the default) = the rule: L = min(smallest power of two >= chunks of the longest message / 32, largest power of two <= 2^16 / n),
+ * one width per call; a call of 2^16 messages or more runs one lane per message.  1, 2, 4 ... 256 force a width (halved while n x L
+ * lanes exceed a 31-bit grid of workgroups); anything else returns 2 and changes nothing.  Needs no device.  Not used by the per-attempt
+ * CRH of the composite mode without CIP22, which stays one lane per attempt. */
+int celo_amd_crh_set_lanes(int lanes);
+/* the width the last CRH kernel of this process ran with (0 before the first); NULL returns 2.  Needs no device. */
+int celo_amd_crh_last_lanes(int* lanes);
 
 /* ---- plain sums of k Jacobian points (host pointers, arkworks layout; host-side, for small k): the fold of per-GPU
  * partial MSM results and small aggregates — Signature::aggregate / PublicKey::aggregate
