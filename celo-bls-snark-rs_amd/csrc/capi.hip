@@ -665,7 +665,12 @@ int groth16_r1cs_qap_at_tau_dev(const void* r1cs, unsigned log_n, const uint64_t
 int groth16_prove_r1cs_with_key(const void* key, const void* r1cs, const uint64_t* z, unsigned log_n, const uint64_t* omega, const uint64_t* omega_inv,
                                 const uint64_t* coset, const uint64_t* coset_inv, const uint64_t* size_inv, const uint64_t* vanishing_inv, uint64_t* out_a,
                                 uint64_t* out_b, uint64_t* out_c) {
-  return groth16_prove_r1cs((const ProvingKey*)key, (const R1cs*)r1cs, z, log_n, omega, omega_inv, coset, coset_inv, size_inv, vanishing_inv, out_a, out_b, out_c);
+  return groth16_prove_r1cs((const ProvingKey*)key, (const R1cs*)r1cs, z, 0, log_n, omega, omega_inv, coset, coset_inv, size_inv, vanishing_inv, out_a, out_b, out_c);
+}
+int groth16_prove_r1cs_with_key_dev(const void* key, const void* r1cs, const uint64_t* d_z, unsigned log_n, const uint64_t* omega, const uint64_t* omega_inv,
+                                    const uint64_t* coset, const uint64_t* coset_inv, const uint64_t* size_inv, const uint64_t* vanishing_inv, uint64_t* out_a,
+                                    uint64_t* out_b, uint64_t* out_c) {
+  return groth16_prove_r1cs((const ProvingKey*)key, (const R1cs*)r1cs, d_z, 1, log_n, omega, omega_inv, coset, coset_inv, size_inv, vanishing_inv, out_a, out_b, out_c);
 }
 int groth16_setup_r1cs_bw6_761(const void* r1cs, unsigned log_n, const uint64_t omega[6], const uint64_t tau[6], const uint64_t toxic[24], const uint64_t g1_xy[24],
                                const uint64_t g2_xy[24], int window_bits, uint64_t* out_vk, uint64_t* out_rows, void** out_key) {
@@ -676,6 +681,43 @@ int groth16_setup_r1cs_bls12_377(const void* r1cs, unsigned log_n, const uint64_
   return groth16_setup_r1cs(1, (const R1cs*)r1cs, log_n, omega, tau, toxic, g1_xy, g2_xy, window_bits, out_vk, out_rows, (ProvingKey**)out_key);
 }
 int celo_amd_r1cs_last_timings(float ms[8]) { if (!ms) return 2; r1cs_last_timings(ms); return 0; }
+
+// ---- the HashToBits circuit of the hash-helper proof (unit_hashbits.hip)
+int hash_to_bits_r1cs_size_bls12_377(size_t n_epochs, uint64_t out[8]) { return hashbits_sizes(n_epochs, out); }
+int hash_to_bits_r1cs_bls12_377(size_t n_epochs, uint64_t* a_row_ptr, uint32_t* a_col, uint64_t* a_val, uint64_t* b_row_ptr, uint32_t* b_col, uint64_t* b_val,
+                                uint64_t* c_row_ptr, uint32_t* c_col, uint64_t* c_val) {
+  uint64_t* const rp[3] = {a_row_ptr, b_row_ptr, c_row_ptr};
+  uint32_t* const col[3] = {a_col, b_col, c_col};
+  uint64_t* const val[3] = {a_val, b_val, c_val};
+  return hashbits_write_csr(n_epochs, rp, col, val);
+}
+int hash_to_bits_r1cs_load_bls12_377(size_t n_epochs, void** out_r1cs) {
+  if (!out_r1cs) return 2;
+  *out_r1cs = nullptr;
+  return hashbits_r1cs_load(n_epochs, (R1cs**)out_r1cs);
+}
+int hash_to_bits_assignment_bls12_377(const uint8_t* rows48, size_t n_epochs, int bit_order, uint64_t* z) {
+  return hashbits_assignment(rows48, n_epochs, bit_order, z, 0, nullptr);
+}
+int hash_to_bits_assignment_bls12_377_dev(const uint8_t* d_rows48, size_t n_epochs, int bit_order, uint64_t* d_z, void* hip_stream) {
+  return hashbits_assignment(d_rows48, n_epochs, bit_order, d_z, 1, hip_stream);
+}
+int celo_amd_hash_to_bits_assignment_host(const uint8_t* rows48, size_t n_epochs, int bit_order, uint64_t* z) {
+  return hashbits_assignment_host(rows48, n_epochs, bit_order, z);
+}
+int hash_to_bits_public_inputs_bls12_377(const uint8_t* rows48, size_t n_proofs, size_t n_epochs, int bit_order, uint64_t* out) {
+  return hashbits_public_inputs(rows48, n_proofs, n_epochs, bit_order, out, 0, nullptr);
+}
+int hash_to_bits_public_inputs_bls12_377_dev(const uint8_t* d_rows48, size_t n_proofs, size_t n_epochs, int bit_order, uint64_t* d_out, void* hip_stream) {
+  return hashbits_public_inputs(d_rows48, n_proofs, n_epochs, bit_order, d_out, 1, hip_stream);
+}
+int groth16_hash_helper_prove_bls12_377(const void* key, const void* r1cs, const uint8_t* rows48, size_t n_epochs, int bit_order, unsigned log_n, const uint64_t* omega,
+                                        const uint64_t* omega_inv, const uint64_t* coset, const uint64_t* coset_inv, const uint64_t* size_inv,
+                                        const uint64_t* vanishing_inv, uint64_t* out_a, uint64_t* out_b, uint64_t* out_c, uint64_t* out_inputs) {
+  return hash_helper_prove((const ProvingKey*)key, (const R1cs*)r1cs, rows48, n_epochs, bit_order, log_n, omega, omega_inv, coset, coset_inv, size_inv, vanishing_inv,
+                           out_a, out_b, out_c, out_inputs);
+}
+int celo_amd_hash_helper_last(float ms[8]) { if (!ms) return 2; hash_helper_last(ms); return 0; }
 int celo_amd_decompress_last_ms(float* ms) { if (!ms) return 2; *ms = wire_last_ms(); return 0; }
 int celo_amd_msm_last_timings(int group, float ms[5], int cfg[3]) {
   return by_group(group, 1, [&](auto g) { return MsmAuxApi<typename decltype(g)::type>::timings(ms, cfg); });

@@ -10,7 +10,7 @@
 //        B = b_g2_query[0] + MSM(b_g2_query[1..], assignment) + beta_g2
 //        C = MSM(l_query, aux_assignment) + MSM(h_query, h)
 //      the four MSMs run concurrently on four engines (msm.h); the handful of point additions around them on the host.
-// R1CS synthesis (running the gadgets) is the circuit's business and stays with the caller.  Evaluating the constraint matrices on the
+// R1CS synthesis (running the gadgets) is the circuit's business and stays with the caller (but for HashToBits: unit_hashbits.hip).  Evaluating the constraint matrices on the
 // assignment is unit_r1cs.hip: groth16_prove_r1cs below starts from matrices + assignment, the entry points above it from a, b, c.
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -274,8 +274,10 @@ int groth16_prove_keyed(const ProvingKey* k, const uint64_t* assignment, size_t 
 
 // ---- matrices + assignment -> proof (groth16_prove_r1cs_with_key): z goes up once; the constraint rows (unit_r1cs.hip), the witness map and the
 // canonical assignment are made on the device and the four fixed-base MSMs read them where they lie.
+// z_mode 0: a host pointer; 1: a device pointer, complete before the call, left as it is (the call works on a device copy: its z becomes
+// canonical in place); 2: a device pointer the call may overwrite (groth16_hash_helper_prove's own buffer).
 template <class C>
-static int prove_r1cs_t(const ProvingKey* k, const R1cs* r, size_t n_vars, size_t n_inputs, const uint64_t* z, unsigned log_n, const uint64_t* omega,
+static int prove_r1cs_t(const ProvingKey* k, const R1cs* r, size_t n_vars, size_t n_inputs, const uint64_t* z, int z_mode, unsigned log_n, const uint64_t* omega,
                         const uint64_t* omega_inv, const uint64_t* coset, const uint64_t* coset_inv, const uint64_t* n_inv, const uint64_t* z_inv, uint64_t* out_a,
                         uint64_t* out_b, uint64_t* out_c) {
   typedef typename C::FR FR;
@@ -285,7 +287,12 @@ static int prove_r1cs_t(const ProvingKey* k, const R1cs* r, size_t n_vars, size_
   HIP_TRY(cs.open(0, nullptr), 10);
   const hipStream_t s = cs.stream();
   uint64_t *d_z, *d_a, *d_b, *d_c;
-  HIP_TRY(cs.in(&d_z, z, n_vars * A * 8, 0), 10);
+  if (z_mode == 1) {
+    HIP_TRY(cs.alloc(&d_z, n_vars * A * 8), 10);
+    HIP_TRY(hipMemcpyAsync(d_z, z, n_vars * A * 8, hipMemcpyDeviceToDevice, s), 10);
+  } else {
+    HIP_TRY(cs.in(&d_z, z, n_vars * A * 8, z_mode), 10);
+  }
   HIP_TRY(cs.alloc(&d_a, n * A * 8), 10); HIP_TRY(cs.alloc(&d_b, n * A * 8), 10); HIP_TRY(cs.alloc(&d_c, n * A * 8), 10);
   if (int rc = r1cs_rows(r, d_z, log_n, d_a, d_b, d_c, 1, s)) return rc;
   if (int rc = witness_map_run<FR>(d_a, d_b, d_c, log_n, omega, omega_inv, coset, coset_inv, n_inv, z_inv, 1, 1, s)) return rc;
@@ -294,10 +301,10 @@ static int prove_r1cs_t(const ProvingKey* k, const R1cs* r, size_t n_vars, size_
   HIP_TRY(hipStreamSynchronize(s), 10);
   return prove_keyed<C>(k, d_z + A, n_vars - 1, n_vars - n_inputs, d_a, n, 1, out_a, out_b, out_c);
 }
-int groth16_prove_r1cs(const ProvingKey* k, const R1cs* r, const uint64_t* z, unsigned log_n, const uint64_t* omega, const uint64_t* omega_inv, const uint64_t* coset,
-                       const uint64_t* coset_inv, const uint64_t* n_inv, const uint64_t* z_inv, uint64_t* out_a, uint64_t* out_b, uint64_t* out_c) {
+int groth16_prove_r1cs(const ProvingKey* k, const R1cs* r, const uint64_t* z, int z_mode, unsigned log_n, const uint64_t* omega, const uint64_t* omega_inv,
+                       const uint64_t* coset, const uint64_t* coset_inv, const uint64_t* n_inv, const uint64_t* z_inv, uint64_t* out_a, uint64_t* out_b, uint64_t* out_c) {
   if (int rc0 = api_enter()) return rc0;
-  if (!k || !r || !z || !omega || !omega_inv || !coset || !coset_inv || !n_inv || !z_inv || !out_a || !out_b || !out_c) return 2;
+  if (!k || !r || !z || z_mode < 0 || z_mode > 2 || !omega || !omega_inv || !coset || !coset_inv || !n_inv || !z_inv || !out_a || !out_b || !out_c) return 2;
   int curve, device;
   size_t m, n_vars, n_inputs;
   r1cs_shape(r, &curve, &device, &m, &n_vars, &n_inputs);
@@ -305,9 +312,14 @@ int groth16_prove_r1cs(const ProvingKey* k, const R1cs* r, const uint64_t* z, un
   if (k->device != api_device() || device != api_device()) return 101;
   if (log_n > 28 || (size_t(1) << log_n) < m + n_inputs) return 2;
   const WallMs wall;
-  const int rc = curve ? prove_r1cs_t<Bls12>(k, r, n_vars, n_inputs, z, log_n, omega, omega_inv, coset, coset_inv, n_inv, z_inv, out_a, out_b, out_c)
-                       : prove_r1cs_t<Bw6>(k, r, n_vars, n_inputs, z, log_n, omega, omega_inv, coset, coset_inv, n_inv, z_inv, out_a, out_b, out_c);
+  const int rc = curve ? prove_r1cs_t<Bls12>(k, r, n_vars, n_inputs, z, z_mode, log_n, omega, omega_inv, coset, coset_inv, n_inv, z_inv, out_a, out_b, out_c)
+                       : prove_r1cs_t<Bw6>(k, r, n_vars, n_inputs, z, z_mode, log_n, omega, omega_inv, coset, coset_inv, n_inv, z_inv, out_a, out_b, out_c);
   r1cs_note_ms(4, wall.ms());
   return rc;
+}
+// the curve and the rows of the four queries (a and b with their row 0, l, h) of a loaded key
+void groth16_key_shape(const ProvingKey* k, int* curve, size_t rows[4]) {
+  *curve = k->curve;
+  rows[0] = k->na; rows[1] = k->nb; rows[2] = k->nl; rows[3] = k->nh;
 }
 }  // namespace celo

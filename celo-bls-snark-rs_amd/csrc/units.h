@@ -230,8 +230,23 @@ int groth16_key_load_dev(int curve, const uint64_t* d_a, const uint8_t* d_ainf, 
 void groth16_key_free(ProvingKey* k);
 int groth16_prove_keyed(const ProvingKey* k, const uint64_t* assignment, size_t n_assign, size_t n_aux, const uint64_t* h, size_t n_h, uint64_t* out_a, uint64_t* out_b,
                         uint64_t* out_c);
-int groth16_prove_r1cs(const ProvingKey* k, const R1cs* r, const uint64_t* z, unsigned log_n, const uint64_t* omega, const uint64_t* omega_inv, const uint64_t* coset,
-                       const uint64_t* coset_inv, const uint64_t* n_inv, const uint64_t* z_inv, uint64_t* out_a, uint64_t* out_b, uint64_t* out_c);
+// z_mode 0: z is a host pointer; 1: a device pointer the call leaves as it is; 2: a device pointer the call may overwrite
+int groth16_prove_r1cs(const ProvingKey* k, const R1cs* r, const uint64_t* z, int z_mode, unsigned log_n, const uint64_t* omega, const uint64_t* omega_inv,
+                       const uint64_t* coset, const uint64_t* coset_inv, const uint64_t* n_inv, const uint64_t* z_inv, uint64_t* out_a, uint64_t* out_b, uint64_t* out_c);
+void groth16_key_shape(const ProvingKey* k, int* curve, size_t rows[4]);
+
+// ---- the HashToBits circuit of the hash-helper proof over Fr(BLS12-377) (unit_hashbits.hip; hashbits.h).  The first three and
+// hashbits_assignment_host are pure host functions (no device needed)
+int hashbits_sizes(size_t m, uint64_t out[8]);
+int hashbits_write_csr(size_t m, uint64_t* const row_ptr[3], uint32_t* const col[3], uint64_t* const val[3]);
+int hashbits_assignment_host(const uint8_t* rows48, size_t m, int bit_order, uint64_t* z);
+int hashbits_r1cs_load(size_t m, R1cs** out);
+int hashbits_assignment(const uint8_t* rows48, size_t m, int bit_order, uint64_t* z, int dev, void* stream);
+int hashbits_public_inputs(const uint8_t* rows48, size_t n_proofs, size_t m, int bit_order, uint64_t* out, int dev, void* stream);
+int hash_helper_prove(const ProvingKey* k, const R1cs* r, const uint8_t* rows48, size_t m, int bit_order, unsigned log_n, const uint64_t* omega, const uint64_t* omega_inv,
+                      const uint64_t* coset, const uint64_t* coset_inv, const uint64_t* n_inv, const uint64_t* z_inv, uint64_t* out_a, uint64_t* out_b, uint64_t* out_c,
+                      uint64_t* out_inputs);
+void hash_helper_last(float ms[8]);
 
 // ---- Groth16 verification of many proofs under one key (groth16_verify_unit.h holds the definitions; unit_groth16_verify.hip instantiates
 // them for C = G16Bw6 and unit_groth16_verify377.hip for C = G16Bls).  Rows: affine arkworks limbs, C::G1W / C::G2W u64 each

@@ -77,6 +77,9 @@ EXPORTS = [
     "verify_aggregated_seals_bls12_377", "celo_amd_aggregate_set_lanes", "celo_amd_aggregate_set_complement", "celo_amd_seals_last",
     "epoch_encoded_size", "epoch_encode_blocks_bls12_377", "epoch_encode_blocks_bls12_377_dev", "epoch_public_inputs_bw6_761", "epoch_public_inputs_bw6_761_dev",
     "verify_epoch_proofs_bw6_761", "celo_amd_epoch_last", "verify_epoch_transitions_bls12_377", "celo_amd_transitions_last",
+    "groth16_prove_r1cs_with_key_dev", "hash_to_bits_r1cs_size_bls12_377", "hash_to_bits_r1cs_bls12_377", "hash_to_bits_r1cs_load_bls12_377",
+    "hash_to_bits_assignment_bls12_377", "hash_to_bits_assignment_bls12_377_dev", "celo_amd_hash_to_bits_assignment_host",
+    "hash_to_bits_public_inputs_bls12_377", "hash_to_bits_public_inputs_bls12_377_dev", "groth16_hash_helper_prove_bls12_377", "celo_amd_hash_helper_last",
 ]
 
 _lib = None
@@ -628,6 +631,15 @@ class ProvingKey:
         rc = lib().groth16_prove_r1cs_with_key(self.h, r1cs.h, _p(zz), C.c_uint(log_n), *[_p(x) for x in k], _p(out[0]), _p(out[1]), _p(out[2]))
         if rc != 0:
             raise RuntimeError("groth16_prove_r1cs_with_key failed with code %d" % rc)
+        return out
+
+    def prove_r1cs_dev(self, r1cs, d_z, log_n, consts):
+        """prove_r1cs with z on the DEVICE (groth16_prove_r1cs_with_key_dev): d_z the address of n_vars rows, complete before the call"""
+        k = [np.ascontiguousarray(consts[n], dtype=np.uint64).reshape(self.sw) for n in ("omega", "omega_inv", "coset", "coset_inv", "size_inv", "vanishing_inv")]
+        out = [np.zeros(w, dtype=np.uint64) for w in self.ow]
+        rc = lib().groth16_prove_r1cs_with_key_dev(self.h, r1cs.h, C.c_void_p(d_z), C.c_uint(log_n), *[_p(x) for x in k], _p(out[0]), _p(out[1]), _p(out[2]))
+        if rc != 0:
+            raise RuntimeError("groth16_prove_r1cs_with_key_dev failed with code %d" % rc)
         return out
 
     def prove(self, assignment, n_aux, h):
@@ -1835,3 +1847,120 @@ def groth16_setup_r1cs(r1cs, log_n, omega, tau, toxic, g1_xy, g2_xy, window_bits
     if rc != 0:
         raise SetupError(curve, rc)
     return _setup_outputs(vk, rows, key, n_vars, n_inputs, n_h, R1)
+
+
+# ---- the HashToBits circuit of the hash-helper proof over BLS12-377 (include/celo_bls_amd.h: hash_to_bits_*, groth16_hash_helper_prove_bls12_377)
+HASH_TO_BITS_SIZE_KEYS = ("n_constraints", "n_vars", "n_inputs", "nnz_a", "nnz_b", "nnz_c", "log_n", "stride")
+
+
+def hash_to_bits_size(n_epochs):
+    """(rc, sizes) of the circuit for n_epochs messages (hash_to_bits_r1cs_size_bls12_377; host only): sizes a dict of HASH_TO_BITS_SIZE_KEYS"""
+    out = np.zeros(8, dtype=np.uint64)
+    rc = lib().hash_to_bits_r1cs_size_bls12_377(C.c_size_t(n_epochs), _p(out))
+    return rc, dict(zip(HASH_TO_BITS_SIZE_KEYS, (int(v) for v in out)))
+
+
+def _hb_size(n_epochs):
+    rc, s = hash_to_bits_size(n_epochs)
+    if rc != 0:
+        raise RuntimeError("hash_to_bits_r1cs_size_bls12_377(%d) failed with code %d" % (n_epochs, rc))
+    return s
+
+
+def hash_to_bits_r1cs(n_epochs):
+    """(sizes, [(row_ptr, col, val (nnz, 4))] for a, b, c): the matrices on the host (hash_to_bits_r1cs_bls12_377)"""
+    s = _hb_size(n_epochs)
+    mats, args = [], []
+    for k in "abc":
+        rp = np.zeros(s["n_constraints"] + 1, dtype=np.uint64)
+        col = np.zeros(s["nnz_" + k], dtype=np.uint32)
+        val = np.zeros((s["nnz_" + k], 4), dtype=np.uint64)
+        mats.append((rp, col, val))
+        args += [_p(rp), _p(col), _p(val)]
+    rc = lib().hash_to_bits_r1cs_bls12_377(C.c_size_t(n_epochs), *args)
+    if rc != 0:
+        raise RuntimeError("hash_to_bits_r1cs_bls12_377 failed with code %d" % rc)
+    return s, mats
+
+
+def _hb_rows(rows48, n=None):
+    r = np.ascontiguousarray(np.frombuffer(rows48, dtype=np.uint8) if isinstance(rows48, (bytes, bytearray)) else rows48, dtype=np.uint8).reshape(-1, 48)
+    assert n is None or r.shape[0] == n
+    return r
+
+
+def hash_to_bits_r1cs_load(n_epochs):
+    """the circuit as an R1CS handle of curve bls12_377 (hash_to_bits_r1cs_load_bls12_377)"""
+    s = _hb_size(n_epochs)
+    r = R1CS.__new__(R1CS)
+    r.curve, r.m, r.n_vars, r.n_inputs, r.N = "bls12_377", s["n_constraints"], s["n_vars"], s["n_inputs"], 4
+    r.h = C.c_void_p()
+    rc = lib().hash_to_bits_r1cs_load_bls12_377(C.c_size_t(n_epochs), C.byref(r.h))
+    if rc != 0:
+        r.h = C.c_void_p()
+        raise R1CSLoadError("bls12_377", rc)
+    return r
+
+
+def hash_to_bits_assignment(rows48, bit_order=0, host=False):
+    """the full assignment (n_vars, 4) of the messages in rows48 ((m, 48) bytes): on the device (hash_to_bits_assignment_bls12_377) or, with
+    host=True, by the host twin (celo_amd_hash_to_bits_assignment_host)"""
+    r = _hb_rows(rows48)
+    s = _hb_size(r.shape[0])
+    z = np.zeros((s["n_vars"], 4), dtype=np.uint64)
+    fn = lib().celo_amd_hash_to_bits_assignment_host if host else lib().hash_to_bits_assignment_bls12_377
+    rc = fn(_p(r), C.c_size_t(r.shape[0]), C.c_int(bit_order), _p(z))
+    if rc != 0:
+        raise RuntimeError("hash_to_bits assignment (%s) failed with code %d" % ("host" if host else "device", rc))
+    return z
+
+
+def hash_to_bits_assignment_dev(d_rows48, n_epochs, bit_order, d_z, stream=0):
+    rc = lib().hash_to_bits_assignment_bls12_377_dev(C.c_void_p(d_rows48), C.c_size_t(n_epochs), C.c_int(bit_order), C.c_void_p(d_z), C.c_void_p(stream or 0))
+    if rc != 0:
+        raise RuntimeError("hash_to_bits_assignment_bls12_377_dev failed with code %d" % rc)
+
+
+def hash_to_bits_public_inputs(rows48, n_proofs, n_epochs, bit_order=0):
+    """(n_proofs, n_inputs - 1, 4) canonical limbs: the inputs of groth16_verify_batch_bls12_377 (hash_to_bits_public_inputs_bls12_377)"""
+    r = _hb_rows(rows48, n_proofs * n_epochs)
+    s = _hb_size(n_epochs)
+    out = np.zeros((n_proofs, s["n_inputs"] - 1, 4), dtype=np.uint64)
+    rc = lib().hash_to_bits_public_inputs_bls12_377(_p(r), C.c_size_t(n_proofs), C.c_size_t(n_epochs), C.c_int(bit_order), _p(out))
+    if rc != 0:
+        raise RuntimeError("hash_to_bits_public_inputs_bls12_377 failed with code %d" % rc)
+    return out
+
+
+def hash_to_bits_public_inputs_dev(d_rows48, n_proofs, n_epochs, bit_order, d_out, stream=0):
+    rc = lib().hash_to_bits_public_inputs_bls12_377_dev(C.c_void_p(d_rows48), C.c_size_t(n_proofs), C.c_size_t(n_epochs), C.c_int(bit_order), C.c_void_p(d_out),
+                                                        C.c_void_p(stream or 0))
+    if rc != 0:
+        raise RuntimeError("hash_to_bits_public_inputs_bls12_377_dev failed with code %d" % rc)
+
+
+def hash_helper_prove_rc(key, r1cs, rows48, bit_order, log_n, consts):
+    """(rc, A, B, C, inputs) of groth16_hash_helper_prove_bls12_377: the return code with the outputs (Jacobian limbs; inputs (n_inputs - 1, 4) canonical)"""
+    r = _hb_rows(rows48)
+    s = _hb_size(r.shape[0])
+    k = [np.ascontiguousarray(consts[n], dtype=np.uint64).reshape(4) for n in ("omega", "omega_inv", "coset", "coset_inv", "size_inv", "vanishing_inv")]
+    out = [np.zeros(w, dtype=np.uint64) for w in (18, 36, 18)]
+    inputs = np.zeros((s["n_inputs"] - 1, 4), dtype=np.uint64)
+    rc = lib().groth16_hash_helper_prove_bls12_377(key.h, r1cs.h, _p(r), C.c_size_t(r.shape[0]), C.c_int(bit_order), C.c_uint(log_n), *[_p(x) for x in k],
+                                                   _p(out[0]), _p(out[1]), _p(out[2]), _p(inputs))
+    return rc, out[0], out[1], out[2], inputs
+
+
+def hash_helper_prove(key, r1cs, rows48, bit_order, log_n, consts):
+    """generate_hash_helper in one call: (A, B, C, inputs)"""
+    rc, a, b, c, inputs = hash_helper_prove_rc(key, r1cs, rows48, bit_order, log_n, consts)
+    if rc != 0:
+        raise RuntimeError("groth16_hash_helper_prove_bls12_377 failed with code %d" % rc)
+    return a, b, c, inputs
+
+
+def hash_helper_last():
+    """the last groth16_hash_helper_prove_bls12_377 call: {trace, expand, pack, prove, wall} in ms"""
+    ms = (C.c_float * 8)()
+    lib().celo_amd_hash_helper_last(ms)
+    return dict(zip(("trace", "expand", "pack", "prove", "wall"), list(ms)[:5]))

@@ -988,8 +988,8 @@ int verify_epoch_transitions_bls12_377(const celo_epoch_blocks* blocks, size_t n
 int celo_amd_transitions_last(int* path, float ms[8]);
 
 /* ---- R1CS matrices on the device: the step of ark-groth16 0.1 between cs.to_matrices() and the entry points above - the constraint evaluation
- * of R1CStoQAP::witness_map (prover) and R1CStoQAP::instance_map_with_evaluation (setup).  Synthesis (running the gadgets) stays with the caller;
- * its result is data: three sparse matrices of n_constraints rows and the full assignment.
+ * of R1CStoQAP::witness_map (prover) and R1CStoQAP::instance_map_with_evaluation (setup).  Synthesis (running the gadgets) stays with the caller
+ * for every circuit but HashToBits (hash_to_bits_* below); its result is data: three sparse matrices of n_constraints rows and the full assignment.
  *
  * One matrix = CSR: row_ptr (n_constraints + 1 offsets, row_ptr[0] = 0, row_ptr[n_constraints] = nnz), col (nnz variable indices: the instance
  * variables first, index 0 the constant one, then the witness), val (nnz x 6 | 4 u64, arkworks Montgomery Fr), nnz (the length of col and val).
@@ -1044,6 +1044,62 @@ int groth16_setup_r1cs_bls12_377(const void* r1cs, unsigned log_n, const uint64_
 /* the last calls' times in ms: [0] load (host wall: validation, transposition, copies), [1] rows kernels, [2] Lagrange kernel, [3] columns kernels,
  * [4] groth16_prove_r1cs_with_key wall, [5] groth16_setup_r1cs_* wall, [6..7] unused */
 int celo_amd_r1cs_last_timings(float ms[8]);
+/* groth16_prove_r1cs_with_key with z as a DEVICE pointer (n_vars x 6 | 4 u64, complete before the call; it is read, not written): the copy of z
+ * to the device is skipped and everything else is the same: the same three points (their Jacobian representatives are not fixed from call to call in
+ * either entry: the MSMs' summation order is not), the same bytes from groth16_serialize_proof_*. */
+int groth16_prove_r1cs_with_key_dev(const void* key, const void* r1cs, const uint64_t* d_z, unsigned log_n, const uint64_t* omega, const uint64_t* omega_inv,
+                                    const uint64_t* coset, const uint64_t* coset_inv, const uint64_t* size_inv, const uint64_t* vanishing_inv, uint64_t* out_a,
+                                    uint64_t* out_b, uint64_t* out_c);
+
+/* ---- The one circuit the library synthesizes itself: HashToBits, the circuit of the hash-helper proof over BLS12-377
+ * (crates/epoch-snark/src/gadgets/hash_to_bits.rs; generate_hash_helper, api/prover.rs:85-118).  For n_epochs messages of 384 bits it states
+ * that the 512 XOF bits of every message are Blake2Xs (two single-block Blake2s compressions under SIG_DOMAIN, DirectHasher::xof(.., 64)) of
+ * its bits.  The instance vector is the reference's:  [1] ++ pack(all message bits) ++ pack(all XOF bits), pack = 252-bit (Fr::CAPACITY)
+ * chunks running across epoch borders, the first bit of a chunk the most significant, a short last chunk:
+ * n_inputs = 1 + ceil(384 n_epochs / 252) + ceil(512 n_epochs / 252).
+ * The LAYOUT is not the reference's: the order of its variables and constraints comes from the arkworks gadgets and is not reproduced, so keys
+ * made for this system and the reference's ceremony keys do not fit each other.  What holds is the same relation over the same instance vector
+ * (the row kinds, the counts and the soundness argument).
+ *
+ * rows48: n_epochs rows of 48 bytes, e.g. out_crh of verify_epoch_transitions_bls12_377 as it lies.  bit_order 0: message bit j = bit j % 8 of
+ * byte j / 8 of the row (bytes_le_to_bits_le, the reference's own test); 1: the 384-bit reversal of that (bytes_le_to_bits_be(row, 384), what
+ * prover.rs:101 feeds from the CRH bytes: the order for out_crh rows).
+ *
+ * hash_to_bits_r1cs_size_*: host only.  out = n_constraints, n_vars, n_inputs, nnz of a, b, c, the smallest log_n (2^log_n >= n_constraints +
+ * n_inputs), the variables per epoch (epoch e's witness lies at n_inputs + e * that).  2: n_epochs == 0, out NULL, or the circuit exceeds the
+ * R1CS limits (n_vars or an nnz >= 2^32, log_n > 28).
+ * hash_to_bits_r1cs_*: host only.  Writes the three matrices into caller-owned arrays of those sizes (row_ptr: n_constraints + 1, col: nnz,
+ * val: 4 nnz u64) - with the nnz, the arguments of groth16_r1cs_load_bls12_377.  2 as above or for a NULL array.
+ * hash_to_bits_r1cs_load_*: both in one; *out_r1cs is an ordinary R1CS handle of curve 1 (groth16_r1cs_free), codes of groth16_r1cs_load_*.
+ * hash_to_bits_assignment_*: the full assignment z (n_vars x 4 u64 Montgomery, z[0] = 1) of the messages.  _dev: rows48 and z are device
+ * pointers, the work runs on hip_stream and is complete on return.  celo_amd_hash_to_bits_assignment_host: the same on the host, from the
+ * same templates (no device needed).  2: a NULL pointer, bit_order not 0 / 1, n_epochs refused by the size query.
+ * hash_to_bits_public_inputs_*: the verifier's side, for n_proofs proofs of n_epochs epochs each (proof p takes rows [p n_epochs,
+ * (p + 1) n_epochs)): out = n_proofs x (n_inputs - 1) x 4 u64 CANONICAL, the constant left out - the inputs of
+ * groth16_verify_batch_bls12_377.  2 as above, or n_proofs == 0 or n_proofs * n_epochs > 2^24.
+ * groth16_hash_helper_prove_*: generate_hash_helper in one call.  The rows go to the device, the assignment is made there, the proof is
+ * groth16_prove_r1cs_with_key's from the device-resident z (A, B, C Jacobian; create_proof_no_zk, no randomisation), and out_inputs receives the
+ * n_inputs - 1 canonical instance rows.  key / r1cs: a BLS12-377 key and the handle of hash_to_bits_r1cs_load_* for the same n_epochs and
+ * log_n (2: another curve, a circuit of another size, a key whose queries are not n_vars, n_vars, n_vars - n_inputs and 2^log_n - 1 rows long;
+ * 101: another device).  Domain constants as for groth16_prove_r1cs_with_key.
+ * celo_amd_hash_helper_last: the last such call in ms: [0] trace, [1] expand, [2] pack kernels, [3] the proof (wall), [4] the call (wall); a
+ * hash_to_bits_assignment_* call leaves its three kernel times in [0..2] and zeroes the rest.
+ *
+ * Limit: groth16_verify_batch_bls12_377 takes at most 64 public inputs (code 36), so it checks helper proofs of at most 17 epochs (61 inputs;
+ * 18 epochs have 65).  Everything here works at any n_epochs within the R1CS limits; 143 epochs make a domain of 2^23. */
+int hash_to_bits_r1cs_size_bls12_377(size_t n_epochs, uint64_t out[8]);
+int hash_to_bits_r1cs_bls12_377(size_t n_epochs, uint64_t* a_row_ptr, uint32_t* a_col, uint64_t* a_val, uint64_t* b_row_ptr, uint32_t* b_col, uint64_t* b_val,
+                                uint64_t* c_row_ptr, uint32_t* c_col, uint64_t* c_val);
+int hash_to_bits_r1cs_load_bls12_377(size_t n_epochs, void** out_r1cs);
+int hash_to_bits_assignment_bls12_377(const uint8_t* rows48, size_t n_epochs, int bit_order, uint64_t* z);
+int hash_to_bits_assignment_bls12_377_dev(const uint8_t* d_rows48, size_t n_epochs, int bit_order, uint64_t* d_z, void* hip_stream);
+int celo_amd_hash_to_bits_assignment_host(const uint8_t* rows48, size_t n_epochs, int bit_order, uint64_t* z);
+int hash_to_bits_public_inputs_bls12_377(const uint8_t* rows48, size_t n_proofs, size_t n_epochs, int bit_order, uint64_t* out);
+int hash_to_bits_public_inputs_bls12_377_dev(const uint8_t* d_rows48, size_t n_proofs, size_t n_epochs, int bit_order, uint64_t* d_out, void* hip_stream);
+int groth16_hash_helper_prove_bls12_377(const void* key, const void* r1cs, const uint8_t* rows48, size_t n_epochs, int bit_order, unsigned log_n, const uint64_t* omega,
+                                        const uint64_t* omega_inv, const uint64_t* coset, const uint64_t* coset_inv, const uint64_t* size_inv,
+                                        const uint64_t* vanishing_inv, uint64_t* out_a, uint64_t* out_b, uint64_t* out_c, uint64_t* out_inputs);
+int celo_amd_hash_helper_last(float ms[8]);
 
 #ifdef __cplusplus
 }
