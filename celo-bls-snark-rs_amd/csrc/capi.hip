@@ -423,6 +423,16 @@ int groth16_verify_batch_bls12_377_serialized(const void* vk, const uint8_t* pro
   if (m && !proofs) return 2;
   return G16Api<G16Bls>::verify((const VerifyingKey*)vk, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, proofs, inputs, m, mode, key, out_ok);
 }
+// the wide loaders: up to VK_MAX_INPUTS_WIDE public inputs where the two above stop at VK_MAX_INPUTS (units.h); the same handle type
+int groth16_vk_load_bls12_377_wide(const uint64_t alpha_g1[12], const uint64_t beta_g2[24], const uint64_t gamma_g2[24], const uint64_t delta_g2[24],
+                                   const uint64_t* gamma_abc_g1, size_t n_abc, void** out_vk) {
+  return G16Api<G16Bls>::vk_load(alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1, n_abc, (VerifyingKey**)out_vk, VK_MAX_INPUTS_WIDE);
+}
+int groth16_vk_load_bls12_377_wide_serialized(const uint8_t* bytes, size_t len, void** out_vk) {
+  return G16Api<G16Bls>::vk_load_serialized(bytes, len, (VerifyingKey**)out_vk, VK_MAX_INPUTS_WIDE);
+}
+int celo_amd_groth16_set_input_lanes(int lanes) { return groth16_set_input_lanes(lanes); }
+int celo_amd_groth16_inputs_last(int* lanes, int* n_inputs) { return groth16_inputs_last(lanes, n_inputs); }
 int celo_amd_groth16_draw_exponents(const uint32_t key[8], size_t m, uint64_t* out) { return groth16_draw_exponents_run(key, m, out); }
 int celo_amd_groth16_verify_last(int* path, int* window_bits, float ms[8]) { return groth16_verify_last(path, window_bits, ms); }
 int celo_amd_wire761_last_timings(float ms[4]) { if (!ms) return 2; wire761_last_timings(ms); return 0; }
@@ -716,6 +726,10 @@ int groth16_hash_helper_prove_bls12_377(const void* key, const void* r1cs, const
                                         const uint64_t* vanishing_inv, uint64_t* out_a, uint64_t* out_b, uint64_t* out_c, uint64_t* out_inputs) {
   return hash_helper_prove((const ProvingKey*)key, (const R1cs*)r1cs, rows48, n_epochs, bit_order, log_n, omega, omega_inv, coset, coset_inv, size_inv, vanishing_inv,
                            out_a, out_b, out_c, out_inputs);
+}
+int groth16_hash_helper_verify_bls12_377(const void* vk, const uint8_t* rows48, size_t n_proofs, size_t n_epochs, int bit_order, const uint8_t* proofs, int mode,
+                                         const uint32_t* key, uint8_t* out_ok) {
+  return hash_helper_verify((const VerifyingKey*)vk, rows48, n_proofs, n_epochs, bit_order, proofs, mode, key, out_ok);
 }
 int celo_amd_hash_helper_last(float ms[8]) { if (!ms) return 2; hash_helper_last(ms); return 0; }
 int celo_amd_decompress_last_ms(float* ms) { if (!ms) return 2; *ms = wire_last_ms(); return 0; }

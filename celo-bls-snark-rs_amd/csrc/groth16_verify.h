@@ -11,12 +11,14 @@
 #include <cstddef>
 #include <cstdint>
 #include <vector>
+#include "aggregate.h"
 #include "fixed_base.h"
 #include "wire761.h"
 
 namespace celo {
 
 constexpr size_t G16_MAX_INPUTS = 64;                 // n_abc - 1; more is refused with G16_ERR_INPUTS
+constexpr size_t G16_MAX_INPUTS_WIDE = 1024;          // the same for the wide loaders of BLS12-377: at 4 window bits their tables fill the budget exactly
 constexpr int G16_ERR_INPUTS = 36;                    // (30 .. 35: the serialized-key and R1CS codes of wire761.h / r1cs.h)
 constexpr size_t G16_TABLE_BUDGET = size_t(64) << 20; // bytes of window tables per key
 constexpr int G16_C_MAX = 10, G16_C_MIN = 4;
@@ -61,7 +63,7 @@ template <class C> inline size_t g16_table_bytes(size_t n_in, int c) {
   return n_in * (size_t)fb_windows(C::SCALAR_BITS, c) * (size_t(1) << (c - 1)) * 2 * C::F::WORDS * 4;
 }
 // the widest window (fewest additions per input) whose tables stay within the budget.  BW6-761: 10 bits up to 15 inputs ... 7 bits at
-// 64; BLS12-377: 10 bits up to 39 inputs, 9 bits from 40 to 64
+// 64; BLS12-377: the last input count of 10 .. 4 bits is 39 | 70 | 128 | 221 | 381 | 642 | 1024 (the narrow loaders stop at 64)
 template <class C> inline int g16_window_bits(size_t n_in) {
   int c = G16_C_MAX;
   while (c > G16_C_MIN && g16_table_bytes<C>(n_in, c) > G16_TABLE_BUDGET) c--;
@@ -97,32 +99,93 @@ template <class F, int N64> HD void g16_add_input(Xyzz<F>& acc, const uint64_t* 
     xyzz_madd(acc, p);
   }
 }
+// acc += x_j abc_j for input j of a proof (x: its inputs, N64 canonical limbs each): the range test, then the table walk.  An input that is
+// not below r sets bit 0 of b and enters as zero.
+template <class C>
+HD void g16_take_input(Xyzz<typename C::F>& acc, const uint64_t* x, uint32_t j, const uint32_t* table, const uint8_t* tinf, int c, int W, uint32_t& b) {
+  typedef typename C::F F;
+  constexpr int N64 = C::N64;
+  const size_t E = (size_t)W << (c - 1);
+  uint64_t s[N64];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int k = 0; k < N64; k++) s[k] = x[(size_t)j * N64 + k];
+  const uint64_t keep = (uint64_t)0 - (uint64_t)g16_below<N64>(s, C::order());      // all ones when x < r
+  b |= (uint32_t)(~keep & 1u);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int k = 0; k < N64; k++) s[k] &= keep;
+  g16_add_input<F, N64>(acc, s, table + j * E * 2 * F::WORDS, tinf + j * E, c, W);
+}
 // One proof's input sum.  x: n_in inputs of N64 limbs; abc0: gamma_abc[0] as a table entry (2 F::WORDS canonical words), abc0_inf its
 // identity flag; table / tinf: n_in tables of W 2^(c-1) entries, base-major.  An input that is not below r sets *bad and enters as zero.
 template <class C>
 HD Xyzz<typename C::F> g16_input_row(const uint64_t* x, uint32_t n_in, const uint32_t* abc0, bool abc0_inf, const uint32_t* table, const uint8_t* tinf, int c, int W, uint32_t* bad) {
   typedef typename C::F F;
-  constexpr int N64 = C::N64;
-  const size_t E = (size_t)W << (c - 1);
   Xyzz<F> acc = Xyzz<F>::identity();
   if (!abc0_inf) acc = Xyzz<F>::from_affine(fb_load_entry<F>(abc0));
   uint32_t b = 0;
-  for (uint32_t j = 0; j < n_in; j++) {
-    uint64_t s[N64];
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-    for (int k = 0; k < N64; k++) s[k] = x[(size_t)j * N64 + k];
-    const uint64_t keep = (uint64_t)0 - (uint64_t)g16_below<N64>(s, C::order());      // all ones when x < r
-    b |= (uint32_t)(~keep & 1u);
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-    for (int k = 0; k < N64; k++) s[k] &= keep;
-    g16_add_input<F, N64>(acc, s, table + j * E * 2 * F::WORDS, tinf + j * E, c, W);
-  }
+  for (uint32_t j = 0; j < n_in; j++) g16_take_input<C>(acc, x, j, table, tinf, c, W, b);
   *bad = b;
   return acc;
+}
+
+// ---- one input sum as the work of L lanes (k_g16_inputs_lanes), L a power of two from 2 to G16_MAX_LANES; aggregate.h's two phases:
+//   phase 1   lane l sums the inputs j = l, l + L, ..; lane 0 starts from gamma_abc[0]; a lane without inputs carries the identity;
+//   phase 2   the round of stride s = L/2 .. 1: lanes [s, 2 s) store their partial into slot lane - s (g16_fold_put), and when those stores
+//             have landed lanes [0, s) add the partial of slot `lane` with a full addition that reads it where it lies (g16_fold_take).
+// Only the upper half of a round's lanes stores, so a sum needs L/2 slots (at L = 256: 34 KiB of LDS where L slots would be 68 KiB), and a
+// round's stores must wait for the previous round's reads of the same slots: two barriers a round.  Doubling (equal partials), cancelling
+// (opposite ones) and the identity are live branches of the full addition.
+constexpr uint32_t G16_MAX_LANES = 256;
+HD bool g16_lanes_ok(int L) { return L >= 1 && L <= (int)G16_MAX_LANES && (L & (L - 1)) == 0; }
+template <class C>
+HD Xyzz<typename C::F> g16_lane_sum(const uint64_t* x, uint32_t n_in, uint32_t lane, uint32_t L, const uint32_t* abc0, bool abc0_inf, const uint32_t* table,
+                                    const uint8_t* tinf, int c, int W, uint32_t* bad) {
+  typedef typename C::F F;
+  Xyzz<F> acc = Xyzz<F>::identity();
+  if (lane == 0 && !abc0_inf) acc = Xyzz<F>::from_affine(fb_load_entry<F>(abc0));
+  uint32_t b = 0;
+  for (uint32_t j = lane; j < n_in; j += L) g16_take_input<C>(acc, x, j, table, tinf, c, W, b);     // (n_in <= 1024: j + L does not wrap)
+  *bad = b;
+  return acc;
+}
+// slots: the L/2 slots of this sum, agg_slot_words<F>() words each
+template <class F> HD void g16_fold_put(uint32_t* slots, const Xyzz<F>& acc, uint32_t lane, uint32_t s) { agg_store<F>(slots + (size_t)(lane - s) * agg_slot_words<F>(), acc); }
+template <class F> HD void g16_fold_take(Xyzz<F>& acc, const uint32_t* slots, uint32_t lane) { agg_add_stored<F>(acc, slots + (size_t)lane * agg_slot_words<F>()); }
+
+// The lanes per sum of a call of m proofs under a key of n_in inputs, in the shape of agg_pick_lanes:
+//   L = min( G16_MAX_LANES, smallest power of two >= n_in / G16_INPUTS_PER_LANE, largest power of two <= G16_FILL_LANES / m ), at least 1
+// and 1 (k_g16_inputs, the kernel every narrow key has always run) for a key of at most G16_MAX_INPUTS inputs.
+// The input sums are latency-bound: one lane takes about 9.7 us per dependent mixed addition, so the time falls as 1 / L until every lane
+// has one input, and a lane more than the inputs costs nothing but an idle lane and a fold round.  Both constants are read off a same-run
+// A/B over all nine widths, every row of which is in profiles/bench_groth16_verify_wide.json (tools/bench_groth16_verify_wide.py; DESIGN.md
+// 6h; kernel + normalisation in ms at L = 1 | 16 | 32 | 64 | 128 | 256, and the width the rule picks):
+//   509 inputs, m = 1       241 | 16.8 | 8.48 | 4.23 | 2.24 | 1.27    rule 256
+//   509 inputs, m = 64      244 | 16.2 | 8.35 | 4.38 | 2.40 | 1.42    rule 256
+//   509 inputs, m = 1 024   244 | 16.3 | 8.57 | 4.97 | 4.64 | 4.60    rule 64
+//   509 inputs, m = 4 096   244 | 17.2 | 15.8 | 15.5 | 15.7 | 15.5    rule 16
+//   509 inputs, m = 16 384  247 | 57.8 | 57.0 | 56.9 | 58.4 | 57.9    rule 4
+//   509 inputs, m = 65 536  250 | 214 | 214 | 216 | 222 | 222    rule 1
+//    65 inputs, m = 1       20.3 | 1.82 | 1.20 | 0.85 | 0.55 | 0.54    rule 128
+//    65 inputs, m = 64      18.3 | 1.84 | 1.31 | 1.03 | 0.67 | 0.71    rule 128
+//    65 inputs, m = 1 024   18.3 | 1.86 | 1.50 | 1.48 | 1.01 | 1.47    rule 64
+//    65 inputs, m = 4 096   18.2 | 2.37 | 2.48 | 3.02 | 2.89 | 3.92    rule 16
+// G16_INPUTS_PER_LANE = 1: at 65 inputs 128 lanes (less than one input a lane) beat 64 at every batch size up to 1 024; at 509 inputs the
+// cap of 256 lanes decides.  G16_FILL_LANES = 2^16 is one wave on every SIMD of the device, aggregate.h's figure, and the largest power
+// of two under which a batch of 2^16 proofs runs one lane per proof, which the rule promises (tests/test_groth16_wide_host.py).  The table
+// would admit 2^17: in every row where that changes the width it is level or ahead - by 1.07 to 1.10 x at 509 inputs from 1 024 proofs up,
+// by 1.47 x (0.5 ms of a 5.9 ms call) at 65 inputs and 1 024 proofs.  Past 2^17 nothing is gained.
+constexpr uint32_t G16_INPUTS_PER_LANE = 1;
+constexpr uint32_t G16_FILL_LANES = 1u << 16;
+inline uint32_t g16_pick_lanes(size_t n_in, size_t m) {
+  if (n_in <= G16_MAX_INPUTS) return 1;
+  uint32_t work = 1, fill = G16_MAX_LANES;
+  while (work < G16_MAX_LANES && (uint64_t)work * G16_INPUTS_PER_LANE < n_in) work <<= 1;
+  while (fill > 1 && (uint64_t)fill * m > G16_FILL_LANES) fill >>= 1;
+  return work < fill ? work : fill;
 }
 
 // k p for k = 2^127 + (hi : lo without its top bit) - 128 bits, the top one always set, so the ladder starts from p and every exponent
@@ -169,16 +232,18 @@ template <class F> inline void g16_negate_row(uint64_t* xy) { g16_neg(F::from_ar
 // ---- host: VerifyingKey::deserialize (compressed, checked):
 //   alpha_g1 | beta_g2 | gamma_g2 | delta_g2 | u64 LE n_abc | gamma_abc_g1[n_abc]      96 B per point (BW6-761); 48 / 96 B (BLS12-377)
 // rows: (4 + n_abc) x 24 u64 in that order, inf: their identity flags (the encoding of the point at infinity is a valid one).
-// 2: a NULL pointer or n_abc == 0; 30 / 31: the bytes end early / go on after the last point; 36: more than 64 public inputs; 33: a point
-// that does not decode or lies outside the prime-order subgroup, *first_bad = its index in serialization order.
-template <class C> inline int g16_vk_parse(const uint8_t* bytes, size_t len, std::vector<uint64_t>& rows, std::vector<uint8_t>& inf, uint64_t* first_bad) {
+// 2: a NULL pointer or n_abc == 0; 30 / 31: the bytes end early / go on after the last point; 36: more than max_inputs public inputs
+// (G16_MAX_INPUTS, or G16_MAX_INPUTS_WIDE for the wide loaders); 33: a point that does not decode or lies outside the prime-order
+// subgroup, *first_bad = its index in serialization order.
+template <class C>
+inline int g16_vk_parse(const uint8_t* bytes, size_t len, std::vector<uint64_t>& rows, std::vector<uint8_t>& inf, uint64_t* first_bad, size_t max_inputs = G16_MAX_INPUTS) {
   constexpr size_t B1 = C::G1_BYTES, B2 = C::G2_BYTES, HEAD = B1 + 3 * B2;
   if (!bytes) return 2;
   if (len < HEAD + 8) return W761_ERR_TRUNCATED;
   uint64_t n_abc = 0;
   for (int b = 7; b >= 0; b--) n_abc = (n_abc << 8) | bytes[HEAD + b];
   if (n_abc == 0) return 2;
-  if (n_abc - 1 > G16_MAX_INPUTS) return G16_ERR_INPUTS;
+  if (n_abc - 1 > max_inputs) return G16_ERR_INPUTS;
   if (len - (HEAD + 8) < B1 * n_abc) return W761_ERR_TRUNCATED;
   if (len - (HEAD + 8) > B1 * n_abc) return W761_ERR_TRAILING;
   rows.assign((size_t)(4 + n_abc) * G16_KW, 0);

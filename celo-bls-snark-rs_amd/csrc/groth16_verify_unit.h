@@ -6,6 +6,8 @@
 //
 //   key load     -alpha, beta, -gamma, -delta and one signed-digit window table per input base (unit_setup.hip's k_fbm_bases / k_fbm_table)
 //   k_g16_inputs one lane per proof: the range test of its inputs and acc = abc_0 + sum_j x_j abc_j from the tables; k_normalize
+//   k_g16_inputs_lanes   BLS12-377 keys of more than 64 inputs (the wide loaders): L lanes per proof, each summing the inputs j = l mod L, folded
+//                through LDS; L by g16_pick_lanes or celo_amd_groth16_set_input_lanes
 //   each         k_g16_pack_each writes (A, B), (acc, -gamma), (C, -delta), (-alpha, beta) per proof into the pairing engine's input
 //                slots: m products of four pairs, m verdicts
 //   combined     exponents r_i from ChaCha20 (unit_batchverify.hip's block kernel), k_g16_scale: r_i A_i by a 128-bit ladder, two
@@ -23,6 +25,8 @@
 #include "units.h"
 
 namespace celo {
+
+static_assert(VK_MAX_INPUTS == G16_MAX_INPUTS && VK_MAX_INPUTS_WIDE == G16_MAX_INPUTS_WIDE, "units.h and groth16_verify.h name one pair of limits");
 
 struct VerifyingKey {
   int curve = 0;                     // C::ID: an entry of the other curve refuses the handle
@@ -70,6 +74,36 @@ k_g16_inputs(const uint64_t* __restrict__ inputs, uint32_t m, uint32_t n_in, con
   uint32_t* o = xyzz + (size_t)i * 4 * FW;
   a.X.store(o); a.Y.store(o + FW); a.ZZ.store(o + 2 * FW); a.ZZZ.store(o + 3 * FW);
   if (bad) status[i] = 1;
+}
+// L lanes per proof (groth16_verify.h: g16_lane_sum and the fold), L a power of two from 2 to 256, in workgroups of max(64, L) lanes: 64 / L
+// proofs per workgroup below 64, one from there.  Dynamic LDS: blockDim.x / 2 slots of agg_slot_words<F>() words - the L / 2 slots of each
+// of the workgroup's proofs one after the other (34 KiB at 256 lanes of the 14-limb field).  Every lane of the workgroup walks the rounds:
+// the barriers are outside the lane tests.  The output is k_g16_inputs's.
+template <class C>
+__global__ void __launch_bounds__(G16_MAX_LANES) __attribute__((amdgpu_waves_per_eu(G16Dev<C>::WAVES, G16Dev<C>::WAVES)))
+k_g16_inputs_lanes(const uint64_t* __restrict__ inputs, uint32_t m, uint32_t n_in, const uint32_t* __restrict__ abc0, int abc0_inf, const uint32_t* __restrict__ table,
+                   const uint8_t* __restrict__ tinf, int c, int W, uint32_t L, uint32_t* __restrict__ xyzz, uint8_t* __restrict__ status) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t g16_lds[];
+  typedef typename C::F F;
+  constexpr int FW = F::WORDS;
+  const uint32_t lane = threadIdx.x & (L - 1), q = threadIdx.x / L, i = blockIdx.x * (blockDim.x / L) + q;
+  const bool live = i < m;
+  uint32_t bad = 0;
+  Xyzz<F> acc = Xyzz<F>::identity();
+  if (live) acc = g16_lane_sum<C>(inputs + (size_t)i * n_in * C::N64, n_in, lane, L, abc0, abc0_inf != 0, table, tinf, c, W, &bad);
+  uint32_t* slots = g16_lds + (size_t)q * (L >> 1) * agg_slot_words<F>();
+  for (uint32_t s = L >> 1; s; s >>= 1) {
+    __syncthreads();                            // the reads of the round before, from the slots this round writes
+    if (lane >= s && lane < 2 * s) g16_fold_put<F>(slots, acc, lane, s);
+    __syncthreads();
+    if (lane < s) g16_fold_take<F>(acc, slots, lane);
+  }
+  if (!live) return;
+  if (bad) status[i] = 1;                       // (several lanes may write the same byte)
+  if (lane == 0) {
+    uint32_t* o = xyzz + (size_t)i * 4 * FW;
+    acc.X.store(o); acc.Y.store(o + FW); acc.ZZ.store(o + 2 * FW); acc.ZZZ.store(o + 3 * FW);
+  }
 }
 // r4: the 4 x u64 the block kernel wrote per proof; sc: N64 x u64 scalars for the MSMs (zero for a proof whose status is set)
 template <int N64>
@@ -274,7 +308,7 @@ template <class C> struct G16Impl {
 
   // Everything after the proofs' rows, identity flags, statuses and inputs are on the device (stream cs.stream()).
   static int verify_core(const VerifyingKey* vk, DevProofs& d, size_t m, int mode, const uint32_t* key, uint8_t* out_ok, CallScope& cs, EvLog& log, float* ms, int* path,
-                         uint8_t* out_refused = nullptr /* m host bytes: the statuses the verdicts were masked with */) {
+                         int* lanes, uint8_t* out_refused = nullptr /* m host bytes: the statuses the verdicts were masked with */) {
     const hipStream_t s = cs.stream();
     const uint32_t m32 = (uint32_t)m, wblocks = (m32 + 63) / 64;
     uint32_t* d_xyzz;
@@ -282,9 +316,19 @@ template <class C> struct G16Impl {
     HIP_TRY(cs.alloc(&d_xyzz, m * 4 * FW * 4), 10);
     HIP_TRY(cs.alloc(&d.acc, m * W1 * 8), 10);
     HIP_TRY(cs.alloc(&d.accinf, m), 10);
+    // the lanes per input sum: one (k_g16_inputs) on BW6-761 and for every narrow key under the rule; BLS12-377: the rule or the forced width
+    uint32_t L = 1;
+    if constexpr (C::ID == 1) { const int forced = groth16_input_lanes(); L = forced ? (uint32_t)forced : g16_pick_lanes(vk->n_in, m); }
     hipEvent_t e0 = log.open();
-    hipLaunchKernelGGL((k_g16_inputs<C>), dim3(wblocks), dim3(64), 0, s, d.inputs, m32, vk->n_in, vk->d_abc0, vk->abc0_inf ? 1 : 0, vk->d_table, vk->d_tinf, vk->c, vk->W,
-                       d_xyzz, d.status);
+    if (L == 1) {
+      hipLaunchKernelGGL((k_g16_inputs<C>), dim3(wblocks), dim3(64), 0, s, d.inputs, m32, vk->n_in, vk->d_abc0, vk->abc0_inf ? 1 : 0, vk->d_table, vk->d_tinf, vk->c, vk->W,
+                         d_xyzz, d.status);
+    } else if constexpr (C::ID == 1) {
+      const uint32_t block = L < 64 ? 64 : L, per = block / L;
+      hipLaunchKernelGGL((k_g16_inputs_lanes<C>), dim3((m32 + per - 1) / per), dim3(block), (size_t)(block / 2) * agg_slot_words<F>() * 4, s, d.inputs, m32, vk->n_in,
+                         vk->d_abc0, vk->abc0_inf ? 1 : 0, vk->d_table, vk->d_tinf, vk->c, vk->W, L, d_xyzz, d.status);
+    }
+    *lanes = (int)L;
     normalize_xyzz<F, true>(d_xyzz, d.acc, d.accinf, m32, 0, s);
     log.close(1, e0);
     HIP_TRY(hipGetLastError(), 10);
@@ -366,24 +410,24 @@ template <class C> struct G16Impl {
 
 template <class C>
 int G16Api<C>::vk_load(const uint64_t* alpha_g1, const uint64_t* beta_g2, const uint64_t* gamma_g2, const uint64_t* delta_g2, const uint64_t* gamma_abc_g1, size_t n_abc,
-                       VerifyingKey** out) {
+                       VerifyingKey** out, size_t max_inputs) {
   constexpr int W1 = C::G1W, W2 = C::G2W, KW = G16_KW;
   if (!out) return 2;
   *out = nullptr;
   if (!alpha_g1 || !beta_g2 || !gamma_g2 || !delta_g2 || !gamma_abc_g1 || n_abc == 0) return 2;
-  if (n_abc - 1 > G16_MAX_INPUTS) return G16_ERR_INPUTS;
+  if (n_abc - 1 > max_inputs) return G16_ERR_INPUTS;
   std::vector<uint64_t> rows((4 + n_abc) * KW, 0);
   memcpy(rows.data(), alpha_g1, W1 * 8); memcpy(rows.data() + KW, beta_g2, W2 * 8); memcpy(rows.data() + 2 * KW, gamma_g2, W2 * 8);
   memcpy(rows.data() + 3 * KW, delta_g2, W2 * 8);
   for (size_t j = 0; j < n_abc; j++) memcpy(rows.data() + (4 + j) * KW, gamma_abc_g1 + j * W1, W1 * 8);
   return G16Impl<C>::vk_build(rows.data(), nullptr, n_abc, out);
 }
-template <class C> int G16Api<C>::vk_load_serialized(const uint8_t* bytes, size_t len, VerifyingKey** out) {
+template <class C> int G16Api<C>::vk_load_serialized(const uint8_t* bytes, size_t len, VerifyingKey** out, size_t max_inputs) {
   if (!out) return 2;
   *out = nullptr;
   std::vector<uint64_t> rows;
   std::vector<uint8_t> inf;
-  if (int rc = g16_vk_parse<C>(bytes, len, rows, inf, nullptr)) return rc;
+  if (int rc = g16_vk_parse<C>(bytes, len, rows, inf, nullptr, max_inputs)) return rc;
   return G16Impl<C>::vk_build(rows.data(), inf.data(), inf.size() - 4, out);
 }
 
@@ -407,7 +451,7 @@ static int g16_verify_call(const VerifyingKey* vk, const uint64_t* a_xy, const u
   if (vk->device != api_device()) return 101;
   const WallMs wall;
   float ms[8] = {};
-  int path = 0;
+  int path = 0, lanes = 1;
   const int rc = [&]() -> int {
     CallScope cs;
     HIP_TRY(cs.open(0, nullptr), 10);
@@ -455,13 +499,13 @@ static int g16_verify_call(const VerifyingKey* vk, const uint64_t* a_xy, const u
       hipLaunchKernelGGL((k_g16_merge_status<C>), dim3(((uint32_t)m + 255) / 256), dim3(256), 0, s, d_pre, (uint32_t)m, d.status);
       HIP_TRY(hipGetLastError(), 10);
     }
-    const int rcv = I::verify_core(vk, d, m, mode, key, out_ok, cs, log, ms, &path, out_refused);
+    const int rcv = I::verify_core(vk, d, m, mode, key, out_ok, cs, log, ms, &path, &lanes, out_refused);
     HIP_TRY(hipStreamSynchronize(s), 10);
     log.sum(ms);
     return rcv;
   }();
   ms[5] = wall.ms();
-  if (!rc) groth16_verify_note(path, vk->c, ms);
+  if (!rc) groth16_verify_note(path, vk->c, ms, lanes, (int)vk->n_in);
   return rc;
 }
 template <class C>

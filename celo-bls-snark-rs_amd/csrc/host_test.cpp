@@ -1,6 +1,8 @@
 // Host-only build of the product's field/curve templates with run-time bounds tracking
 // (-DCELO_FP_TRACK): every mul/sub asserts the limb/value bounds of fp.h's contract.
 // Driven by tests/test_host_field.py through ctypes; never shipped.
+#include <memory>
+#include <mutex>
 #include <vector>
 #include "curve.h"
 #include "gls.h"
@@ -761,38 +763,112 @@ uint32_t ht_aggregate_pick_lanes(uint32_t max_adds, size_t m) { return agg_pick_
 // out n G1 rows (a zero row and inf = 1 for the identity), status[i] = 1 for a row with an input that is not below r.  The tables are built as
 // k_fbm_bases / k_fbm_table build them, one per base.
 extern "C++" {
-template <class C>
-static void g16_input_row_host(const uint64_t* abc, size_t n_abc, const uint64_t* inputs, size_t n, int c, uint64_t* out, uint8_t* inf, uint8_t* status) {
+// the affine forms of a list of XYZZ points by one inversion for the whole list (Montgomery's trick); ok[k] = 0: the identity
+template <class F> static void g16_batch_affine(const std::vector<Xyzz<F>>& pts, std::vector<Affine<F>>& out, std::vector<uint8_t>& ok) {
+  const size_t n = pts.size();
+  std::vector<F> t(n, F::zero()), pre(n, F::zero());
+  out.assign(n, Affine<F>{F::zero(), F::zero()});
+  ok.assign(n, 0);
+  F run = F::one();
+  for (size_t k = 0; k < n; k++) {
+    if (pts[k].is_identity() || pts[k].ZZ.is_zero_mod_p()) continue;
+    ok[k] = 1;
+    t[k] = F::norm(F::mul(pts[k].ZZ, pts[k].ZZZ));
+    pre[k] = run;
+    run = F::norm(F::mul(run, t[k]));
+  }
+  F inv = F::norm(F::inv(run));
+  for (size_t k = n; k-- > 0;) {
+    if (!ok[k]) continue;
+    const F ti = F::norm(F::mul(inv, pre[k]));
+    inv = F::norm(F::mul(inv, t[k]));
+    out[k] = {F::norm(F::mul(pts[k].X, F::mul(ti, pts[k].ZZZ))), F::norm(F::mul(pts[k].Y, F::mul(ti, pts[k].ZZ)))};
+  }
+}
+// the key's side of an input sum as vk_build leaves it: gamma_abc[0] as a table entry and one window table per input base - the points of
+// k_fbm_bases / k_fbm_table (fb_window_base, fb_table_entry), made affine list by list: the W window bases of a base, then its W 2^(c-1)
+// entries - two inversions per base where one per entry took 20 s for the 10^5 entries of a 257-input key
+template <class C> struct G16HostTables {
   typedef typename C::F F;
-  constexpr int FW = F::WORDS, A = F::ARK64, W1 = C::G1W;
-  const size_t n_in = n_abc - 1;
-  const int W = fb_windows(C::SCALAR_BITS, c);
-  const uint32_t H = 1u << (c - 1), E = (uint32_t)W * H;
-  std::vector<uint32_t> table((size_t)(n_in ? n_in : 1) * E * 2 * FW), abc0(2 * FW);
-  std::vector<uint8_t> tinf((size_t)(n_in ? n_in : 1) * E);
-  fb_store_entry(abc0.data(), Affine<F>{F::norm(F::from_ark(abc)), F::norm(F::from_ark(abc + A))});
-  for (size_t j = 0; j < n_in; j++) {
-    const uint64_t* gen = abc + (j + 1) * W1;
-    const Affine<F> g = {F::norm(F::from_ark(gen)), F::norm(F::from_ark(gen + A))};
-    for (int w = 0; w < W; w++) {
-      Affine<F> b = {F::zero(), F::zero()};
-      const bool okb = fb_to_affine(fb_window_base(g, w, c), b);
-      for (uint32_t d = 1; d <= H; d++) {
-        const size_t e = j * E + (size_t)w * H + d - 1;
-        Affine<F> r = {F::zero(), F::zero()};
-        const bool ok = okb && fb_to_affine(fb_table_entry(b, d), r);
-        fb_store_entry(&table[e * 2 * FW], r);
-        tinf[e] = ok ? 0 : 1;
+  static constexpr int FW = F::WORDS, A = F::ARK64, W1 = C::G1W;
+  size_t n_in;
+  int c, W;
+  std::vector<uint64_t> rows;          // the gamma_abc rows the tables were made from
+  std::vector<uint32_t> table, abc0;
+  std::vector<uint8_t> tinf;
+  G16HostTables(const uint64_t* abc, size_t n_abc, int c_) : n_in(n_abc - 1), c(c_), W(fb_windows(C::SCALAR_BITS, c_)), rows(abc, abc + n_abc * W1) {
+    const uint32_t H = 1u << (c - 1), E = (uint32_t)W * H;
+    table.resize((size_t)(n_in ? n_in : 1) * E * 2 * FW);
+    abc0.resize(2 * FW);
+    tinf.resize((size_t)(n_in ? n_in : 1) * E);
+    fb_store_entry(abc0.data(), Affine<F>{F::norm(F::from_ark(abc)), F::norm(F::from_ark(abc + A))});
+    std::vector<Xyzz<F>> wb(W), ent(E);
+    std::vector<Affine<F>> wa, ea;
+    std::vector<uint8_t> wok, eok;
+    for (size_t j = 0; j < n_in; j++) {
+      const uint64_t* gen = abc + (j + 1) * W1;
+      const Affine<F> g = {F::norm(F::from_ark(gen)), F::norm(F::from_ark(gen + A))};
+      for (int w = 0; w < W; w++) wb[w] = fb_window_base(g, w, c);
+      g16_batch_affine(wb, wa, wok);
+      for (int w = 0; w < W; w++)
+        for (uint32_t d = 1; d <= H; d++) ent[(size_t)w * H + d - 1] = wok[w] ? fb_table_entry(wa[w], d) : Xyzz<F>::identity();
+      g16_batch_affine(ent, ea, eok);
+      for (uint32_t e = 0; e < E; e++) {
+        fb_store_entry(&table[(j * E + e) * 2 * FW], ea[e]);
+        tinf[j * E + e] = eok[e] ? 0 : 1;
       }
     }
   }
+  // the tables of the last key, kept: a key whose rows are a prefix of it (tables are base-major) at the same window bits reuses them
+  static std::shared_ptr<const G16HostTables> of(const uint64_t* abc, size_t n_abc, int c) {
+    static std::mutex mu;
+    static std::shared_ptr<const G16HostTables> last;
+    std::lock_guard<std::mutex> lk(mu);
+    if (!last || last->c != c || last->rows.size() < n_abc * W1 || memcmp(last->rows.data(), abc, n_abc * W1 * 8) != 0) last.reset(new G16HostTables(abc, n_abc, c));
+    return last;
+  }
+  static void write_row(const Xyzz<F>& a, uint64_t* o, uint8_t* inf) {
+    Affine<F> r;
+    if (fb_to_affine(a, r)) { r.x.to_ark(o); r.y.to_ark(o + A); *inf = 0; }
+    else { for (int k = 0; k < W1; k++) o[k] = 0; *inf = 1; }
+  }
+};
+template <class C>
+static void g16_input_row_host(const uint64_t* abc, size_t n_abc, const uint64_t* inputs, size_t n, int c, uint64_t* out, uint8_t* inf, uint8_t* status) {
+  const auto tables = G16HostTables<C>::of(abc, n_abc, c);
+  const G16HostTables<C>& T = *tables;
+  const size_t n_in = n_abc - 1;
   for (size_t i = 0; i < n; i++) {
     uint32_t bad = 0;
-    const Xyzz<F> a = g16_input_row<C>(inputs + i * n_in * C::N64, (uint32_t)n_in, abc0.data(), false, table.data(), tinf.data(), c, W, &bad);
-    Affine<F> r;
-    uint64_t* o = out + i * W1;
-    if (fb_to_affine(a, r)) { r.x.to_ark(o); r.y.to_ark(o + A); inf[i] = 0; }
-    else { for (int k = 0; k < W1; k++) o[k] = 0; inf[i] = 1; }
+    const Xyzz<typename C::F> a = g16_input_row<C>(inputs + i * n_in * C::N64, (uint32_t)n_in, T.abc0.data(), false, T.table.data(), T.tinf.data(), c, T.W, &bad);
+    G16HostTables<C>::write_row(a, out + i * C::G1W, &inf[i]);
+    status[i] = bad ? 1 : 0;
+  }
+}
+// k_g16_inputs_lanes in host loops: the L lanes of a sum one after the other, their partials folded through a buffer of L / 2 slots in the
+// kernel's rounds (the upper half of a round's lanes stores, then the lower half adds)
+template <class C>
+static void g16_input_lanes_host(const uint64_t* abc, size_t n_abc, const uint64_t* inputs, size_t n, int c, uint32_t L, uint64_t* out, uint8_t* inf, uint8_t* status) {
+  typedef typename C::F F;
+  const auto tables = G16HostTables<C>::of(abc, n_abc, c);
+  const G16HostTables<C>& T = *tables;
+  const size_t n_in = n_abc - 1;
+  const size_t SW = agg_slot_words<F>();
+  std::vector<Xyzz<F>> acc(L);
+  std::vector<uint4> slots((L / 2 ? L / 2 : 1) * SW / 4);
+  uint32_t* sl = reinterpret_cast<uint32_t*>(slots.data());
+  for (size_t i = 0; i < n; i++) {
+    uint32_t bad = 0;
+    for (uint32_t l = 0; l < L; l++) {
+      uint32_t b = 0;
+      acc[l] = g16_lane_sum<C>(inputs + i * n_in * C::N64, (uint32_t)n_in, l, L, T.abc0.data(), false, T.table.data(), T.tinf.data(), c, T.W, &b);
+      bad |= b;
+    }
+    for (uint32_t s = L >> 1; s; s >>= 1) {
+      for (uint32_t l = s; l < 2 * s; l++) g16_fold_put<F>(sl, acc[l], l, s);
+      for (uint32_t l = 0; l < s; l++) g16_fold_take<F>(acc[l], sl, l);
+    }
+    G16HostTables<C>::write_row(acc[0], out + i * C::G1W, &inf[i]);
     status[i] = bad ? 1 : 0;
   }
 }
@@ -813,10 +889,11 @@ template <class C> static void g16_scale_host(const uint64_t* xy, const uint64_t
 }
 // the host parse of a serialized verifying key.  rows: (4 + n_abc) x 24 u64 on both curves, with room for cap rows; *n_abc out; *first_bad
 // (may be NULL): the index of the point that was refused with 33
-template <class C> static int g16_vk_parse_host(const uint8_t* bytes, size_t len, size_t cap, uint64_t* rows, uint8_t* inf, uint64_t* n_abc, uint64_t* first_bad) {
+template <class C>
+static int g16_vk_parse_host(const uint8_t* bytes, size_t len, size_t cap, uint64_t* rows, uint8_t* inf, uint64_t* n_abc, uint64_t* first_bad, size_t max_inputs = G16_MAX_INPUTS) {
   std::vector<uint64_t> r;
   std::vector<uint8_t> f;
-  const int rc = g16_vk_parse<C>(bytes, len, r, f, first_bad);
+  const int rc = g16_vk_parse<C>(bytes, len, r, f, first_bad, max_inputs);
   if (rc) return rc;
   if (f.size() > cap) return 2;
   memcpy(rows, r.data(), r.size() * 8);
@@ -841,6 +918,18 @@ int ht_g16_vk_parse_377(const uint8_t* bytes, size_t len, size_t cap, uint64_t* 
 }
 int ht_g16_window_bits(size_t n_in) { return g16_window_bits<G16Bw6>(n_in); }
 int ht_g16_window_bits_377(size_t n_in) { return g16_window_bits<G16Bls>(n_in); }
+// the wide loaders of BLS12-377 (up to G16_MAX_INPUTS_WIDE inputs): the lane sum and fold for a given L (2: L is no power of two in 1 .. 256),
+// the window rule past 64 inputs (-1 above the limit), the width rule and the parse
+int ht_g16_input_lanes_377(const uint64_t* abc, size_t n_abc, const uint64_t* inputs, size_t n, int c, int lanes, uint64_t* out, uint8_t* inf, uint8_t* status) {
+  if (!g16_lanes_ok(lanes) || n_abc == 0 || n_abc - 1 > G16_MAX_INPUTS_WIDE) return 2;
+  g16_input_lanes_host<G16Bls>(abc, n_abc, inputs, n, c, (uint32_t)lanes, out, inf, status);
+  return 0;
+}
+int ht_g16_window_bits_wide_377(size_t n_in) { return n_in > G16_MAX_INPUTS_WIDE ? -1 : g16_window_bits<G16Bls>(n_in); }
+uint32_t ht_g16_pick_lanes(size_t n_in, size_t m) { return g16_pick_lanes(n_in, m); }
+int ht_g16_vk_parse_wide_377(const uint8_t* bytes, size_t len, size_t cap, uint64_t* rows, uint8_t* inf, uint64_t* n_abc, uint64_t* first_bad) {
+  return g16_vk_parse_host<G16Bls>(bytes, len, cap, rows, inf, n_abc, first_bad, G16_MAX_INPUTS_WIDE);
+}
 // the setup's scalar lists as unit_setup.hip lays them out: G1 [alpha, beta, delta, gamma_abc, a, b, h, l], G2 [beta, gamma, delta, b]
 extern "C++" {
 template <class FR> static void setup_host(const uint64_t* qa, const uint64_t* qb, const uint64_t* qc, size_t n_vars, size_t n_inputs, const uint64_t* zt,

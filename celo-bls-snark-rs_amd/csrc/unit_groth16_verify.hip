@@ -2,6 +2,7 @@
 // crates/epoch-snark/src/api/verifier.rs:35), and what both curves of the verifier share: the registry of live handles, the record of the
 // last call and the exponent draw.  DESIGN.md section 6h.
 #include "groth16_verify_unit.h"
+#include <atomic>
 #include <mutex>
 #include <set>
 
@@ -32,14 +33,28 @@ int groth16_vk_release(VerifyingKey* vk) {
 
 // the last call: path 0 = each, 1 = combined accepted, 2 = combined rejected then each; ms: [0] decoding, [1] input sums, [2] exponents
 // and ladders, [3] the two MSMs and (sum r) alpha (wall), [4] pairing products (HIP events of the engine, both passes of path 2),
-// [5] wall, [6] transfers to the device
+// [5] wall, [6] transfers to the device; lanes / n_in: the lanes per input sum and the key's input count
 static std::mutex g_last_mu;
-static struct { int path = -1, c = 0; float ms[8] = {}; } g_last;
-void groth16_verify_note(int path, int window_bits, const float ms[8]) {
+static struct { int path = -1, c = 0, lanes = 0, n_in = 0; float ms[8] = {}; } g_last;
+void groth16_verify_note(int path, int window_bits, const float ms[8], int lanes, int n_inputs) {
   std::lock_guard<std::mutex> lk(g_last_mu);
-  g_last.path = path; g_last.c = window_bits;
+  g_last.path = path; g_last.c = window_bits; g_last.lanes = lanes; g_last.n_in = n_inputs;
   for (int i = 0; i < 8; i++) g_last.ms[i] = ms[i];
 }
+int groth16_inputs_last(int* lanes, int* n_inputs) {
+  if (!lanes || !n_inputs) return 2;
+  std::lock_guard<std::mutex> lk(g_last_mu);
+  *lanes = g_last.lanes; *n_inputs = g_last.n_in;
+  return 0;
+}
+// a test and tuning switch: 0 = the rule (g16_pick_lanes), else the lanes per input sum of every BLS12-377 call; an atomic, no device needed
+static std::atomic<int> g_input_lanes{0};
+int groth16_set_input_lanes(int lanes) {
+  if (lanes != 0 && !g16_lanes_ok(lanes)) return 2;
+  g_input_lanes.store(lanes);
+  return 0;
+}
+int groth16_input_lanes() { return g_input_lanes.load(); }
 
 // tests / tooling: the exponents a combined call under `key` gives its m proofs, 2 x u64 each, on the host
 int groth16_draw_exponents_run(const uint32_t key[8], size_t m, uint64_t* out) {

@@ -215,4 +215,29 @@ int hash_helper_prove(const ProvingKey* k, const R1cs* r, const uint8_t* rows48,
   return 0;
 }
 
+// The verifier's side of generate_hash_helper in one call: n_proofs proofs (192 bytes each) of chains of m epochs, proof p over rows
+// [p m, (p + 1) m).  The rows go up, the canonical inputs are made on the device (hashbits_public_inputs' kernels) and the Groth16 verifier
+// reads them where they lie.  2: a NULL pointer, a size the size query refuses, or a key whose input count is not n_inputs(m) - 1 (a handle
+// that is not a live BLS12-377 one among them) - all before any device use; else the verifier's codes.
+int hash_helper_verify(const VerifyingKey* vk, const uint8_t* rows48, size_t n_proofs, size_t m, int bit_order, const uint8_t* proofs, int mode, const uint32_t* key,
+                       uint8_t* out_ok) {
+  HbSizes s;
+  if (!vk || !rows48 || !proofs || !out_ok || bit_order < 0 || bit_order > 1 || (mode != 0 && mode != 1)) return 2;
+  if (n_proofs == 0 || n_proofs > (size_t(1) << 24)) return 2;
+  if (int rc = hb_sizes(m, &s)) return rc;
+  if (n_proofs * m > (size_t(1) << 24)) return 2;
+  if (groth16_vk_inputs(vk, 1) != (int)(s.n_inputs - 1)) return 2;
+  if (int rc0 = api_enter()) return rc0;
+  CallScope cs;
+  HIP_TRY(cs.open(0, nullptr), 10);
+  uint8_t* d_rows;
+  uint64_t* d_in;
+  HIP_TRY(cs.in(&d_rows, rows48, n_proofs * m * HB_ROW_BYTES, 0), 10);
+  HIP_TRY(cs.alloc(&d_in, n_proofs * (s.n_inputs - 1) * 32), 10);
+  EvLog log(cs.stream());
+  if (int rc = enqueue(cs, log, d_rows, n_proofs, m, bit_order, s, nullptr, d_in)) return rc;
+  HIP_TRY(hipStreamSynchronize(cs.stream()), 10);          // the verifier works on a stream of its own
+  return G16Api<G16Bls>::verify_staged(vk, proofs, d_in, nullptr, n_proofs, mode, key, out_ok, nullptr);
+}
+
 }  // namespace celo

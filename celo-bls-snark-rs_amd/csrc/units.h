@@ -250,10 +250,13 @@ void hash_helper_last(float ms[8]);
 
 // ---- Groth16 verification of many proofs under one key (groth16_verify_unit.h holds the definitions; unit_groth16_verify.hip instantiates
 // them for C = G16Bw6 and unit_groth16_verify377.hip for C = G16Bls).  Rows: affine arkworks limbs, C::G1W / C::G2W u64 each
+// the most public inputs (n_abc - 1) a loader takes: the narrow loaders of both curves, and the wide loaders of BLS12-377.  groth16_verify.h's
+// G16_MAX_INPUTS / G16_MAX_INPUTS_WIDE (what the parse and the kernels' bounds use) are held equal to them by groth16_verify_unit.h
+constexpr size_t VK_MAX_INPUTS = 64, VK_MAX_INPUTS_WIDE = 1024;
 template <class C> struct G16Api {
   static int vk_load(const uint64_t* alpha_g1, const uint64_t* beta_g2, const uint64_t* gamma_g2, const uint64_t* delta_g2, const uint64_t* gamma_abc_g1, size_t n_abc,
-                     VerifyingKey** out);
-  static int vk_load_serialized(const uint8_t* bytes, size_t len, VerifyingKey** out);
+                     VerifyingKey** out, size_t max_inputs = VK_MAX_INPUTS);
+  static int vk_load_serialized(const uint8_t* bytes, size_t len, VerifyingKey** out, size_t max_inputs = VK_MAX_INPUTS);
   static int verify(const VerifyingKey* vk, const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf, const uint64_t* c_xy,
                     const uint8_t* c_inf, const uint8_t* proofs, const uint64_t* inputs, size_t m, int mode, const uint32_t* key, uint8_t* out_ok);
   // the serialized entry with the inputs (m x n_in x N64 u64, canonical) and one status byte per proof already on the DEVICE (unit_epoch.hip): a
@@ -268,9 +271,15 @@ void groth16_vk_adopt(VerifyingKey* vk);
 bool groth16_vk_is_live(const VerifyingKey* vk, int curve);
 int groth16_vk_inputs(const VerifyingKey* vk, int curve);        // the number of public inputs of a live handle of `curve`, or -1
 int groth16_vk_release(VerifyingKey* vk);
-void groth16_verify_note(int path, int window_bits, const float ms[8]);
+void groth16_verify_note(int path, int window_bits, const float ms[8], int lanes, int n_inputs);
 int groth16_draw_exponents_run(const uint32_t key[8], size_t m, uint64_t* out);
 int groth16_verify_last(int* path, int* window_bits, float ms[8]);
+int groth16_set_input_lanes(int lanes);          // lanes per input sum of a BLS12-377 call: 0 = the rule (groth16_verify.h g16_pick_lanes), else 1, 2, 4 .. 256
+int groth16_input_lanes();                       // the forced width, or 0
+int groth16_inputs_last(int* lanes, int* n_inputs);
+// generate_hash_helper's verifier in one call (unit_hashbits.hip): rows to the device, canonical inputs made there, verify_staged on them
+int hash_helper_verify(const VerifyingKey* vk, const uint8_t* rows48, size_t n_proofs, size_t m, int bit_order, const uint8_t* proofs, int mode, const uint32_t* key,
+                       uint8_t* out_ok);
 int wire377_proof_serialize(const uint64_t* a_xyz, const uint64_t* b_xyz, const uint64_t* c_xyz, uint8_t* out);      // unit_wire_encode.hip
 
 int ubench_fp_run(float out[9]);                 // unit_ubench.hip

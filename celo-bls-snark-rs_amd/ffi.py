@@ -80,6 +80,8 @@ EXPORTS = [
     "groth16_prove_r1cs_with_key_dev", "hash_to_bits_r1cs_size_bls12_377", "hash_to_bits_r1cs_bls12_377", "hash_to_bits_r1cs_load_bls12_377",
     "hash_to_bits_assignment_bls12_377", "hash_to_bits_assignment_bls12_377_dev", "celo_amd_hash_to_bits_assignment_host",
     "hash_to_bits_public_inputs_bls12_377", "hash_to_bits_public_inputs_bls12_377_dev", "groth16_hash_helper_prove_bls12_377", "celo_amd_hash_helper_last",
+    "groth16_vk_load_bls12_377_wide", "groth16_vk_load_bls12_377_wide_serialized", "celo_amd_groth16_set_input_lanes", "celo_amd_groth16_inputs_last",
+    "groth16_hash_helper_verify_bls12_377",
 ]
 
 _lib = None
@@ -670,6 +672,8 @@ class VerifyError(RuntimeError):
 
 VERIFY_PATHS = {0: "each", 1: "combined accepted", 2: "combined then each"}
 VK_ERR_INPUTS = 36
+VK_WIDE_INPUTS = 1024                   # the most public inputs of a wide BLS12-377 key (csrc/groth16_verify.h G16_MAX_INPUTS_WIDE)
+G16_INPUT_LANES = (1, 2, 4, 8, 16, 32, 64, 128, 256)   # the widths celo_amd_groth16_set_input_lanes accepts besides 0
 
 
 # per curve of the verifier: u64 of a G1 / G2 row, of one input, bytes of a compressed G1 / G2 point
@@ -679,10 +683,13 @@ VERIFY_CURVES = {"bw6_761": (24, 24, 6, 96, 96), "bls12_377": (12, 24, 4, 48, 96
 class VerifyingKey:
     """A loaded Groth16 verifying key over BW6-761 or BLS12-377 (groth16_vk_load_<curve>): verify() checks m proofs under it in one call.
     alpha_g1 and the rows of gamma_abc_g1 (n_abc of them): 24 u64 each over BW6-761, 12 over BLS12-377; beta_g2 / gamma_g2 / delta_g2: 24 u64;
-    affine arkworks limbs.  Raises VerifyError (.code)."""
-    def __init__(self, alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1, curve="bw6_761"):
+    affine arkworks limbs.  wide (BLS12-377 only): the loaders that take up to VK_WIDE_INPUTS public inputs where the others stop at 64.
+    Raises VerifyError (.code)."""
+    def __init__(self, alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1, curve="bw6_761", wide=False):
+        assert not wide or curve == "bls12_377", "wide keys: BLS12-377 only"
         self.h = C.c_void_p()
         self.curve = curve
+        self._load = "groth16_vk_load_" + curve + ("_wide" if wide else "")
         self.w1, self.w2, self.n64, b1, b2 = VERIFY_CURVES[curve]
         self.proof_bytes, self.key_head = 2 * b1 + b2, b1 + 3 * b2
         if alpha_g1 is None:                # from_serialized fills the handle
@@ -690,20 +697,20 @@ class VerifyingKey:
         pts = [np.ascontiguousarray(x, dtype=np.uint64).reshape(w) for x, w in zip((alpha_g1, beta_g2, gamma_g2, delta_g2), (self.w1, self.w2, self.w2, self.w2))]
         abc = _rows(gamma_abc_g1, self.w1)
         self.n_inputs = abc.shape[0] - 1
-        rc = getattr(lib(), "groth16_vk_load_" + curve)(*[_p(x) for x in pts], _p(abc), C.c_size_t(abc.shape[0]), C.byref(self.h))
+        rc = getattr(lib(), self._load)(*[_p(x) for x in pts], _p(abc), C.c_size_t(abc.shape[0]), C.byref(self.h))
         if rc != 0:
             self.h = C.c_void_p()
-            raise VerifyError("groth16_vk_load_" + curve, rc)
+            raise VerifyError(self._load, rc)
 
     @classmethod
-    def from_serialized(cls, data, curve="bw6_761"):
+    def from_serialized(cls, data, curve="bw6_761", wide=False):
         """from VerifyingKey::serialize bytes (compressed; decoded and checked as VerifyingKey::deserialize does)"""
-        k = cls(None, None, None, None, None, curve=curve)
+        k = cls(None, None, None, None, None, curve=curve, wide=wide)
         buf = np.frombuffer(bytes(data), dtype=np.uint8)
-        rc = getattr(lib(), "groth16_vk_load_%s_serialized" % curve)(_p(buf), C.c_size_t(buf.size), C.byref(k.h))
+        rc = getattr(lib(), k._load + "_serialized")(_p(buf), C.c_size_t(buf.size), C.byref(k.h))
         if rc != 0:
             k.h = C.c_void_p()
-            raise VerifyError("groth16_vk_load_%s_serialized" % curve, rc)
+            raise VerifyError(k._load + "_serialized", rc)
         k.n_inputs = int.from_bytes(bytes(data)[k.key_head:k.key_head + 8], "little") - 1
         return k
 
@@ -774,6 +781,21 @@ def groth16_verify_last():
     ms = (C.c_float * 8)()
     lib().celo_amd_groth16_verify_last(C.byref(path), C.byref(c), ms)
     return VERIFY_PATHS.get(path.value, "none"), c.value, list(ms)
+
+
+def groth16_set_input_lanes(lanes):
+    """Lanes per input sum of every later BLS12-377 verify call (celo_amd_groth16_set_input_lanes): 0 = the rule, else one of G16_INPUT_LANES.
+    A test and tuning switch; no device call."""
+    rc = lib().celo_amd_groth16_set_input_lanes(C.c_int(lanes))
+    if rc != 0:
+        raise ValueError("celo_amd_groth16_set_input_lanes(%d) failed with code %d" % (lanes, rc))
+
+
+def groth16_inputs_last():
+    """(lanes per input sum, public inputs of the key) of the last verify call (celo_amd_groth16_inputs_last)"""
+    lanes, n_in = C.c_int(0), C.c_int(0)
+    assert lib().celo_amd_groth16_inputs_last(C.byref(lanes), C.byref(n_in)) == 0
+    return lanes.value, n_in.value
 
 
 # ---- the hash-helper proof's field and curve: Fr(BLS12-377) elements are 4 u64, G1 points 12 u64 affine / 18 Jacobian, G2 24 / 36
@@ -1957,6 +1979,23 @@ def hash_helper_prove(key, r1cs, rows48, bit_order, log_n, consts):
     if rc != 0:
         raise RuntimeError("groth16_hash_helper_prove_bls12_377 failed with code %d" % rc)
     return a, b, c, inputs
+
+
+def hash_helper_verify(vk, rows48, n_epochs, proofs, bit_order=0, mode=0, key=None):
+    """The verifier's side of generate_hash_helper in one call (groth16_hash_helper_verify_bls12_377): vk a BLS12-377 VerifyingKey of
+    n_inputs(n_epochs) - 1 inputs, rows48 (n_proofs x n_epochs, 48) CRH rows, proofs n_proofs x 192 serialized bytes -> uint8 [n_proofs] verdicts.
+    Raises VerifyError (.code)."""
+    buf = np.frombuffer(bytes(proofs), dtype=np.uint8)
+    assert buf.size % 192 == 0
+    n_proofs = buf.size // 192
+    r = np.ascontiguousarray(rows48, dtype=np.uint8).reshape(-1, 48)
+    assert r.shape[0] == n_proofs * n_epochs, "rows48: n_proofs x n_epochs rows of 48 bytes"
+    k = None if key is None else np.ascontiguousarray(key, dtype=np.uint32).reshape(8)
+    out = np.zeros(n_proofs, dtype=np.uint8)
+    rc = lib().groth16_hash_helper_verify_bls12_377(vk.h, _p(r), C.c_size_t(n_proofs), C.c_size_t(n_epochs), C.c_int(bit_order), _p(buf), C.c_int(mode), _p(k), _p(out))
+    if rc != 0:
+        raise VerifyError("groth16_hash_helper_verify_bls12_377", rc)
+    return out
 
 
 def hash_helper_last():

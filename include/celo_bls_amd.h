@@ -497,6 +497,18 @@ int celo_amd_groth16_verify_last(int* path, int* window_bits, float ms[8]);
  * (decompress_bls12_377_*_dev, check_subgroup = 1).
  * Window tables: entries are 2 x 16 words (the 14 limbs of a coordinate in the field's stored form), 128 B; the widest of 10 .. 4 bits whose
  * tables fit 64 MiB is 10 bits up to 39 inputs and 9 bits from 40 to 64.
+ * Wide keys.  groth16_vk_load_bls12_377_wide[_serialized] take the arguments and return the codes of the two loaders above, and accept up to
+ * 1024 public inputs (n_abc <= 1025; 36 above) where those stop at 64: the hash-helper proof of n epochs has ceil(384 n / 252) + ceil(512 n / 252)
+ * inputs, 509 at the production size of 143 epochs.  The window rule is the same; the last input count of 10 .. 4 bits is 39 | 70 | 128 | 221 | 381 |
+ * 642 | 1024 (1024 inputs at 4 bits fill the 64 MiB exactly; 143 epochs get 5 bits, 287 epochs with 1022 inputs are the most that fit).  The
+ * handle is an ordinary BLS12-377 handle: every entry here, groth16_vk_free and celo_amd_groth16_verify_last take it; a BW6-761 entry
+ * refuses it with 2.  Past 64 inputs one lane per proof is too little (509 inputs at 5 bits: about 26 000 dependent additions), so the
+ * input sums of such a key are the work of L lanes per proof, folded through LDS (csrc/groth16_verify.h g16_pick_lanes: L follows the input
+ * count and falls as the batch grows; a key of at most 64 inputs keeps the one-lane kernel).
+ * celo_amd_groth16_set_input_lanes: a test and tuning switch, no device call.  0: the rule; 1, 2, 4, .. 256: every later BLS12-377 verify
+ * call of the process runs its input sums with that many lanes per proof, whatever the key.  2: any other value.
+ * celo_amd_groth16_inputs_last: the lanes per input sum and the key's public-input count of the last successful verify call (either
+ * curve; BW6-761 always reports 1 lane).  2: a NULL pointer.
  * groth16_vk_free, celo_amd_groth16_draw_exponents and celo_amd_groth16_verify_last serve both curves.  A handle knows its curve: a
  * BLS12-377 handle given to a BW6-761 entry, or the reverse, returns 2 before anything is read.
  * Dispatch: a product of four pairs is one more than the BLS12-377 latency path takes, so mode 0 runs the per-pair lane kernels below
@@ -519,6 +531,11 @@ int groth16_verify_batch_bls12_377(const void* vk, const uint64_t* a_xy /* m x 1
 int groth16_verify_batch_bls12_377_serialized(const void* vk, const uint8_t* proofs /* m x 192 */, const uint64_t* inputs, size_t m, int mode,
                                               const uint32_t* key /* 8, or NULL */, uint8_t* out_ok /* m */);
 int groth16_serialize_proof_bls12_377(const uint64_t a_xyz[18], const uint64_t b_xyz[36], const uint64_t c_xyz[18], uint8_t out[192]);
+int groth16_vk_load_bls12_377_wide(const uint64_t alpha_g1[12], const uint64_t beta_g2[24], const uint64_t gamma_g2[24], const uint64_t delta_g2[24],
+                                   const uint64_t* gamma_abc_g1 /* n_abc x 12 */, size_t n_abc, void** out_vk);
+int groth16_vk_load_bls12_377_wide_serialized(const uint8_t* bytes, size_t len, void** out_vk);
+int celo_amd_groth16_set_input_lanes(int lanes);
+int celo_amd_groth16_inputs_last(int* lanes, int* n_inputs);
 
 /* ---- bulk ENCODING into the same wire form: n affine points (arkworks Montgomery limbs, the rows the decoders, normalize_* and the MSM
  * entry points use) -> n encodings, one point per GPU lane.  Replaces n calls of GroupAffine::serialize (compress_*: x little-endian with
@@ -1085,8 +1102,16 @@ int groth16_prove_r1cs_with_key_dev(const void* key, const void* r1cs, const uin
  * celo_amd_hash_helper_last: the last such call in ms: [0] trace, [1] expand, [2] pack kernels, [3] the proof (wall), [4] the call (wall); a
  * hash_to_bits_assignment_* call leaves its three kernel times in [0..2] and zeroes the rest.
  *
- * Limit: groth16_verify_batch_bls12_377 takes at most 64 public inputs (code 36), so it checks helper proofs of at most 17 epochs (61 inputs;
- * 18 epochs have 65).  Everything here works at any n_epochs within the R1CS limits; 143 epochs make a domain of 2^23. */
+ * groth16_hash_helper_verify_*: the verifier's side of generate_hash_helper in one call, for n_proofs serialized proofs (192 B each; proof p
+ * over rows [p n_epochs, (p + 1) n_epochs)).  The rows go to the device, the canonical inputs are written there and the verifier of
+ * groth16_verify_batch_bls12_377_serialized reads them where they lie; mode, key and out_ok (n_proofs verdicts) are that entry's.  vk: a
+ * BLS12-377 handle of n_inputs - 1 public inputs.  2, before any device use: a NULL pointer (key may be NULL), bit_order or mode not 0 / 1,
+ * n_proofs or n_epochs refused by hash_to_bits_public_inputs_*, a handle that is not a live BLS12-377 one or whose input count is not
+ * n_inputs(n_epochs) - 1.  Otherwise the verifier's codes.
+ *
+ * Limit: a key from groth16_vk_load_bls12_377[_serialized] takes at most 64 public inputs (code 36): helper proofs of at most 17 epochs (61
+ * inputs; 18 epochs have 65).  A key from groth16_vk_load_bls12_377_wide[_serialized] takes 1024: up to 287 epochs, the production size of
+ * 143 (509 inputs) among them.  Everything else here works at any n_epochs within the R1CS limits; 143 epochs make a domain of 2^23. */
 int hash_to_bits_r1cs_size_bls12_377(size_t n_epochs, uint64_t out[8]);
 int hash_to_bits_r1cs_bls12_377(size_t n_epochs, uint64_t* a_row_ptr, uint32_t* a_col, uint64_t* a_val, uint64_t* b_row_ptr, uint32_t* b_col, uint64_t* b_val,
                                 uint64_t* c_row_ptr, uint32_t* c_col, uint64_t* c_val);
@@ -1100,6 +1125,8 @@ int groth16_hash_helper_prove_bls12_377(const void* key, const void* r1cs, const
                                         const uint64_t* omega_inv, const uint64_t* coset, const uint64_t* coset_inv, const uint64_t* size_inv,
                                         const uint64_t* vanishing_inv, uint64_t* out_a, uint64_t* out_b, uint64_t* out_c, uint64_t* out_inputs);
 int celo_amd_hash_helper_last(float ms[8]);
+int groth16_hash_helper_verify_bls12_377(const void* vk, const uint8_t* rows48 /* n_proofs x n_epochs x 48 */, size_t n_proofs, size_t n_epochs, int bit_order,
+                                         const uint8_t* proofs /* n_proofs x 192 */, int mode, const uint32_t* key /* 8, or NULL */, uint8_t* out_ok /* n_proofs */);
 
 #ifdef __cplusplus
 }
