@@ -3,7 +3,6 @@
 #include "msm.h"
 #include "runtime.h"
 #include "units.h"
-#include <mutex>
 #include <thread>
 #include <atomic>
 
@@ -86,18 +85,13 @@ template <class F> int sum_jacobian_impl(const uint64_t* jac, size_t k, uint64_t
 
 // "last call" record of a group (what celo_amd_msm_last_timings reports); engines are pooled, so the record is a copy
 struct MsmLast {
-  std::mutex mu;
-  MsmTimings tm;
-  int c = 0, nw = 0;
-  uint32_t buckets = 0;
-  template <class E> void note(const E& e) {
-    std::lock_guard<std::mutex> lk(mu);
-    tm = e.tm; c = e.last_c; nw = e.last_nw; buckets = e.last_buckets;
-  }
+  struct Rec { MsmTimings tm; int c = 0, nw = 0; uint32_t buckets = 0; };
+  Last<Rec> rec;
+  template <class E> void note(const E& e) { rec.note({e.tm, e.last_c, e.last_nw, e.last_buckets}); }
   void read(float ms[5], int cfg[3]) {
-    std::lock_guard<std::mutex> lk(mu);
-    ms[0] = tm.convert; ms[1] = tm.sort; ms[2] = tm.accumulate; ms[3] = tm.reduce; ms[4] = tm.total;
-    cfg[0] = c; cfg[1] = nw; cfg[2] = (int)buckets;
+    const Rec r = rec.read();
+    ms[0] = r.tm.convert; ms[1] = r.tm.sort; ms[2] = r.tm.accumulate; ms[3] = r.tm.reduce; ms[4] = r.tm.total;
+    cfg[0] = r.c; cfg[1] = r.nw; cfg[2] = (int)r.buckets;
   }
 };
 

@@ -8,18 +8,23 @@
 //                           own non-blocking HIP stream); a new one is created when all are busy (up to MAX_PER_DEVICE,
 //                           then callers wait),
 //   3. runs, copies its timings to the per-kind "last call" record, and returns the engine.
+// The records (last_call.h): a call keeps its times in its own frame and publishes them once - at its successful end, or, for the composed bulk
+// calls, through a TimedCall on every exit; a sub-call hands its time up through a trailing `float* kernel_ms` (units.h) and notes its own record
+// besides; no unit reads another's record, and a getter takes the record's lock alone.  The whole-call locks of the bulk units stay (one call fills
+// the GPU) and guard: hash_mu the hash scratch, its stream and the generator tables' device copies; agg_mu, vb_mu and setup_mu their units' settings
+// (g_agg_lanes / g_agg_complement, g_vb_c / g_vb_chunk, g_fb_c); wire_mu, w761_mu, wenc_mu, trans_mu and epoch_mu serialisation only.
 // Independent calls therefore overlap on the GPU (separate streams) and several devices can be driven from one process:
 // celo_amd_use_device() binds a host thread to a device, the msm_*_multi entry points do that internally (one thread per device).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <sys/random.h>
 #include <atomic>
-#include <chrono>
 #include <condition_variable>
 #include <cstdio>
 #include <memory>
 #include <mutex>
 #include <vector>
+#include "last_call.h"
 
 // a failed HIP call: logged (the expression, HIP's message, where), then the calling function returns rc
 #define HIP_TRY(x, rc)                                                                                            \
@@ -139,16 +144,6 @@ inline bool os_random(void* buf, size_t n) {
   return true;
 }
 
-// Wall-clock ms since construction.  With a slot: written there on destruction - declared in front of a CallScope, the time includes
-// the release of the call's resources on every exit.
-struct WallMs {
-  explicit WallMs(float* slot_ = nullptr) : slot(slot_) {}
-  ~WallMs() { if (slot) *slot = ms(); }
-  float ms() const { return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-  const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-  float* const slot;
-};
-
 // The device resources of ONE call: its allocations, its events and, when create_stream() made one, its stream.  The call runs on
 // stream() - the caller's, the null stream, or its own.  Released on every exit, in this order: the stream is synchronised, the
 // allocations freed, the events destroyed, then an owned stream destroyed.
@@ -232,18 +227,20 @@ class CallScope {
 };
 
 
-// kernel-time accounting by event pairs per category (read after the call's final synchronisation)
+// kernel-time accounting by event pairs per category (read after the call's final synchronisation).  The log owns every event from its creation:
+// a call that leaves between open() and close() leaks none
 struct EvLog {
   struct Rec { int cat; hipEvent_t a, b; };
   std::vector<Rec> recs;
+  std::vector<hipEvent_t> events;
   hipStream_t s;
   explicit EvLog(hipStream_t st) : s(st) {}
-  hipEvent_t open() { hipEvent_t e = nullptr; if (hipEventCreate(&e) != hipSuccess) return nullptr; (void)hipEventRecord(e, s); return e; }
-  void close(int cat, hipEvent_t a) { hipEvent_t e = nullptr; if (a && hipEventCreate(&e) == hipSuccess) { (void)hipEventRecord(e, s); recs.push_back({cat, a, e}); } }
+  hipEvent_t open() { hipEvent_t e = nullptr; if (hipEventCreate(&e) != hipSuccess) return nullptr; events.push_back(e); (void)hipEventRecord(e, s); return e; }
+  void close(int cat, hipEvent_t a) { if (hipEvent_t e = a ? open() : nullptr) recs.push_back({cat, a, e}); }
   void sum(float* ms) {
     for (auto& r : recs) { float t = 0.f; if (hipEventElapsedTime(&t, r.a, r.b) == hipSuccess) ms[r.cat] += t; }
   }
-  ~EvLog() { for (auto& r : recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); } }
+  ~EvLog() { for (hipEvent_t e : events) (void)hipEventDestroy(e); }
 };
 
 // ---- chaining engines on the device (batch verification: MSM results -> normalise -> pairing inputs, no host round trip)
@@ -258,7 +255,7 @@ struct PairingStage { void* lease = nullptr; uint64_t* d_g1 = nullptr; uint64_t*
 // pack kernel and tail uploads into ps's slots on ps.stream, run().  An engine that was staged and not run goes back to its pool.
 template <class D> struct StagedProduct {
   PairingStage ps;
-  ~StagedProduct() { if (ps.lease) (void)D::run_staged(&ps, nullptr, 0, nullptr); }
+  ~StagedProduct() { if (ps.lease) (void)D::run_staged(&ps, nullptr, 0, nullptr, nullptr); }
   int stage(uint32_t pairs, size_t products) { return D::stage(pairs, products, &ps); }
   int after(CallScope& cs) {          // the engine's stream waits for what cs.stream() holds now
     hipEvent_t ready;
@@ -267,12 +264,12 @@ template <class D> struct StagedProduct {
     HIP_TRY(hipStreamWaitEvent(ps.stream, ready, 0), 10);
     return 0;
   }
-  // m verdicts (host bytes) for the products [off[p], off[p + 1]); synchronises the engine's stream, and a producer's through after()'s event
+  // m verdicts (host bytes) for the products [off[p], off[p + 1]); synchronises the engine's stream, and a producer's through after()'s event.
+  // The engine's time for this product is ADDED to *ms_pair
   int run(const uint32_t* off, size_t m, uint8_t* is_one, float* ms_pair) {
-    if (int rc = D::run_staged(&ps, off, m, is_one)) return rc;
-    float pm[4];
-    D::timings(pm);
-    *ms_pair += pm[3];
+    float pm = 0.f;
+    if (int rc = D::run_staged(&ps, off, m, is_one, &pm)) return rc;
+    *ms_pair += pm;
     return 0;
   }
 };

@@ -14,9 +14,9 @@
 
 namespace celo {
 
-// bulk calls, serialised per process like the decoders' (one fills the GPU); the lock also keeps the last call's record whole
+// bulk calls, serialised per process like the decoders' (one fills the GPU).  The lock guards nothing else: serialisation only
 static std::mutex epoch_mu;
-static float g_epoch_ms[8] = {};
+static Last<CallTimes> g_epoch_last;          // published on every exit of a call that has entered
 enum { EP_DECODE = 0, EP_SUMS = 1, EP_PACK = 2, EP_HASH = 3, EP_XFER = 4, EP_VERIFY = 5, EP_WALL = 6 };
 
 // the per-block fields on the device
@@ -270,8 +270,7 @@ int epoch_encode_blocks(const EpochBlocks* b, size_t nb, int kind, const uint64_
     if (out_off[i + 1] < out_off[i] || out_off[i + 1] - out_off[i] != (epoch_encoded_bits(kind, b->key_off[i + 1] - b->key_off[i], b->max_validators[i]) + 7) / 8) return 2;
   if (int rc0 = api_enter()) return rc0;
   std::lock_guard<std::mutex> lk(epoch_mu);
-  for (float& t : g_epoch_ms) t = 0.f;
-  const WallMs wall(&g_epoch_ms[EP_WALL]);
+  TimedCall call(g_epoch_last, EP_WALL);
   CallScope cs;
   HIP_TRY(cs.open(dev, stream), 10);
   EvLog log(cs.stream());
@@ -295,7 +294,7 @@ int epoch_encode_blocks(const EpochBlocks* b, size_t nb, int kind, const uint64_
   HIP_TRY(cs.copy_back(), 10);
   log.close(EP_XFER, e0);
   HIP_TRY(hipStreamSynchronize(cs.stream()), 10);
-  log.sum(g_epoch_ms);
+  log.sum(call.t.ms);
   return 0;
 }
 
@@ -326,8 +325,7 @@ int epoch_public_inputs(const EpochBlocks* first, const EpochBlocks* last, size_
   if (int rc = epoch_refuse(*last, m, false)) return rc;
   if (int rc0 = api_enter()) return rc0;
   std::lock_guard<std::mutex> lk(epoch_mu);
-  for (float& t : g_epoch_ms) t = 0.f;
-  const WallMs wall(&g_epoch_ms[EP_WALL]);
+  TimedCall call(g_epoch_last, EP_WALL);
   CallScope cs;
   HIP_TRY(cs.open(dev, stream), 10);
   EvLog log(cs.stream());
@@ -340,7 +338,7 @@ int epoch_public_inputs(const EpochBlocks* first, const EpochBlocks* last, size_
   HIP_TRY(cs.copy_back(), 10);
   log.close(EP_XFER, e0);
   HIP_TRY(hipStreamSynchronize(cs.stream()), 10);
-  log.sum(g_epoch_ms);
+  log.sum(call.t.ms);
   return 0;
 }
 
@@ -353,8 +351,7 @@ int verify_epoch_proofs(const VerifyingKey* vk, const uint8_t* proofs, const Epo
   if (groth16_vk_inputs(vk, 0) != 2) return 2;             // a live BW6-761 handle with exactly the two inputs of the epoch circuit
   if (int rc0 = api_enter()) return rc0;
   std::lock_guard<std::mutex> lk(epoch_mu);
-  for (float& t : g_epoch_ms) t = 0.f;
-  const WallMs wall(&g_epoch_ms[EP_WALL]);
+  TimedCall call(g_epoch_last, EP_WALL);
   std::vector<uint8_t> pre(m), refused(m), ok(m);
   CallScope cs;
   HIP_TRY(cs.open(0, nullptr), 10);
@@ -369,10 +366,10 @@ int verify_epoch_proofs(const VerifyingKey* vk, const uint8_t* proofs, const Epo
   log.close(EP_XFER, e0);
   HIP_TRY(hipStreamSynchronize(cs.stream()), 10);          // the verifier runs on a stream of its own
   {
-    const WallMs wall_v(&g_epoch_ms[EP_VERIFY]);
+    const WallMs wall_v(&call.t.ms[EP_VERIFY]);
     if (int rc = G16Api<G16Bw6>::verify_staged(vk, proofs, d_inputs, d_status, m, mode, key, ok.data(), refused.data())) return rc;
   }
-  log.sum(g_epoch_ms);
+  log.sum(call.t.ms);
   for (size_t i = 0; i < m; i++) {
     const uint8_t st = pre[i] ? pre[i] : refused[i] ? 3 : ok[i] ? 0 : 4;
     out_ok[i] = st == 0 ? 1 : 0;
@@ -382,8 +379,8 @@ int verify_epoch_proofs(const VerifyingKey* vk, const uint8_t* proofs, const Epo
 }
 
 void epoch_last(float ms[8]) {
-  std::lock_guard<std::mutex> lk(epoch_mu);
-  for (int i = 0; i < 8; i++) ms[i] = g_epoch_ms[i];
+  const CallTimes t = g_epoch_last.read();
+  for (int i = 0; i < 8; i++) ms[i] = t.ms[i];
 }
 
 }  // namespace celo

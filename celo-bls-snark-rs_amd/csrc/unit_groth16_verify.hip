@@ -34,17 +34,17 @@ int groth16_vk_release(VerifyingKey* vk) {
 // the last call: path 0 = each, 1 = combined accepted, 2 = combined rejected then each; ms: [0] decoding, [1] input sums, [2] exponents
 // and ladders, [3] the two MSMs and (sum r) alpha (wall), [4] pairing products (HIP events of the engine, both passes of path 2),
 // [5] wall, [6] transfers to the device; lanes / n_in: the lanes per input sum and the key's input count
-static std::mutex g_last_mu;
-static struct { int path = -1, c = 0, lanes = 0, n_in = 0; float ms[8] = {}; } g_last;
+struct G16Last { int path = -1, c = 0, lanes = 0, n_in = 0; float ms[8] = {}; };
+static Last<G16Last> g_last;
 void groth16_verify_note(int path, int window_bits, const float ms[8], int lanes, int n_inputs) {
-  std::lock_guard<std::mutex> lk(g_last_mu);
-  g_last.path = path; g_last.c = window_bits; g_last.lanes = lanes; g_last.n_in = n_inputs;
-  for (int i = 0; i < 8; i++) g_last.ms[i] = ms[i];
+  G16Last r{path, window_bits, lanes, n_inputs};
+  for (int i = 0; i < 8; i++) r.ms[i] = ms[i];
+  g_last.note(r);
 }
 int groth16_inputs_last(int* lanes, int* n_inputs) {
   if (!lanes || !n_inputs) return 2;
-  std::lock_guard<std::mutex> lk(g_last_mu);
-  *lanes = g_last.lanes; *n_inputs = g_last.n_in;
+  const G16Last r = g_last.read();
+  *lanes = r.lanes; *n_inputs = r.n_in;
   return 0;
 }
 // a test and tuning switch: 0 = the rule (g16_pick_lanes), else the lanes per input sum of every BLS12-377 call; an atomic, no device needed
@@ -81,10 +81,10 @@ int groth16_draw_exponents_run(const uint32_t key[8], size_t m, uint64_t* out) {
 }
 
 int groth16_verify_last(int* path, int* window_bits, float ms[8]) {
-  std::lock_guard<std::mutex> lk(g_last_mu);
-  if (path) *path = g_last.path;
-  if (window_bits) *window_bits = g_last.c;
-  if (ms) for (int i = 0; i < 8; i++) ms[i] = g_last.ms[i];
+  const G16Last r = g_last.read();
+  if (path) *path = r.path;
+  if (window_bits) *window_bits = r.c;
+  if (ms) for (int i = 0; i < 8; i++) ms[i] = r.ms[i];
   return 0;
 }
 

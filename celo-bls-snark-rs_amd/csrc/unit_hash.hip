@@ -16,7 +16,7 @@
 #define FROW_OCC __attribute__((amdgpu_waves_per_eu(2, 2)))
 #endif
 namespace celo {
-static std::mutex hash_mu;                 // bulk calls, serialised per process (each fills the GPU; buffers are per call)
+static std::mutex hash_mu;                 // bulk calls, serialised per process; guards the per-device scratch, its stream and the generator tables' device copies
 
 struct HashDom { uint8_t b[8]; };
 struct HashIn { const uint8_t* msgs; const uint64_t* msg_off; const uint8_t* extras; const uint64_t* extra_off; };
@@ -169,14 +169,15 @@ static int hash_scratch(size_t need, HashScratch** out, size_t keep = 0) {
 // Where a call's operands live.  msgs / rest: the message bytes / the extras, rows and attempts are DEVICE pointers (the _dev entries set both; the
 // second step of a CIP22 call reads its messages, the CRH rows, at the head of the scratch in either form).  stream: the caller's, with rest.
 // head: bytes at the start of the scratch that the call leaves alone.
-// at_head: the messages ARE the head of the scratch (the `msgs` argument is not used).
-struct HashWhere { bool msgs = false, rest = false, at_head = false; hipStream_t stream = nullptr; size_t head = 0; };
-static float g_hash_ms = 0.f;
-static int g_hash_rounds = 0;
-static int g_crh_last_lanes = 0;                // the width of the last CRH kernel (under hash_mu; celo_amd_crh_last_lanes)
+// at_head: the messages ARE the head of the scratch (the `msgs` argument is not used).  kernel_ms (optional): receives what the step notes as its time.
+struct HashWhere { bool msgs = false, rest = false, at_head = false; hipStream_t stream = nullptr; size_t head = 0; float* kernel_ms = nullptr; };
+// the kernel ms of the last round loop or CRH that succeeded (a CIP22 composite call runs both: its CRH's time is overwritten by the loop's, so
+// such a call reports its tail alone), the rounds of the last loop, the width of the last CRH kernel (celo_amd_crh_last_lanes)
+struct HashLast { float ms = 0.f; int rounds = 0, crh_lanes = 0; };
+static Last<HashLast> g_hash_last;
 static std::atomic<int> g_crh_lanes{0};         // 0 = the rule (crh_pick_lanes), else 1, 2, 4, .. 256 (celo_amd_crh_set_lanes)
 
-static float g_hash_g2_ms[2] = {0.f, 0.f};      // the last G2 call's candidate rounds / finish kernel
+static Last<CallTimes> g_hash_g2_last;          // the last G2 call's [0] candidate rounds, [1] finish kernel
 static std::atomic<int> g_g2_budget_log{17};    // celo_amd_hash_g2_set_lane_budget_log
 
 // What differs between the groups: the row width, the two kernels, the serial loop, the lane budget.  compat reaches only G2.
@@ -217,10 +218,10 @@ struct HashG2 {
   }
 };
 
-// The round loop of both groups, under hash_mu.  split_ms (optional): kernel time of the candidate rounds and of the finish kernel.
+// The round loop of both groups, under hash_mu.  split: the G2 record of the candidate rounds and the finish kernel is noted too.
 template <class G>
 static int hash_rounds_locked(const uint8_t* domain, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off, size_t n, int compat,
-                              uint64_t* out_xy, uint8_t* attempts, int mode, float* split_ms, const EdPoint* h_gens, size_t ngens, const HashWhere& w) {
+                              uint64_t* out_xy, uint8_t* attempts, int mode, bool split, const EdPoint* h_gens, size_t ngens, const HashWhere& w) {
   constexpr int ROW = G::ROW;
   if (n == 0) return 0;
   if (mode == TAI_COMPOSITE) {
@@ -263,7 +264,7 @@ static int hash_rounds_locked(const uint8_t* domain, const uint8_t* msgs, const 
   hipEvent_t e0, e1, em = nullptr;
   HIP_TRY(cs.event(&e0), 10);
   HIP_TRY(cs.event(&e1), 10);
-  if (split_ms) HIP_TRY(cs.event(&em), 10);
+  if (split) HIP_TRY(cs.event(&em), 10);
   HIP_TRY(hipEventRecord(e0, st), 10);
   const HashIn in = {d_msgs, d_off, d_extras, extra_off ? d_off + n + 1 : nullptr};
   const size_t budget = size_t(1) << G::budget_log();
@@ -282,8 +283,7 @@ static int hash_rounds_locked(const uint8_t* domain, const uint8_t* msgs, const 
     base += 1u << cand_log;
     round++;
   }
-  g_hash_rounds = round;
-  if (split_ms) HIP_TRY(hipEventRecord(em, st), 10);
+  if (split) HIP_TRY(hipEventRecord(em, st), 10);
   G::finish(dim3(((uint32_t)n + 63) / 64), st, d_cand, d_att, d_out, d_redo, (uint32_t)n);
   HIP_TRY(hipGetLastError(), 10);
   HIP_TRY(hipEventRecord(e1, st), 10);
@@ -293,10 +293,15 @@ static int hash_rounds_locked(const uint8_t* domain, const uint8_t* msgs, const 
   }
   HIP_TRY(hipMemcpyAsync(redo.data(), d_redo, n, hipMemcpyDeviceToHost, st), 10);
   HIP_TRY(hipStreamSynchronize(st), 10);
-  HIP_TRY(hipEventElapsedTime(&g_hash_ms, e0, e1), 10);
-  if (split_ms) {
-    HIP_TRY(hipEventElapsedTime(&split_ms[0], e0, em), 10);
-    HIP_TRY(hipEventElapsedTime(&split_ms[1], em, e1), 10);
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, e0, e1), 10);
+  g_hash_last.update([&](HashLast& r) { r.ms = ms; r.rounds = round; });
+  if (w.kernel_ms) *w.kernel_ms = ms;
+  if (split) {
+    CallTimes sp;
+    HIP_TRY(hipEventElapsedTime(&sp.ms[0], e0, em), 10);
+    HIP_TRY(hipEventElapsedTime(&sp.ms[1], em, e1), 10);
+    g_hash_g2_last.note(sp);
   }
   // the counter whose cofactor multiple was the identity is skipped like the reference's loop does: continue serially after it.  What lies on
   // the device is fetched for the flagged row alone, and the row and its counter go back where the caller reads them.
@@ -326,19 +331,20 @@ static int hash_rounds_locked(const uint8_t* domain, const uint8_t* msgs, const 
 }
 static int pedersen_crh_locked(const uint8_t* msgs, const uint64_t* msg_off, size_t n, uint8_t* out48, const EdPoint* gens, size_t ngens, const HashWhere& w, bool out_at_head);
 // The hash step of a protocol mode (units.h): the round loop in the caller's mode, or for CIP22 (mode 3) one CRH per message and then the
-// loops over xof(c || extra || inner)
+// loops over xof(c || extra || inner) - kernel_ms is then the loops' time alone, as the record's
 template <class G>
 static int hash_step(const uint8_t* domain, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off, size_t n, int compat,
-                     uint64_t* out_xy, uint8_t* attempts, int mode, float* split_ms, int dev = 0, void* stream = nullptr) {
+                     uint64_t* out_xy, uint8_t* attempts, int mode, bool split, int dev = 0, void* stream = nullptr, float* kernel_ms = nullptr) {
   HashWhere w;
   w.msgs = w.rest = dev != 0;
   w.stream = (hipStream_t)stream;
+  w.kernel_ms = kernel_ms;
   if (mode != 3) {
     size_t ngens = 0;
     const EdPoint* h_gens = mode == TAI_COMPOSITE ? celo_composite_gens(&ngens) : nullptr;   // before the lock: 0.5 s on first use
     if (int rc0 = api_enter()) return rc0;
     std::lock_guard<std::mutex> lk(hash_mu);
-    return hash_rounds_locked<G>(domain, msgs, msg_off, extras, extra_off, n, compat, out_xy, attempts, mode, split_ms, h_gens, ngens, w);
+    return hash_rounds_locked<G>(domain, msgs, msg_off, extras, extra_off, n, compat, out_xy, attempts, mode, split, h_gens, ngens, w);
   }
   if (n == 0) return 0;
   if (!msg_off) return 2;
@@ -353,16 +359,16 @@ static int hash_step(const uint8_t* domain, const uint8_t* msgs, const uint64_t*
   wc.head = (n * 48 + 255) & ~size_t(255);
   if (int rc = pedersen_crh_locked(msgs, msg_off, n, nullptr, h_gens, ngens, wc, true)) return rc;
   wc.at_head = true;
-  return hash_rounds_locked<G>(domain, nullptr, ioff.data(), extras, extra_off, n, compat, out_xy, attempts, 1, split_ms, nullptr, 0, wc);
+  return hash_rounds_locked<G>(domain, nullptr, ioff.data(), extras, extra_off, n, compat, out_xy, attempts, 1, split, nullptr, 0, wc);
 }
 int hash_to_g1_direct_run(const uint8_t* domain, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off,
-                          size_t n, uint64_t* out_xy, uint8_t* attempts, int mode, int dev, void* stream) {
-  return hash_step<HashG1>(domain, msgs, msg_off, extras, extra_off, n, 0, out_xy, attempts, mode, nullptr, dev, stream);
+                          size_t n, uint64_t* out_xy, uint8_t* attempts, int mode, int dev, void* stream, float* kernel_ms) {
+  return hash_step<HashG1>(domain, msgs, msg_off, extras, extra_off, n, 0, out_xy, attempts, mode, false, dev, stream, kernel_ms);
 }
 int hash_to_g2_run(const uint8_t* domain, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off, size_t n, int compat,
                    uint64_t* out_xy, uint8_t* attempts, int mode) {
   if (compat != 0 && compat != 1) return 2;
-  return hash_step<HashG2>(domain, msgs, msg_off, extras, extra_off, n, compat, out_xy, attempts, mode, g_hash_g2_ms);
+  return hash_step<HashG2>(domain, msgs, msg_off, extras, extra_off, n, compat, out_xy, attempts, mode, true);
 }
 // one message on the host, no device touched: mode 0 direct, 1 the CIP22 tail (`msg` is the inner CRH), 2 composite, 3 composite CIP22
 int hash_to_g2_one_run(const uint8_t* domain, const uint8_t* msg, size_t mlen, const uint8_t* extra, size_t elen, int mode, int compat, uint64_t* out_xy, int* attempt) {
@@ -388,7 +394,7 @@ int hash_g2_set_lane_budget_log(int log) {
   g_g2_budget_log.store(log);
   return 0;
 }
-void hash_g2_last_split(float ms[2]) { ms[0] = g_hash_g2_ms[0]; ms[1] = g_hash_g2_ms[1]; }
+void hash_g2_last_split(float ms[2]) { const CallTimes sp = g_hash_g2_last.read(); ms[0] = sp.ms[0]; ms[1] = sp.ms[1]; }
 // ---- bulk Pedersen CRH (pedersen.h): one message per lane; the 52080-generator table (11.7 MB) is uploaded on first use
 __global__ void __launch_bounds__(64) FROW_OCC
 k_pedersen_crh(const EdPoint* __restrict__ gens, const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ off, uint8_t* __restrict__ out, uint32_t n) {
@@ -426,24 +432,24 @@ static int pedersen_crh_locked(const uint8_t* msgs, const uint64_t* msg_off, siz
   const uint8_t* d_bytes = w.msgs ? msgs : hs->buf + o_bytes;
   if (mb && !w.msgs) HIP_TRY(hipMemcpyAsync(hs->buf + o_bytes, msgs, mb, hipMemcpyHostToDevice, st), 10);
   HIP_TRY(hipMemcpyAsync(d_off, msg_off, (n + 1) * 8, hipMemcpyHostToDevice, st), 10);
-  hipEvent_t e0, e1;
-  HIP_TRY(cs.event(&e0), 10);
-  HIP_TRY(cs.event(&e1), 10);
-  HIP_TRY(hipEventRecord(e0, st), 10);
+  EvLog log(st);
+  const hipEvent_t e0 = log.open();
   if (L == 1) hipLaunchKernelGGL(k_pedersen_crh, dim3(((uint32_t)n + 63) / 64), dim3(64), 0, st, d_gens, d_bytes, d_off, d_out, (uint32_t)n);
   else {
     const uint32_t per = CRH_BLOCK / L;         // messages per workgroup
     crh_lanes_launch((uint32_t)((n + per - 1) / per), st, d_gens, d_bytes, d_off, d_out, (uint32_t)n, L);
   }
   HIP_TRY(hipGetLastError(), 10);
-  HIP_TRY(hipEventRecord(e1, st), 10);
+  log.close(0, e0);
   if (!to_dev) HIP_TRY(hipMemcpyAsync(out48, d_out, n * 48, hipMemcpyDeviceToHost, st), 10);
   HIP_TRY(hipStreamSynchronize(st), 10);
-  HIP_TRY(hipEventElapsedTime(&g_hash_ms, e0, e1), 10);
-  g_crh_last_lanes = (int)L;
+  float ms = 0.f;
+  log.sum(&ms);
+  g_hash_last.update([&](HashLast& r) { r.ms = ms; r.crh_lanes = (int)L; });
+  if (w.kernel_ms) *w.kernel_ms = ms;
   return 0;
 }
-int pedersen_crh_run(const uint8_t* msgs, const uint64_t* msg_off, size_t n, uint8_t* out48, int dev, void* stream) {
+int pedersen_crh_run(const uint8_t* msgs, const uint64_t* msg_off, size_t n, uint8_t* out48, int dev, void* stream, float* kernel_ms) {
   size_t ngens = 0;
   const EdPoint* gens = celo_composite_gens(&ngens);      // before the lock: building the table takes 0.5 s on first use
   if (int rc0 = api_enter()) return rc0;
@@ -451,6 +457,7 @@ int pedersen_crh_run(const uint8_t* msgs, const uint64_t* msg_off, size_t n, uin
   HashWhere w;
   w.msgs = w.rest = dev != 0;
   w.stream = (hipStream_t)stream;
+  w.kernel_ms = kernel_ms;
   return pedersen_crh_locked(msgs, msg_off, n, out48, gens, ngens, w, false);
 }
 int crh_set_lanes(int lanes) {
@@ -458,10 +465,7 @@ int crh_set_lanes(int lanes) {
   g_crh_lanes.store(lanes);
   return 0;
 }
-int crh_last_lanes() {
-  std::lock_guard<std::mutex> lk(hash_mu);
-  return g_crh_last_lanes;
-}
-float hash_last_ms() { return g_hash_ms; }
-int hash_last_rounds() { return g_hash_rounds; }
+int crh_last_lanes() { return g_hash_last.read().crh_lanes; }
+float hash_last_ms() { return g_hash_last.read().ms; }
+int hash_last_rounds() { return g_hash_last.read().rounds; }
 }  // namespace celo

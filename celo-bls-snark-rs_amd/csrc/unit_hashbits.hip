@@ -17,10 +17,8 @@ constexpr uint32_t HB_TRACE_BLOCK = 64, HB_EXPAND_BLOCK = 256, HB_PACK_BLOCK = 6
 
 // the last groth16_hash_helper_prove or hash_to_bits_assignment call in ms: [0] trace, [1] expand, [2] pack (kernel times), and for the former
 // [3] the proof (wall), [4] the call (wall)
-static float g_hh_ms[8] = {};
-static std::mutex g_hh_mu;
-void hash_helper_last(float ms[8]) { std::lock_guard<std::mutex> lk(g_hh_mu); for (int i = 0; i < 8; i++) ms[i] = g_hh_ms[i]; }
-static void note_last(const float ms[8]) { std::lock_guard<std::mutex> lk(g_hh_mu); for (int i = 0; i < 8; i++) g_hh_ms[i] = ms[i]; }
+static Last<CallTimes> g_hh_last;
+void hash_helper_last(float ms[8]) { const CallTimes t = g_hh_last.read(); for (int i = 0; i < 8; i++) ms[i] = t.ms[i]; }
 
 __global__ void __launch_bounds__(HB_TRACE_BLOCK) k_hashbits_trace(const uint8_t* __restrict__ rows48, uint32_t n_epochs, int bit_order, uint32_t* __restrict__ trace) {
   const uint32_t lane = blockIdx.x * HB_TRACE_BLOCK + threadIdx.x, e = lane >> 1;
@@ -148,9 +146,9 @@ int hashbits_assignment(const uint8_t* rows48, size_t m, int bit_order, uint64_t
   if (int rc = enqueue(cs, log, d_rows, 1, m, bit_order, s, d_z, nullptr)) return rc;
   HIP_TRY(cs.copy_back(), 10);
   HIP_TRY(hipStreamSynchronize(cs.stream()), 10);
-  float ms[8] = {};
-  log.sum(ms);
-  note_last(ms);
+  CallTimes t;
+  log.sum(t.ms);
+  g_hh_last.note(t);
   return 0;
 }
 // out: n_proofs x (n_inputs - 1) x 4 canonical limbs, the layout groth16_verify_batch_bls12_377 takes; proof p reads rows [p m, (p + 1) m)
@@ -191,7 +189,7 @@ int hash_helper_prove(const ProvingKey* k, const R1cs* r, const uint8_t* rows48,
   if (log_n > 28 || log_n < s.log_n) return 2;
   if (krows[0] != n_vars || krows[1] != n_vars || krows[2] != n_vars - n_inputs || krows[3] != (size_t(1) << log_n) - 1) return 2;
   if (device != api_device()) return 101;
-  float ms[8] = {};
+  CallTimes t;
   const WallMs wall;
   {
     CallScope cs;
@@ -205,13 +203,13 @@ int hash_helper_prove(const ProvingKey* k, const R1cs* r, const uint8_t* rows48,
     if (int rc = enqueue(cs, log, d_rows, 1, m, bit_order, s, d_z, d_in)) return rc;
     HIP_TRY(cs.copy_back(), 10);
     HIP_TRY(hipStreamSynchronize(cs.stream()), 10);
-    log.sum(ms);
+    log.sum(t.ms);
     const WallMs prove;
     if (int rc = groth16_prove_r1cs(k, r, d_z, 2, log_n, omega, omega_inv, coset, coset_inv, n_inv, z_inv, out_a, out_b, out_c)) return rc;
-    ms[3] = prove.ms();
+    t.ms[3] = prove.ms();
   }
-  ms[4] = wall.ms();
-  note_last(ms);
+  t.ms[4] = wall.ms();
+  g_hh_last.note(t);
   return 0;
 }
 

@@ -1,20 +1,15 @@
 // Translation unit: BW6-761 pairing kernels + engine (see pairing.h).
 #include "pairing.h"
 #include "units.h"
-#include <mutex>
 
 namespace celo {
 static EnginePool<PairingEngine<PP761>>& pool_761() { static auto* p = new EnginePool<PairingEngine<PP761>>(); return *p; }
-static std::mutex tm_mu_761;
-static PairingTimings tm_last_761;
 
 int pairing_run_761(const uint64_t* g1, const uint8_t* inf1, const uint64_t* g2, const uint8_t* inf2, const uint32_t* offsets, size_t m,
                     uint8_t* is_one, uint64_t* gt, int mode) {
   if (int rc = api_enter()) return rc;
   auto e = pool_761().lease();
-  const int rc = e->run(g1, inf1, g2, inf2, offsets, m, is_one, gt, mode, e->own_stream());
-  if (!rc && m) { std::lock_guard<std::mutex> lk(tm_mu_761); tm_last_761 = e->tm; }
-  return rc;
+  return e->run(g1, inf1, g2, inf2, offsets, m, is_one, gt, mode, e->own_stream());
 }
 int pairing_stage_761(uint32_t k, size_t m, PairingStage* st) {
   if (int rc = api_enter()) return rc;
@@ -25,22 +20,17 @@ int pairing_stage_761(uint32_t k, size_t m, PairingStage* st) {
   *st = {l, sg.d_g1, sg.d_g2, sg.d_i1, sg.d_i2, (*l)->own_stream()};
   return 0;
 }
-int pairing_run_staged_761(PairingStage* st, const uint32_t* offsets, size_t m, uint8_t* is_one) {
+int pairing_run_staged_761(PairingStage* st, const uint32_t* offsets, size_t m, uint8_t* is_one, float* kernel_ms) {
   typedef EnginePool<PairingEngine<PP761>>::Lease L;
   L* l = (L*)st->lease;
   if (!l) return 2;
   int rc = 0;
   if (offsets) {
     rc = (*l)->run_staged(offsets, m, true, true, is_one, nullptr, 0, st->stream);
-    if (!rc && m) { std::lock_guard<std::mutex> lk(tm_mu_761); tm_last_761 = (*l)->tm; }
+    if (!rc && m && kernel_ms) *kernel_ms = (*l)->tm.total;
   }
   delete l;
   st->lease = nullptr;
   return rc;
-}
-int pairing_timings_761(float ms[4]) {
-  std::lock_guard<std::mutex> lk(tm_mu_761);
-  ms[0] = tm_last_761.miller; ms[1] = tm_last_761.product; ms[2] = tm_last_761.final_exp; ms[3] = tm_last_761.total;
-  return 0;
 }
 }  // namespace celo

@@ -4,7 +4,6 @@
 #include "r1cs.h"
 #include <hip/hip_runtime.h>
 #include <cstring>
-#include <mutex>
 #include <vector>
 #include "runtime.h"
 #include "units.h"
@@ -16,11 +15,10 @@ typedef Fp<P253> FrBls;          // the scalar field of BLS12-377
 
 // the last call's timings in ms: [0] load (validation, transposition, binning, copies: host wall), [1] the rows kernels, [2] the Lagrange kernel,
 // [3] the columns kernels, [4] groth16_prove_r1cs_with_key wall, [5] groth16_setup_r1cs_* wall
-static float g_r1cs_ms[8] = {};
-static std::mutex g_r1cs_ms_mu;
-static void note_ms(int slot, float v) { std::lock_guard<std::mutex> lk(g_r1cs_ms_mu); g_r1cs_ms[slot] = v; }
-void r1cs_note_ms(int slot, float v) { note_ms(slot, v); }
-void r1cs_last_timings(float ms[8]) { std::lock_guard<std::mutex> lk(g_r1cs_ms_mu); for (int i = 0; i < 8; i++) ms[i] = g_r1cs_ms[i]; }
+static Last<CallTimes> g_r1cs_last;
+// every writer owns its slots: the calls of this unit [0] .. [3], the prover [4], the setup [5]
+void r1cs_note_ms(int slot, float v) { g_r1cs_last.update([&](CallTimes& t) { t.ms[slot] = v; }); }
+void r1cs_last_timings(float ms[8]) { const CallTimes t = g_r1cs_last.read(); for (int i = 0; i < 8; i++) ms[i] = t.ms[i]; }
 
 // one CSR structure on the device with its binning
 struct DevCsr {
@@ -155,7 +153,7 @@ static int load_t(int curve, size_t m, size_t n_vars, size_t n_inputs, const R1c
   }
   if (rc) { r1cs_free(r); return rc; }
   *out = r;
-  note_ms(0, wall.ms());
+  r1cs_note_ms(0, wall.ms());
   return 0;
 }
 int r1cs_load(int curve, size_t m, size_t n_vars, size_t n_inputs, const uint64_t* const row_ptr[3], const uint32_t* const col[3], const uint64_t* const val[3],
@@ -200,7 +198,7 @@ static int rows_t(const R1cs* r, const uint64_t* z, unsigned log_n, uint64_t* oa
   HIP_TRY(cs.copy_back(), 10);
   HIP_TRY(hipStreamSynchronize(s), 10);
   log.sum(ms);
-  note_ms(1, ms[1]);
+  r1cs_note_ms(1, ms[1]);
   return 0;
 }
 int r1cs_rows(const R1cs* r, const uint64_t* z, unsigned log_n, uint64_t* oa, uint64_t* ob, uint64_t* oc, int dev, void* stream) {
@@ -271,8 +269,8 @@ static int qap_t(const R1cs* r, unsigned log_n, const uint64_t* omega, const uin
   HIP_TRY(cs.copy_back(), 10);
   HIP_TRY(hipStreamSynchronize(s), 10);
   log.sum(ms);
-  note_ms(2, ms[2]);
-  note_ms(3, ms[3]);
+  r1cs_note_ms(2, ms[2]);
+  r1cs_note_ms(3, ms[3]);
   return 0;
 }
 int r1cs_qap_at_tau(const R1cs* r, unsigned log_n, const uint64_t* omega, const uint64_t* tau, uint64_t* oa, uint64_t* ob, uint64_t* oc, uint64_t* ozt, int dev,

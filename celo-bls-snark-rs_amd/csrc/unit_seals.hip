@@ -14,14 +14,13 @@
 
 namespace celo {
 
-// calls from several host threads are serialised per process (bulk calls: one fills the GPU), which also keeps the last call's record whole
+// calls from several host threads are serialised per process (bulk calls: one fills the GPU).  Guards the settings g_agg_lanes and g_agg_complement
 static std::mutex agg_mu;
 static int g_agg_lanes = 0;                  // 0 = the rule (agg_pick_lanes), else 1, 2, 4, .. 64 (celo_amd_aggregate_set_lanes)
 static int g_agg_complement = -1;            // -1 = the rule (agg_side), 0 never, 1 always on the shared-set form (celo_amd_aggregate_set_complement)
 static constexpr int AGG_BLOCK = 64;         // one wave per workgroup: 64 / L sums each
-// the last call's record: path, the lane width used and the times of include/celo_bls_amd.h (celo_amd_seals_last)
-static int g_agg_last_lanes = 0, g_agg_last_path = -1;
-static float g_agg_ms[8] = {};
+// the last call's record (celo_amd_seals_last): the times of include/celo_bls_amd.h, tag[0] the path, tag[1] the lane width; published on every exit
+static Last<CallTimes> g_agg_last;
 
 // where seal i reads: per-seal sets (shared_n == ~0u) rows and bytes [off[i], off[i+1]); the shared set rows off[0] .. and bytes i n ..
 struct AggSpan { uint32_t row0, n; size_t bit0; };
@@ -136,9 +135,7 @@ static int agg_call(const void* xy, const void* inf, const uint32_t* offsets, si
   if (int rc = agg_refuse(xy, offsets, n_sets, bits, m, out_xy, out_inf)) return rc;
   if (int rc0 = api_enter()) return rc0;
   std::lock_guard<std::mutex> lk(agg_mu);
-  for (float& t : g_agg_ms) t = 0.f;
-  g_agg_last_path = -1;
-  const WallMs wall(&g_agg_ms[6]);
+  TimedCall call(g_agg_last, 6);
   CallScope cs;
   HIP_TRY(cs.open(dev, stream_), 10);
   EvLog log(cs.stream());
@@ -153,11 +150,11 @@ static int agg_call(const void* xy, const void* inf, const uint32_t* offsets, si
   HIP_TRY(cs.out(&d_oinf, out_inf, m, dev), 10);
   HIP_TRY(cs.out(&d_count, out_count, m * 4, dev), 10);
   if (!d_count) HIP_TRY(cs.alloc(&d_count, m * 4), 10);            // the counts are optional to the caller, not to the sums
-  if (int rcr = Agg<F>::run(d_xy, d_inf, offsets, n_sets, d_bits, m, d_out, d_oinf, d_count, cs.stream(), &log, &g_agg_last_lanes)) return rcr;
+  if (int rcr = Agg<F>::run(d_xy, d_inf, offsets, n_sets, d_bits, m, d_out, d_oinf, d_count, cs.stream(), &log, &call.t.tag[1])) return rcr;
   HIP_TRY(cs.copy_back(), 10);
   HIP_TRY(hipStreamSynchronize(cs.stream()), 10);
-  log.sum(g_agg_ms);
-  g_agg_ms[0] += g_agg_ms[7];
+  log.sum(call.t.ms);
+  call.t.ms[0] += call.t.ms[7];
   return 0;
 }
 
@@ -254,18 +251,16 @@ int verify_aggregated_seals_377(const uint64_t* pk_xy, const uint8_t* pk_inf, co
   if (!domain || !msgs || !msg_off || !sig48 || !neg_g2_xy || !out_ok || (hash_mode != 0 && hash_mode != 2 && hash_mode != 3) || (mode != 0 && mode != 1)) return 2;
   if (int rc = agg_refuse(pk_xy, offsets, n_sets, bits, m, pk_xy, pk_xy)) return rc;
   if (int rc0 = api_enter()) return rc0;
-  const WallMs wall;
+  TimedCall call(g_agg_last, 6);
+  float* const ms = call.t.ms;
   // the message hashes: the hash unit hands its rows back on the host, as in sign_batch
   std::vector<uint64_t> hxy(m * 12);
   std::vector<uint8_t> att(m);
-  if (int rc = hash_to_g1_direct_run(domain, msgs, msg_off, extras, extra_off, m, hxy.data(), att.data(), hash_mode)) return rc;
-  const float ms_hash = hash_last_ms();
+  if (int rc = hash_to_g1_direct_run(domain, msgs, msg_off, extras, extra_off, m, hxy.data(), att.data(), hash_mode, 0, nullptr, &ms[2])) return rc;
   SealNegG2 ng2;
   for (int q = 0; q < 24; q++) ng2.xy[q] = neg_g2_xy[q];
   std::vector<uint8_t> h_status(m), is_one(m, 0);
   std::lock_guard<std::mutex> lk(agg_mu);
-  for (float& t : g_agg_ms) t = 0.f;
-  g_agg_ms[2] = ms_hash;
   int path = 0;
   const int rc = [&]() -> int {
     CallScope cs;
@@ -294,9 +289,8 @@ int verify_aggregated_seals_377(const uint64_t* pk_xy, const uint8_t* pk_inf, co
     HIP_TRY(cs.in(&d_inf, pk_inf, rows, 0, 8), 10);
     HIP_TRY(cs.in(&d_min, min_signers, m * 4, 0), 10);
     log.close(5, e0);
-    if (int rcr = Agg<Fp2<P377>>::run(d_xy, d_inf, offsets, n_sets, d_bits, m, d.apk, d.apkinf, d_count, s, &log, &g_agg_last_lanes)) return rcr;
-    if (int rcw = wire_decompress(0, d_sig48, m, 1, d.sig, d_wire, 1, s)) return rcw;
-    g_agg_ms[1] = wire_last_ms();
+    if (int rcr = Agg<Fp2<P377>>::run(d_xy, d_inf, offsets, n_sets, d_bits, m, d.apk, d.apkinf, d_count, s, &log, &call.t.tag[1])) return rcr;
+    if (int rcw = wire_decompress(0, d_sig48, m, 1, d.sig, d_wire, 1, s, &ms[1])) return rcw;
     hipLaunchKernelGGL(k_seal_status, dim3((m32 + 255) / 256), dim3(256), 0, s, d_count, d_min, d_wire, d_att, m32, d.status, d.siginf);
     HIP_TRY(hipGetLastError(), 10);
     e0 = log.open();
@@ -305,7 +299,7 @@ int verify_aggregated_seals_377(const uint64_t* pk_xy, const uint8_t* pk_inf, co
     HIP_TRY(hipStreamSynchronize(s), 10);
     size_t clean = 0;
     for (size_t i = 0; i < m; i++) clean += h_status[i] == 0;
-    if (clean == 0) { path = mode; log.sum(g_agg_ms); return 0; }            // no product to check: every verdict is its status
+    if (clean == 0) { path = mode; log.sum(ms); return 0; }            // no product to check: every verdict is its status
     if (mode == 1) {
       uint32_t k8[8];
       if (key) memcpy(k8, key, sizeof k8);
@@ -332,7 +326,7 @@ int verify_aggregated_seals_377(const uint64_t* pk_xy, const uint8_t* pk_inf, co
       if (int rcm = MsmApi<G1_377>::dev(d.sig, d.siginf, d_sc, m, 1, jac, s)) return rcm;
       HIP_TRY(hipStreamSynchronize(s), 10);
       if (int rcn = wire_normalize(0, jac, 1, tail, &tinf)) return rcn;
-      g_agg_ms[3] = wall_msm.ms();
+      ms[3] = wall_msm.ms();
       uint8_t v = 0;
       {
         StagedProduct<Pairing377> g;
@@ -343,23 +337,22 @@ int verify_aggregated_seals_377(const uint64_t* pk_xy, const uint8_t* pk_inf, co
         HIP_TRY(hipMemcpyAsync(g.ps.d_g1 + m * 12, tail, sizeof tail, hipMemcpyHostToDevice, g.ps.stream), 10);
         HIP_TRY(hipMemcpyAsync(g.ps.d_i1 + m, &tinf, 1, hipMemcpyHostToDevice, g.ps.stream), 10);
         const uint32_t off[2] = {0, m32 + 1};
-        if (int rcp = g.run(off, 1, &v, &g_agg_ms[4])) return rcp;
+        if (int rcp = g.run(off, 1, &v, &ms[4])) return rcp;
       }
       if (v) {
         for (size_t i = 0; i < m; i++) is_one[i] = 1;
         path = 1;
-        log.sum(g_agg_ms);
+        log.sum(ms);
         return 0;
       }
       path = 2;
     }
-    if (int rce = seals_run_each(d, ng2, m, cs, is_one.data(), &g_agg_ms[4])) return rce;
-    log.sum(g_agg_ms);
+    if (int rce = seals_run_each(d, ng2, m, cs, is_one.data(), &ms[4])) return rce;
+    log.sum(ms);
     return 0;
   }();
-  g_agg_ms[0] += g_agg_ms[7];
-  g_agg_last_path = path;
-  g_agg_ms[6] = wall.ms();
+  ms[0] += ms[7];
+  call.t.tag[0] = path;
   if (rc) return rc;
   for (size_t i = 0; i < m; i++) {
     const uint8_t st = h_status[i] ? h_status[i] : is_one[i] ? 0 : 4;
@@ -382,10 +375,10 @@ int aggregate_set_complement(int mode) {
   return 0;
 }
 void seals_last(int* path, int* lanes, float ms[8]) {
-  std::lock_guard<std::mutex> lk(agg_mu);
-  *path = g_agg_last_path;
-  *lanes = g_agg_last_lanes;
-  for (int i = 0; i < 8; i++) ms[i] = g_agg_ms[i];
+  const CallTimes t = g_agg_last.read();
+  *path = t.tag[0];
+  *lanes = t.tag[1];
+  for (int i = 0; i < 8; i++) ms[i] = t.ms[i];
 }
 
 }  // namespace celo

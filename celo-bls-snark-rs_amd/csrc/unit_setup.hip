@@ -15,13 +15,13 @@ namespace celo {
 typedef Fp<P377> FrBw6;          // the scalar field of BW6-761 (the base field of BLS12-377)
 typedef Fp<P253> FrBls;          // the scalar field of BLS12-377
 
-// calls from several host threads are serialised per process (bulk calls: one fills the GPU)
+// calls from several host threads are serialised per process (bulk calls: one fills the GPU).  Guards the setting g_fb_c
 static std::mutex setup_mu;
 // window bits of the generator tables: 0 = the default (FB_DEFAULT_C), else 2 .. 14 (celo_amd_fixed_base_set_window, for the A/B of DESIGN 6f)
 static int g_fb_c = 0;
 static constexpr int FB_DEFAULT_C = 10;   // same-box A/B on 2^20 BW6-761 G1 rows: c = 6 36.7 ms, 8 28.7, 10 22.6
 // the last call's timings in ms: [0] table build, [1] Fr preparation, [2] G1 rows, [3] G2 rows, [4] normalisation, [5] key tables, [6] wall
-static float g_setup_ms[8] = {};
+static Last<CallTimes> g_setup_last;
 
 template <class FR> struct FrParams;
 template <class P> struct FrParams<Fp<P>> { typedef P type; };
@@ -170,13 +170,12 @@ static int fbm_mul(const uint64_t* gen, const void* scalars, size_t n, void* out
   if (!gen || (n && (!scalars || !out_xy || !inf)) || n > 0x7fffffffu) return 2;
   if (gen_is_identity<F>(gen)) return 2;
   std::lock_guard<std::mutex> lk(setup_mu);
-  for (float& t : g_setup_ms) t = 0.f;
   if (n == 0) return 0;
   if (!dev) {
     const uint64_t* sc = (const uint64_t*)scalars;
     for (size_t i = 0; i < n; i++) if (!fb_below<N64>(sc + i * N64, FrParams<FR>::type::P64)) return 2;
   }
-  const WallMs wall(&g_setup_ms[6]);
+  TimedCall call(g_setup_last, 6);
   CallScope cs;
   HIP_TRY(cs.open(dev, stream_), 10);
   EvLog log(cs.stream());
@@ -191,7 +190,7 @@ static int fbm_mul(const uint64_t* gen, const void* scalars, size_t n, void* out
   if (int rcr = fb.rows(d_sc, n, d_out, d_inf, 0, cs.stream(), &log, 2)) return rcr;
   HIP_TRY(cs.copy_back(), 10);
   HIP_TRY(hipStreamSynchronize(cs.stream()), 10);
-  log.sum(g_setup_ms);
+  log.sum(call.t.ms);
   return 0;
 }
 
@@ -209,7 +208,7 @@ int fixed_base_set_window(int c) {
   g_fb_c = c;
   return 0;
 }
-void setup_last_timings(float ms[8]) { for (int i = 0; i < 8; i++) ms[i] = g_setup_ms[i]; }
+void setup_last_timings(float ms[8]) { const CallTimes t = g_setup_last.read(); for (int i = 0; i < 8; i++) ms[i] = t.ms[i]; }
 
 // The table of k_fbm_bases / k_fbm_table for each of n bases over the field F instead of one generator (the Groth16 verifier's gamma_abc rows,
 // groth16_verify_unit.h): gens n x 2 F::ARK64 u64 affine arkworks limbs and inf their identity flags, both on the HOST; d_table n x W 2^(c-1)
@@ -271,8 +270,7 @@ static int setup_run(int curve, int dev_in, const uint64_t* qa, const uint64_t* 
   setup_canon<FR>(toxic, head1); setup_canon<FR>(toxic + N, head1 + N); setup_canon<FR>(toxic + 3 * N, head1 + 2 * N);
   setup_canon<FR>(toxic + N, head2); setup_canon<FR>(toxic + 2 * N, head2 + N); setup_canon<FR>(toxic + 3 * N, head2 + 2 * N);
   std::lock_guard<std::mutex> lk(setup_mu);
-  for (float& t : g_setup_ms) t = 0.f;
-  const WallMs wall(&g_setup_ms[6]);     // (declared in front of the call's resources: their release is inside the wall time)
+  TimedCall call(g_setup_last, 6);       // (declared in front of the call's resources: their release is inside the wall time)
   CallScope cs;
   HIP_TRY(cs.open(0, nullptr), 10);
   const hipStream_t s = cs.stream();
@@ -331,7 +329,7 @@ static int setup_run(int curve, int dev_in, const uint64_t* qa, const uint64_t* 
     HIP_TRY(hipMemcpyAsync(o, d_r1 + r_h * R1, (n_h + n_vars - n_inputs) * R1 * 8, hipMemcpyDeviceToHost, s), 10);
   }
   HIP_TRY(hipStreamSynchronize(s), 10);
-  log.sum(g_setup_ms);
+  log.sum(call.t.ms);
   if (!out_key) return 0;
   // the four key elements the composition keeps on the host (query[0] of a and b_g2, alpha_g1, beta_g2): four rows, not a query
   uint64_t a0[R1], b0[R2], al[R1], be[R2];
@@ -343,7 +341,7 @@ static int setup_run(int curve, int dev_in, const uint64_t* qa, const uint64_t* 
   // (sets *out_key only on success; the key is the call's last step, so nothing after it can fail)
   const int rck = groth16_key_load_dev(curve, d_r1 + r_a * R1, d_i1 + r_a, n_vars, d_r2 + 3 * R2, d_i2 + 3, n_vars, d_r1 + r_h * R1, d_i1 + r_h, n_h,
                                        d_r1 + r_l * R1, d_i1 + r_l, n_vars - n_inputs, a0, b0, al, be, window_bits, out_key);
-  g_setup_ms[5] = wall_key.ms();
+  call.t.ms[5] = wall_key.ms();
   return rck;
 }
 

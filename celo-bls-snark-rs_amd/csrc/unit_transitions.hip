@@ -16,10 +16,9 @@
 
 namespace celo {
 
-// bulk calls, serialised per process; the lock also keeps the last call's record whole
+// bulk calls, serialised per process (one fills the GPU).  The lock guards nothing else: serialisation only
 static std::mutex trans_mu;
-static float g_trans_ms[8] = {};
-static int g_trans_path = -1;
+static Last<CallTimes> g_trans_last;          // tag[0]: the path; published on every exit of a call that has entered
 // the slots of celo_amd_epoch_last, with the products where the proofs are there and the signatures in the spare slot
 enum { TR_MS_DECODE = 0, TR_MS_SUMS = 1, TR_MS_PACK = 2, TR_MS_HASH = 3, TR_MS_XFER = 4, TR_MS_PAIR = 5, TR_MS_WALL = 6, TR_MS_SIGS = 7 };
 
@@ -145,9 +144,8 @@ int verify_epoch_transitions(const EpochBlocks* blocks, size_t nb, const uint32_
   for (size_t t = 0; t <= T; t++) { seven[t] = 7 * t; fortyeight[t] = 48 * t; }
   if (int rc0 = api_enter()) return rc0;
   std::lock_guard<std::mutex> lk(trans_mu);
-  for (float& t : g_trans_ms) t = 0.f;
-  g_trans_path = -1;
-  const WallMs wall(&g_trans_ms[TR_MS_WALL]);
+  TimedCall call(g_trans_last, TR_MS_WALL);
+  float* const ms = call.t.ms;
   TrNegG2 ng2;
   for (int q = 0; q < 24; q++) ng2.xy[q] = neg_g2_xy[q];
   static const TrNegG2 gen = transitions_generator_row();
@@ -196,18 +194,17 @@ int verify_epoch_transitions(const EpochBlocks* blocks, size_t nb, const uint32_
     hipLaunchKernelGGL(k_transition_extras, dim3((nb32 + 255) / 256), dim3(256), 0, s, E, X, nb32, d_extras);
     log.close(TR_MS_PACK, e0);
     HIP_TRY(hipGetLastError(), 10);
-    if (int rc = pedersen_crh_run(E.bytes, msg_off.data(), T, d_crh, 1, s)) return rc;
-    g_trans_ms[TR_MS_HASH] += hash_last_ms();
-    if (int rc = hash_to_g1_direct_run(domain, d_crh, fortyeight.data(), d_extras, seven.data(), T, d_hash, d_att, 1, 1, s)) return rc;
-    g_trans_ms[TR_MS_HASH] += hash_last_ms();
+    float ms_crh = 0.f;
+    if (int rc = pedersen_crh_run(E.bytes, msg_off.data(), T, d_crh, 1, s, &ms_crh)) return rc;
+    if (int rc = hash_to_g1_direct_run(domain, d_crh, fortyeight.data(), d_extras, seven.data(), T, d_hash, d_att, 1, 1, s, &ms[TR_MS_HASH])) return rc;
+    ms[TR_MS_HASH] += ms_crh;
   }
   // ---- 4: seal p = the keys of block p under the bytes below them: the aggregated key of transition p + 1 (the last of a chain signs nothing here)
   e0 = log.open();
   if (int rc = aggregate_by_bitmap(1, E.rows, E.inf, B.key_off, nb, d_bits, nb, d_apk, d_apkinf, d_count, 1, s)) return rc;
   log.close(TR_MS_SUMS, e0);
   // ---- 5, 6: signatures, statuses
-  if (int rc = wire_decompress(0, d_sig48, nb, 1, d_sig, d_wire, 1, s)) return rc;
-  g_trans_ms[TR_MS_SIGS] += wire_last_ms();
+  if (int rc = wire_decompress(0, d_sig48, nb, 1, d_sig, d_wire, 1, s, &ms[TR_MS_SIGS])) return rc;
   e0 = log.open();
   hipLaunchKernelGGL(k_transition_status, dim3((nb32 + 255) / 256), dim3(256), 0, s, E, X, d_bits, d_count, d_wire, d_att, gen, nb32, d_status, d_siginf, d_sigsel, d_signot);
   log.close(TR_MS_SIGS, e0);
@@ -253,7 +250,7 @@ int verify_epoch_transitions(const EpochBlocks* blocks, size_t nb, const uint32_
       hipLaunchKernelGGL(k_pack_chain_pairs, dim3((unsigned)((nb * 24 + 255) / 256)), dim3(256), 0, g.ps.stream, d_asig, d_asiginf, d_hash, d_apk, d_apkinf, d_skip, X, ng2, nb32,
                          g.ps.d_g1, g.ps.d_g2, g.ps.d_i1, g.ps.d_i2);
       HIP_TRY(hipGetLastError(), 10);
-      if (int rc = g.run(chain_off, n_chains, v.data(), &g_trans_ms[TR_MS_PAIR])) return rc;
+      if (int rc = g.run(chain_off, n_chains, v.data(), &ms[TR_MS_PAIR])) return rc;
       HIP_TRY(hipStreamSynchronize(s), 10);
     }
     for (size_t c = 0; c < n_chains; c++) {
@@ -274,11 +271,11 @@ int verify_epoch_transitions(const EpochBlocks* blocks, size_t nb, const uint32_
     HIP_TRY(hipGetLastError(), 10);
     std::vector<uint32_t> off(nb + 1);
     for (size_t p = 0; p <= nb; p++) off[p] = (uint32_t)(2 * p);
-    if (int rc = g.run(off.data(), nb, each.data(), &g_trans_ms[TR_MS_PAIR])) return rc;
+    if (int rc = g.run(off.data(), nb, each.data(), &ms[TR_MS_PAIR])) return rc;
     HIP_TRY(hipStreamSynchronize(s), 10);
   }
-  log.sum(g_trans_ms);
-  g_trans_path = path;
+  log.sum(ms);
+  call.t.tag[0] = path;
   // ---- the outputs
   for (size_t c = 0; c < n_chains; c++) {
     bool all = true;
@@ -300,9 +297,9 @@ int verify_epoch_transitions(const EpochBlocks* blocks, size_t nb, const uint32_
 }
 
 void transitions_last(int* path, float ms[8]) {
-  std::lock_guard<std::mutex> lk(trans_mu);
-  *path = g_trans_path;
-  for (int i = 0; i < 8; i++) ms[i] = g_trans_ms[i];
+  const CallTimes t = g_trans_last.read();
+  *path = t.tag[0];
+  for (int i = 0; i < 8; i++) ms[i] = t.ms[i];
 }
 
 }  // namespace celo

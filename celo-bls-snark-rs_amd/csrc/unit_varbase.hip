@@ -13,7 +13,7 @@
 
 namespace celo {
 
-// calls from several host threads are serialised per process (bulk calls: one fills the GPU), which also keeps the last call's record whole
+// calls from several host threads are serialised per process (bulk calls: one fills the GPU).  Guards the settings g_vb_c and g_vb_chunk
 static std::mutex vb_mu;
 static int g_vb_c = 0;                       // 0 = the default of the group (vb_default_c), else VB_MIN_C .. VB_MAX_C (celo_amd_scalar_mul_set_window)
 static uint32_t g_vb_chunk = 0;              // rows per chunk; 0 = the default (vb_default_chunk)
@@ -22,8 +22,8 @@ static uint32_t g_vb_chunk = 0;              // rows per chunk; 0 = the default 
 template <class F> constexpr int vb_default_c() { return sizeof(F) <= 64 ? 4 : 3; }
 static constexpr size_t VB_WORKSPACE = size_t(1) << 28;   // the default chunk keeps table + chain below this
 static constexpr int VB_BLOCK = 64;          // one wave per workgroup: the kernels are register-heavy and the batches often small
-// the last call's timings in ms: [0] table build, [1] ladder, [2] normalisation, [3] whole call (wall)
-static float g_vb_ms[4] = {};
+// the last call's timings in ms: [0] table build, [1] ladder, [2] normalisation, [3] whole call (wall); published on every exit of a call that has entered
+static Last<CallTimes> g_vb_last;
 
 // lane i -> the table of P_i (var_base.h vb_build_table).  xy: rows of 2 A arkworks limbs; inf: flags or null.
 template <class F>
@@ -118,8 +118,7 @@ static int vb_mul(const void* xy, const void* inf, const void* scalars, size_t n
     for (size_t i = 0; i < n_sc; i++) if (!fb_below<N64>(sc + i * N64, vb_order<N64>())) return 2;
   }
   std::lock_guard<std::mutex> lk(vb_mu);
-  for (float& t : g_vb_ms) t = 0.f;
-  const WallMs wall(&g_vb_ms[3]);
+  TimedCall call(g_vb_last, 3);
   CallScope cs;
   HIP_TRY(cs.open(dev, stream_), 10);
   EvLog log(cs.stream());
@@ -134,7 +133,7 @@ static int vb_mul(const void* xy, const void* inf, const void* scalars, size_t n
   if (int rcr = VB::template run<GLV>(d_xy, d_inf, d_sc, n_sc, n, d_out, d_oinf, cs.stream(), &log)) return rcr;
   HIP_TRY(cs.copy_back(), 10);
   HIP_TRY(hipStreamSynchronize(cs.stream()), 10);
-  log.sum(g_vb_ms);
+  log.sum(call.t.ms);
   return 0;
 }
 
@@ -163,8 +162,8 @@ int scalar_mul_set_chunk_rows(uint32_t rows) {
   return 0;
 }
 void scalar_mul_last_ms(float ms[4]) {
-  std::lock_guard<std::mutex> lk(vb_mu);
-  for (int i = 0; i < 4; i++) ms[i] = g_vb_ms[i];
+  const CallTimes t = g_vb_last.read();
+  for (int i = 0; i < 4; i++) ms[i] = t.ms[i];
 }
 
 // ---- sign_batch_bls12_377: sig_i = [sk_i] H(msg_i), compressed.  The hash unit's run function hands its rows back on the host (96 B per
@@ -177,37 +176,31 @@ int sign_batch_377(const uint64_t* sk, size_t n_sk, const uint8_t* domain, const
   if (!sk || !domain || !msgs || !msg_off || !out_sig48 || !attempts || (n_sk != 1 && n_sk != n) || n > 0x7fffffffu) return 2;
   if (mode != 0 && mode != 2 && mode != 3) return 2;
   for (size_t i = 0; i < n_sk; i++) if (!fb_below<4>(sk + i * 4, P253::P64)) return 2;
-  const WallMs wall;
+  TimedCall call(g_vb_last, 3);
   std::vector<uint64_t> hxy(n * 12);
   std::vector<uint8_t> att(n), hinf(n);
   if (int rc = hash_to_g1_direct_run(domain, msgs, msg_off, extras, extra_off, n, hxy.data(), att.data(), mode)) return rc;
   for (size_t i = 0; i < n; i++) hinf[i] = att[i] == 255 ? 1 : 0;
   std::vector<uint8_t> sig(n * 48);
   std::lock_guard<std::mutex> lk(vb_mu);
-  for (float& t : g_vb_ms) t = 0.f;
-  const int rc = [&]() -> int {     // the device work: its resources are released before the wall time is taken
-    CallScope cs;
-    HIP_TRY(cs.open(0, nullptr), 10);
-    const hipStream_t s = cs.stream();
-    EvLog log(s);
-    uint64_t *d_xy, *d_sc, *d_out;
-    uint8_t *d_inf, *d_oinf, *d_sig, *d_status;
-    HIP_TRY(cs.in(&d_xy, hxy.data(), n * 96, 0), 10);
-    HIP_TRY(cs.in(&d_sc, sk, n_sk * 32, 0), 10);
-    HIP_TRY(cs.in(&d_inf, hinf.data(), n, 0), 10);
-    HIP_TRY(cs.alloc(&d_out, n * 96), 10);
-    HIP_TRY(cs.alloc(&d_oinf, n), 10);
-    HIP_TRY(cs.out(&d_sig, sig.data(), n * 48, 0), 10);
-    HIP_TRY(cs.alloc(&d_status, n), 10);
-    if (int rcr = VbmG1_377::run<true>(d_xy, d_inf, d_sc, n_sk, n, d_out, d_oinf, s, &log)) return rcr;
-    if (int rce = wire_encode(0, 1, d_out, d_oinf, n, d_sig, d_status, 1, s)) return rce;
-    HIP_TRY(cs.copy_back(), 10);
-    HIP_TRY(hipStreamSynchronize(s), 10);
-    log.sum(g_vb_ms);
-    return 0;
-  }();
-  g_vb_ms[3] = wall.ms();
-  if (rc) return rc;
+  CallScope cs;
+  HIP_TRY(cs.open(0, nullptr), 10);
+  const hipStream_t s = cs.stream();
+  EvLog log(s);
+  uint64_t *d_xy, *d_sc, *d_out;
+  uint8_t *d_inf, *d_oinf, *d_sig, *d_status;
+  HIP_TRY(cs.in(&d_xy, hxy.data(), n * 96, 0), 10);
+  HIP_TRY(cs.in(&d_sc, sk, n_sk * 32, 0), 10);
+  HIP_TRY(cs.in(&d_inf, hinf.data(), n, 0), 10);
+  HIP_TRY(cs.alloc(&d_out, n * 96), 10);
+  HIP_TRY(cs.alloc(&d_oinf, n), 10);
+  HIP_TRY(cs.out(&d_sig, sig.data(), n * 48, 0), 10);
+  HIP_TRY(cs.alloc(&d_status, n), 10);
+  if (int rcr = VbmG1_377::run<true>(d_xy, d_inf, d_sc, n_sk, n, d_out, d_oinf, s, &log)) return rcr;
+  if (int rce = wire_encode(0, 1, d_out, d_oinf, n, d_sig, d_status, 1, s)) return rce;
+  HIP_TRY(cs.copy_back(), 10);
+  HIP_TRY(hipStreamSynchronize(s), 10);
+  log.sum(call.t.ms);
   for (size_t i = 0; i < n; i++) {
     if (hinf[i]) memset(out_sig48 + i * 48, 0, 48);
     else memcpy(out_sig48 + i * 48, sig.data() + i * 48, 48);

@@ -13,7 +13,7 @@
 #endif
 namespace celo {
 // decode / normalise calls stage through the call frame of runtime.h and run on the caller's stream in both forms (the null stream when
-// none is given); calls from several host threads are serialised per process by this lock (they are bulk calls: one fills the GPU)
+// none is given); calls from several host threads are serialised per process by this lock (bulk calls: one fills the GPU) - serialisation only
 static std::mutex wire_mu;
 
 // in: n x 48 (G1) / n x 96 (G2) wire bytes.  out: n x 12 / n x 24 u64, affine (x, y) in arkworks Montgomery limbs (the layout
@@ -65,7 +65,7 @@ int wire_consts_device(WireConsts& out) {
   out.tab = d_tab;
   return 0;
 }
-static float g_wire_ms = 0.f;
+static Last<float> g_wire_last;               // kernel ms of the last decode or normalise call that succeeded
 
 // one decode launch on device buffers (the entry points below; the serialized-key loader of unit_wire761.hip, one per section)
 int wire377_launch_decode(int g2, int compressed, const uint8_t* d_in, size_t n, int check, uint64_t* d_out, uint8_t* d_st, hipStream_t stream) {
@@ -83,11 +83,11 @@ int wire377_launch_decode(int g2, int compressed, const uint8_t* d_in, size_t n,
   return hipGetLastError() == hipSuccess ? 0 : 10;
 }
 
-int wire_decompress(int g2, const uint8_t* in, size_t n, int check, uint64_t* out, uint8_t* status, int dev, void* stream_) {
-  return wire377_decode(g2, 1, in, n, check, out, status, dev, stream_);
+int wire_decompress(int g2, const uint8_t* in, size_t n, int check, uint64_t* out, uint8_t* status, int dev, void* stream_, float* kernel_ms) {
+  return wire377_decode(g2, 1, in, n, check, out, status, dev, stream_, kernel_ms);
 }
 // compressed: 1 = 48 / 96 B points (k_decompress), 0 = 96 / 192 B (k_decode377u)
-int wire377_decode(int g2, int compressed, const uint8_t* in, size_t n, int check, uint64_t* out, uint8_t* status, int dev, void* stream_) {
+int wire377_decode(int g2, int compressed, const uint8_t* in, size_t n, int check, uint64_t* out, uint8_t* status, int dev, void* stream_, float* kernel_ms) {
   if (int rc0 = api_enter()) return rc0;
   std::lock_guard<std::mutex> lk(wire_mu);
   if (n == 0) return 0;
@@ -105,15 +105,16 @@ int wire377_decode(int g2, int compressed, const uint8_t* in, size_t n, int chec
   HIP_TRY(cs.in(&d_in, in, n * ib, dev), 10);
   HIP_TRY(cs.out(&d_out, out, n * ow * 8, dev), 10);
   HIP_TRY(cs.out(&d_st, status, n, dev), 10);
-  hipEvent_t e0, e1;
-  HIP_TRY(cs.event(&e0), 10);
-  HIP_TRY(cs.event(&e1), 10);
-  HIP_TRY(hipEventRecord(e0, stream), 10);
+  EvLog log(stream);
+  const hipEvent_t e0 = log.open();
   if (int rcl = wire377_launch_decode(g2, compressed, d_in, n, check, d_out, d_st, stream)) return rcl;
-  HIP_TRY(hipEventRecord(e1, stream), 10);
+  log.close(0, e0);
   HIP_TRY(cs.copy_back(), 10);
   HIP_TRY(hipStreamSynchronize(stream), 10);
-  HIP_TRY(hipEventElapsedTime(&g_wire_ms, e0, e1), 10);
+  float ms = 0.f;
+  log.sum(&ms);
+  g_wire_last.note(ms);
+  if (kernel_ms) *kernel_ms = ms;
   return 0;
 }
 // Jacobian -> affine for n points (normalize.h): jac n x 3 coordinates, out_xy n x (x, y), zero rows + inf[i] = 1 for the identity.
@@ -130,20 +131,20 @@ int wire_normalize(int group, const uint64_t* jac, size_t n, uint64_t* out_xy, u
   HIP_TRY(cs.in(&d_in, jac, n * 3 * cw * 8, 0), 10);
   HIP_TRY(cs.out(&d_out, out_xy, n * 2 * cw * 8, 0), 10);
   HIP_TRY(cs.out(&d_inf, inf, n, 0), 10);
-  hipEvent_t e0, e1;
-  HIP_TRY(cs.event(&e0), 10);
-  HIP_TRY(cs.event(&e1), 10);
-  HIP_TRY(hipEventRecord(e0, 0), 10);
+  EvLog log(nullptr);
+  const hipEvent_t e0 = log.open();
   const dim3 grid4(((uint32_t)((n + 3) / 4) + 63) / 64), grid8(((uint32_t)((n + 7) / 8) + 63) / 64);
   if (group == 2) hipLaunchKernelGGL((k_normalize<Fp<P761>, 4, true, 0, true>), grid4, dim3(64), 0, 0, d_in, d_out, d_inf, (uint32_t)n, 0);
   else if (group == 1) hipLaunchKernelGGL((k_normalize<Fq2, 4, true, 2, false>), grid4, dim3(64), 0, 0, d_in, d_out, d_inf, (uint32_t)n, 0);
   else hipLaunchKernelGGL((k_normalize<Fq, 8, true, 2, false>), grid8, dim3(64), 0, 0, d_in, d_out, d_inf, (uint32_t)n, 0);
   HIP_TRY(hipGetLastError(), 10);
-  HIP_TRY(hipEventRecord(e1, 0), 10);
+  log.close(0, e0);
   HIP_TRY(cs.copy_back(), 10);
   HIP_TRY(hipStreamSynchronize(0), 10);
-  HIP_TRY(hipEventElapsedTime(&g_wire_ms, e0, e1), 10);
+  float ms = 0.f;
+  log.sum(&ms);
+  g_wire_last.note(ms);
   return 0;
 }
-float wire_last_ms() { return g_wire_ms; }
+float wire_last_ms() { return g_wire_last.read(); }
 }  // namespace celo

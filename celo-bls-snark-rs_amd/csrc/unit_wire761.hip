@@ -16,9 +16,10 @@
 #endif
 namespace celo {
 // calls from several host threads are serialised per process (they are bulk calls: one fills the GPU); each runs on a stream of its own
-// (host-pointer calls) or on the caller's (the _dev forms)
+// (host-pointer calls) or on the caller's (the _dev forms).  The lock guards nothing else: serialisation only
 static std::mutex w761_mu;
-static float g_w761_ms[4] = {0.f, 0.f, 0.f, 0.f};   // kernel ms of the last decode call; the last key load's transfer / decode / table build
+// [0] kernel ms of the last decode call; [1] .. [3] the last key load's transfer / decode / table build (each call owns its slots)
+static Last<CallTimes> g_w761_last;
 
 // Two passes, one point per lane.  k_decode761: in n x 96 B (compressed) / n x 192 B (uncompressed) -> out n x 24 u64, (x, y) in arkworks
 // Montgomery limbs (the layout of msm_bw6_761_*), zeros unless status == WIRE_OK; everything but the subgroup test.  k_subgroup761: r P == O
@@ -78,16 +79,16 @@ int wire761_decode(int g2, int compressed, const uint8_t* in, size_t n, int chec
   HIP_TRY(cs.in(&d_in, in, n * ib, dev), 10);
   HIP_TRY(cs.out(&d_out, out, n * 24 * 8, dev), 10);
   HIP_TRY(cs.out(&d_st, status, n, dev), 10);
-  hipEvent_t e0, e1;
-  HIP_TRY(cs.event(&e0), 10);
-  HIP_TRY(cs.event(&e1), 10);
-  HIP_TRY(hipEventRecord(e0, stream), 10);
+  EvLog log(stream);
+  const hipEvent_t e0 = log.open();
   launch_decode761(g2, compressed, d_in, n, check, d_out, d_st, stream);
   HIP_TRY(hipGetLastError(), 10);
-  HIP_TRY(hipEventRecord(e1, stream), 10);
+  log.close(0, e0);
   HIP_TRY(cs.copy_back(), 10);
   HIP_TRY(hipStreamSynchronize(stream), 10);
-  HIP_TRY(hipEventElapsedTime(&g_w761_ms[0], e0, e1), 10);
+  float ms = 0.f;
+  log.sum(&ms);
+  g_w761_last.update([&](CallTimes& t) { t.ms[0] = ms; });
   return 0;
 }
 
@@ -163,8 +164,10 @@ int wire_key_load(int curve, const uint8_t* bytes, size_t len, int form, int win
   HIP_TRY(hipEventRecord(ev[2], stream), 10);
   HIP_TRY(hipMemcpyAsync(&first, d_first, sizeof first, hipMemcpyDeviceToHost, stream), 10);
   HIP_TRY(hipStreamSynchronize(stream), 10);
-  HIP_TRY(hipEventElapsedTime(&g_w761_ms[1], ev[0], ev[1]), 10);
-  HIP_TRY(hipEventElapsedTime(&g_w761_ms[2], ev[1], ev[2]), 10);
+  float ms_xfer = 0.f, ms_decode = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms_xfer, ev[0], ev[1]), 10);
+  HIP_TRY(hipEventElapsedTime(&ms_decode, ev[1], ev[2]), 10);
+  g_w761_last.update([&](CallTimes& t) { t.ms[1] = ms_xfer; t.ms[2] = ms_decode; });
   if (first != ~0ull) {
     if (first_bad) *first_bad = first;
     return W761_ERR_POINT;
@@ -183,8 +186,8 @@ int wire_key_load(int curve, const uint8_t* bytes, size_t len, int form, int win
   // (frees the key itself when it fails, and sets *out_key only on success: the call's last step)
   const int rc = groth16_key_load_dev(curve, rows_of(4), d_st + base[4], L[W761_A], rows_of(6), d_st + base[6], L[W761_BG2], rows_of(7), d_st + base[7], L[W761_H],
                                       rows_of(8), d_st + base[8], L[W761_L], host_rows[0], host_rows[1], host_rows[2], host_rows[3], window_bits, out_key);
-  g_w761_ms[3] = wall.ms();
+  g_w761_last.update([&](CallTimes& t) { t.ms[3] = wall.ms(); });
   return rc;
 }
-void wire761_last_timings(float ms[4]) { for (int i = 0; i < 4; i++) ms[i] = g_w761_ms[i]; }
+void wire761_last_timings(float ms[4]) { const CallTimes t = g_w761_last.read(); for (int i = 0; i < 4; i++) ms[i] = t.ms[i]; }
 }  // namespace celo

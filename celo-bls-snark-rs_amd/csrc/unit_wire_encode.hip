@@ -3,17 +3,15 @@
 // of either curve (what groth16_load_key_<curve>_serialized reads) and of a Proof.
 #include "wire761.h"
 #include <hip/hip_runtime.h>
-#include <atomic>
 #include <mutex>
 #include "runtime.h"
 #include "units.h"
 
 namespace celo {
-// bulk calls, serialised per process like the decoders'; host-pointer calls run on a stream of their own, the _dev forms on the caller's
+// bulk calls, serialised per process like the decoders' (serialisation only); host-pointer calls run on a stream of their own, the _dev forms on the caller's
 static std::mutex wenc_mu;
-// written under the lock, read by the timing getters from any thread
-static std::atomic<float> g_wenc_ms{0.f};                              // kernel ms of the last encode call (the key writer: all its launches)
-static std::atomic<float> g_wenc_key_ms[3] = {{0.f}, {0.f}, {0.f}};    // the last key writer call: rows in, encode, bytes out
+static Last<float> g_wenc_last;              // kernel ms of the last encode call (the key writer: all its launches)
+static Last<CallTimes> g_wenc_key_last;      // the last key writer call: [0] rows in, [1] encode, [2] bytes out
 
 // E: a WireEnc instantiation.  in: n rows of E::ROW_WORDS u64; out: n x E::OUT_WORDS u64 (48 .. 192 B per point), written as 64-bit words;
 // status: n bytes.  The control flow is uniform up to WireEnc::row's per-lane exits (identity, not a field element).
@@ -75,22 +73,20 @@ int wire_encode(int group, int compressed, const uint64_t* rows, const uint8_t* 
   HIP_TRY(cs.in(&d_inf, inf, n, dev), 10);
   HIP_TRY(cs.out(&d_out, out, n * ob, dev), 10);
   HIP_TRY(cs.out(&d_st, status, n, dev), 10);
-  hipEvent_t e0, e1;
-  HIP_TRY(cs.event(&e0), 10);
-  HIP_TRY(cs.event(&e1), 10);
-  HIP_TRY(hipEventRecord(e0, stream), 10);
+  EvLog log(stream);
+  const hipEvent_t e0 = log.open();
   launch_encode(group, compressed, d_in, d_inf, d_out, d_st, n, 0, stream);
   HIP_TRY(hipGetLastError(), 10);
-  HIP_TRY(hipEventRecord(e1, stream), 10);
+  log.close(0, e0);
   HIP_TRY(cs.copy_back(), 10);
   HIP_TRY(hipStreamSynchronize(stream), 10);
   float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, e0, e1), 10);
-  g_wenc_ms.store(ms);
+  log.sum(&ms);
+  g_wenc_last.note(ms);
   return 0;
 }
-float wire_encode_last_ms() { return g_wenc_ms.load(); }
-void wire_encode_key_timings(float ms[3]) { for (int i = 0; i < 3; i++) ms[i] = g_wenc_key_ms[i].load(); }
+float wire_encode_last_ms() { return g_wenc_last.read(); }
+void wire_encode_key_timings(float ms[3]) { const CallTimes t = g_wenc_key_last.read(); for (int i = 0; i < 3; i++) ms[i] = t.ms[i]; }
 
 int wire_key_size(int curve, size_t n_inputs, size_t n_vars, size_t n_h, int form, int vk_only, uint64_t* len) { return wkey_size(curve, n_inputs, n_vars, n_h, form, vk_only, len); }
 
@@ -173,12 +169,10 @@ int wire_key_serialize(int curve, const uint64_t* vk, size_t n_inputs, const uin
   HIP_TRY(hipMemcpyAsync(out, d_out, need, hipMemcpyDeviceToHost, stream), 10);
   HIP_TRY(hipEventRecord(ev[3], stream), 10);
   HIP_TRY(hipStreamSynchronize(stream), 10);
-  for (int i = 0; i < 3; i++) {
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ev[i], ev[i + 1]), 10);
-    g_wenc_key_ms[i].store(ms);
-    if (i == 1) g_wenc_ms.store(ms);
-  }
+  CallTimes t;
+  for (int i = 0; i < 3; i++) HIP_TRY(hipEventElapsedTime(&t.ms[i], ev[i], ev[i + 1]), 10);
+  g_wenc_key_last.note(t);
+  g_wenc_last.note(t.ms[1]);
   for (int r = 0; r < nr; r++) {
     if (!runs[r].vec) continue;
     for (int b = 0; b < 8; b++) out[runs[r].off - 8 + b] = (uint8_t)(runs[r].n >> (8 * b));

@@ -70,21 +70,19 @@ int witness_map_run(uint64_t* a, uint64_t* b, uint64_t* c, unsigned log_n, const
 int pairing_run_377(const uint64_t* g1, const uint8_t* inf1, const uint64_t* g2, const uint8_t* inf2, const uint32_t* offsets, size_t m, uint8_t* is_one, uint64_t* gt, int mode);
 int pairing_run_761(const uint64_t* g1, const uint8_t* inf1, const uint64_t* g2, const uint8_t* inf2, const uint32_t* offsets, size_t m, uint8_t* is_one, uint64_t* gt, int mode);
 int pairing_stage_377(uint32_t k, size_t m, PairingStage* st);
-int pairing_run_staged_377(PairingStage* st, const uint32_t* offsets, size_t m, uint8_t* is_one);
+// kernel_ms (optional, here and below): the time the call's own "last call" record reports for THIS call, handed to the caller
+int pairing_run_staged_377(PairingStage* st, const uint32_t* offsets, size_t m, uint8_t* is_one, float* kernel_ms = nullptr);
 int pairing_timings_377(float ms[4]);
 int pairing_stage_761(uint32_t k, size_t m, PairingStage* st);
-int pairing_run_staged_761(PairingStage* st, const uint32_t* offsets, size_t m, uint8_t* is_one);
-int pairing_timings_761(float ms[4]);
+int pairing_run_staged_761(PairingStage* st, const uint32_t* offsets, size_t m, uint8_t* is_one, float* kernel_ms = nullptr);
 // the staged entry points of a curve's engine as one type (runtime.h StagedProduct, groth16_verify_unit.h G16Dev)
 struct Pairing377 {
   static int stage(uint32_t k, size_t m, PairingStage* st) { return pairing_stage_377(k, m, st); }
-  static int run_staged(PairingStage* st, const uint32_t* off, size_t m, uint8_t* is_one) { return pairing_run_staged_377(st, off, m, is_one); }
-  static int timings(float ms[4]) { return pairing_timings_377(ms); }
+  static int run_staged(PairingStage* st, const uint32_t* off, size_t m, uint8_t* is_one, float* ms) { return pairing_run_staged_377(st, off, m, is_one, ms); }
 };
 struct Pairing761 {
   static int stage(uint32_t k, size_t m, PairingStage* st) { return pairing_stage_761(k, m, st); }
-  static int run_staged(PairingStage* st, const uint32_t* off, size_t m, uint8_t* is_one) { return pairing_run_staged_761(st, off, m, is_one); }
-  static int timings(float ms[4]) { return pairing_timings_761(ms); }
+  static int run_staged(PairingStage* st, const uint32_t* off, size_t m, uint8_t* is_one, float* ms) { return pairing_run_staged_761(st, off, m, is_one, ms); }
 };
 void final_exp_w3_377(const uint32_t* prod, uint8_t* is_one, uint64_t* gt, uint32_t m, hipStream_t s);
 void final_exp_w2_377(const uint32_t* prod, uint8_t* is_one, uint64_t* gt, uint32_t m, hipStream_t s);
@@ -101,8 +99,8 @@ int bv_mirror_gather(int words, const uint64_t* mirror_xy, const uint8_t* mirror
 int bv_draw_exponents(const uint32_t key[8], const uint32_t* d_offsets, size_t m, size_t tot, uint64_t* d_out, hipStream_t stream);
 
 // ---- point decoding and normalisation (unit_wire.hip, unit_wire761.hip).  group 0 / 1: BLS12-377 G1 / G2, 2: BW6-761
-int wire_decompress(int g2, const uint8_t* in, size_t n, int check, uint64_t* out, uint8_t* status, int dev, void* stream);
-int wire377_decode(int g2, int compressed, const uint8_t* in, size_t n, int check, uint64_t* out, uint8_t* status, int dev, void* stream);
+int wire_decompress(int g2, const uint8_t* in, size_t n, int check, uint64_t* out, uint8_t* status, int dev, void* stream, float* kernel_ms = nullptr);
+int wire377_decode(int g2, int compressed, const uint8_t* in, size_t n, int check, uint64_t* out, uint8_t* status, int dev, void* stream, float* kernel_ms = nullptr);
 int wire377_launch_decode(int g2, int compressed, const uint8_t* d_in, size_t n, int check, uint64_t* d_out, uint8_t* d_st, hipStream_t stream);
 int wire_normalize(int group, const uint64_t* jac, size_t n, uint64_t* out_xy, uint8_t* inf);
 int wire_consts_device(WireConsts& out);
@@ -124,10 +122,11 @@ int wire761_proof_serialize(const uint64_t* a_xyz, const uint64_t* b_xyz, const 
 // ---- hash to G1 (unit_hash.hip; the composite hasher's generator table is seam_hash.hip's).  mode, for both groups: 0 direct, 1 the CIP22
 // tail (msgs are the inner CRHs), 2 composite, 3 composite CIP22: one CRH per message (pedersen_crh_run), then the tail over the 48-byte inners
 // dev = 1 (G1 and the CRH): the bytes, rows and attempts are DEVICE pointers and the work is enqueued on the caller's stream; the offsets are host
-// arrays in both forms, and both return after the work has drained
+// arrays in both forms, and both return after the work has drained.  kernel_ms: what celo_amd_hash_last_ms reports for the call - for mode 3 the
+// tail's round loop alone, as the record (the CRH's time is overwritten there)
 int hash_to_g1_direct_run(const uint8_t* domain, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off, size_t n, uint64_t* out_xy,
-                          uint8_t* attempts, int mode, int dev = 0, void* stream = nullptr);
-int pedersen_crh_run(const uint8_t* msgs, const uint64_t* msg_off, size_t n, uint8_t* out48, int dev = 0, void* stream = nullptr);
+                          uint8_t* attempts, int mode, int dev = 0, void* stream = nullptr, float* kernel_ms = nullptr);
+int pedersen_crh_run(const uint8_t* msgs, const uint64_t* msg_off, size_t n, uint8_t* out48, int dev = 0, void* stream = nullptr, float* kernel_ms = nullptr);
 // ---- hash to G2 (unit_hash.hip): the same round loop, rows of 24 limbs; compat 0 / 1: the flags as the XOF gives them / the deployed remap
 int hash_to_g2_run(const uint8_t* domain, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* extras, const uint64_t* extra_off, size_t n, int compat,
                    uint64_t* out_xy, uint8_t* attempts, int mode);
