@@ -381,6 +381,37 @@ int decode_uncompressed_bls12_377_g1_dev(const uint8_t* d_in, size_t n, int chec
 int decode_uncompressed_bls12_377_g2_dev(const uint8_t* d_in, size_t n, int check, uint64_t* d_out_xy, uint8_t* d_status, void* hip_stream) {
   return wire377_decode(1, 0, d_in, n, check, d_out_xy, d_status, 1, hip_stream);
 }
+// ---- bulk validation of affine rows (unit_check.hip)
+int check_points_bls12_377_g1(const uint64_t* xy, const uint8_t* inf, size_t n, int level, uint8_t* out_status, uint64_t* out_first_bad) {
+  return check_points(0, xy, inf, n, level, out_status, out_first_bad, 0, nullptr);
+}
+int check_points_bls12_377_g2(const uint64_t* xy, const uint8_t* inf, size_t n, int level, uint8_t* out_status, uint64_t* out_first_bad) {
+  return check_points(1, xy, inf, n, level, out_status, out_first_bad, 0, nullptr);
+}
+int check_points_bw6_761_g1(const uint64_t* xy, const uint8_t* inf, size_t n, int level, uint8_t* out_status, uint64_t* out_first_bad) {
+  return check_points(2, xy, inf, n, level, out_status, out_first_bad, 0, nullptr);
+}
+int check_points_bw6_761_g2(const uint64_t* xy, const uint8_t* inf, size_t n, int level, uint8_t* out_status, uint64_t* out_first_bad) {
+  return check_points(3, xy, inf, n, level, out_status, out_first_bad, 0, nullptr);
+}
+int check_points_bls12_377_g1_dev(const uint64_t* d_xy, const uint8_t* d_inf, size_t n, int level, uint8_t* d_out_status, uint64_t* out_first_bad, void* hip_stream) {
+  return check_points(0, d_xy, d_inf, n, level, d_out_status, out_first_bad, 1, hip_stream);
+}
+int check_points_bls12_377_g2_dev(const uint64_t* d_xy, const uint8_t* d_inf, size_t n, int level, uint8_t* d_out_status, uint64_t* out_first_bad, void* hip_stream) {
+  return check_points(1, d_xy, d_inf, n, level, d_out_status, out_first_bad, 1, hip_stream);
+}
+int check_points_bw6_761_g1_dev(const uint64_t* d_xy, const uint8_t* d_inf, size_t n, int level, uint8_t* d_out_status, uint64_t* out_first_bad, void* hip_stream) {
+  return check_points(2, d_xy, d_inf, n, level, d_out_status, out_first_bad, 1, hip_stream);
+}
+int check_points_bw6_761_g2_dev(const uint64_t* d_xy, const uint8_t* d_inf, size_t n, int level, uint8_t* d_out_status, uint64_t* out_first_bad, void* hip_stream) {
+  return check_points(3, d_xy, d_inf, n, level, d_out_status, out_first_bad, 1, hip_stream);
+}
+int celo_amd_check_points_last_ms(float* ms) {
+  if (!ms) return 2;
+  *ms = check_points_last_ms();
+  return 0;
+}
+int celo_amd_wire761_set_subgroup_test(int form) { return wire761_set_subgroup_test(form); }
 int groth16_key_layout_bw6_761(const uint8_t* bytes, size_t len, int form, uint64_t out[16]) { return wire_key_layout(0, bytes, len, form, out); }
 int groth16_key_layout_bls12_377(const uint8_t* bytes, size_t len, int form, uint64_t out[16]) { return wire_key_layout(1, bytes, len, form, out); }
 int groth16_load_key_bw6_761_serialized(const uint8_t* bytes, size_t len, int form, int window_bits, void** out_key, uint64_t* first_bad_point) {

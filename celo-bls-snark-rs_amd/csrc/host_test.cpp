@@ -11,6 +11,7 @@
 #include "curve_lanes.h"
 #include "wire.h"
 #include "wire761.h"
+#include "check.h"
 #include "fixed_base.h"
 #include "var_base.h"
 #include "aggregate.h"
@@ -405,6 +406,25 @@ int ht_wire_subgroup_both(int g2, const uint64_t* xy) {
   }
   const Affine<Fq> q = {Fq::norm(Fq::from_ark(xy)), Fq::norm(Fq::from_ark(xy + 6))};
   return (wire_in_subgroup(q, k) ? 1 : 0) | (wire_in_subgroup_ladder(q, k) ? 2 : 0);
+}
+// the two forms of the BW6-761 subgroup test on one affine on-curve point (24 u64, ark limbs): bit 0 = the endomorphism form
+// (w761_in_subgroup_endo, what the decoders and check_points_* run), bit 1 = the r * P ladder (w761_in_subgroup, the definition)
+int ht_w761_subgroup_both(int g2, const uint64_t* xy) {
+  const Affine<Fw761> p = {Fw761::norm(Fw761::from_ark(xy)), Fw761::norm(Fw761::from_ark(xy + 12))};
+  return ((g2 ? w761_in_subgroup_endo<4>(p) : w761_in_subgroup_endo<-1>(p)) ? 1 : 0) | (w761_in_subgroup(p) ? 2 : 0);
+}
+// check.h under bounds tracking: n rows of group cg (0 / 1: BLS12-377 G1 / G2, 2 / 3: BW6-761 G1 / G2) -> status, what k_check_rows and
+// k_endo761 run per lane; inf may be NULL; ladder761: the BW6-761 rows take the ladder.  2 for a group or level that does not exist
+int ht_check_rows(int cg, const uint64_t* xy, const uint8_t* inf, size_t n, int level, int ladder761, uint8_t* status) {
+  if (cg < 0 || cg > 3 || level < 1 || level > 2) return 2;
+  const WireConsts& k = wire_consts();
+  for (size_t i = 0; i < n; i++) {
+    const uint64_t* row = xy + i * check_row_words(cg);
+    const bool f = inf && inf[i];
+    status[i] = cg == 0 ? check_row<0>(row, f, level, k) : cg == 1 ? check_row<1>(row, f, level, k) : cg == 2 ? check_row<2>(row, f, level, k, ladder761 != 0)
+                                                                                                       : check_row<3>(row, f, level, k, ladder761 != 0);
+  }
+  return 0;
 }
 // hash_direct.h under bounds tracking: one try-and-increment hash; returns the attempt counter, -1 when none succeeds
 int ht_hash_to_g1_direct(const uint8_t* dom, const uint8_t* msg, size_t mlen, const uint8_t* extra, size_t elen, uint64_t* out_xy) {

@@ -3,6 +3,7 @@
 // sections on the device straight into the buffers the fixed-base table build reads.
 #include "wire761.h"
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <cstdio>
 #include <mutex>
 #include "runtime.h"
@@ -21,7 +22,7 @@ static std::mutex w761_mu;
 // [0] kernel ms of the last decode call; [1] .. [3] the last key load's transfer / decode / table build (each call owns its slots)
 static Last<CallTimes> g_w761_last;
 
-// Two passes, one point per lane.  k_decode761: in n x 96 B (compressed) / n x 192 B (uncompressed) -> out n x 24 u64, (x, y) in arkworks
+// Two passes, one point per lane (the second is unit_check.hip's k_endo761 by default; k_subgroup761 is its twin, hook 1).  k_decode761: in n x 96 B (compressed) / n x 192 B (uncompressed) -> out n x 24 u64, (x, y) in arkworks
 // Montgomery limbs (the layout of msm_bw6_761_*), zeros unless status == WIRE_OK; everything but the subgroup test.  k_subgroup761: r P == O
 // for the rows still at status 0 (status 3 and a zero row otherwise); one kernel for both groups (the ladder does not depend on b).  Split
 // because the square root's four odd powers and the ladder's XYZZ state are never live together then: the first pass needs no scratch.
@@ -52,6 +53,8 @@ __global__ void __launch_bounds__(256) k_first_bad761(const uint8_t* __restrict_
   if (i < n && status[i] >= WIRE_INVALID) atomicMin(first, (unsigned long long)i);
 }
 
+// which subgroup pass the decoders (and check_points_bw6_761_*) launch: 0 = k_endo761 (unit_check.hip), 1 = k_subgroup761 above
+static std::atomic<int> g_w761_subgroup_test{0};
 static void launch_decode761(int g2, int compressed, const uint8_t* d_in, size_t n, int check, uint64_t* d_out, uint8_t* d_st, hipStream_t s) {
   const dim3 grid(((uint32_t)n + 63) / 64), block(64);
   if (g2) {
@@ -61,7 +64,21 @@ static void launch_decode761(int g2, int compressed, const uint8_t* d_in, size_t
     if (compressed) hipLaunchKernelGGL((k_decode761<-1, true>), grid, block, 0, s, d_in, d_out, d_st, (uint32_t)n, check);
     else hipLaunchKernelGGL((k_decode761<-1, false>), grid, block, 0, s, d_in, d_out, d_st, (uint32_t)n, check);
   }
-  if (check) hipLaunchKernelGGL(k_subgroup761, grid, block, 0, s, d_out, d_st, (uint32_t)n);
+  if (!check) return;
+  // the subgroup pass: the endomorphism form (unit_check.hip k_endo761) unless the hook asks for the ladder; the verdicts and rows are the same
+  if (g_w761_subgroup_test.load() == 0) check761_launch_endo(g2, d_out, d_out, d_st, n, s);
+  else hipLaunchKernelGGL(k_subgroup761, grid, block, 0, s, d_out, d_st, (uint32_t)n);
+}
+// celo_amd_wire761_set_subgroup_test: 0 = [a]P + [b]phi(P) == O (the default), 1 = the r P ladder; 2 for anything else
+int wire761_set_subgroup_test(int form) {
+  if (form != 0 && form != 1) return 2;
+  g_w761_subgroup_test.store(form);
+  return 0;
+}
+int wire761_subgroup_test() { return g_w761_subgroup_test.load(); }
+// the ladder pass on rows the caller owns (unit_check.hip, under hook 1)
+void wire761_launch_ladder(uint64_t* d_rows, uint8_t* d_st, size_t n, hipStream_t s) {
+  hipLaunchKernelGGL(k_subgroup761, dim3(((uint32_t)n + 63) / 64), dim3(64), 0, s, d_rows, d_st, (uint32_t)n);
 }
 
 // g2: 0 = G1 (b = -1), 1 = G2 (b = 4); compressed: 1 = 96 B points, 0 = 192 B; dev: all four pointers are device pointers, run on stream_
@@ -107,7 +124,7 @@ static WireStatus key_host_row(int curve, int g2, int compressed, const uint8_t*
 
 // ProvingKey::<E>::deserialize (form 0) / deserialize_uncompressed (1) / deserialize_unchecked (2), then groth16_load_key_<curve>; curve 0 =
 // BW6-761, 1 = BLS12-377.  The whole byte string crosses to the device once; every point of every section is decoded there (one launch per
-// section: k_decode761 + k_subgroup761, or unit_wire.hip's k_decompress / k_decode377u) into a G1 row buffer and a G2 row buffer (24 u64 per
+// section: k_decode761 + the subgroup pass, or unit_wire.hip's k_decompress / k_decode377u) into a G1 row buffer and a G2 row buffer (24 u64 per
 // row; BLS12-377 G1: 12), each in serialization order, with one status array indexed by the point's position in serialization order.  The first
 // rejected index is found by an atomic minimum, and the four queries' rows and statuses are handed to the table build where they lie (a status-1
 // row - the point at infinity - is that query's identity through the build's `inf` bytes: after the check every status is 0 or 1).

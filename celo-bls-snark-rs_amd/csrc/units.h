@@ -110,6 +110,16 @@ int wire761_decode(int g2, int compressed, const uint8_t* in, size_t n, int chec
 int wire_key_layout(int curve, const uint8_t* bytes, size_t len, int form, uint64_t out[16]);
 int wire_key_load(int curve, const uint8_t* bytes, size_t len, int form, int window_bits, ProvingKey** out_key, uint64_t* first_bad);
 void wire761_last_timings(float ms[4]);
+// the subgroup pass of the BW6-761 decoders and of check_points_bw6_761_*: 0 = the endomorphism form (k_endo761), 1 = the r P ladder (k_subgroup761)
+int wire761_set_subgroup_test(int form);
+int wire761_subgroup_test();
+void wire761_launch_ladder(uint64_t* d_rows, uint8_t* d_st, size_t n, hipStream_t s);
+// ---- bulk validation of affine rows (unit_check.hip; check.h).  cg 0 / 1: BLS12-377 G1 / G2, 2 / 3: BW6-761 G1 / G2; level 1: the curve
+// equation, 2: and the subgroup.  dev: xy, inf and status are device pointers, the work runs on `stream`; first_bad is a host pointer (may be NULL)
+int check_points(int cg, const uint64_t* xy, const uint8_t* inf, size_t n, int level, uint8_t* status, uint64_t* first_bad, int dev, void* stream);
+float check_points_last_ms();
+// k_endo761 on the rows at status 0: status 3 where [a]P + [b]phi(P) != O, and that row of d_zero_rows (may be d_rows itself, or NULL) zeroed
+void check761_launch_endo(int g2, const uint64_t* d_rows, uint64_t* d_zero_rows, uint8_t* d_st, size_t n, hipStream_t s);
 // ---- point encoding and the key / proof writers (unit_wire_encode.hip).  group as above; compressed: 1 = x with the sign flag, 0 = x || y
 int wire_encode(int group, int compressed, const uint64_t* rows, const uint8_t* inf, size_t n, uint8_t* out, uint8_t* status, int dev, void* stream);
 float wire_encode_last_ms();

@@ -14,7 +14,7 @@
 //   a coordinate >= q                            -> 2
 //   compressed: rhs has no square root           -> 2
 //   uncompressed, checked: (x, y) not on the curve -> 2
-//   checked: r P != O (r = r_BW6 = q_BLS12-377)  -> WIRE_NOT_IN_SUBGROUP (3)
+//   checked: r P != O (r = r_BW6 = q_BLS12-377)  -> WIRE_NOT_IN_SUBGROUP (3)   (w761_in_subgroup_endo; w761_in_subgroup is its definition)
 //   otherwise                                    -> WIRE_OK (0)
 // The uncompressed checked form tests the curve equation before the subgroup: stricter than ark 0.1's deserialize_uncompressed, which
 // runs only is_in_correct_subgroup_assuming_on_curve - an off-curve (x, y) is rejected here (2) where ark may accept or reject it.
@@ -119,7 +119,8 @@ HD bool w761_madd(Xyzz<Fw761>& a, const Affine<Fw761>& p) { return xyzz_madd_unl
 // r P == O with r = q_BLS12-377 (377 bits), MSB-first double-and-add over XYZZ: ark-ec 0.1 is_in_correct_subgroup_assuming_on_curve as
 // written.  The XYZZ formulas of curve.h do not depend on b, so one ladder serves both groups.
 // One group operation per iteration (stage 0: double for bit i; 1: add p for bit i; 2: acc was p, double instead of adding).
-// (No endomorphism form: that would come with this ladder kept as its twin, as wire.h does for BLS12-377.)
+// Kept word for word as the definition w761_in_subgroup_endo below is checked against (tests/test_subgroup_host.py,
+// tests/test_check_points_gpu.py), as wire.h keeps wire_in_subgroup_ladder for BLS12-377; hook 1 of celo_amd_wire761_set_subgroup_test runs it.
 HD bool w761_in_subgroup(const Affine<Fw761>& p) {
   Xyzz<Fw761> acc = Xyzz<Fw761>::from_affine(p);     // bit 376, the top bit of r
   int i = 375, stage = 0;
@@ -135,6 +136,139 @@ HD bool w761_in_subgroup(const Affine<Fw761>& p) {
     if (stage == 2) { stage = 0; i--; }
     else if (w761_exp_bit(P377::P64, i)) stage = 1;
     else i--;
+  }
+  return acc.is_identity() || acc.ZZ.is_zero_mod_p();
+}
+
+// ---- The same predicate through the endomorphism phi(x, y) = (beta x, y), beta a primitive cube root of unity in Fq (both curves have
+// j = 0), so phi^2 + phi + 1 = 0 on all of E(Fq).  With x = 0x8508c00000000001 (the BLS12-377 parameter; r = q_BLS12-377) take
+//     a = (2 x^3 - 2 x^2 - x + 1) / 3   (189 bits)        b = (x^3 - x^2 - 2 x - 1) / 3   (188 bits).
+// Norm and exactness.  a^2 - a b + b^2 = r exactly (asserted below), and that is the degree of the endomorphism a + b phi (Z[phi] is the
+//   ring of Eisenstein integers).  A separable endomorphism of degree r has a kernel of exactly r points.  beta is the cube root whose phi
+//   acts on the order-r subgroup as the eigenvalue lambda with a + b lambda = 0 (mod r) - so the subgroup lies in the kernel, and having r
+//   points it IS the kernel:  [a]P + [b]phi(P) == O  holds exactly when  r P == O, for every point of the curve.  No cofactor condition.
+// Which beta.  G1 (y^2 = x^3 - 1) and G2 (y^2 = x^3 + 4) need different roots: with g = 2, G1 takes g^((q-1)/3) and G2 its square
+//   (tests/test_subgroup_cases.py derives both and pins them on a subgroup point).
+// Not the better-known short vector (x + 1, x^3 - x^2 + 1): its norm is 3 r, so its kernel has 3 r points.  On G1 that is still exact
+//   (3 does not divide the cofactor h1); on G2 it is wrong: 3 | h2, T = (0, 2) has order 3 with phi(T) = T, and T, G + T, G - T all pass.
+// Cost: one two-scalar ladder over separate NAFs of a and b (weights 36 and 37 over 190 columns): 189 doublings and 73 mixed additions
+//   (one of them the first, a copy), about 2 430 field products where the 377-bit ladder (376 doublings, 134 additions) takes about 4 720.
+//
+// Compile-time integers of up to 512 bits, for the digit program and the identities asserted on it
+struct W761Wide { uint64_t w[8] = {}; };
+constexpr W761Wide w761w(uint64_t v) { W761Wide r; r.w[0] = v; return r; }
+constexpr W761Wide w761w_add(const W761Wide& a, const W761Wide& b) {
+  W761Wide r;
+  unsigned __int128 c = 0;
+  for (int i = 0; i < 8; i++) { c += (unsigned __int128)a.w[i] + b.w[i]; r.w[i] = (uint64_t)c; c >>= 64; }
+  return r;
+}
+constexpr W761Wide w761w_sub(const W761Wide& a, const W761Wide& b) {   // a >= b
+  W761Wide r;
+  uint64_t borrow = 0;
+  for (int i = 0; i < 8; i++) {
+    const uint64_t d = a.w[i] - b.w[i], e = d - borrow;
+    borrow = (a.w[i] < b.w[i]) || (d < borrow) ? 1 : 0;
+    r.w[i] = e;
+  }
+  return r;
+}
+constexpr W761Wide w761w_mul(const W761Wide& a, const W761Wide& b) {   // the low 512 bits (every product below fits)
+  W761Wide r;
+  for (int i = 0; i < 8; i++) {
+    unsigned __int128 c = 0;
+    for (int j = 0; i + j < 8; j++) { c += (unsigned __int128)a.w[i] * b.w[j] + r.w[i + j]; r.w[i + j] = (uint64_t)c; c >>= 64; }
+  }
+  return r;
+}
+constexpr W761Wide w761w_div3(const W761Wide& a) {                      // floor(a / 3); exactness is asserted by multiplying back
+  W761Wide r;
+  unsigned __int128 rem = 0;
+  for (int i = 7; i >= 0; i--) { const unsigned __int128 t = (rem << 64) | a.w[i]; r.w[i] = (uint64_t)(t / 3); rem = t % 3; }
+  return r;
+}
+constexpr bool w761w_eq(const W761Wide& a, const W761Wide& b) {
+  for (int i = 0; i < 8; i++) if (a.w[i] != b.w[i]) return false;
+  return true;
+}
+constexpr bool w761w_is_zero(const W761Wide& a) { return w761w_eq(a, W761Wide{}); }
+// The program of [a]P + [b]phi(P): columns from the top, one step each.  0: double; 1 / 2: add +P / -P; 3 / 4: add +phi(P) / -phi(P).
+// Built at compile time from x, as W761Chain is: the same constant in every lane, branches scalar, nothing indexed at run time but the program.
+struct W761EndoProgram {
+  W761Wide a, b, three_a, three_b;
+  int len = 0, doublings = 0, additions = 0;
+  uint8_t step[320] = {};
+};
+constexpr int w761_naf(W761Wide k, int8_t* digits) {                    // non-adjacent form, least significant digit first; the length
+  int n = 0;
+  while (!w761w_is_zero(k)) {
+    int d = 0;
+    if (k.w[0] & 1) {
+      d = (k.w[0] & 3) == 1 ? 1 : -1;
+      k = d == 1 ? w761w_sub(k, w761w(1)) : w761w_add(k, w761w(1));
+    }
+    digits[n++] = (int8_t)d;
+    for (int i = 0; i < 8; i++) k.w[i] = (k.w[i] >> 1) | (i + 1 < 8 ? k.w[i + 1] << 63 : 0);
+  }
+  return n;
+}
+constexpr W761EndoProgram w761_endo_program() {
+  const W761Wide x = w761w(0x8508c00000000001ULL), x2 = w761w_mul(x, x), x3 = w761w_mul(x2, x), one = w761w(1);
+  W761EndoProgram c;
+  c.three_a = w761w_add(w761w_sub(w761w_sub(w761w_add(x3, x3), w761w_add(x2, x2)), x), one);                 // 2 x^3 - 2 x^2 - x + 1
+  c.three_b = w761w_sub(w761w_sub(w761w_sub(x3, x2), w761w_add(x, x)), one);                                 // x^3 - x^2 - 2 x - 1
+  c.a = w761w_div3(c.three_a);
+  c.b = w761w_div3(c.three_b);
+  int8_t da[512] = {}, db[512] = {};
+  const int na = w761_naf(c.a, da), nb = w761_naf(c.b, db);
+  for (int col = (na > nb ? na : nb) - 1; col >= 0; col--) {
+    if (c.len) { c.step[c.len++] = 0; c.doublings++; }
+    if (da[col]) { c.step[c.len++] = da[col] > 0 ? 1 : 2; c.additions++; }
+    if (db[col]) { c.step[c.len++] = db[col] > 0 ? 3 : 4; c.additions++; }
+  }
+  return c;
+}
+constexpr bool w761_endo_norm_is_r(const W761EndoProgram& c) {          // a^2 - a b + b^2 == r = q_BLS12-377
+  const W761Wide n = w761w_sub(w761w_add(w761w_mul(c.a, c.a), w761w_mul(c.b, c.b)), w761w_mul(c.a, c.b));
+  W761Wide r;
+  for (int i = 0; i < 6; i++) r.w[i] = P377::P64[i];
+  return w761w_eq(n, r);
+}
+struct W761Endo {
+  static constexpr W761EndoProgram C = w761_endo_program();
+  // g^((q-1)/3) for g = 2 and its square, canonical, little-endian words: the beta of G1 and of G2
+  static constexpr uint64_t BETA_G1[12] = {0x962140000000002a, 0xc547ba8a4000002f, 0xb6290012d96f8819, 0xf2f082d4dcb5e37c, 0xc65759fc45183151, 0x8e0a235a0a398300,
+                                           0xab5e57926fa70184, 0xee4a737f73b6f952, 0x2d17be416c5e4426, 0x6c1f31e53bd9603c, 0xaa846c61024e4cca, 0x531dc16c6ecd27};
+  static constexpr uint64_t BETA_G2[12] = {0x5e7bc00000000060, 0x214983de30000053, 0x5fe3f89c11811c1e, 0xa5b093ed79b1c57b, 0xab8579e02ed3cddc, 0xf87fa59308c07a8f,
+                                           0x5870636cb60d217f, 0x823132b971cdefc6, 0x256ab7ae14297a1a, 0x4d06e68545f7e64c, 0x27035cdf02acb274, 0xcfca638f1500e3};
+};
+static_assert(w761w_eq(w761w_mul(W761Endo::C.a, w761w(3)), W761Endo::C.three_a), "3 a = 2 x^3 - 2 x^2 - x + 1");
+static_assert(w761w_eq(w761w_mul(W761Endo::C.b, w761w(3)), W761Endo::C.three_b), "3 b = x^3 - x^2 - 2 x - 1");
+static_assert(w761_endo_norm_is_r(W761Endo::C), "a^2 - a b + b^2 = r: the endomorphism a + b phi has degree r");
+static_assert(W761Endo::C.doublings == 189 && W761Endo::C.additions == 73 && W761Endo::C.len == 262, "190 columns, NAF weights 36 and 37");
+static_assert(W761Endo::C.step[0] != 0 && W761Endo::C.len <= 320, "the program starts with an addition and fits its array");
+
+// [a]P + [b]phi(P) == O for a finite point p of the curve with b = B (the curve constant picks beta).  One group operation per step, through
+// one addition site and one doubling site.  The addition is complete on every input: an accumulator at the identity takes the addend
+// (xyzz_madd_unless_equal), one opposite to the addend becomes the identity, one EQUAL to it is doubled at the doubling site (which maps a
+// point with y = 0 to the identity) - so points of low order, where these branches are taken constantly, and phi(P) == P (x = 0) need no case of
+// their own.  The addends are (x or beta x, y or -y): phi(P) costs the one product beta x, kept for the whole ladder; -y is formed per addition.
+template <int B> HD bool w761_in_subgroup_endo(const Affine<Fw761>& p) {
+  static_assert(B == -1 || B == 4, "BW6-761: G1 has b = -1, the M-twist G2 b = 4");
+  constexpr const W761EndoProgram& C = W761Endo::C;
+  const Fw761 bx = Fw761::norm(Fw761::mul(Fw761::from_canonical(B < 0 ? W761Endo::BETA_G1 : W761Endo::BETA_G2), p.x));
+  Xyzz<Fw761> acc = Xyzz<Fw761>::identity();
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+  for (int i = 0; i < C.len; i++) {
+    const int op = C.step[i];
+    bool dbl = op == 0;
+    if (!dbl) {
+      const Affine<Fw761> q = {op >= 3 ? bx : p.x, (op & 1) ? p.y : w761_neg(p.y)};
+      dbl = !w761_madd(acc, q);
+    }
+    if (dbl) acc = xyzz_dbl(acc);
   }
   return acc.is_identity() || acc.ZZ.is_zero_mod_p();
 }
@@ -158,10 +292,10 @@ template <int B, bool COMPRESSED> HD WireStatus w761_parse(const uint8_t* in, bo
   p = {Fw761::norm(x), Fw761::norm(y)};
   return WIRE_OK;
 }
-// the whole decoding (the kernels run it in two passes, w761_parse and w761_in_subgroup: unit_wire761.hip)
+// the whole decoding (the kernels run it in two passes, w761_parse and the subgroup test: unit_wire761.hip, unit_check.hip)
 template <int B, bool COMPRESSED> HD WireStatus w761_decode(const uint8_t* in, bool check, Affine<Fw761>& p) {
   const WireStatus st = w761_parse<B, COMPRESSED>(in, check, p);
-  if (st == WIRE_OK && check && !w761_in_subgroup(p)) return WIRE_NOT_IN_SUBGROUP;
+  if (st == WIRE_OK && check && !w761_in_subgroup_endo<B>(p)) return WIRE_NOT_IN_SUBGROUP;
   return st;
 }
 // the row form the MSM entry points take: 24 u64, (x, y) as arkworks Montgomery limbs; zeros unless WIRE_OK

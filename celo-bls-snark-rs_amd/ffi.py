@@ -82,6 +82,9 @@ EXPORTS = [
     "hash_to_bits_public_inputs_bls12_377", "hash_to_bits_public_inputs_bls12_377_dev", "groth16_hash_helper_prove_bls12_377", "celo_amd_hash_helper_last",
     "groth16_vk_load_bls12_377_wide", "groth16_vk_load_bls12_377_wide_serialized", "celo_amd_groth16_set_input_lanes", "celo_amd_groth16_inputs_last",
     "groth16_hash_helper_verify_bls12_377",
+    "check_points_bls12_377_g1", "check_points_bls12_377_g2", "check_points_bw6_761_g1", "check_points_bw6_761_g2",
+    "check_points_bls12_377_g1_dev", "check_points_bls12_377_g2_dev", "check_points_bw6_761_g1_dev", "check_points_bw6_761_g2_dev",
+    "celo_amd_check_points_last_ms", "celo_amd_wire761_set_subgroup_test",
 ]
 
 _lib = None
@@ -973,6 +976,52 @@ def decode_uncompressed_dev(group, d_in, n, d_out, d_status, check=True, stream=
     """The same on device buffers (integer device addresses), on `stream`: BLS12-377 only ("g1" / "g2"); returns the entry point's code."""
     fn = _UNCOMPRESSED[group][2] + "_dev"
     return getattr(lib(), fn)(C.c_void_p(d_in), C.c_size_t(n), C.c_int(1 if check else 0), C.c_void_p(d_out), C.c_void_p(d_status), C.c_void_p(stream))
+
+
+# ---- validation of affine rows (include/celo_bls_amd.h: check_points_*)
+CHECK_GROUPS = {"bls12_377_g1": 12, "bls12_377_g2": 24, "bw6_761_g1": 24, "bw6_761_g2": 24}          # u64 per row
+
+
+def check_points(group, xy, inf=None, level=2):
+    """Bulk validation of affine rows (check_points_<group>): xy (n, 12 | 24) uint64 arkworks Montgomery limbs, inf (n,) uint8 or None;
+    level 1: the curve equation, 2: the curve and the prime-order subgroup.  Returns (status (n,) uint8, first_bad): 0 good, 1 the row is
+    flagged as the identity, 2 a coordinate is not below q or the point is off the curve, 3 outside the subgroup; first_bad is the smallest
+    index with status 2 or 3, n if there is none."""
+    words = CHECK_GROUPS[group]
+    rows = _rows(xy, words)
+    n = rows.shape[0]
+    flags = None if inf is None else np.ascontiguousarray(inf, dtype=np.uint8)
+    assert flags is None or flags.size == n
+    st = np.zeros(n, dtype=np.uint8)
+    first = C.c_uint64(0)
+    rc = getattr(lib(), "check_points_" + group)(_p(rows), _p(flags), C.c_size_t(n), C.c_int(level), _p(st), C.byref(first))
+    if rc != 0:
+        raise RuntimeError("check_points_%s failed with code %d" % (group, rc))
+    return st, first.value
+
+
+def check_points_dev(group, d_xy, d_inf, n, d_status, level=2, stream=0):
+    """The same on device buffers (integer device addresses; d_inf may be 0), on `stream`.  Returns first_bad (the call drains the stream)."""
+    first = C.c_uint64(0)
+    rc = getattr(lib(), "check_points_%s_dev" % group)(C.c_void_p(d_xy), C.c_void_p(d_inf or None), C.c_size_t(n), C.c_int(level), C.c_void_p(d_status),
+                                                      C.byref(first), C.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError("check_points_%s_dev failed with code %d" % (group, rc))
+    return first.value
+
+
+def check_points_last_ms():
+    """kernel time of the last check_points_* call (HIP events around its kernels)"""
+    ms = C.c_float(0)
+    assert lib().celo_amd_check_points_last_ms(C.byref(ms)) == 0
+    return ms.value
+
+
+def wire761_set_subgroup_test(form):
+    """Which subgroup test the BW6-761 decoders, the serialized key loader and verifiers and check_points_bw6_761_* run: 0 = the
+    endomorphism form [a]P + [b]phi(P) == O (the default), 1 = the r P ladder, its definition.  The verdicts are the same."""
+    if lib().celo_amd_wire761_set_subgroup_test(C.c_int(form)) != 0:
+        raise ValueError("celo_amd_wire761_set_subgroup_test: 0 or 1, not %r" % (form,))
 
 
 # ---- encoding into the wire form (include/celo_bls_amd.h: compress_*, encode_uncompressed_*, groth16_serialize_*)

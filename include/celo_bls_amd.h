@@ -354,7 +354,9 @@ int celo_amd_decompress_last_ms(float* ms);
  * CanonicalDeserialize of G1 (y^2 = x^3 - 1) and G2 (the M-twist y^2 = x^3 + 4, coordinates in Fq) points, 96 B per coordinate,
  * little-endian, flags in the two top bits of the last byte (0x40 infinity, 0x80 "y is the larger root").  One point per GPU lane
  * (csrc/wire761.h, csrc/unit_wire761.hip): the square root rhs^((q+1)/4), the sign choice and, when checked, r*P == O with
- * r = r_BW6 = q_BLS12-377 by a 377-bit ladder - the predicate of ark-ec 0.1 is_in_correct_subgroup_assuming_on_curve.
+ * r = r_BW6 = q_BLS12-377 - the predicate of ark-ec 0.1 is_in_correct_subgroup_assuming_on_curve, evaluated as [a]P + [b]phi(P) == O for the
+ * endomorphism a + b phi of degree exactly r (two 189-bit scalars in one ladder; the argument is at check_points_* below and in
+ * csrc/wire761.h), with the 377-bit ladder kept as its twin (celo_amd_wire761_set_subgroup_test).
  *   decompress_bw6_761_*:          96 B points; check_subgroup != 0 is GroupAffine::deserialize (what ark-groth16 runs per point of a
  *                                  ProvingKey / VerifyingKey / Proof: crates/epoch-snark/src/api/setup.rs:12,17-20, the "serialized byte
  *                                  arrays of compressed elements" of crates/bls-snark-sys/src/snark/mod.rs:13-17), 0 skips the subgroup test.
@@ -371,6 +373,41 @@ int decompress_bw6_761_g1_dev(const uint8_t* d_in, size_t n, int check_subgroup,
 int decompress_bw6_761_g2_dev(const uint8_t* d_in, size_t n, int check_subgroup, uint64_t* d_out_xy, uint8_t* d_status, void* hip_stream);
 int decode_uncompressed_bw6_761_g1(const uint8_t* in /* n x 192 */, size_t n, int check, uint64_t* out_xy /* n x 24 */, uint8_t* status /* n */);
 int decode_uncompressed_bw6_761_g2(const uint8_t* in /* n x 192 */, size_t n, int check, uint64_t* out_xy /* n x 24 */, uint8_t* status /* n */);
+/* Which subgroup test the BW6-761 decoders above run - and with them groth16_load_key_bw6_761_serialized, the serialized BW6-761 verifiers
+ * and check_points_bw6_761_*: 0 = the endomorphism form (the default), 1 = the r*P ladder, its definition.  Verdicts and rows are identical;
+ * the switch exists for the same-run comparison (tools/bench_subgroup.py) and the tests.  Process-wide; 2 for any other value. */
+int celo_amd_wire761_set_subgroup_test(int form);
+/* ---- validation of points held as affine rows: is_on_curve / is_in_correct_subgroup for all four groups, in bulk (csrc/check.h,
+ * csrc/unit_check.hip; one row per GPU lane).  Every other group entry point of this header trusts its rows ("points off the curve are not
+ * validated"; the _subgroup entries, batch_verify_bls12_377 and verify_aggregated_seals_bls12_377 rest on "the caller vouches"): a caller that
+ * holds limb rows rather than wire bytes validates them here first.
+ *   xy:    n rows of affine (x, y) in arkworks Montgomery limbs - BLS12-377 G1 12 u64; BLS12-377 G2 24 u64 (x.c0, x.c1, y.c0, y.c1); BW6-761
+ *          G1 and G2 24 u64 - the layout the MSM, pairing and key entry points take.  Only read.
+ *   inf:   n identity flags, or NULL for none.
+ *   level: 1 = the curve equation only; 2 = the curve and the prime-order subgroup.
+ *   out_status[i], the first that applies (the decoders' codes): 1 the flag is set - the coordinates are not looked at; 2 a coordinate (an Fq2
+ *          component) is not below q as the limbs stand, or (x, y) is not on the curve; 3 (level 2) on the curve but r*P != O; 0 good.
+ *   out_first_bad: may be NULL; the smallest i with status 2 or 3, n if there is none.  A host pointer in the _dev forms as well.
+ * Returns 0 whatever the statuses are, and for n = 0; 2 with nothing written and before any device use for xy or out_status NULL (n > 0), a
+ * level outside {1, 2} or n > 2^31 - 1.  The _dev forms take device pointers for xy, inf and out_status, run on hip_stream (0: the null
+ * stream) and return after the work has drained; calls are serialised per process.
+ * The subgroup tests are the decoders': for BLS12-377 the endomorphism tests of decompress_bls12_377_* (phi(P) == -[x^2]P on G1, psi(P) == [x]P
+ * on G2), for BW6-761 the following.  phi(x, y) = (beta x, y) with beta a primitive cube root of unity in Fq satisfies phi^2 + phi + 1 = 0 on
+ * both curves.  With x = 0x8508c00000000001, a = (2x^3 - 2x^2 - x + 1)/3 and b = (x^3 - x^2 - 2x - 1)/3 have a^2 - ab + b^2 = r exactly, so
+ * a + b phi is an endomorphism of degree r whose kernel has r points; beta is chosen (one root for G1, the other for G2) so that phi acts on
+ * the order-r subgroup as the lambda with a + b lambda = 0 (mod r), hence the kernel IS the subgroup: [a]P + [b]phi(P) == O exactly when
+ * r*P == O, for every curve point, with no cofactor condition.  (The better-known vector (x + 1, x^3 - x^2 + 1) has norm 3r and is wrong on
+ * G2, whose cofactor is divisible by 3: (0, 2) passes it.)  About 2 430 field products per point where the ladder takes 4 720. */
+int check_points_bls12_377_g1(const uint64_t* xy /* n x 12 */, const uint8_t* inf /* n or NULL */, size_t n, int level, uint8_t* out_status /* n */, uint64_t* out_first_bad);
+int check_points_bls12_377_g2(const uint64_t* xy /* n x 24 */, const uint8_t* inf /* n or NULL */, size_t n, int level, uint8_t* out_status /* n */, uint64_t* out_first_bad);
+int check_points_bw6_761_g1(const uint64_t* xy /* n x 24 */, const uint8_t* inf /* n or NULL */, size_t n, int level, uint8_t* out_status /* n */, uint64_t* out_first_bad);
+int check_points_bw6_761_g2(const uint64_t* xy /* n x 24 */, const uint8_t* inf /* n or NULL */, size_t n, int level, uint8_t* out_status /* n */, uint64_t* out_first_bad);
+int check_points_bls12_377_g1_dev(const uint64_t* d_xy, const uint8_t* d_inf, size_t n, int level, uint8_t* d_out_status, uint64_t* out_first_bad, void* hip_stream);
+int check_points_bls12_377_g2_dev(const uint64_t* d_xy, const uint8_t* d_inf, size_t n, int level, uint8_t* d_out_status, uint64_t* out_first_bad, void* hip_stream);
+int check_points_bw6_761_g1_dev(const uint64_t* d_xy, const uint8_t* d_inf, size_t n, int level, uint8_t* d_out_status, uint64_t* out_first_bad, void* hip_stream);
+int check_points_bw6_761_g2_dev(const uint64_t* d_xy, const uint8_t* d_inf, size_t n, int level, uint8_t* d_out_status, uint64_t* out_first_bad, void* hip_stream);
+/* kernel time (HIP events) of the last check_points_* call */
+int celo_amd_check_points_last_ms(float* ms);
 /* ---- the same uncompressed forms for BLS12-377 (csrc/wire.h wire_decode_row_*, csrc/unit_wire.hip k_decode377u): what
  * GroupAffine::deserialize_uncompressed / deserialize_unchecked run per point of a large ProvingKey<Bls12_377> - no square root per point.
  * in: n x 96 B (G1: x, then y) / n x 192 B (G2: x.c0, x.c1, y.c0, y.c1); the flags sit on the last byte of y (G2: of y.c1).  out_xy and
