@@ -351,6 +351,24 @@ int decompress_bls12_377_g1_dev(const uint8_t* d_in, size_t n, int check_subgrou
 int decompress_bls12_377_g2_dev(const uint8_t* d_in, size_t n, int check_subgroup, uint64_t* d_out_xy, uint8_t* d_status, void* hip_stream) {
   return wire_decompress(1, d_in, n, check_subgroup, d_out_xy, d_status, 1, hip_stream);
 }
+// ---- the same keys decoded once per distinct byte string (unit_dedup.hip)
+int decompress_bls12_377_g1_dedup(const uint8_t* in, size_t n, int check_subgroup, uint64_t* out_xy, uint8_t* status, uint32_t* out_rep, uint64_t* out_decoded) {
+  return wire_decompress_dedup(0, in, n, check_subgroup, out_xy, status, out_rep, out_decoded, 0, nullptr);
+}
+int decompress_bls12_377_g2_dedup(const uint8_t* in, size_t n, int check_subgroup, uint64_t* out_xy, uint8_t* status, uint32_t* out_rep, uint64_t* out_decoded) {
+  return wire_decompress_dedup(1, in, n, check_subgroup, out_xy, status, out_rep, out_decoded, 0, nullptr);
+}
+int decompress_bls12_377_g1_dedup_dev(const uint8_t* d_in, size_t n, int check_subgroup, uint64_t* d_out_xy, uint8_t* d_status, uint32_t* d_out_rep, uint64_t* out_decoded,
+                                      void* hip_stream) {
+  return wire_decompress_dedup(0, d_in, n, check_subgroup, d_out_xy, d_status, d_out_rep, out_decoded, 1, hip_stream);
+}
+int decompress_bls12_377_g2_dedup_dev(const uint8_t* d_in, size_t n, int check_subgroup, uint64_t* d_out_xy, uint8_t* d_status, uint32_t* d_out_rep, uint64_t* out_decoded,
+                                      void* hip_stream) {
+  return wire_decompress_dedup(1, d_in, n, check_subgroup, d_out_xy, d_status, d_out_rep, out_decoded, 1, hip_stream);
+}
+int celo_amd_key_dedup_set(int on, int slack_log, int max_probes) { return key_dedup_set(on, slack_log, max_probes); }
+int celo_amd_key_dedup_get(int out[3]) { return key_dedup_get(out); }
+int celo_amd_key_dedup_last(uint64_t counts[2], float ms[4]) { return key_dedup_last(counts, ms); }
 int decompress_bw6_761_g1(const uint8_t* in, size_t n, int check_subgroup, uint64_t* out_xy, uint8_t* status) {
   return wire761_decode(0, 1, in, n, check_subgroup, out_xy, status, 0, nullptr);
 }

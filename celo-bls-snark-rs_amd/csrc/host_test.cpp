@@ -12,6 +12,7 @@
 #include "wire.h"
 #include "wire761.h"
 #include "check.h"
+#include "dedup.h"
 #include "fixed_base.h"
 #include "var_base.h"
 #include "aggregate.h"
@@ -1091,5 +1092,18 @@ void ht_epoch_inputs(const uint8_t* h_first32, const uint8_t* h_last32, uint64_t
   uint32_t a[8] = {}, b[8] = {};
   for (int i = 0; i < 32; i++) { a[i / 4] |= (uint32_t)h_first32[i] << (8 * (i % 4)); b[i / 4] |= (uint32_t)h_last32[i] << (8 * (i % 4)); }
   epoch_inputs(a, b, out12);
+}
+// ---- dedup.h: the host twin of k_dedup_insert / k_dedup_rep (the same templates, key after key).  kb: 48 or 96
+uint64_t ht_dedup_mix(int kb, const uint8_t* key) { return kb == 96 ? dedup_hash<96, false>(key) : dedup_hash<48, false>(key); }
+uint64_t ht_dedup_slots(uint64_t n, int slack_log) { return dedup_slots(n, slack_log); }
+int ht_dedup_pick(uint64_t n) { return key_dedup_pick(n) ? 1 : 0; }
+uint64_t ht_dedup_n0() { return DEDUP_N0; }
+// rep, slot_of, list, rank: n each; returns U, or -1 for arguments the table does not take
+int64_t ht_dedup_run(int kb, const uint8_t* keys, uint32_t n, int slack_log, uint32_t max_probes, uint32_t* slot_of, uint32_t* rep, uint32_t* list, uint32_t* rank) {
+  if ((kb != 48 && kb != 96) || n == 0 || n > 0x7fffffffu || slack_log < 0 || slack_log > DEDUP_SLACK_MAX || max_probes < 1 || max_probes > (uint32_t)DEDUP_PROBES_MAX) return -1;
+  const uint64_t S = dedup_slots(n, slack_log);
+  std::vector<uint32_t> owner(S), first(S);
+  return kb == 96 ? dedup_host<96>(keys, n, slack_log, max_probes, owner.data(), first.data(), slot_of, rep, list, rank)
+                  : dedup_host<48>(keys, n, slack_log, max_probes, owner.data(), first.data(), slot_of, rep, list, rank);
 }
 }

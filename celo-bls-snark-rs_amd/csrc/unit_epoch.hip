@@ -174,7 +174,12 @@ static int epoch_stage(CallScope& cs, EvLog& log, const EpochBlocks& b, size_t n
     HIP_TRY(cs.alloc(&d_kst, (size_t)nkeys + 8), 10);
     log.close(EP_XFER, e0);
     e0 = log.open();
-    if (nkeys) if (int rc = wire_decompress(1, d_k96, nkeys, 1, d_rows, d_kst, 1, s)) return rc;
+    // a validator set changes by a handful of keys per epoch: when the switch says so (celo_amd_key_dedup_set), each distinct key is decoded once
+    if (nkeys) {
+      const int rc = key_dedup_use(nkeys) ? wire_decompress_dedup(1, d_k96, nkeys, 1, d_rows, d_kst, nullptr, nullptr, 1, s)
+                                          : wire_decompress(1, d_k96, nkeys, 1, d_rows, d_kst, 1, s);
+      if (rc) return rc;
+    }
     log.close(EP_DECODE, e0);
   } else {
     if (nkeys) {

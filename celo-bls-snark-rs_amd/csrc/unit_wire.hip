@@ -65,6 +65,7 @@ int wire_consts_device(WireConsts& out) {
   out.tab = d_tab;
   return 0;
 }
+int wire_consts_warm() { WireConsts k; return wire_consts_device(k); }
 static Last<float> g_wire_last;               // kernel ms of the last decode or normalise call that succeeded
 
 // one decode launch on device buffers (the entry points below; the serialized-key loader of unit_wire761.hip, one per section)

@@ -104,6 +104,7 @@ int wire377_decode(int g2, int compressed, const uint8_t* in, size_t n, int chec
 int wire377_launch_decode(int g2, int compressed, const uint8_t* d_in, size_t n, int check, uint64_t* d_out, uint8_t* d_st, hipStream_t stream);
 int wire_normalize(int group, const uint64_t* jac, size_t n, uint64_t* out_xy, uint8_t* inf);
 int wire_consts_device(WireConsts& out);
+int wire_consts_warm();                          // the upload of wire_consts_device alone (first use on the calling thread's device), for units that do not see wire.h
 float wire_last_ms();
 int wire761_decode(int g2, int compressed, const uint8_t* in, size_t n, int check, uint64_t* out, uint8_t* status, int dev, void* stream);
 // the serialized Groth16 proving key of curve 0 = BW6-761 / 1 = BLS12-377: the layout walk and the loader
@@ -114,6 +115,14 @@ void wire761_last_timings(float ms[4]);
 int wire761_set_subgroup_test(int form);
 int wire761_subgroup_test();
 void wire761_launch_ladder(uint64_t* d_rows, uint8_t* d_st, size_t n, hipStream_t s);
+// ---- compressed BLS12-377 keys decoded once per distinct byte string (unit_dedup.hip; dedup.h).  As wire_decompress, plus out_rep (n
+// representatives, or NULL; a device pointer with dev) and out_decoded (the number of keys that went through the decoder; a host pointer, or
+// NULL).  The stage times go to the call's own record (key_dedup_last); a composed caller times the whole of it with its own event pair
+int wire_decompress_dedup(int g2, const uint8_t* in, size_t n, int check, uint64_t* out, uint8_t* status, uint32_t* out_rep, uint64_t* out_decoded, int dev, void* stream);
+int key_dedup_set(int on, int slack_log, int max_probes);       // on: -1 the rule (dedup.h key_dedup_pick), 0 never, 1 always - for the composed callers
+int key_dedup_get(int out[3]);                   // on, slack_log, max_probes as they stand (the defaults resolved)
+bool key_dedup_use(size_t n);                   // what the switch says for a composed call with n keys
+int key_dedup_last(uint64_t counts[2], float ms[4]);
 // ---- bulk validation of affine rows (unit_check.hip; check.h).  cg 0 / 1: BLS12-377 G1 / G2, 2 / 3: BW6-761 G1 / G2; level 1: the curve
 // equation, 2: and the subgroup.  dev: xy, inf and status are device pointers, the work runs on `stream`; first_bad is a host pointer (may be NULL)
 int check_points(int cg, const uint64_t* xy, const uint8_t* inf, size_t n, int level, uint8_t* status, uint64_t* first_bad, int dev, void* stream);

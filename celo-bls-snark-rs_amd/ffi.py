@@ -85,6 +85,8 @@ EXPORTS = [
     "check_points_bls12_377_g1", "check_points_bls12_377_g2", "check_points_bw6_761_g1", "check_points_bw6_761_g2",
     "check_points_bls12_377_g1_dev", "check_points_bls12_377_g2_dev", "check_points_bw6_761_g1_dev", "check_points_bw6_761_g2_dev",
     "celo_amd_check_points_last_ms", "celo_amd_wire761_set_subgroup_test",
+    "decompress_bls12_377_g1_dedup", "decompress_bls12_377_g2_dedup", "decompress_bls12_377_g1_dedup_dev", "decompress_bls12_377_g2_dedup_dev",
+    "celo_amd_key_dedup_set", "celo_amd_key_dedup_get", "celo_amd_key_dedup_last",
 ]
 
 _lib = None
@@ -950,6 +952,57 @@ def decompress_dev(group, d_in, n, d_out, d_status, check_subgroup=True, stream=
     rc = getattr(lib(), fn)(C.c_void_p(d_in), C.c_size_t(n), C.c_int(1 if check_subgroup else 0), C.c_void_p(d_out), C.c_void_p(d_status), C.c_void_p(stream))
     if rc != 0:
         raise RuntimeError("%s failed with code %d" % (fn, rc))
+
+
+def decompress_dedup(group, data, check_subgroup=True, want_rep=True):
+    """decompress() for "g1" / "g2" with each distinct byte string decoded once (decompress_bls12_377_g1/_g2_dedup).  Returns
+    (xy, status, rep, decoded): xy and status as decompress(); rep (n,) uint32 (None without want_rep): a key with the same bytes at or
+    before each key; decoded: how many keys went through the decoder."""
+    size, words, fn = {"g1": (48, 12, "decompress_bls12_377_g1_dedup"), "g2": (96, 24, "decompress_bls12_377_g2_dedup")}[group]
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    assert buf.size % size == 0
+    n = buf.size // size
+    xy = np.zeros((n, words), dtype=np.uint64)
+    st = np.zeros(n, dtype=np.uint8)
+    rep = np.zeros(n, dtype=np.uint32) if want_rep else None
+    decoded = C.c_uint64(0)
+    rc = getattr(lib(), fn)(_p(buf), C.c_size_t(n), C.c_int(1 if check_subgroup else 0), _p(xy), _p(st), _p(rep), C.byref(decoded))
+    if rc != 0:
+        raise RuntimeError("%s failed with code %d" % (fn, rc))
+    return xy, st, rep, decoded.value
+
+
+def decompress_dedup_dev(group, d_in, n, d_out, d_status, d_rep=0, check_subgroup=True, stream=0):
+    """The same on device buffers (integer device addresses; d_rep may be 0), on `stream`.  Returns decoded (the call drains the stream)."""
+    fn = {"g1": "decompress_bls12_377_g1_dedup_dev", "g2": "decompress_bls12_377_g2_dedup_dev"}[group]
+    decoded = C.c_uint64(0)
+    rc = getattr(lib(), fn)(C.c_void_p(d_in), C.c_size_t(n), C.c_int(1 if check_subgroup else 0), C.c_void_p(d_out), C.c_void_p(d_status), C.c_void_p(d_rep or None),
+                            C.byref(decoded), C.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError("%s failed with code %d" % (fn, rc))
+    return decoded.value
+
+
+def key_dedup_set(on=-1, slack_log=-1, max_probes=0):
+    """The key de-duplication switch (celo_amd_key_dedup_set).  on: -1 the rule, 0 never, 1 always, for the composed epoch entry points;
+    slack_log 0 .. 2 (-1: the default); max_probes 1 .. 1024 (0: the default)."""
+    if lib().celo_amd_key_dedup_set(C.c_int(on), C.c_int(slack_log), C.c_int(max_probes)) != 0:
+        raise ValueError("celo_amd_key_dedup_set: on -1 .. 1, slack_log -1 .. 2, max_probes 0 .. 1024, not %r" % ((on, slack_log, max_probes),))
+
+
+def key_dedup_get():
+    """(on, slack_log, max_probes) as they stand"""
+    out = (C.c_int * 3)()
+    assert lib().celo_amd_key_dedup_get(out) == 0
+    return tuple(out)
+
+
+def key_dedup_last():
+    """(keys, decoded, ms): the last de-duplicating call; ms = [table + representatives + compaction, gather, decode, scatter] (HIP events)"""
+    counts = (C.c_uint64 * 2)()
+    ms = (C.c_float * 4)()
+    assert lib().celo_amd_key_dedup_last(counts, ms) == 0
+    return int(counts[0]), int(counts[1]), list(ms)
 
 
 _UNCOMPRESSED = {"g1": (96, 12, "decode_uncompressed_bls12_377_g1"), "g2": (192, 24, "decode_uncompressed_bls12_377_g2"),

@@ -341,6 +341,38 @@ int decompress_bls12_377_g1(const uint8_t* in /* n x 48 */, size_t n, int check_
 int decompress_bls12_377_g2(const uint8_t* in /* n x 96 */, size_t n, int check_subgroup, uint64_t* out_xy /* n x 24 */, uint8_t* status /* n */);
 int decompress_bls12_377_g1_dev(const uint8_t* d_in, size_t n, int check_subgroup, uint64_t* d_out_xy, uint8_t* d_status, void* hip_stream);
 int decompress_bls12_377_g2_dev(const uint8_t* d_in, size_t n, int check_subgroup, uint64_t* d_out_xy, uint8_t* d_status, void* hip_stream);
+/* ---- the same decoding with each distinct byte string decoded once (csrc/dedup.h, csrc/unit_dedup.hip): a validator set changes by a
+ * handful of keys per epoch, so the keys of many blocks are almost all repeats - what PublicKeyCache::deserialize
+ * (crates/bls-crypto/src/bls/cache.rs, "the aggregated public key changes slowly") is on the host.  A device hash table over the raw bytes
+ * finds, for every key, a representative with identical bytes; only the representatives go through the decoder above; every key then
+ * receives its representative's row and status.  out_xy and status are exactly those of decompress_bls12_377_g1 / _g2.
+ *   out_rep (n, or NULL): rep[i] <= i, key rep[i] has the bytes of key i, rep[rep[i]] == rep[i]; unless a probe sequence of the table
+ *                         reached its cap (below), rep[i] is the smallest j whose key equals key i
+ *   out_decoded (or NULL): the number of keys that went through the decoder: the number of distinct keys, plus the keys that hit the cap
+ * Refusals, the n = 0 answer (0; *out_decoded = 0) and the return codes are those of the plain entries; the refusals need no device.  The
+ * _dev forms take device pointers for in (any byte alignment), out_xy, status and out_rep, a host pointer for out_decoded, run on
+ * hip_stream and return after the work has drained (one 8-byte read of the number of representatives sizes the decoder's launch).
+ * Memory beside the outputs: 8 S + 16 n bytes with S = next_pow2(n) << slack_log table slots, and the decoded representatives. */
+int decompress_bls12_377_g1_dedup(const uint8_t* in /* n x 48 */, size_t n, int check_subgroup, uint64_t* out_xy /* n x 12 */, uint8_t* status /* n */,
+                                  uint32_t* out_rep /* n, or NULL */, uint64_t* out_decoded /* or NULL */);
+int decompress_bls12_377_g2_dedup(const uint8_t* in /* n x 96 */, size_t n, int check_subgroup, uint64_t* out_xy /* n x 24 */, uint8_t* status /* n */,
+                                  uint32_t* out_rep /* n, or NULL */, uint64_t* out_decoded /* or NULL */);
+int decompress_bls12_377_g1_dedup_dev(const uint8_t* d_in, size_t n, int check_subgroup, uint64_t* d_out_xy, uint8_t* d_status, uint32_t* d_out_rep, uint64_t* out_decoded,
+                                      void* hip_stream);
+int decompress_bls12_377_g2_dedup_dev(const uint8_t* d_in, size_t n, int check_subgroup, uint64_t* d_out_xy, uint8_t* d_status, uint32_t* d_out_rep, uint64_t* out_decoded,
+                                      void* hip_stream);
+/* The switch.  on: whether the composed entry points that decode compressed validator keys (epoch_encode_blocks_bls12_377,
+ * epoch_public_inputs_bw6_761, verify_epoch_proofs_bw6_761, verify_epoch_transitions_bls12_377) de-duplicate them: -1 the rule
+ * (csrc/dedup.h key_dedup_pick), 0 never, 1 always; their outputs are the same either way.  The four _dedup entries above always
+ * de-duplicate.  slack_log 0 .. 2 (-1: the default, 1): the table has next_pow2(n) << slack_log slots.  max_probes 1 .. 1024 (0: the
+ * default, 64): a key that has probed so many slots without finding its bytes or a free slot is decoded on its own - the bound on the
+ * work for crafted keys that share one slot.  Process-wide; 2 for any other value, and nothing changes.  _get: on, slack_log, max_probes
+ * as they stand. */
+int celo_amd_key_dedup_set(int on, int slack_log, int max_probes);
+int celo_amd_key_dedup_get(int out[3]);
+/* The last de-duplicating call that succeeded (a _dedup entry, or the key decoding of a composed call): counts = keys, keys decoded;
+ * ms (HIP events) = table + representatives + compaction, gather, decode, scatter. */
+int celo_amd_key_dedup_last(uint64_t counts[2], float ms[4]);
 /* Jacobian -> affine for n points in one launch (Montgomery's trick inside each lane): replaces
  * ProjectiveCurve::batch_normalization_into_affine as called before every MSM (crates/bls-crypto/src/bls/signature.rs:82,
  * public.rs:58).  jac: n x (X, Y, Z) arkworks Montgomery limbs (G1: 18 u64, G2: 36 u64 per point; identity = Z == 0);

@@ -1,11 +1,12 @@
 """Epoch blocks to Groth16 public inputs and verdicts on the device (verify_epoch_proofs_bw6_761, csrc/unit_epoch.hip).
 
-  python tools/bench_epoch_inputs.py [--runs 3] [--out profiles/bench_epoch_inputs.json] [--batches 64,1024,16421]
+  python tools/bench_epoch_inputs.py [--runs 3] [--out profiles/bench_epoch_inputs.json] [--batches 64,1024,16421] [--keys 110,150]
 
 Batches of 64 / 1 024 / 16 421 proofs with blocks of 110 and of 150 keys (n_keys = maximum_validators).  The blocks and proofs repeat a pool of
 four (first, last) pairs with one proof each, valid BY CONSTRUCTION for the oracle's inputs of its pair (tests/groth16_verify_cases.py), so every
 verdict is 1 and every stage does its whole work.  Per shape, in one process: --runs calls after one warm-up; the stage times of
 celo_amd_epoch_last (HIP events; the verifier and the whole call are wall clocks) with their spread, and the wall time seen from Python.
+key_dedup: the call with the key de-duplication switch (celo_amd_key_dedup_set) at 0, -1 and 1 in the same run.
 In the same run, what the call replaces:
   seam_a_loop        one Seam A `verify` per proof (64 proofs; host decoding, encoding and hashing, GPU input MSM and product)
   pieces_through_host decompress_bls12_377_g2 for every key, the blocks encoded and hashed on the host - by the Python restatement
@@ -126,6 +127,34 @@ def run_shape(vk, pairs, sers, m, runs):
     return out
 
 
+def run_key_dedup(vk, pairs, sers, m, runs):
+    """verify_epoch_proofs with the key de-duplication switch (celo_amd_key_dedup_set) at 0 (never), -1 (the rule) and 1 (always), in one run:
+    the "decode" slot of celo_amd_epoch_last, the wall clock inside the call and the one seen from Python"""
+    idx = [i % POOL for i in range(m)]
+    bf = ffi.EpochBlocks(**EC.arrays([pairs[i][0] for i in idx]))
+    bl = ffi.EpochBlocks(**EC.arrays([pairs[i][1] for i in idx]))
+    proofs = b"".join(sers[i] for i in idx)
+    out = {}
+    try:
+        for label, on in (("off", 0), ("rule", -1), ("always", 1)):
+            ffi.key_dedup_set(on)
+            recs = []
+            for r in range(runs + 1):
+                t0 = time.perf_counter()
+                ok, st = ffi.verify_epoch_proofs(vk, proofs, bf, bl, mode=0)
+                wall = (time.perf_counter() - t0) * 1e3
+                assert ok.all() and not st.any()
+                if r:
+                    recs.append(dict(ffi.epoch_last(), python_wall=wall))
+            out[label] = {"decode_ms": spread([x["decode"] for x in recs]), "wall_ms": spread([x["wall"] for x in recs]), "python_wall_ms": spread([x["python_wall"] for x in recs])}
+        out["last_dedup_call"] = dict(zip(("keys", "decoded", "stage_ms"), ffi.key_dedup_last()))
+    finally:
+        ffi.key_dedup_set(-1)
+    out["decode_off_over_always"] = round(out["off"]["decode_ms"]["median"] / out["always"]["decode_ms"]["median"], 3)
+    out["wall_off_over_always"] = round(out["off"]["wall_ms"]["median"] / out["always"]["wall_ms"]["median"], 3)
+    return out
+
+
 def dump(doc, path):
     js = json.dumps(doc, indent=1)
     if path:
@@ -139,6 +168,7 @@ def main():
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--out", default=None)
     ap.add_argument("--batches", default="64,1024,16421")
+    ap.add_argument("--keys", default="110,150", help="keys per block")
     a = ap.parse_args()
     ffi.init(0)
     key = gc.Key(2, 0xBE7C)
@@ -146,7 +176,7 @@ def main():
     doc = {"device": torch.cuda.get_device_name(0), "runs": a.runs, "mode": "each",
            "timer": "stages: HIP events on the call's stream (celo_amd_epoch_last); verify, wall: wall clocks inside the call; python_wall: around the wrapper",
            "shapes": {}}
-    for n_keys in (110, 150):
+    for n_keys in [int(v) for v in a.keys.split(",")]:
         pairs = pair_pool(n_keys)
         rng = ecc.SplitMix64(n_keys)
         batch = gc.Batch(key, [gc.valid_proof(key, rng, x=EC.expected_inputs(f, l)) for f, l in pairs])
@@ -156,6 +186,7 @@ def main():
             label = "%dx%d" % (m, n_keys)
             print("[bench_epoch_inputs] %s" % label, file=sys.stderr, flush=True)
             rec = {"proofs": m, "keys_per_block": n_keys, "keys": 2 * m * n_keys, "verify_epoch_proofs": run_shape(vk, pairs, sers, m, a.runs)}
+            rec["key_dedup"] = run_key_dedup(vk, pairs, sers, m, a.runs)
             rec["pieces_through_host"] = pieces_through_host(vk, pairs, sers, m, min(a.runs, 2), m <= 64)
             ours = rec["verify_epoch_proofs"]["python_wall"]["median"]
             if m <= 64:

@@ -7,6 +7,7 @@ Shapes: one chain of 143 transitions x 150 keys (a proof's range), 2 048 transit
 seeded secrets from a pool, 2/3 + 1 .. all of a set sign, every transition is valid (signed in the run by sign_batch_bls12_377, composite CIP22).
 Per shape, in one process, --runs runs after one warm-up, with spread:
   the call in both modes with the stage split of celo_amd_transitions_last;
+  the call with the key de-duplication switch (celo_amd_key_dedup_set) at 0, -1 and 1: the "decode" slot and the wall time of each;
   the same job through the pieces that were there before, via the host: decompress_bls12_377_g2 + epoch_encode_blocks_bls12_377 (inner) +
   verify_aggregated_seals_bls12_377 (hash mode 3, per-seal sets) - the keys decoded twice, the hash rows through the host;
   at 64 transitions, a loop of the Seam A calls (encode_epoch_block_to_bytes_cip22 + aggregate_public_keys + verify_signature).
@@ -88,6 +89,23 @@ def run_call(w, mode, runs):
     walls, recs = timed(once, runs)
     out = {"python_wall_ms": spread(walls), "path": recs[-1]["path"]}
     out["stages_ms"] = {k: spread([r["ms"][k] for r in recs]) for k in recs[-1]["ms"]}
+    return out
+
+
+def run_key_dedup(w, runs):
+    """the call (mode each) with the key de-duplication switch at 0 (never), -1 (the rule) and 1 (always), in one run: the "decode" slot of
+    celo_amd_transitions_last and the wall time"""
+    out = {}
+    try:
+        for label, on in (("off", 0), ("rule", -1), ("always", 1)):
+            ffi.key_dedup_set(on)
+            r = run_call(w, 0, runs)
+            out[label] = {"decode_ms": r["stages_ms"]["decode"], "wall_ms": r["stages_ms"]["wall"], "python_wall_ms": r["python_wall_ms"]}
+        out["last_dedup_call"] = dict(zip(("keys", "decoded", "stage_ms"), ffi.key_dedup_last()))
+    finally:
+        ffi.key_dedup_set(-1)
+    out["decode_off_over_always"] = round(out["off"]["decode_ms"]["median"] / out["always"]["decode_ms"]["median"], 3)
+    out["wall_off_over_always"] = round(out["off"]["wall_ms"]["median"] / out["always"]["wall_ms"]["median"], 3)
     return out
 
 
@@ -186,7 +204,7 @@ def main():
     for name, n_tr, n_keys, per in (("proof_143x150", 143, 150, 143), ("sync_2048x110", 2048, 110, 143), ("small_64x110", 64, 110, 64)):
         w = world(n_tr, n_keys, per, sks, enc, rng)
         rec = {"transitions": n_tr, "keys": n_keys, "chains": len(w["chain_off"]) - 1, "each": run_call(w, 0, a.runs), "chain": run_call(w, 1, a.runs),
-               "pieces_via_host": run_pieces(w, a.runs)}
+               "pieces_via_host": run_pieces(w, a.runs), "key_dedup": run_key_dedup(w, a.runs)}
         if n_tr == 64:
             rec["seam_a_loop"] = run_seam_a(w, enc, a.runs)
         each, chain, pieces = (rec[k]["python_wall_ms"]["median"] for k in ("each", "chain", "pieces_via_host"))
